@@ -121,7 +121,16 @@ def parse_args():
                    help="skip the short 1280x720 / 832x480 runs of the default line (the reference's other tuned sizes)")
     p.add_argument("--min-seconds", type=float, default=2.0,
                    help="length of the `sustained` region behind the K timed steps (0 = none)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the K timed steps, write what the last of them returned (compress and decompress results, rank 0) "
+                        "as DIR/<name>.npy: float32, integers float64, at most 64 MB in all - an array beyond its share is "
+                        "replaced by a fixed seeded sample of its elements. The inputs are seeded: two builds compare output "
+                        "for output")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and (a.sweep64 or a.handoff > 0):
+        raise SystemExit("--dump-outputs dumps the timed loop of the default mode (not --sweep64 / --handoff)")
     if a.resolution is None:
         a.resolution = "3840x2160" if a.sweep64 else "%dx%d" % (WIDTH, HEIGHT)
     try:
@@ -344,15 +353,57 @@ class FanoutWorkload(InterWorkload):
 
 
 def run_steps(work, first, n):
-    """n pipelined steps (no host synchronisation between them) -> coded bytes"""
+    """n pipelined steps (no host synchronisation between them) -> coded bytes. The last step's compress / decompress
+    results are left in work.last_step (proxy-owned tensors: valid until the workload's next codec call)."""
     nbytes = 0
+    enc = dec = None
     for i in range(first, first + n):
         qp = QPS[i % len(QPS)]
         work.prepare(i)
         enc = work.compress(i, qp)
-        work.decompress(i, qp, enc)
+        dec = work.decompress(i, qp, enc)
         nbytes += len(enc["bit_stream"])
+    work.last_step = (enc, dec)
     return nbytes
+
+
+DUMP_BYTES = 64 << 20
+
+
+def _host_arrays(name, obj, out):
+    """a codec call's result as a caller receives it -> host arrays: tensors as float32 (float64 stays), bit streams as
+    their byte values in float32, integers as float64; None (a picture a fan-out rank does not reconstruct) is left out"""
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _host_arrays("%s_%s" % (name, k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for k, v in enumerate(obj):
+            _host_arrays("%s_%d" % (name, k), v, out)
+    elif isinstance(obj, torch.Tensor):
+        out[name] = obj.detach().to("cpu", torch.float64 if obj.dtype == torch.float64 else torch.float32).numpy()
+    elif isinstance(obj, (bytes, bytearray)):
+        out[name] = np.frombuffer(obj, dtype=np.uint8).astype(np.float32)
+    elif obj is not None:
+        out[name] = np.asarray(obj, dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, enc, dec):
+    """--dump-outputs: the results of one step as <path>/compress_*.npy and <path>/decompress_*.npy. Beyond DUMP_BYTES in all,
+    every array keeps its share of the budget as a sample of its flattened elements at indices drawn from a generator seeded
+    with 0 (sorted): the same shape gives the same indices in every run. -> {name: shape of the full array}"""
+    arrays = _host_arrays("decompress", dec, _host_arrays("compress", enc, {}))
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 1024 * len(arrays)          # room for the .npy headers
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        shapes[name] = list(a.shape)
+        if total > budget and a.size > 1:
+            keep = max(1, a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return shapes
 
 
 def run_steps_overlapped(work, first, n, depth=int(os.environ.get("DCVC_BENCH_DEPTH", "2"))):
@@ -810,6 +861,9 @@ def run_default(env, make_work):
     nbytes = run_steps(work, args.warmup + mine.start, args.steps)
     env.sync()
     elapsed = env.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:         # before the next codec call overwrites the proxy-owned outputs
+        shapes = dump_outputs(args.dump_outputs, *work.last_step)
+        print("bench.py: step %d's outputs in %s: %s" % (args.warmup + args.steps - 1, args.dump_outputs, shapes), file=sys.stderr)
 
     # the same loop for >= --min-seconds: the K-step region of a short driver run lasts a fraction of a second
     sustained = None

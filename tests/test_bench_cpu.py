@@ -244,6 +244,62 @@ def test_timed_region_runs_exactly_k_steps(fake_gpu, monkeypatch, capsys):
     assert "roofline" not in d and "cpu_baseline" not in d and "other_workloads" not in d and "sustained" not in d
 
 
+class _FakeOutputs(_FakeWork):
+    """a stand-in whose results name the step that produced them, in the shapes the codecs return (intra: compress gives
+    bytes, x_hat and ec_parallel; HT: decompress gives a list of pictures)"""
+
+    def compress(self, i, qp):
+        super().compress(i, qp)
+        return {"bit_stream": bytes([i, qp]) * 3, "ec_parallel": 2, "x_hat": torch.full((1, 3, 4, 4), float(i), dtype=torch.float16)}
+
+    def decompress(self, i, qp, enc):
+        super().decompress(i, qp, enc)
+        return {"x_hat": [torch.full((1, 3, 4, 4), float(i), dtype=torch.float16), None]}
+
+
+def test_dump_outputs_holds_the_last_timed_step(fake_gpu, monkeypatch, capsys, tmp_path):
+    import numpy as np
+    monkeypatch.setattr(bench, "IntraWorkload", _FakeOutputs)
+    _run(monkeypatch, capsys, ["--steps", "5", "--warmup", "3", "--no-extras", "--no-roofline", "--no-cpu-baseline",
+                               "--min-seconds", "0.1", "--dump-outputs", str(tmp_path)])
+    assert len([c for c in _FakeOutputs.made[0].calls if c[0] == "c"]) > 8       # codec calls after the timed steps
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["compress_bit_stream", "compress_ec_parallel", "compress_x_hat", "decompress_x_hat_0"]
+    last = 3 + 5 - 1                                    # warm-up steps 0 - 2, timed steps 3 - 7
+    assert got["compress_x_hat"].dtype == np.float32 and got["compress_x_hat"].shape == (1, 3, 4, 4)
+    assert (got["compress_x_hat"] == last).all() and (got["decompress_x_hat_0"] == last).all()
+    assert got["compress_bit_stream"].dtype == np.float32
+    assert got["compress_bit_stream"].tolist() == [last, bench.QPS[last % len(bench.QPS)]] * 3
+    assert got["compress_ec_parallel"].dtype == np.float64 and got["compress_ec_parallel"] == 2
+    with pytest.raises(SystemExit):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--sweep64", "--dump-outputs", str(tmp_path)])
+        bench.main()
+
+
+def test_dump_outputs_samples_beyond_the_budget(monkeypatch, tmp_path):
+    """over the budget every array keeps its share as a seeded sample: the same elements in every run"""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    x = torch.arange(3 * 64 * 64, dtype=torch.float32).reshape(1, 3, 64, 64)
+    enc = {"bit_stream": bytes(range(256)) * 40, "x_hat": x}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), enc, {"x_hat": x + 1})
+    bench.dump_outputs(str(tmp_path / "b"), enc, {"x_hat": x + 1})
+    assert shapes == {"compress_bit_stream": [10240], "compress_x_hat": [1, 3, 64, 64], "decompress_x_hat": [1, 3, 64, 64]}
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 10
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    for name, arr in a.items():
+        assert np.array_equal(arr, np.load(tmp_path / "b" / name)), name
+        assert arr.ndim == 1 and 0 < arr.size
+    # a sample, in index order, of the array's own elements
+    assert np.all(np.diff(a["compress_x_hat.npy"]) > 0) and np.array_equal(a["decompress_x_hat.npy"], a["compress_x_hat.npy"] + 1)
+
+
+def test_steps_must_be_positive(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+
+
 def test_resolution_flag(fake_gpu, monkeypatch, capsys):
     d = _run(monkeypatch, capsys, ["--steps", "3", "--warmup", "1", "--resolution", "3840x2160", "--no-extras",
                                    "--no-cpu-baseline", "--min-seconds", "0"])

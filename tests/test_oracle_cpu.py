@@ -273,11 +273,11 @@ def test_vector_and_scalar_contractions_are_identical(kind):
         lib.orc_avx512(1)
 
 
-def test_torch_restatement_of_the_reference_cpu_path(golden):
-    """oracle/torch_graph.py (what bench.py times as the reference's CPU path on the GPU box, where
-    /root/reference does not exist) against x_hat made by the reference's own
-    DMCI.forward_one_frame (tests/golden/make_dmci_golden.py), and live against the reference module
-    when the tree is present. fp32 graph vs fp32 graph: equal up to summation order."""
+def test_torch_restatement_of_the_reference_cpu_path(golden, golden_dir):
+    """oracle/torch_graph.py (what bench.py times as the reference's CPU path) against x_hat made by the
+    reference's own DMCI.forward_one_frame: fp16-stored cases (tests/golden/make_dmci_golden.py) and one
+    fp32-stored case (tests/golden/make_torch_graph_golden.py). fp32 graph vs fp32 graph: equal up to
+    summation order."""
     import torch
     from dcvc_amd import arch, synthetic
     from oracle import torch_graph
@@ -289,26 +289,11 @@ def test_torch_restatement_of_the_reference_cpu_path(golden):
         # a flipped rounding decision moves a latent by one step: bound the damage, demand near-identity
         psnr = 10 * np.log10(1.0 / np.mean((got - want) ** 2))
         assert psnr > 55, (i, psnr)
-    if os.path.isdir("/root/reference/src/models"):
-        import sys
-        from oracle import build_oracle, rans as orc
-        try:
-            build_oracle.build_ref()
-            sys.modules.setdefault("MLCodec_extensions_cpp", orc.load_ref())
-            sys.path.insert(0, "/root/reference")
-            from src.models.image_model import DMCI
-        except Exception as e:
-            pytest.skip("reference module does not import here: %s" % e)
-        finally:
-            if "/root/reference" in sys.path:
-                sys.path.remove("/root/reference")
-        net = DMCI().eval()
-        net.load_state_dict(sd, strict=True)
-        x = torch.rand((1, 3, 64, 128), generator=torch.Generator().manual_seed(3)) - 0.5
-        with torch.no_grad():
-            want = net.forward_one_frame(x, torch.tensor([20]), recon_only=True)
-        got = torch_graph.forward_one_frame(sd, x, 20)
-        assert torch.allclose(got, want, atol=2e-5), float((got - want).abs().max())
+    # fp32 output of the reference module itself on a seeded picture (tests/golden/make_torch_graph_golden.py)
+    g = np.load(os.path.join(golden_dir, "torch_graph_golden.npz"))
+    want = torch.from_numpy(g["x_hat"])
+    got = torch_graph.forward_one_frame(sd, torch.from_numpy(g["x"]), int(g["qp"][0]))
+    assert torch.allclose(got, want, atol=2e-5), float((got - want).abs().max())
 
 
 def test_c_abi_exports_every_declared_symbol():

@@ -1,10 +1,11 @@
 """Native bit-stream container (include/dcvc_amd_stream.h) against the Python
 mirror of stream_helper.py (dcvc_amd/stream_helper.py, itself checked against bytes produced by the
-reference's own module in tests/test_io_cpu.py) and, when /root/reference is present, against the
-reference module directly. CPU only: the library loads and the host code runs without a GPU."""
+reference's own module in tests/test_io_cpu.py) and against the bytes the reference module writes for the same units
+(tests/golden/stream_golden.json). CPU only: the library loads and the host code runs without a GPU."""
 import ctypes
-import importlib.util
+import hashlib
 import io
+import json
 import os
 
 import numpy as np
@@ -132,13 +133,9 @@ def test_errors(nat):
                           ctypes.byref(pl), ctypes.byref(n)) == -2
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/utils/stream_helper.py"), reason="reference tree absent")
-def test_writer_matches_the_reference_module(nat):
-    spec = importlib.util.spec_from_file_location("ref_stream_helper", "/root/reference/src/utils/stream_helper.py")
-    try:
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-    except Exception as e:                       # the reference needs Python >= 3.12 syntax in places
-        pytest.skip("reference stream_helper does not import here: %s" % e)
-    units = _sequence()
-    assert _native_bytes(nat, units) == _python_bytes(units, ref)
+def test_writer_matches_the_reference_module(nat, golden_dir):
+    """the bytes the reference's own module writes for _sequence(), as length + sha256 (tests/golden/make_stream_golden.py)"""
+    with open(os.path.join(golden_dir, "stream_golden.json")) as f:
+        want = json.load(f)
+    got = _native_bytes(nat, _sequence())
+    assert len(got) == want["bytes"] and hashlib.sha256(got).hexdigest() == want["sha256"]

@@ -137,7 +137,10 @@ namespace {
 struct AsyncBuf {
     void* p = nullptr;
     hipStream_t st = nullptr;
-    AsyncBuf(size_t bytes, hipStream_t stream) : st(stream) { dcvc::hip_check(hipMallocAsync(&p, bytes, st), "hipMallocAsync(packed weights)"); }
+    AsyncBuf(size_t bytes, hipStream_t stream, const char* what = "hipMallocAsync(packed weights)") : st(stream)
+    {
+        dcvc::hip_check(hipMallocAsync(&p, bytes, st), what);
+    }
     ~AsyncBuf() { if (p) (void)hipFreeAsync(p, st); }
     AsyncBuf(const AsyncBuf&) = delete;
     AsyncBuf& operator=(const AsyncBuf&) = delete;
@@ -416,6 +419,19 @@ int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H_, int W_, void* y1
     return dcvc::guarded([&] {
         dcvc::x_to_yuv420(H(x_hat), row_pixels, H_, W_, H(y16), H(uv16), static_cast<uint8_t*>(y8),
                           static_cast<uint8_t*>(uv8), S(stream));
+    });
+}
+
+int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_,
+                int row_stride, long long plane_stride, double* out, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::MsssimDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        dcvc::msssim_validate(d);      // before the workspace is sized: a bad geometry never reaches the allocator
+        const AsyncBuf ws(dcvc::msssim_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(msssim workspace)");
+        dcvc::msssim(d, ws.p, S(stream));
     });
 }
 

@@ -10,9 +10,13 @@
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
 //               [--intra-period -1] [--reset-interval 32] -o out.bin
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
+//               [--calc-ssim 1] [--verbose-json 1]
 //               (the container carries no picture count: the last chunk of an 8-picture model is padded by repeating
 //               the final picture, test_video.py:104-110 - give -n, or --ref whose length then trims the output, as the
 //               reference's maximum_read = min(g_frame_delay, frame_num - decoded) does)
+//               --calc-ssim 1: MS-SSIM of every picture on the GPU (dcvc_msssim; test_video.py:45-51 --calc_ssim), logged as
+//               ave_{i,p,all}_frame_msssim{,_y,_u,_v}; needs --ref and both sides >= 176 (chroma planes >= 88).
+//               --verbose-json 1: per-picture lists as the reference's --verbose_json writes them (common.py:90-98).
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -187,10 +191,13 @@ struct DeviceBuffers {
     uint8_t* out8 = nullptr;       // u8 planes of a reconstruction
     uint8_t* h_yuv = nullptr;      // pinned
     uint16_t* h_p16 = nullptr;     // pinned fp16 planes
+    uint8_t* src8 = nullptr;       // u8 planes of the source picture (--calc-ssim)
+    double* ssim = nullptr;        // MS-SSIM of Y, U, V (--calc-ssim)
+    double* h_ssim = nullptr;      // pinned
     hipStream_t st = nullptr;
 };
 
-DeviceBuffers make_buffers(const Geometry& g, int frames)
+DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false)
 {
     DeviceBuffers b;
     hip_ok(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking), "hipStreamCreate");
@@ -201,15 +208,22 @@ DeviceBuffers make_buffers(const Geometry& g, int frames)
     hip_ok(hipMalloc(&b.out8, g.frame_bytes()), "hipMalloc");
     hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_yuv), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
     hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_p16), g.frame_bytes() * 2, hipHostMallocDefault), "hipHostMalloc");
+    if (ssim) {
+        hip_ok(hipMalloc(&b.src8, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&b.ssim, 3 * sizeof(double)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_ssim), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+    }
     return b;
 }
 
 void free_buffers(DeviceBuffers& b)
 {
     if (b.st) hip_ok(hipStreamSynchronize(b.st), "sync");
-    for (void* d : {static_cast<void*>(b.yuv8), b.x, b.x_hat, b.y16, static_cast<void*>(b.out8)}) {
+    for (void* d : {static_cast<void*>(b.yuv8), b.x, b.x_hat, b.y16, static_cast<void*>(b.out8), static_cast<void*>(b.src8),
+                    static_cast<void*>(b.ssim)}) {
         if (d) hip_ok(hipFree(d), "hipFree");
     }
+    if (b.h_ssim) hip_ok(hipHostFree(b.h_ssim), "hipHostFree");
     if (b.h_yuv) hip_ok(hipHostFree(b.h_yuv), "hipHostFree");
     if (b.h_p16) hip_ok(hipHostFree(b.h_p16), "hipHostFree");
     if (b.st) hip_ok(hipStreamDestroy(b.st), "hipStreamDestroy");
@@ -230,6 +244,23 @@ double psnr_plane(const uint8_t* src, const uint16_t* rec16, size_t n)
     if (std::isnan(mse) || std::isinf(mse)) return -999.9;
     const double p = mse > 1e-10 ? 10.0 * std::log10(255.0 * 255.0 / mse) : 999.9;
     return p < 99.9 ? p : 99.9;
+}
+
+// a JSON number as Python's json.dump writes it: NaN and the infinities as NaN / Infinity / -Infinity, else 17 digits
+std::string jnum(double v)
+{
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v > 0 ? "Infinity" : "-Infinity";
+    char buf[32];
+    snprintf(buf, sizeof(buf), "%.17g", v);
+    return buf;
+}
+
+std::string jlist(const std::vector<double>& v)
+{
+    std::string s = "[";
+    for (size_t i = 0; i < v.size(); ++i) s += (i ? ", " : "") + jnum(v[i]);
+    return s + "]";
 }
 
 struct Args {
@@ -355,6 +386,8 @@ int decode(const Args& a)
     FILE* ref = a.has("ref") ? fopen(a.str("ref").c_str(), "rb") : nullptr;
     if (a.has("o") && !rec) die("cannot write " + a.str("o"));
     if (a.has("ref") && !ref) die("cannot open " + a.str("ref"));
+    const bool calc_ssim = a.num("calc-ssim", 0) != 0, verbose_json = a.num("verbose-json", 0) != 0;
+    if (calc_ssim && !ref) die("--calc-ssim needs --ref (the source pictures)");
     const int limit = a.num("n", 1 << 30);
     dcvc::stream::Reader rd(bin.data(), bin.size());
     dcvc::stream::SpsTable sps;
@@ -364,7 +397,7 @@ int decode(const Args& a)
     std::vector<uint8_t> src;
     // log (src/utils/common.py:46-116)
     std::vector<int> types;
-    std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v;
+    std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v, ssim, ssim_y, ssim_u, ssim_v;
     size_t pending_sps_bits = 0;
     int decoded = 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -392,9 +425,14 @@ int decode(const Args& a)
             if (s->height < 2 || s->width < 2 || s->height > kMaxPictureSide || s->width > kMaxPictureSide) {
                 die("unsupported picture size in the stream: " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
+            // MS-SSIM needs both sides of every plane >= 88 (metrics.py asserts): refused before anything is decoded
+            if (calc_ssim && (s->height < 176 || s->width < 176)) {
+                die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), the "
+                    "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
+            }
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width);
-            b = make_buffers(g, c.frames_per_p);
+            b = make_buffers(g, c.frames_per_p, calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
@@ -437,13 +475,26 @@ int decode(const Args& a)
                 if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) die("short write");
             }
             if (ref) {
+                const size_t ny = g.y_bytes(), nc = ny / 4;
+                if (calc_ssim) {
+                    // the source picture next to the decoded fp16 planes; Y as one plane, U + V as two
+                    hip_ok(hipMemcpyAsync(b.src8, src.data(), g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                    abi_ok(dcvc_msssim(b.src8, DCVC_SAMPLE_U8, y16, DCVC_SAMPLE_F16, 1, g.H, g.W, g.W, static_cast<long long>(ny), b.ssim,
+                                       b.st), "msssim (Y)");
+                    abi_ok(dcvc_msssim(b.src8 + ny, DCVC_SAMPLE_U8, y16 + ny * 2, DCVC_SAMPLE_F16, 2, g.H / 2, g.W / 2, g.W / 2,
+                                       static_cast<long long>(nc), b.ssim + 1, b.st), "msssim (U, V)");
+                    hip_ok(hipMemcpyAsync(b.h_ssim, b.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                }
                 hip_ok(hipMemcpyAsync(b.h_p16, b.y16, g.frame_bytes() * 2, hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
-                const size_t ny = g.y_bytes(), nc = ny / 4;
                 const double py = psnr_plane(src.data(), b.h_p16, ny);
                 const double pu = psnr_plane(src.data() + ny, b.h_p16 + ny, nc);
                 const double pv = psnr_plane(src.data() + ny + nc, b.h_p16 + ny + nc, nc);
                 psnr.push_back((6 * py + pu + pv) / 8); psnr_y.push_back(py); psnr_u.push_back(pu); psnr_v.push_back(pv);
+                if (calc_ssim) {
+                    const double sy = b.h_ssim[0], su = b.h_ssim[1], sv = b.h_ssim[2];
+                    ssim.push_back((6 * sy + su + sv) / 8); ssim_y.push_back(sy); ssim_u.push_back(su); ssim_v.push_back(sv);
+                }
             }
             types.push_back(intra ? 0 : 1);
             bits.push_back(j == 0 ? unit_bits : 0.0);
@@ -474,6 +525,32 @@ int decode(const Args& a)
         for (int k = 0; k < 4; ++k) {
             fprintf(jf, "  \"ave_i_frame_psnr%s\": %.9g,\n  \"ave_p_frame_psnr%s\": %.9g,\n  \"ave_all_frame_psnr%s\": %.9g,\n", sfx[k],
                     ni ? ip[k] / ni : 0.0, sfx[k], np ? pp[k] / np : 0.0, sfx[k], (ip[k] + pp[k]) / std::max(1, ni + np));
+        }
+        if (calc_ssim) {
+            // common.py:78-114: the i / p / all averages of (6 y + u + v) / 8 and of each plane (0 for an empty class)
+            const std::vector<double>* sv[4] = {&ssim, &ssim_y, &ssim_u, &ssim_v};
+            for (int k = 0; k < 4; ++k) {
+                double si = 0, sp = 0;
+                for (size_t i = 0; i < types.size(); ++i) (types[i] == 0 ? si : sp) += (*sv[k])[i];
+                fprintf(jf, "  \"ave_i_frame_msssim%s\": %s,\n  \"ave_p_frame_msssim%s\": %s,\n  \"ave_all_frame_msssim%s\": %s,\n",
+                        sfx[k], jnum(ni ? si / ni : 0.0).c_str(), sfx[k], jnum(np ? sp / np : 0.0).c_str(), sfx[k],
+                        jnum((si + sp) / std::max(1, ni + np)).c_str());
+            }
+        }
+        if (verbose_json) {
+            // common.py:90-98
+            std::vector<double> bpp(bits.size());
+            for (size_t i = 0; i < bits.size(); ++i) bpp[i] = bits[i] / px;
+            std::string ft = "[";
+            for (size_t i = 0; i < types.size(); ++i) ft += (i ? ", " : "") + std::to_string(types[i]);
+            ft += "]";
+            fprintf(jf, "  \"frame_bpp\": %s,\n  \"frame_type\": %s,\n", jlist(bpp).c_str(), ft.c_str());
+            const std::vector<double>* pv[4] = {&psnr, &psnr_y, &psnr_u, &psnr_v};
+            const std::vector<double>* mv[4] = {&ssim, &ssim_y, &ssim_u, &ssim_v};
+            for (int k = 0; k < 4; ++k) {
+                fprintf(jf, "  \"frame_psnr%s\": %s,\n", sfx[k], jlist(*pv[k]).c_str());
+                if (calc_ssim) fprintf(jf, "  \"frame_msssim%s\": %s,\n", sfx[k], jlist(*mv[k]).c_str());
+            }
         }
         fprintf(jf, "  \"ave_all_frame_bpp\": %.9g,\n  \"test_time\": %.3f\n}\n", (ib + pb) / (std::max(1, ni + np) * px), secs);
         fclose(jf);

@@ -241,6 +241,22 @@ void yuv420_to_x(const uint8_t* y, const uint8_t* uv, int H, int W, half_t* x, i
 void x_to_yuv420(const half_t* x, int row_pixels, int H, int W, half_t* y16, half_t* uv16, uint8_t* y8,
                  uint8_t* uv8, hipStream_t stream);
 
+// ---------------------------------------------------------------- MS-SSIM (msssim.hip)
+// metrics.py:27-91 calc_msssim of n_planes pairs of H x W planes (u8 or fp16 samples in 0..255; src and rec share row_stride
+// and plane_stride, in samples), fp64 after the load; out[plane] (device, fp64). The workspace (msssim_workspace_bytes) holds the
+// downsampled planes and the per-workgroup partial sums; 1 + 4 or 5 launches on `stream`.
+constexpr int kSampleU8 = 0, kSampleF16 = 1;        // DCVC_SAMPLE_U8 / DCVC_SAMPLE_F16
+struct MsssimDesc {
+    const void* src = nullptr; int src_dtype = kSampleU8;
+    const void* rec = nullptr; int rec_dtype = kSampleU8;
+    int n_planes = 0, H = 0, W = 0;
+    int row_stride = 0; long long plane_stride = 0;
+    double* out = nullptr;
+};
+void msssim_validate(const MsssimDesc& d);       // throws std::invalid_argument for a geometry or operand msssim() refuses
+size_t msssim_workspace_bytes(int n_planes, int H, int W);
+void msssim(const MsssimDesc& d, void* workspace, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

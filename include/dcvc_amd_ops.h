@@ -168,6 +168,16 @@ int dcvc_yuv420_to_x(const void* y, const void* uv, int H, int W, void* x, int l
 int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H, int W, void* y16, void* uv16, void* y8,
                      void* uv8, void* stream);
 
+/* sample types of dcvc_msssim */
+#define DCVC_SAMPLE_U8  0
+#define DCVC_SAMPLE_F16 1
+/* metrics.py:27-91 calc_msssim on the GPU, one value per plane. n_planes planes of H x W samples (u8, or fp16 holding 0..255);
+ * src and rec share the geometry (row_stride, plane_stride in samples). out: device memory, n_planes doubles, written
+ * asynchronously on `stream`. fp64 after the load; 5 levels when both sides are >= 176, else 4; H or W < 88 -> error (the
+ * reference asserts). A negative cs mean gives NaN, as numpy does. The workspace is a stream-ordered temporary. */
+int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W,
+                int row_stride, long long plane_stride, double* out, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

@@ -178,7 +178,7 @@ def _build_locked(force, verbose, srcs, manifest, digest):
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
             list(ex.map(run, jobs))
     cmd = [_hipcc(), "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", LIB] + objs + \
-          ["-lpthread", "-Wl,-rpath,/opt/rocm/lib"]
+          ["-lpthread", "-lz", "-Wl,-rpath,/opt/rocm/lib"]      # zlib: the PNG codec (csrc/image); libamdhip64 needs libz.so.1 too
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)

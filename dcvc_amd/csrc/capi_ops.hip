@@ -435,6 +435,60 @@ int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, 
     });
 }
 
+int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H_, int W_,
+                  void* x, int ldx, void* planar, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::RgbToXDesc d;
+        d.src = static_cast<const uint8_t*>(src);
+        d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
+        d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint8_t*>(planar);
+        dcvc::rgb_to_x(d, S(stream));
+    });
+}
+
+int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H_, int W_, void* rgb16, void* rgb8, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::x_to_rgb(H(x_hat), row_pixels, H_, W_, H(rgb16), static_cast<uint8_t*>(rgb8), S(stream));
+    });
+}
+
+int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
+             long long plane_stride, double* out, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::SseDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        dcvc::sse_validate(d);         // before the workspace is sized: a bad geometry never reaches the allocator
+        const AsyncBuf ws(dcvc::sse_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(sse workspace)");
+        dcvc::sse(d, ws.p, S(stream));
+    });
+}
+
+long long dcvc_sse_workspace_bytes(int n_planes, int H_, int W_)
+{
+    if (n_planes <= 0 || H_ <= 0 || W_ <= 0) return 0;
+    return static_cast<long long>(dcvc::sse_workspace_bytes(n_planes, H_, W_));
+}
+
+int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
+                long long plane_stride, double* out, void* workspace, long long workspace_bytes, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::SseDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        dcvc::sse_validate(d);
+        if (workspace == nullptr || workspace_bytes < 0 ||
+            static_cast<unsigned long long>(workspace_bytes) < dcvc::sse_workspace_bytes(n_planes, H_, W_)) {
+            throw std::invalid_argument("sse: workspace missing or smaller than dcvc_sse_workspace_bytes");
+        }
+        dcvc::sse(d, workspace, S(stream));
+    });
+}
+
 int dcvc_mask_step_enc(void* y, int ldy, const void* q_dec, int ldq, const void* scales, int lds,
                        const void* means, int ldm, void* y_hat, int ldh, void* sym, void* cond,
                        void* block_count, void* compact_out, void* totals, int Hh, int W, int C,

@@ -1,16 +1,24 @@
-// dcvc - standalone DCVC-UF encoder / decoder for 8-bit YUV420 files on an MI355X.
+// dcvc - standalone DCVC-UF encoder / decoder for 8-bit YUV420 and RGB pictures on an MI355X.
 //
 // The codec without the research harness: what test_video.py:166-399 (run_one_point_with_stream)
-// does around the plugin - read YUV420 frames, code them picture by picture into the reference's
+// does around the plugin - read YUV420 frames or RGB pictures, code them picture by picture into the reference's
 // stream container, decode the container again, write the reconstruction, log bits and PSNR - as a
-// native tool on top of the C ABI only (include/dcvc_amd_codec.h, _ops.h, _stream.h). No Python, no
+// native tool on top of the C ABI only (include/dcvc_amd_codec.h, _ops.h, _stream.h, _image.h). No Python, no
 // torch: weights come from a .dcvw file (python -m dcvc_amd.export_weights), pictures travel as u8
-// planes and are converted on the device (frame_io.hip).
+// planes and are converted on the device (frame_io.hip, rgb_io.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
-//               [--intra-period -1] [--reset-interval 32] -o out.bin
+//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] -o out.bin
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1]
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png]
+//               --src-type (test_video.py's src_type; default yuv420): rgb24 = packed 8-bit RGB pictures back to back in
+//               one file (ffmpeg -pix_fmt rgb24 -f rawvideo), -W / -H required to encode; png = -i (encode), --ref and -o
+//               are directories of im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-45; the writer uses
+//               im00001.png, ...), the size is taken from the first picture and every picture must have it. RGB is
+//               converted with BT.709 on the device (dcvc_rgb_to_x / dcvc_x_to_rgb, test_video.py:55-64, 87-122,
+//               366-370); the log then holds the RGB PSNR (dcvc_sse, calc_psnr over 3 H W samples) and, with --calc-ssim,
+//               the mean of the three planes' MS-SSIM (calc_msssim_rgb), without _y / _u / _v keys. Both sides must be
+//               even, and >= 88 for --calc-ssim.
 //               (the container carries no picture count: the last chunk of an 8-picture model is padded by repeating
 //               the final picture, test_video.py:104-110 - give -n, or --ref whose length then trims the output, as the
 //               reference's maximum_read = min(g_frame_delay, frame_num - decoded) does)
@@ -22,6 +30,7 @@
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
 // test_video.py:204-233, 95-110, 240-257, 32-45 and src/utils/common.py:46-116.
 #include "dcvc_amd_codec.h"
+#include "dcvc_amd_image.h"
 #include "dcvc_amd_ops.h"
 #include "dcvc_amd_rans.h"
 #include "stream/container.h"
@@ -33,6 +42,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <fstream>
 #include <map>
 #include <stdexcept>
@@ -168,16 +178,23 @@ Codecs make_codecs(const std::string& intra_path, const std::string& inter_path)
 // ------------------------------------------------------------------------------------ pictures
 struct Geometry {
     int H = 0, W = 0, Hp = 0, Wp = 0;      // picture, padded to multiples of 16
+    bool rgb = false;                      // 8-bit RGB pictures (--src-type rgb24 / png) instead of YUV420
     size_t y_bytes() const { return static_cast<size_t>(H) * W; }
     size_t uv_bytes() const { return static_cast<size_t>(H / 2) * (W / 2) * 2; }
-    size_t frame_bytes() const { return y_bytes() + uv_bytes(); }
+    // one u8 picture: YUV420 planes, or packed RGB (u8 planes [3][H][W] on the device)
+    size_t frame_bytes() const { return rgb ? 3 * y_bytes() : y_bytes() + uv_bytes(); }
 };
 
-Geometry geometry(int H, int W)
+Geometry geometry(int H, int W, bool rgb = false)
 {
+    if (rgb && (H <= 0 || W <= 0 || (H & 1) || (W & 1))) {
+        die("picture size must be positive and even (RGB pictures are coded as YUV420 is: even sides), got " +
+            std::to_string(W) + "x" + std::to_string(H));
+    }
     if (H <= 0 || W <= 0 || (H & 1) || (W & 1)) die("picture size must be positive and even (YUV420)");
     Geometry g;
     g.H = H; g.W = W; g.Hp = (H + 15) / 16 * 16; g.Wp = (W + 15) / 16 * 16;
+    g.rgb = rgb;
     return g;
 }
 
@@ -194,6 +211,11 @@ struct DeviceBuffers {
     uint8_t* src8 = nullptr;       // u8 planes of the source picture (--calc-ssim)
     double* ssim = nullptr;        // MS-SSIM of Y, U, V (--calc-ssim)
     double* h_ssim = nullptr;      // pinned
+    double* sse = nullptr;         // sums of squares of R, G, B (RGB --ref)
+    double* h_sse = nullptr;       // pinned
+    void* sse_ws = nullptr;        // dcvc_sse_ws's workspace
+    long long sse_ws_bytes = 0;
+    uint8_t* h_src = nullptr;      // pinned: the source picture (RGB --ref)
     hipStream_t st = nullptr;
 };
 
@@ -213,6 +235,14 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false)
         hip_ok(hipMalloc(&b.ssim, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_ssim), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
     }
+    if (g.rgb) {
+        if (!b.src8) hip_ok(hipMalloc(&b.src8, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&b.sse, 3 * sizeof(double)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_src), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        b.sse_ws_bytes = dcvc_sse_workspace_bytes(3, g.H, g.W);
+        hip_ok(hipMalloc(&b.sse_ws, static_cast<size_t>(b.sse_ws_bytes)), "hipMalloc");
+    }
     return b;
 }
 
@@ -220,10 +250,12 @@ void free_buffers(DeviceBuffers& b)
 {
     if (b.st) hip_ok(hipStreamSynchronize(b.st), "sync");
     for (void* d : {static_cast<void*>(b.yuv8), b.x, b.x_hat, b.y16, static_cast<void*>(b.out8), static_cast<void*>(b.src8),
-                    static_cast<void*>(b.ssim)}) {
+                    static_cast<void*>(b.ssim), static_cast<void*>(b.sse), b.sse_ws}) {
         if (d) hip_ok(hipFree(d), "hipFree");
     }
     if (b.h_ssim) hip_ok(hipHostFree(b.h_ssim), "hipHostFree");
+    if (b.h_sse) hip_ok(hipHostFree(b.h_sse), "hipHostFree");
+    if (b.h_src) hip_ok(hipHostFree(b.h_src), "hipHostFree");
     if (b.h_yuv) hip_ok(hipHostFree(b.h_yuv), "hipHostFree");
     if (b.h_p16) hip_ok(hipHostFree(b.h_p16), "hipHostFree");
     if (b.st) hip_ok(hipStreamDestroy(b.st), "hipStreamDestroy");
@@ -244,6 +276,72 @@ double psnr_plane(const uint8_t* src, const uint16_t* rec16, size_t n)
     if (std::isnan(mse) || std::isinf(mse)) return -999.9;
     const double p = mse > 1e-10 ? 10.0 * std::log10(255.0 * 255.0 / mse) : 999.9;
     return p < 99.9 ? p : 99.9;
+}
+
+// metrics.py:10-24 from the fp64 sum of squared differences over n samples
+double psnr_of_sse(double se, double n)
+{
+    const double mse = se / n;
+    if (std::isnan(mse) || std::isinf(mse)) return -999.9;
+    const double p = mse > 1e-10 ? 10.0 * std::log10(255.0 * 255.0 / mse) : 999.9;
+    return p < 99.9 ? p : 99.9;
+}
+
+// a directory of PNG pictures im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-45 PNGReader; its naming
+// rule: im1.png present -> no padding, else im00001.png present -> 5 digits, else an error)
+struct PngDir {
+    std::string dir;
+    int pad = 5, next = 1;
+    std::string path(int n) const
+    {
+        std::string num = std::to_string(n);
+        if (static_cast<int>(num.size()) < pad) num.insert(0, static_cast<size_t>(pad) - num.size(), '0');
+        return (std::filesystem::path(dir) / ("im" + num + ".png")).string();
+    }
+    bool exists(int n) const { return std::filesystem::is_regular_file(path(n)); }
+    int count() const
+    {
+        int n = 0;
+        while (exists(n + 1)) ++n;
+        return n;
+    }
+    // the next picture into buf (packed RGB, g.frame_bytes()); false when the sequence has ended
+    bool read(uint8_t* buf, const Geometry& g)
+    {
+        if (!exists(next)) return false;
+        const std::string p = path(next++);
+        int w = 0, h = 0;
+        abi_ok(dcvc_png_info(p.c_str(), &w, &h), "png read");
+        if (w != g.W || h != g.H) {
+            die(p + " is " + std::to_string(w) + "x" + std::to_string(h) + ", the sequence is " + std::to_string(g.W) + "x" +
+                std::to_string(g.H));
+        }
+        abi_ok(dcvc_png_read_rgb(p.c_str(), buf, g.frame_bytes(), &w, &h), "png read");
+        return true;
+    }
+};
+
+PngDir png_dir(const std::string& dir)
+{
+    std::error_code ec;
+    if (!std::filesystem::is_directory(dir, ec)) die(dir + " is not a directory (--src-type png reads a directory of PNG pictures)");
+    PngDir d;
+    d.dir = dir;
+    d.pad = 1;
+    if (d.exists(1)) return d;
+    d.pad = 5;
+    if (d.exists(1)) return d;
+    die(dir + ": unknown image naming convention (im1.png or im00001.png expected)");
+}
+
+enum class SrcType { Yuv420, Rgb24, Png };
+
+SrcType src_type(const std::string& s)
+{
+    if (s == "yuv420") return SrcType::Yuv420;
+    if (s == "rgb24") return SrcType::Rgb24;
+    if (s == "png") return SrcType::Png;
+    die("unknown --src-type " + s + " (yuv420, rgb24 or png)");
 }
 
 // a JSON number as Python's json.dump writes it: NaN and the infinities as NaN / Infinity / -Infinity, else 17 digits
@@ -292,7 +390,21 @@ bool is_intra_picture(int idx, int intra_period)
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
-    const Geometry g = geometry(a.num("H", 0), a.num("W", 0));
+    const SrcType type = src_type(a.str("src-type", "yuv420"));
+    const bool rgb = type != SrcType::Yuv420;
+    int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
+    PngDir pngs;
+    if (type == SrcType::Png) {
+        // the size of the first picture; -W / -H, when given, must agree with it
+        pngs = png_dir(a.str("i"));
+        abi_ok(dcvc_png_info(pngs.path(1).c_str(), &pic_w, &pic_h), "png info");
+        if ((a.has("W") && a.num("W", 0) != pic_w) || (a.has("H") && a.num("H", 0) != pic_h)) {
+            die(pngs.path(1) + " is " + std::to_string(pic_w) + "x" + std::to_string(pic_h) + ", not the -W x -H given");
+        }
+    } else if (rgb && (!a.has("W") || !a.has("H"))) {
+        die("--src-type rgb24 needs -W and -H");
+    }
+    const Geometry g = geometry(pic_h, pic_w, rgb);
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     const bool force_intra = !c.has_inter();
     const int intra_period = force_intra ? 1 : a.num("intra-period", -1);
@@ -300,11 +412,17 @@ int encode(const Args& a)
     const int qp_i = a.num("qp-i", 32), qp_p = a.num("qp-p", qp_i);
     const int delay = c.frames_per_p;
     if (intra_period > 1 && intra_period % delay != 0) die("intra period must be a multiple of the chunk size");
-    FILE* in = fopen(a.str("i").c_str(), "rb");
-    if (!in) die("cannot open " + a.str("i"));
-    fseek(in, 0, SEEK_END);
-    const long long total = ftell(in) / static_cast<long long>(g.frame_bytes());
-    fseek(in, 0, SEEK_SET);
+    FILE* in = nullptr;
+    long long total = 0;
+    if (type == SrcType::Png) {
+        total = pngs.count();
+    } else {
+        in = fopen(a.str("i").c_str(), "rb");
+        if (!in) die("cannot open " + a.str("i"));
+        fseek(in, 0, SEEK_END);
+        total = ftell(in) / static_cast<long long>(g.frame_bytes());
+        fseek(in, 0, SEEK_SET);
+    }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
     DeviceBuffers b = make_buffers(g, delay);
@@ -320,10 +438,18 @@ int encode(const Args& a)
         const int ldx = 3 * slots;
         for (int j = 0; j < slots; ++j) {
             if (j < want) {          // a short last chunk repeats its final picture (test_video.py:104-110)
-                if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) die("short read");
+                if (type == SrcType::Png) {
+                    if (!pngs.read(b.h_yuv, g)) die("short read");
+                } else if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) {
+                    die("short read");
+                }
                 hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
             }
-            abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, b.st), "yuv420_to_x");
+            if (rgb) {
+                abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, nullptr, b.st), "rgb_to_x");
+            } else {
+                abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, b.st), "yuv420_to_x");
+            }
             hip_ok(hipStreamSynchronize(b.st), "sync");      // the staging buffers are reused
         }
         int ec = 0, reset = 0, qp = qp_i;
@@ -360,7 +486,7 @@ int encode(const Args& a)
         idx += want;
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
-    fclose(in);
+    if (in) fclose(in);
     FILE* of = fopen(a.str("o").c_str(), "wb");
     if (!of || fwrite(out.data(), 1, out.size(), of) != out.size()) die("cannot write " + a.str("o"));
     fclose(of);
@@ -382,12 +508,24 @@ int decode(const Args& a)
         f.seekg(0);
         f.read(reinterpret_cast<char*>(bin.data()), static_cast<std::streamsize>(bin.size()));
     }
-    FILE* rec = a.has("o") ? fopen(a.str("o").c_str(), "wb") : nullptr;
-    FILE* ref = a.has("ref") ? fopen(a.str("ref").c_str(), "rb") : nullptr;
-    if (a.has("o") && !rec) die("cannot write " + a.str("o"));
-    if (a.has("ref") && !ref) die("cannot open " + a.str("ref"));
+    const SrcType type = src_type(a.str("src-type", "yuv420"));
+    const bool rgb = type != SrcType::Yuv420, png = type == SrcType::Png;
+    const bool has_rec = a.has("o"), has_ref = a.has("ref");
+    // raw files (yuv420, rgb24), or directories of PNG pictures
+    FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
+    FILE* ref = has_ref && !png ? fopen(a.str("ref").c_str(), "rb") : nullptr;
+    if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
+    if (has_ref && !png && !ref) die("cannot open " + a.str("ref"));
+    PngDir ref_pngs, rec_pngs;
+    if (png && has_ref) ref_pngs = png_dir(a.str("ref"));
+    if (png && has_rec) {
+        std::error_code fe;
+        std::filesystem::create_directories(a.str("o"), fe);
+        if (!std::filesystem::is_directory(a.str("o"), fe)) die("cannot create the directory " + a.str("o"));
+        rec_pngs.dir = a.str("o");      // the writer's names: im00001.png, ... (video_writer.py:9-30)
+    }
     const bool calc_ssim = a.num("calc-ssim", 0) != 0, verbose_json = a.num("verbose-json", 0) != 0;
-    if (calc_ssim && !ref) die("--calc-ssim needs --ref (the source pictures)");
+    if (calc_ssim && !has_ref) die("--calc-ssim needs --ref (the source pictures)");
     const int limit = a.num("n", 1 << 30);
     dcvc::stream::Reader rd(bin.data(), bin.size());
     dcvc::stream::SpsTable sps;
@@ -402,7 +540,7 @@ int decode(const Args& a)
     int decoded = 0;
     const auto t0 = std::chrono::steady_clock::now();
     bool source_ended = false;
-    if (c.ht && c.frames_per_p > 1 && !a.has("n") && !ref) {
+    if (c.ht && c.frames_per_p > 1 && !a.has("n") && !has_ref) {
         fprintf(stderr, "dcvc: warning: %d-picture chunks and neither -n nor --ref: a short last chunk is written with its "
                         "padding pictures (the container does not carry the picture count)\n", c.frames_per_p);
     }
@@ -426,12 +564,16 @@ int decode(const Args& a)
                 die("unsupported picture size in the stream: " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             // MS-SSIM needs both sides of every plane >= 88 (metrics.py asserts): refused before anything is decoded
-            if (calc_ssim && (s->height < 176 || s->width < 176)) {
+            if (calc_ssim && rgb && (s->height < 88 || s->width < 88)) {
+                die("--calc-ssim needs both picture sides >= 88 (MS-SSIM of the R, G and B planes), the stream holds " +
+                    std::to_string(s->width) + "x" + std::to_string(s->height));
+            }
+            if (calc_ssim && !rgb && (s->height < 176 || s->width < 176)) {
                 die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), the "
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
-            g = geometry(s->height, s->width);
+            g = geometry(s->height, s->width, rgb);
             b = make_buffers(g, c.frames_per_p, calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
@@ -460,21 +602,51 @@ int decode(const Args& a)
         for (int j = 0; j < frames && decoded < limit; ++j) {
             const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
             char* y16 = static_cast<char*>(b.y16);
-            abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
+            if (rgb) {
+                // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
+                abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_rgb");
+            } else {
+                abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
+            }
             // the source first: when it ends inside a chunk, the remaining pictures of the chunk are the encoder's
             // padding (repeats of the final picture) and must reach neither the log nor rec.yuv
-            if (ref) {
-                if (fread(src.data(), 1, g.frame_bytes(), ref) != g.frame_bytes()) {
+            if (has_ref) {
+                uint8_t* sp = rgb ? b.h_src : src.data();      // RGB: straight into pinned memory
+                const bool got = png ? ref_pngs.read(sp, g) : fread(sp, 1, g.frame_bytes(), ref) == g.frame_bytes();
+                if (!got) {
                     if (j > 0) { source_ended = true; break; }
                     die("reference file is shorter than the stream");
                 }
             }
-            if (rec) {
+            if (has_rec) {
                 hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
-                if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) die("short write");
+                if (png) {
+                    abi_ok(dcvc_png_write_rgb(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
+                } else if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) {
+                    die("short write");
+                }
             }
-            if (ref) {
+            if (has_ref && rgb) {
+                // get_distortion (png branch): calc_psnr over the 3 H W samples from the device's sums of squares; the
+                // source's planar copy next to the fp16 planes for dcvc_sse and dcvc_msssim
+                // (the copy leaves from pinned memory, and the workspace is the tool's own: nothing in this loop depends on
+                // how the runtime stages a pageable copy or recycles a stream-ordered allocation)
+                const size_t plane = g.y_bytes();
+                hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, b.src8, b.st), "rgb_to_x (planar source)");
+                abi_ok(dcvc_sse_ws(b.src8, DCVC_SAMPLE_U8, y16, DCVC_SAMPLE_F16, 3, g.H, g.W, g.W, static_cast<long long>(plane), b.sse,
+                                   b.sse_ws, b.sse_ws_bytes, b.st), "sse");
+                hip_ok(hipMemcpyAsync(b.h_sse, b.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (calc_ssim) {
+                    abi_ok(dcvc_msssim(b.src8, DCVC_SAMPLE_U8, y16, DCVC_SAMPLE_F16, 3, g.H, g.W, g.W, static_cast<long long>(plane),
+                                       b.ssim, b.st), "msssim (R, G, B)");
+                    hip_ok(hipMemcpyAsync(b.h_ssim, b.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                }
+                hip_ok(hipStreamSynchronize(b.st), "sync");
+                psnr.push_back(psnr_of_sse((b.h_sse[0] + b.h_sse[1]) + b.h_sse[2], 3.0 * static_cast<double>(plane)));
+                if (calc_ssim) ssim.push_back(((0.0 + b.h_ssim[0]) + b.h_ssim[1] + b.h_ssim[2]) / 3);    // calc_msssim_rgb
+            } else if (has_ref) {
                 const size_t ny = g.y_bytes(), nc = ny / 4;
                 if (calc_ssim) {
                     // the source picture next to the decoded fp16 planes; Y as one plane, U + V as two
@@ -504,6 +676,7 @@ int decode(const Args& a)
     if (have_buffers) free_buffers(b);
     if (rec) fclose(rec);
     if (ref) fclose(ref);
+    const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
     if (a.has("json")) {
@@ -515,21 +688,28 @@ int decode(const Args& a)
             double* t = types[i] == 0 ? ip : pp;
             (types[i] == 0 ? ib : pb) += bits[i];
             (types[i] == 0 ? ni : np) += 1;
-            t[0] += psnr[i]; t[1] += psnr_y[i]; t[2] += psnr_u[i]; t[3] += psnr_v[i];
+            t[0] += psnr[i];
+            if (!rgb) { t[1] += psnr_y[i]; t[2] += psnr_u[i]; t[3] += psnr_v[i]; }
         }
         FILE* jf = fopen(a.str("json").c_str(), "w");
         if (!jf) die("cannot write " + a.str("json"));
         const char* sfx[4] = {"", "_y", "_u", "_v"};
         fprintf(jf, "{\n  \"arith_policy\": %d,\n  \"frame_pixel_num\": %.0f,\n  \"i_frame_num\": %d,\n  \"p_frame_num\": %d,\n", dcvc_arith_policy_version(), px, ni, np);
         fprintf(jf, "  \"ave_i_frame_bpp\": %.9g,\n  \"ave_p_frame_bpp\": %.9g,\n", ni ? ib / ni / px : 0.0, np ? pb / np / px : 0.0);
-        for (int k = 0; k < 4; ++k) {
-            fprintf(jf, "  \"ave_i_frame_psnr%s\": %.9g,\n  \"ave_p_frame_psnr%s\": %.9g,\n  \"ave_all_frame_psnr%s\": %.9g,\n", sfx[k],
-                    ni ? ip[k] / ni : 0.0, sfx[k], np ? pp[k] / np : 0.0, sfx[k], (ip[k] + pp[k]) / std::max(1, ni + np));
+        if (rgb) {
+            // 17 digits, as Python's json writes a float (the YUV log keeps its 9)
+            fprintf(jf, "  \"ave_i_frame_psnr\": %s,\n  \"ave_p_frame_psnr\": %s,\n  \"ave_all_frame_psnr\": %s,\n",
+                    jnum(ni ? ip[0] / ni : 0.0).c_str(), jnum(np ? pp[0] / np : 0.0).c_str(), jnum((ip[0] + pp[0]) / std::max(1, ni + np)).c_str());
+        } else {
+            for (int k = 0; k < 4; ++k) {
+                fprintf(jf, "  \"ave_i_frame_psnr%s\": %.9g,\n  \"ave_p_frame_psnr%s\": %.9g,\n  \"ave_all_frame_psnr%s\": %.9g,\n", sfx[k],
+                        ni ? ip[k] / ni : 0.0, sfx[k], np ? pp[k] / np : 0.0, sfx[k], (ip[k] + pp[k]) / std::max(1, ni + np));
+            }
         }
         if (calc_ssim) {
             // common.py:78-114: the i / p / all averages of (6 y + u + v) / 8 and of each plane (0 for an empty class)
             const std::vector<double>* sv[4] = {&ssim, &ssim_y, &ssim_u, &ssim_v};
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < nk; ++k) {
                 double si = 0, sp = 0;
                 for (size_t i = 0; i < types.size(); ++i) (types[i] == 0 ? si : sp) += (*sv[k])[i];
                 fprintf(jf, "  \"ave_i_frame_msssim%s\": %s,\n  \"ave_p_frame_msssim%s\": %s,\n  \"ave_all_frame_msssim%s\": %s,\n",
@@ -547,7 +727,7 @@ int decode(const Args& a)
             fprintf(jf, "  \"frame_bpp\": %s,\n  \"frame_type\": %s,\n", jlist(bpp).c_str(), ft.c_str());
             const std::vector<double>* pv[4] = {&psnr, &psnr_y, &psnr_u, &psnr_v};
             const std::vector<double>* mv[4] = {&ssim, &ssim_y, &ssim_u, &ssim_v};
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < nk; ++k) {
                 fprintf(jf, "  \"frame_psnr%s\": %s,\n", sfx[k], jlist(*pv[k]).c_str());
                 if (calc_ssim) fprintf(jf, "  \"frame_msssim%s\": %s,\n", sfx[k], jlist(*mv[k]).c_str());
             }

@@ -257,6 +257,36 @@ void msssim_validate(const MsssimDesc& d);       // throws std::invalid_argument
 size_t msssim_workspace_bytes(int n_planes, int H, int W);
 void msssim(const MsssimDesc& d, void* workspace, hipStream_t stream);
 
+// ---------------------------------------------------------------- RGB pictures (rgb_io.hip)
+// test_video.py:87-122 + transforms.py:17-27 (BT.709 rgb2ycbcr): u8 RGB read through (row, pixel, channel) strides in bytes
+// (packed HWC: 3W, 3, 1; planar CHW: W, 1, H*W) -> x fp16 at pixel stride ldx (3 channels written; 3 for one picture, 24
+// for the slots of an 8-picture chunk) and / or a planar u8 copy [3][H][W] of the source. Either output may be null.
+struct RgbToXDesc {
+    const uint8_t* src = nullptr;
+    long long row_stride = 0, pixel_stride = 0, channel_stride = 0;
+    int H = 0, W = 0;
+    half_t* x = nullptr; int ldx = 3;
+    uint8_t* planar = nullptr;
+};
+void rgb_to_x(const RgbToXDesc& d, hipStream_t stream);
+// test_video.py:55-64 + transforms.py:53-66 (ycbcr2rgb) and :366-370: x_hat fp16 [rows][row_pixels][3] -> the top-left
+// H x W picture as planar fp16 [3][H][W] in 0..255 (the distortion planes) and / or packed u8 HWC (rint of those, the
+// writer's pixels). Null outputs are skipped.
+void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, hipStream_t stream);
+// metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8 or fp16 samples; src and rec share
+// row_stride and plane_stride, in samples) -> out[plane] (device). Per-workgroup partials in the workspace
+// (sse_workspace_bytes), reduced by a second launch in a fixed order.
+struct SseDesc {
+    const void* src = nullptr; int src_dtype = kSampleU8;
+    const void* rec = nullptr; int rec_dtype = kSampleU8;
+    int n_planes = 0, H = 0, W = 0;
+    int row_stride = 0; long long plane_stride = 0;
+    double* out = nullptr;
+};
+void sse_validate(const SseDesc& d);             // throws std::invalid_argument for a geometry or operand sse() refuses
+size_t sse_workspace_bytes(int n_planes, int H, int W);
+void sse(const SseDesc& d, void* workspace, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -178,6 +178,32 @@ int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H, int W, void* y16,
 int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W,
                 int row_stride, long long plane_stride, double* out, void* stream);
 
+/* RGB pictures on the device (BT.709: Kr, Kg, Kb = 0.2126, 0.7152, 0.0722; transforms.py:10-14). Every step rounds as the
+ * reference's torch op on a GPU does: one fp32 operation each, and a tensor divided by a scalar is a * fp32(1 / b).
+ * test_video.py:87-122 get_src_frame (png branch) + transforms.py:17-27 rgb2ycbcr:
+ *   src: u8 RGB read at src[h * row_stride + w * pixel_stride + c * channel_stride] (bytes; packed HWC: 3W, 3, 1; planar CHW:
+ *   W, 1, H*W) -> x fp16 at pixel stride ldx (3 channels written): x = fp16(fp16(clamp(ycbcr(v / 255), 0, 1)) - 0.5);
+ *   planar: u8 [3][H][W] copy of the source (for the metrics). Either output may be NULL, not both. H, W positive and even;
+ *   the strides must be positive and must not make two samples overlap. */
+int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H, int W,
+                  void* x, int ldx, void* planar, void* stream);
+/* test_video.py:55-64 get_distortion (png branch) + transforms.py:53-66 ycbcr2rgb, and :366-370 (the PNG writer):
+ *   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture; rgb16: fp16 [3][H][W] = clamp(fp16(clamp(rgb, 0, 1)) * 255,
+ *   0, 255), the distortion planes; rgb8: packed u8 [H][W][3] = rint(rgb16) (half to even). NULL = skip. */
+int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8, void* stream);
+/* metrics.py:10-24 calc_psnr's fp64 sum of squared differences, one value per plane: n_planes planes of H x W samples (u8, or
+ * fp16; DCVC_SAMPLE_*), src and rec sharing the geometry (row_stride, plane_stride in samples). out: device memory, n_planes
+ * doubles, written asynchronously on `stream`. Per-workgroup partials reduced in a fixed order: the same bits on every run and
+ * for every n_planes. The workspace is a stream-ordered temporary. */
+int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W, int row_stride,
+             long long plane_stride, double* out, void* stream);
+/* dcvc_sse with a workspace of the caller (device memory of at least dcvc_sse_workspace_bytes(n_planes, H, W) bytes, not
+ * touched by other work until the call's launches have run on `stream`): nothing is allocated, for a caller that measures
+ * picture after picture. The same bits as dcvc_sse. */
+long long dcvc_sse_workspace_bytes(int n_planes, int H, int W);
+int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W, int row_stride,
+                long long plane_stride, double* out, void* workspace, long long workspace_bytes, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

@@ -422,14 +422,50 @@ int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H_, int W_, void* y1
     });
 }
 
+int dcvc_yuv420p16_to_x(const void* y, const void* uv, int H_, int W_, int bit_depth, void* x, int ldx, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::yuv420p16_to_x(static_cast<const uint16_t*>(y), static_cast<const uint16_t*>(uv), H_, W_, bit_depth, H(x), ldx,
+                             S(stream));
+    });
+}
+
+int dcvc_x_to_yuv420p16(const void* x_hat, int row_pixels, int H_, int W_, int bit_depth, void* dist32, void* yuv16, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::x_to_yuv420p16(H(x_hat), row_pixels, H_, W_, bit_depth, static_cast<float*>(dist32), static_cast<uint16_t*>(yuv16),
+                             S(stream));
+    });
+}
+
 int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_,
                 int row_stride, long long plane_stride, double* out, void* stream)
+{
+    return dcvc::guarded([&] {
+        // this entry's contract: u8 and fp16 samples in 0..255 only (dcvc_msssim_range takes the others)
+        for (int t : {src_dtype, rec_dtype}) {
+            if (t != dcvc::kSampleU8 && t != dcvc::kSampleF16) {
+                throw std::invalid_argument("msssim: sample type must be DCVC_SAMPLE_U8 or DCVC_SAMPLE_F16");
+            }
+        }
+        dcvc::MsssimDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        dcvc::msssim_validate(d);      // before the workspace is sized: a bad geometry never reaches the allocator
+        const AsyncBuf ws(dcvc::msssim_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(msssim workspace)");
+        dcvc::msssim(d, ws.p, S(stream));
+    });
+}
+
+int dcvc_msssim_range(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_,
+                      int row_stride, long long plane_stride, double data_range, double* out, void* stream)
 {
     return dcvc::guarded([&] {
         dcvc::MsssimDesc d;
         d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
         d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
-        dcvc::msssim_validate(d);      // before the workspace is sized: a bad geometry never reaches the allocator
+        d.data_range = data_range;
+        dcvc::msssim_validate(d);
         const AsyncBuf ws(dcvc::msssim_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(msssim workspace)");
         dcvc::msssim(d, ws.p, S(stream));
     });

@@ -1,4 +1,4 @@
-// dcvc - standalone DCVC-UF encoder / decoder for 8-bit YUV420 and RGB pictures on an MI355X.
+// dcvc - standalone DCVC-UF encoder / decoder for 8- to 16-bit YUV420 and 8-bit RGB pictures on an MI355X.
 //
 // The codec without the research harness: what test_video.py:166-399 (run_one_point_with_stream)
 // does around the plugin - read YUV420 frames or RGB pictures, code them picture by picture into the reference's
@@ -8,9 +8,15 @@
 // planes and are converted on the device (frame_io.hip, rgb_io.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
-//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] -o out.bin
+//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png]
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16]
+//               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
+//               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
+//               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
+//               stream does not carry it: decode with the depth the source had. PSNR per plane is 10 log10(max_val^2 / mse)
+//               over fp32 distortion planes, summed on the device (dcvc_sse_ws), and --calc-ssim uses data_range = max_val;
+//               the log has the 8-bit YUV420 log's keys.
 //               --src-type (test_video.py's src_type; default yuv420): rgb24 = packed 8-bit RGB pictures back to back in
 //               one file (ffmpeg -pix_fmt rgb24 -f rawvideo), -W / -H required to encode; png = -i (encode), --ref and -o
 //               are directories of im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-45; the writer uses
@@ -179,13 +185,15 @@ Codecs make_codecs(const std::string& intra_path, const std::string& inter_path)
 struct Geometry {
     int H = 0, W = 0, Hp = 0, Wp = 0;      // picture, padded to multiples of 16
     bool rgb = false;                      // 8-bit RGB pictures (--src-type rgb24 / png) instead of YUV420
-    size_t y_bytes() const { return static_cast<size_t>(H) * W; }
-    size_t uv_bytes() const { return static_cast<size_t>(H / 2) * (W / 2) * 2; }
-    // one u8 picture: YUV420 planes, or packed RGB (u8 planes [3][H][W] on the device)
-    size_t frame_bytes() const { return rgb ? 3 * y_bytes() : y_bytes() + uv_bytes(); }
+    int bit_depth = 8;                     // YUV420: 9..16 = uint16 samples (--bit-depth)
+    bool hbd() const { return bit_depth > 8; }
+    size_t y_bytes() const { return static_cast<size_t>(H) * W; }                 // samples of the Y plane
+    size_t uv_bytes() const { return static_cast<size_t>(H / 2) * (W / 2) * 2; } // samples of the U and V planes
+    // one picture: u8 or u16 YUV420 planes, or packed RGB (u8 planes [3][H][W] on the device)
+    size_t frame_bytes() const { return rgb ? 3 * y_bytes() : (y_bytes() + uv_bytes()) * (hbd() ? 2 : 1); }
 };
 
-Geometry geometry(int H, int W, bool rgb = false)
+Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8)
 {
     if (rgb && (H <= 0 || W <= 0 || (H & 1) || (W & 1))) {
         die("picture size must be positive and even (RGB pictures are coded as YUV420 is: even sides), got " +
@@ -195,6 +203,7 @@ Geometry geometry(int H, int W, bool rgb = false)
     Geometry g;
     g.H = H; g.W = W; g.Hp = (H + 15) / 16 * 16; g.Wp = (W + 15) / 16 * 16;
     g.rgb = rgb;
+    g.bit_depth = bit_depth;
     return g;
 }
 
@@ -204,18 +213,18 @@ struct DeviceBuffers {
     uint8_t* yuv8 = nullptr;       // staging for one u8 picture (planes)
     void* x = nullptr;             // fp16 [H][W][3 * frames]
     void* x_hat = nullptr;         // fp16 [frames][Hp][Wp][3]
-    void* y16 = nullptr;           // fp16 planes for PSNR
+    void* y16 = nullptr;           // fp16 planes for PSNR (fp32 at a high bit depth)
     uint8_t* out8 = nullptr;       // u8 planes of a reconstruction
     uint8_t* h_yuv = nullptr;      // pinned
     uint16_t* h_p16 = nullptr;     // pinned fp16 planes
     uint8_t* src8 = nullptr;       // u8 planes of the source picture (--calc-ssim)
     double* ssim = nullptr;        // MS-SSIM of Y, U, V (--calc-ssim)
     double* h_ssim = nullptr;      // pinned
-    double* sse = nullptr;         // sums of squares of R, G, B (RGB --ref)
+    double* sse = nullptr;         // sums of squares of R, G, B or Y, U, V (RGB or high-bit-depth --ref)
     double* h_sse = nullptr;       // pinned
     void* sse_ws = nullptr;        // dcvc_sse_ws's workspace
     long long sse_ws_bytes = 0;
-    uint8_t* h_src = nullptr;      // pinned: the source picture (RGB --ref)
+    uint8_t* h_src = nullptr;      // pinned: the source picture (RGB or high-bit-depth --ref)
     hipStream_t st = nullptr;
 };
 
@@ -235,12 +244,14 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false)
         hip_ok(hipMalloc(&b.ssim, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_ssim), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
     }
-    if (g.rgb) {
+    if (g.rgb || g.hbd()) {
         if (!b.src8) hip_ok(hipMalloc(&b.src8, g.frame_bytes()), "hipMalloc");
         hip_ok(hipMalloc(&b.sse, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_src), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
-        b.sse_ws_bytes = dcvc_sse_workspace_bytes(3, g.H, g.W);
+        // RGB: one call over the three planes; YUV420: Y, then U and V, one after the other on the same workspace
+        b.sse_ws_bytes = g.rgb ? dcvc_sse_workspace_bytes(3, g.H, g.W)
+                               : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.H / 2, g.W / 2));
         hip_ok(hipMalloc(&b.sse_ws, static_cast<size_t>(b.sse_ws_bytes)), "hipMalloc");
     }
     return b;
@@ -278,12 +289,12 @@ double psnr_plane(const uint8_t* src, const uint16_t* rec16, size_t n)
     return p < 99.9 ? p : 99.9;
 }
 
-// metrics.py:10-24 from the fp64 sum of squared differences over n samples
-double psnr_of_sse(double se, double n)
+// metrics.py:10-24 from the fp64 sum of squared differences over n samples, at the data range `peak`
+double psnr_of_sse(double se, double n, double peak = 255.0)
 {
     const double mse = se / n;
     if (std::isnan(mse) || std::isinf(mse)) return -999.9;
-    const double p = mse > 1e-10 ? 10.0 * std::log10(255.0 * 255.0 / mse) : 999.9;
+    const double p = mse > 1e-10 ? 10.0 * std::log10(peak * peak / mse) : 999.9;
     return p < 99.9 ? p : 99.9;
 }
 
@@ -387,11 +398,24 @@ bool is_intra_picture(int idx, int intra_period)
     return intra_period > 1 && idx != 1 && idx % intra_period == 1;
 }
 
+// --bit-depth: 8 (the default, u8 samples) or 9..16 (u16 samples), YUV420 sources only
+int bit_depth_arg(const Args& a, SrcType type)
+{
+    if (!a.has("bit-depth")) return 8;
+    const std::string s = a.str("bit-depth");
+    if (type != SrcType::Yuv420) die("--bit-depth is for --src-type yuv420 only (RGB sources are 8-bit)");
+    char* end = nullptr;
+    const long v = strtol(s.c_str(), &end, 10);
+    if (s.empty() || *end != '\0' || v < 8 || v > 16) die("--bit-depth must be 8 or 9..16, got " + s);
+    return static_cast<int>(v);
+}
+
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
     const SrcType type = src_type(a.str("src-type", "yuv420"));
     const bool rgb = type != SrcType::Yuv420;
+    const int depth = bit_depth_arg(a, type);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     PngDir pngs;
     if (type == SrcType::Png) {
@@ -404,7 +428,7 @@ int encode(const Args& a)
     } else if (rgb && (!a.has("W") || !a.has("H"))) {
         die("--src-type rgb24 needs -W and -H");
     }
-    const Geometry g = geometry(pic_h, pic_w, rgb);
+    const Geometry g = geometry(pic_h, pic_w, rgb, depth);
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     const bool force_intra = !c.has_inter();
     const int intra_period = force_intra ? 1 : a.num("intra-period", -1);
@@ -447,6 +471,9 @@ int encode(const Args& a)
             }
             if (rgb) {
                 abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, nullptr, b.st), "rgb_to_x");
+            } else if (g.hbd()) {
+                abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, static_cast<char*>(b.x) + 6 * j, ldx,
+                                           b.st), "yuv420p16_to_x");
             } else {
                 abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, b.st), "yuv420_to_x");
             }
@@ -510,6 +537,7 @@ int decode(const Args& a)
     }
     const SrcType type = src_type(a.str("src-type", "yuv420"));
     const bool rgb = type != SrcType::Yuv420, png = type == SrcType::Png;
+    const int depth = bit_depth_arg(a, type);
     const bool has_rec = a.has("o"), has_ref = a.has("ref");
     // raw files (yuv420, rgb24), or directories of PNG pictures
     FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
@@ -573,7 +601,7 @@ int decode(const Args& a)
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
-            g = geometry(s->height, s->width, rgb);
+            g = geometry(s->height, s->width, rgb, depth);
             b = make_buffers(g, c.frames_per_p, calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
@@ -605,13 +633,16 @@ int decode(const Args& a)
             if (rgb) {
                 // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
                 abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_rgb");
+            } else if (g.hbd()) {
+                // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
+                abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_yuv420p16");
             } else {
                 abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
             }
             // the source first: when it ends inside a chunk, the remaining pictures of the chunk are the encoder's
             // padding (repeats of the final picture) and must reach neither the log nor rec.yuv
             if (has_ref) {
-                uint8_t* sp = rgb ? b.h_src : src.data();      // RGB: straight into pinned memory
+                uint8_t* sp = rgb || g.hbd() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
                 const bool got = png ? ref_pngs.read(sp, g) : fread(sp, 1, g.frame_bytes(), ref) == g.frame_bytes();
                 if (!got) {
                     if (j > 0) { source_ended = true; break; }
@@ -646,6 +677,34 @@ int decode(const Args& a)
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 psnr.push_back(psnr_of_sse((b.h_sse[0] + b.h_sse[1]) + b.h_sse[2], 3.0 * static_cast<double>(plane)));
                 if (calc_ssim) ssim.push_back(((0.0 + b.h_ssim[0]) + b.h_ssim[1] + b.h_ssim[2]) / 3);    // calc_msssim_rgb
+            } else if (has_ref && g.hbd()) {
+                // as the RGB branch: sums of squares and MS-SSIM on the device from the pinned source, data range max_val
+                const size_t ny = g.y_bytes(), nc = ny / 4;
+                const double peak = static_cast<double>((1 << g.bit_depth) - 1);
+                const uint8_t* src_uv = b.src8 + ny * 2;
+                const char* dist_uv = y16 + ny * 4;
+                hip_ok(hipMemcpyAsync(b.src8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                abi_ok(dcvc_sse_ws(b.src8, DCVC_SAMPLE_U16, y16, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), b.sse,
+                                   b.sse_ws, b.sse_ws_bytes, b.st), "sse (Y)");
+                abi_ok(dcvc_sse_ws(src_uv, DCVC_SAMPLE_U16, dist_uv, DCVC_SAMPLE_F32, 2, g.H / 2, g.W / 2, g.W / 2, static_cast<long long>(nc),
+                                   b.sse + 1, b.sse_ws, b.sse_ws_bytes, b.st), "sse (U, V)");
+                hip_ok(hipMemcpyAsync(b.h_sse, b.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (calc_ssim) {
+                    abi_ok(dcvc_msssim_range(b.src8, DCVC_SAMPLE_U16, y16, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny),
+                                             peak, b.ssim, b.st), "msssim (Y)");
+                    abi_ok(dcvc_msssim_range(src_uv, DCVC_SAMPLE_U16, dist_uv, DCVC_SAMPLE_F32, 2, g.H / 2, g.W / 2, g.W / 2,
+                                             static_cast<long long>(nc), peak, b.ssim + 1, b.st), "msssim (U, V)");
+                    hip_ok(hipMemcpyAsync(b.h_ssim, b.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                }
+                hip_ok(hipStreamSynchronize(b.st), "sync");
+                const double py = psnr_of_sse(b.h_sse[0], static_cast<double>(ny), peak);
+                const double pu = psnr_of_sse(b.h_sse[1], static_cast<double>(nc), peak);
+                const double pv = psnr_of_sse(b.h_sse[2], static_cast<double>(nc), peak);
+                psnr.push_back((6 * py + pu + pv) / 8); psnr_y.push_back(py); psnr_u.push_back(pu); psnr_v.push_back(pv);
+                if (calc_ssim) {
+                    const double sy = b.h_ssim[0], su = b.h_ssim[1], sv = b.h_ssim[2];
+                    ssim.push_back((6 * sy + su + sv) / 8); ssim_y.push_back(sy); ssim_u.push_back(su); ssim_v.push_back(sv);
+                }
             } else if (has_ref) {
                 const size_t ny = g.y_bytes(), nc = ny / 4;
                 if (calc_ssim) {

@@ -4,7 +4,8 @@
 // scipy.signal.fftconvolve over the valid region, K1 = 0.01, K2 = 0.03, data range 255, the mean of the ssim and cs maps
 // per level, a 2 x 2 block mean (ndimage.convolve mode='reflect', then [::2, ::2]: the last row / column replicated when a
 // side is odd) between levels, and prod(cs[0:L-1] ** w[0:L-1]) * ssim[L-1] ** w[L-1] over 5 levels (4 when a side is
-// below 176). Here everything after the load is fp64 too: the Gaussian is applied as two 11-tap passes (it is separable),
+// below 176). A data range other than 255 (high-bit-depth samples) only changes C1 and C2, computed in fp64 from it.
+// Here everything after the load is fp64 too: the Gaussian is applied as two 11-tap passes (it is separable),
 // which agrees with the reference's FFT to a few 1e-15; fp32 would be off by ~1e-6, visible in the log.
 //
 // One launch per pyramid level for all planes (blockIdx.z = plane): a workgroup loads a 16 x 32 output tile plus its
@@ -26,15 +27,15 @@ constexpr int kInH = kTH + kHalo, kInW = kTW + kHalo;
 constexpr int kThreads = 256;
 constexpr int kMaxLevels = 5;
 
-constexpr double kC1 = (0.01 * 255) * (0.01 * 255);
-constexpr double kC2 = (0.03 * 255) * (0.03 * 255);
-
 struct Taps {
     double g[kTaps];
+    double c1, c2;      // (K1 data_range)^2, (K2 data_range)^2
 };
 
 __device__ __forceinline__ double sample(const uint8_t* p, long long i) { return static_cast<double>(p[i]); }
 __device__ __forceinline__ double sample(const half_t* p, long long i) { return static_cast<double>(static_cast<float>(p[i])); }
+__device__ __forceinline__ double sample(const uint16_t* p, long long i) { return static_cast<double>(p[i]); }
+__device__ __forceinline__ double sample(const float* p, long long i) { return static_cast<double>(p[i]); }
 __device__ __forceinline__ double sample(const double* p, long long i) { return p[i]; }
 
 // fixed-order sum of one value per thread over the workgroup (256 threads = 4 waves); the result is valid in thread 0
@@ -141,8 +142,8 @@ __global__ void __launch_bounds__(kThreads) msssim_level_kernel(const TA* __rest
         }
         const double mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
         const double s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu1_mu2;
-        const double num_cs = 2 * s12 + kC2, den_cs = s1 + s2 + kC2;
-        acc.x += ((2 * mu1_mu2 + kC1) * num_cs) / ((mu1_sq + mu2_sq + kC1) * den_cs);
+        const double num_cs = 2 * s12 + taps.c2, den_cs = s1 + s2 + taps.c2;
+        acc.x += ((2 * mu1_mu2 + taps.c1) * num_cs) / ((mu1_sq + mu2_sq + taps.c1) * den_cs);
         acc.y += num_cs / den_cs;
     }
     const double2 s = block_sum(acc, red);
@@ -216,7 +217,7 @@ Pyramid pyramid(int n_planes, int H, int W)
     return py;
 }
 
-Taps gauss_taps()
+Taps gauss_taps(double data_range)
 {
     // fspecial_gauss(11, 1.5) = e(x) e(y) / sum: the outer product of e / sum(e) with itself
     Taps t;
@@ -227,27 +228,34 @@ Taps gauss_taps()
         s += t.g[k];
     }
     for (int k = 0; k < kTaps; ++k) t.g[k] /= s;
+    t.c1 = (0.01 * data_range) * (0.01 * data_range);
+    t.c2 = (0.03 * data_range) * (0.03 * data_range);
     return t;
 }
 
 template <typename TA, typename TB>
 void launch_level(const TA* a, const TB* b, int n_planes, int h, int w, long long row_stride, long long plane_stride,
-                  int tx, int ty, double2* partial, double* next_a, double* next_b, hipStream_t stream)
+                  int tx, int ty, double2* partial, double* next_a, double* next_b, const Taps& taps, hipStream_t stream)
 {
     hipLaunchKernelGGL((msssim_level_kernel<TA, TB>), dim3(tx, ty, n_planes), dim3(kThreads), 0, stream, a, b, h, w, row_stride,
-                       plane_stride, gauss_taps(), partial, next_a, next_b);
+                       plane_stride, taps, partial, next_a, next_b);
     hip_check(hipGetLastError(), "msssim level launch");
 }
 
 template <typename TA>
 void launch_level0(const TA* a, const void* b, int b_dtype, int n_planes, int h, int w, long long row_stride,
-                   long long plane_stride, int tx, int ty, double2* partial, double* next_a, double* next_b, hipStream_t stream)
+                   long long plane_stride, int tx, int ty, double2* partial, double* next_a, double* next_b, const Taps& taps,
+                   hipStream_t stream)
 {
-    if (b_dtype == kSampleU8) {
-        launch_level(a, static_cast<const uint8_t*>(b), n_planes, h, w, row_stride, plane_stride, tx, ty, partial, next_a, next_b, stream);
-    } else {
-        launch_level(a, static_cast<const half_t*>(b), n_planes, h, w, row_stride, plane_stride, tx, ty, partial, next_a, next_b, stream);
+#define LEVEL0(TB) launch_level(a, static_cast<const TB*>(b), n_planes, h, w, row_stride, plane_stride, tx, ty, partial, next_a, \
+                               next_b, taps, stream)
+    switch (b_dtype) {
+    case kSampleU8: LEVEL0(uint8_t); break;
+    case kSampleF16: LEVEL0(half_t); break;
+    case kSampleU16: LEVEL0(uint16_t); break;
+    default: LEVEL0(float); break;
     }
+#undef LEVEL0
 }
 
 }  // namespace
@@ -261,9 +269,10 @@ void msssim_validate(const MsssimDesc& d)
 {
     if (d.H < 88 || d.W < 88) throw std::invalid_argument("msssim: both sides must be at least 88 samples (metrics.py asserts)");
     if (d.n_planes < 1 || d.n_planes > 65535) throw std::invalid_argument("msssim: 1 to 65535 planes");
-    if ((d.src_dtype != kSampleU8 && d.src_dtype != kSampleF16) || (d.rec_dtype != kSampleU8 && d.rec_dtype != kSampleF16)) {
-        throw std::invalid_argument("msssim: sample type must be DCVC_SAMPLE_U8 or DCVC_SAMPLE_F16");
+    if (!known_sample(d.src_dtype) || !known_sample(d.rec_dtype)) {
+        throw std::invalid_argument("msssim: sample type must be DCVC_SAMPLE_U8, _F16, _U16 or _F32");
     }
+    if (!(d.data_range > 0) || std::isinf(d.data_range)) throw std::invalid_argument("msssim: data_range must be positive and finite");
     if (d.row_stride < d.W) throw std::invalid_argument("msssim: row_stride must be >= W");
     if (d.n_planes > 1 && d.plane_stride < static_cast<long long>(d.H - 1) * d.row_stride + d.W) {
         throw std::invalid_argument("msssim: planes overlap (plane_stride < (H - 1) * row_stride + W)");
@@ -278,6 +287,7 @@ void msssim(const MsssimDesc& d, void* workspace, hipStream_t stream)
     const Pyramid py = pyramid(d.n_planes, d.H, d.W);
     double* ws = static_cast<double*>(workspace);
     double2* partial = reinterpret_cast<double2*>(ws);
+    const Taps taps = gauss_taps(d.data_range);
     LevelSums ls;
     ls.levels = py.levels;
     static const double w5[5] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333}, w4[4] = {0.0517, 0.3295, 0.3462, 0.2726};
@@ -288,18 +298,20 @@ void msssim(const MsssimDesc& d, void* workspace, hipStream_t stream)
         double* nb = last ? nullptr : na + d.n_planes * n_next;
         double2* part = partial + py.partial_off[l];
         if (l == 0) {
-            if (d.src_dtype == kSampleU8) {
-                launch_level0(static_cast<const uint8_t*>(d.src), d.rec, d.rec_dtype, d.n_planes, d.H, d.W, d.row_stride,
-                              d.plane_stride, py.tiles_x[0], py.tiles_y[0], part, na, nb, stream);
-            } else {
-                launch_level0(static_cast<const half_t*>(d.src), d.rec, d.rec_dtype, d.n_planes, d.H, d.W, d.row_stride,
-                              d.plane_stride, py.tiles_x[0], py.tiles_y[0], part, na, nb, stream);
+#define LEVEL0(TA) launch_level0(static_cast<const TA*>(d.src), d.rec, d.rec_dtype, d.n_planes, d.H, d.W, d.row_stride, \
+                                 d.plane_stride, py.tiles_x[0], py.tiles_y[0], part, na, nb, taps, stream)
+            switch (d.src_dtype) {
+            case kSampleU8: LEVEL0(uint8_t); break;
+            case kSampleF16: LEVEL0(half_t); break;
+            case kSampleU16: LEVEL0(uint16_t); break;
+            default: LEVEL0(float); break;
             }
+#undef LEVEL0
         } else {
             const long long n = static_cast<long long>(py.h[l]) * py.w[l];
             const double* a = ws + py.plane_off[l];
             launch_level(a, a + d.n_planes * n, d.n_planes, py.h[l], py.w[l], py.w[l], n, py.tiles_x[l], py.tiles_y[l], part, na, nb,
-                         stream);
+                         taps, stream);
         }
         ls.offset[l] = py.partial_off[l];
         ls.tiles[l] = py.tiles_x[l] * py.tiles_y[l];

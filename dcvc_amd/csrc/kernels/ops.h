@@ -241,17 +241,30 @@ void yuv420_to_x(const uint8_t* y, const uint8_t* uv, int H, int W, half_t* x, i
 void x_to_yuv420(const half_t* x, int row_pixels, int H, int W, half_t* y16, half_t* uv16, uint8_t* y8,
                  uint8_t* uv8, hipStream_t stream);
 
+// ---------------------------------------------------------------- high-bit-depth picture I/O (frame_io16.hip)
+// uint16 YUV420 planes of bit depth 9..16 (y [H][W], uv [2][H/2][W/2]) -> x fp16 at pixel stride ldx, as yuv420_to_x:
+// nearest-neighbour chroma, x = fp16(fp16(fp32(v) / fp32(max_val)) - 0.5) with max_val = 2^b - 1 (DCVC-FM's YUVReader).
+void yuv420p16_to_x(const uint16_t* y, const uint16_t* uv, int H, int W, int bit_depth, half_t* x, int ldx, hipStream_t stream);
+// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as fp32 distortion planes [H][W] + [2][H/2][W/2]
+// (clamp(t * max_val, 0, max_val), t as x_to_yuv420 computes it before its * 255) and / or uint16 samples (rint of those,
+// half to even, all three planes: DCVC-FM's YUVWriter). Null outputs are skipped.
+void x_to_yuv420p16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* yuv, hipStream_t stream);
+
 // ---------------------------------------------------------------- MS-SSIM (msssim.hip)
 // metrics.py:27-91 calc_msssim of n_planes pairs of H x W planes (u8 or fp16 samples in 0..255; src and rec share row_stride
 // and plane_stride, in samples), fp64 after the load; out[plane] (device, fp64). The workspace (msssim_workspace_bytes) holds the
 // downsampled planes and the per-workgroup partial sums; 1 + 4 or 5 launches on `stream`.
+// u16 / fp32 samples (high bit depth) in 0..data_range; C1 and C2 follow data_range (fp64), 255 by default.
 constexpr int kSampleU8 = 0, kSampleF16 = 1;        // DCVC_SAMPLE_U8 / DCVC_SAMPLE_F16
+constexpr int kSampleU16 = 3, kSampleF32 = 4;       // DCVC_SAMPLE_U16 / DCVC_SAMPLE_F32 (2 stays unassigned)
+inline bool known_sample(int t) { return t == kSampleU8 || t == kSampleF16 || t == kSampleU16 || t == kSampleF32; }
 struct MsssimDesc {
     const void* src = nullptr; int src_dtype = kSampleU8;
     const void* rec = nullptr; int rec_dtype = kSampleU8;
     int n_planes = 0, H = 0, W = 0;
     int row_stride = 0; long long plane_stride = 0;
     double* out = nullptr;
+    double data_range = 255.0;
 };
 void msssim_validate(const MsssimDesc& d);       // throws std::invalid_argument for a geometry or operand msssim() refuses
 size_t msssim_workspace_bytes(int n_planes, int H, int W);
@@ -273,7 +286,7 @@ void rgb_to_x(const RgbToXDesc& d, hipStream_t stream);
 // H x W picture as planar fp16 [3][H][W] in 0..255 (the distortion planes) and / or packed u8 HWC (rint of those, the
 // writer's pixels). Null outputs are skipped.
 void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, hipStream_t stream);
-// metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8 or fp16 samples; src and rec share
+// metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8, fp16, u16 or fp32 samples; src and rec share
 // row_stride and plane_stride, in samples) -> out[plane] (device). Per-workgroup partials in the workspace
 // (sse_workspace_bytes), reduced by a second launch in a fixed order.
 struct SseDesc {

@@ -192,10 +192,24 @@ __global__ void __launch_bounds__(kThreads) x_to_rgb_kernel(const half_t* __rest
 
 __device__ __forceinline__ double sample(uint8_t v) { return static_cast<double>(v); }
 __device__ __forceinline__ double sample(half_t v) { return static_cast<double>(static_cast<float>(v)); }
+__device__ __forceinline__ double sample(uint16_t v) { return static_cast<double>(v); }
+__device__ __forceinline__ double sample(float v) { return static_cast<double>(v); }
 
-template <typename T> struct Vec8;
-template <> struct Vec8<uint8_t> { typedef uint2 type; };
-template <> struct Vec8<half_t> { typedef half8 type; };
+// 8 samples in one access (u8: 8 B; fp16, u16: 16 B) or two (fp32: 2 x 16 B)
+template <typename T> struct Vec8 { T v[8]; };
+template <typename T> __device__ __forceinline__ Vec8<T> load8(const T* p)
+{
+    Vec8<T> r;
+    if constexpr (sizeof(T) == 1) {
+        *reinterpret_cast<uint2*>(r.v) = *reinterpret_cast<const uint2*>(p);
+    } else if constexpr (sizeof(T) == 2) {
+        *reinterpret_cast<uint4*>(r.v) = *reinterpret_cast<const uint4*>(p);
+    } else {
+        reinterpret_cast<uint4*>(r.v)[0] = reinterpret_cast<const uint4*>(p)[0];
+        reinterpret_cast<uint4*>(r.v)[1] = reinterpret_cast<const uint4*>(p)[1];
+    }
+    return r;
+}
 
 // fixed-order sum over the workgroup (256 threads = 4 waves); valid in thread 0
 __device__ __forceinline__ double block_sum(double v, double* scratch)
@@ -225,13 +239,11 @@ __global__ void __launch_bounds__(kThreads) sse_partial_kernel(const TA* __restr
         const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
         const long long off = base + h * row_stride + w0;
         if constexpr (VEC) {
-            const typename Vec8<TA>::type va = *reinterpret_cast<const typename Vec8<TA>::type*>(a + off);
-            const typename Vec8<TB>::type vb = *reinterpret_cast<const typename Vec8<TB>::type*>(b + off);
-            const TA* ea = reinterpret_cast<const TA*>(&va);
-            const TB* eb = reinterpret_cast<const TB*>(&vb);
+            const Vec8<TA> va = load8(a + off);
+            const Vec8<TB> vb = load8(b + off);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const double d = sample(ea[e]) - sample(eb[e]);
+                const double d = sample(va.v[e]) - sample(vb.v[e]);
                 s += d * d;
             }
         } else {
@@ -274,9 +286,9 @@ int sse_parts(int H, int W)
 template <typename TA, typename TB>
 void launch_sse(const TA* a, const TB* b, const SseDesc& d, double* partial, int parts, hipStream_t stream)
 {
-    // 8-sample pieces: one 8-B (u8) or 16-B (fp16) load per operand
+    // 8-sample pieces: one 8-B (u8) or 16-B (fp16, u16) load, or two 16-B loads (fp32), per operand
     const bool vec = d.W % 8 == 0 && d.row_stride % 8 == 0 && (d.n_planes == 1 || d.plane_stride % 8 == 0) &&
-                     aligned(a, 8 * sizeof(TA)) && aligned(b, 8 * sizeof(TB));
+                     aligned(a, std::min<size_t>(16, 8 * sizeof(TA))) && aligned(b, std::min<size_t>(16, 8 * sizeof(TB)));
     const dim3 grid(static_cast<unsigned>(parts), static_cast<unsigned>(d.n_planes));
     if (vec) {
         hipLaunchKernelGGL((sse_partial_kernel<TA, TB, true>), grid, dim3(kThreads), 0, stream, a, b, d.H, d.W,
@@ -290,8 +302,12 @@ void launch_sse(const TA* a, const TB* b, const SseDesc& d, double* partial, int
 template <typename TA>
 void launch_sse_b(const TA* a, const SseDesc& d, double* partial, int parts, hipStream_t stream)
 {
-    if (d.rec_dtype == kSampleU8) launch_sse(a, static_cast<const uint8_t*>(d.rec), d, partial, parts, stream);
-    else launch_sse(a, static_cast<const half_t*>(d.rec), d, partial, parts, stream);
+    switch (d.rec_dtype) {
+    case kSampleU8: launch_sse(a, static_cast<const uint8_t*>(d.rec), d, partial, parts, stream); break;
+    case kSampleF16: launch_sse(a, static_cast<const half_t*>(d.rec), d, partial, parts, stream); break;
+    case kSampleU16: launch_sse(a, static_cast<const uint16_t*>(d.rec), d, partial, parts, stream); break;
+    default: launch_sse(a, static_cast<const float*>(d.rec), d, partial, parts, stream); break;
+    }
 }
 
 }  // namespace
@@ -359,7 +375,7 @@ void sse_validate(const SseDesc& d)
 {
     if (d.src == nullptr || d.rec == nullptr || d.out == nullptr) throw std::invalid_argument("sse: null operand");
     for (int t : {d.src_dtype, d.rec_dtype}) {
-        if (t != kSampleU8 && t != kSampleF16) throw std::invalid_argument("sse: unknown sample type " + std::to_string(t));
+        if (!known_sample(t)) throw std::invalid_argument("sse: unknown sample type " + std::to_string(t));
     }
     if (d.n_planes <= 0 || d.H <= 0 || d.W <= 0) throw std::invalid_argument("sse: empty geometry");
     if (d.n_planes > 65535) throw std::invalid_argument("sse: at most 65535 planes per call");
@@ -383,8 +399,12 @@ void sse(const SseDesc& d, void* workspace, hipStream_t stream)
     sse_validate(d);
     double* partial = static_cast<double*>(workspace);
     const int parts = sse_parts(d.H, d.W);
-    if (d.src_dtype == kSampleU8) launch_sse_b(static_cast<const uint8_t*>(d.src), d, partial, parts, stream);
-    else launch_sse_b(static_cast<const half_t*>(d.src), d, partial, parts, stream);
+    switch (d.src_dtype) {
+    case kSampleU8: launch_sse_b(static_cast<const uint8_t*>(d.src), d, partial, parts, stream); break;
+    case kSampleF16: launch_sse_b(static_cast<const half_t*>(d.src), d, partial, parts, stream); break;
+    case kSampleU16: launch_sse_b(static_cast<const uint16_t*>(d.src), d, partial, parts, stream); break;
+    default: launch_sse_b(static_cast<const float*>(d.src), d, partial, parts, stream); break;
+    }
     hip_check(hipGetLastError(), "sse launch");
     hipLaunchKernelGGL(sse_final_kernel, dim3(d.n_planes), dim3(kThreads), 0, stream, partial, parts, d.out);
     hip_check(hipGetLastError(), "sse final launch");

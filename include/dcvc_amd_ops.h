@@ -168,15 +168,32 @@ int dcvc_yuv420_to_x(const void* y, const void* uv, int H, int W, void* x, int l
 int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H, int W, void* y16, void* uv16, void* y8,
                      void* uv8, void* stream);
 
-/* sample types of dcvc_msssim */
+/* High-bit-depth YUV420 (yuv420p10le and the like: uint16 samples of bit depth 9..16, max_val = 2^bit_depth - 1; DCVC-FM's
+ * YUVReader / YUVWriter, video_reader.py:130-183, video_writer.py:86-130). H, W positive and even.
+ *   y: u16 [H][W], uv: u16 [2][H/2][W/2] (device) -> x fp16 at pixel stride ldx >= 3 (3 channels written): nearest chroma,
+ *   x = fp16(fp16(fp32(v) / fp32(max_val)) - 0.5), a correctly rounded division. Samples above max_val are not checked. */
+int dcvc_yuv420p16_to_x(const void* y, const void* uv, int H, int W, int bit_depth, void* x, int ldx, void* stream);
+/*   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture; dist32: fp32 [H][W] then [2][H/2][W/2], the distortion
+ *   planes clamp(fp32(t) * max_val, 0, max_val) with t = fp16(x_hat + 0.5) (Y) or fp16(2 x 2 fp32 mean of it) (U, V), as
+ *   dcvc_x_to_yuv420 before its * 255; yuv16: u16 samples in the same layout, rint(dist32) (half to even, all planes).
+ *   NULL = skip. */
+int dcvc_x_to_yuv420p16(const void* x_hat, int row_pixels, int H, int W, int bit_depth, void* dist32, void* yuv16, void* stream);
+
+/* sample types of dcvc_msssim (U8, F16) and of dcvc_sse / dcvc_sse_ws / dcvc_msssim_range (all four; 2 is unassigned) */
 #define DCVC_SAMPLE_U8  0
 #define DCVC_SAMPLE_F16 1
+#define DCVC_SAMPLE_U16 3
+#define DCVC_SAMPLE_F32 4
 /* metrics.py:27-91 calc_msssim on the GPU, one value per plane. n_planes planes of H x W samples (u8, or fp16 holding 0..255);
  * src and rec share the geometry (row_stride, plane_stride in samples). out: device memory, n_planes doubles, written
  * asynchronously on `stream`. fp64 after the load; 5 levels when both sides are >= 176, else 4; H or W < 88 -> error (the
  * reference asserts). A negative cs mean gives NaN, as numpy does. The workspace is a stream-ordered temporary. */
 int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W,
                 int row_stride, long long plane_stride, double* out, void* stream);
+/* dcvc_msssim for samples in 0..data_range (any DCVC_SAMPLE_* type): C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2 in
+ * fp64 (metrics.py calc_msssim's data_range argument). data_range = 255 gives dcvc_msssim's bits; data_range <= 0 -> error. */
+int dcvc_msssim_range(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W,
+                      int row_stride, long long plane_stride, double data_range, double* out, void* stream);
 
 /* RGB pictures on the device (BT.709: Kr, Kg, Kb = 0.2126, 0.7152, 0.0722; transforms.py:10-14). Every step rounds as the
  * reference's torch op on a GPU does: one fp32 operation each, and a tensor divided by a scalar is a * fp32(1 / b).
@@ -191,8 +208,8 @@ int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride,
  *   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture; rgb16: fp16 [3][H][W] = clamp(fp16(clamp(rgb, 0, 1)) * 255,
  *   0, 255), the distortion planes; rgb8: packed u8 [H][W][3] = rint(rgb16) (half to even). NULL = skip. */
 int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8, void* stream);
-/* metrics.py:10-24 calc_psnr's fp64 sum of squared differences, one value per plane: n_planes planes of H x W samples (u8, or
- * fp16; DCVC_SAMPLE_*), src and rec sharing the geometry (row_stride, plane_stride in samples). out: device memory, n_planes
+/* metrics.py:10-24 calc_psnr's fp64 sum of squared differences, one value per plane: n_planes planes of H x W samples (u8,
+ * fp16, u16 or fp32; DCVC_SAMPLE_*), src and rec sharing the geometry (row_stride, plane_stride in samples). out: device memory, n_planes
  * doubles, written asynchronously on `stream`. Per-workgroup partials reduced in a fixed order: the same bits on every run and
  * for every n_planes. The workspace is a stream-ordered temporary. */
 int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W, int row_stride,

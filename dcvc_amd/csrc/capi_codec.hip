@@ -43,6 +43,12 @@ void check_padding16(int height, int width, int padding_b, int padding_r)
     }
 }
 
+void check_batch(const dcvc_dmci* c, int n)
+{
+    if (c == nullptr) throw std::invalid_argument("null codec");
+    if (n < 1 || n > dcvc::DmciCodec::kMaxBatch) throw std::invalid_argument("batch size must be in [1, 16]");
+}
+
 }  // namespace
 
 extern "C" {
@@ -94,6 +100,51 @@ int dcvc_dmci_decompress(dcvc_dmci* c, const uint8_t* bit_stream, size_t nbytes,
     return dcvc::guarded([&] {
         c->codec.decompress(bit_stream, nbytes, qp, height, width, ec_parallel,
                             static_cast<dcvc::half_t*>(x_hat), static_cast<hipStream_t>(stream));
+    });
+}
+
+int dcvc_dmci_compress_batch(dcvc_dmci* c, int n, const void* x, int height, int width, int qp, int padding_b,
+                             int padding_r, void* x_hat, int* ec_parallel_out, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_batch(c, n);
+        if (x == nullptr || x_hat == nullptr || ec_parallel_out == nullptr) {
+            throw std::invalid_argument("compress_batch: null picture, reconstruction or ec_parallel pointer");
+        }
+        check_padding16(height, width, padding_b, padding_r);
+        c->codec.compress_batch(n, static_cast<const dcvc::half_t*>(x), height, width, qp, static_cast<dcvc::half_t*>(x_hat),
+                                ec_parallel_out, static_cast<hipStream_t>(stream));
+    });
+}
+
+int64_t dcvc_dmci_get_stream_at(dcvc_dmci* c, int i, uint8_t* dst, size_t cap)
+{
+    int64_t n = -1;
+    const int rc = dcvc::guarded([&] {
+        if (c == nullptr) throw std::invalid_argument("get_stream_at: null codec");
+        const auto& s = c->codec.stream_at(i);
+        if (dst != nullptr) std::memcpy(dst, s.data(), s.size() < cap ? s.size() : cap);
+        n = static_cast<int64_t>(s.size());
+    });
+    return rc < 0 ? rc : n;
+}
+
+int dcvc_dmci_decompress_batch(dcvc_dmci* c, int n, const uint8_t* const* streams, const size_t* nbytes,
+                               const int* ec_parallel, int qp, int height, int width, void* x_hat, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_batch(c, n);
+        if (streams == nullptr || nbytes == nullptr || ec_parallel == nullptr || x_hat == nullptr) {
+            throw std::invalid_argument("decompress_batch: null stream list, sizes, ec_parallel or reconstruction pointer");
+        }
+        for (int i = 0; i < n; ++i) {
+            if (streams[i] == nullptr && nbytes[i] > 0) throw std::invalid_argument("decompress_batch: null stream");
+            if (ec_parallel[i] < 1 || ec_parallel[i] > dcvc::kMaxEcParallel) {
+                throw std::invalid_argument("decompress_batch: ec_parallel must be in [1, 8]");
+            }
+        }
+        c->codec.decompress_batch(n, streams, nbytes, ec_parallel, qp, height, width, static_cast<dcvc::half_t*>(x_hat),
+                                  static_cast<hipStream_t>(stream));
     });
 }
 

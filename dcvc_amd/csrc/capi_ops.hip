@@ -1,5 +1,6 @@
 // C ABI of the individual kernels (include/dcvc_amd_ops.h).
 #include "capi_common.h"
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -74,6 +75,98 @@ int dcvc_dwconv3x3(const void* x, int ldx, const void* w, void* y, int ldy, int 
                    void* stream)
 {
     return dcvc::guarded([&] { dcvc::dwconv3x3(H(x), ldx, H(w), H(y), ldy, Hh, W, C, S(stream)); });
+}
+
+// ---- batched forms (intra batches): argument checks before any launch
+namespace {
+
+void check_b(int n, std::initializer_list<const void*> ptrs, std::initializer_list<int> dims, const char* what)
+{
+    if (n < 1 || n > 16) throw std::invalid_argument(std::string(what) + ": n must be in [1, 16]");
+    for (const void* p : ptrs) {
+        if (p == nullptr) throw std::invalid_argument(std::string(what) + ": null pointer");
+    }
+    for (int d : dims) {
+        if (d <= 0) throw std::invalid_argument(std::string(what) + ": sizes must be positive");
+    }
+}
+
+}  // namespace
+
+int dcvc_dwconv3x3_b(const void* x, int ldx, const void* w, void* y, int ldy, int Hh, int W, int C, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {x, w, y}, {Hh, W, C}, "dwconv3x3_b");
+        if (ldx < C || ldy < C) throw std::invalid_argument("dwconv3x3_b: leading dimensions below C");
+        dcvc::dwconv3x3_b(H(x), ldx, H(w), H(y), ldy, Hh, W, C, n, S(stream));
+    });
+}
+
+int dcvc_conv_kxk_b(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int in_h, int in_w, int cin,
+                    int cout, int ksize, int stride, int pad, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {x, w, y}, {in_h, in_w, cin, cout, ksize, stride}, "conv_kxk_b");
+        if (pad < 0 || in_h + 2 * pad < ksize || in_w + 2 * pad < ksize) throw std::invalid_argument("conv_kxk_b: bad padding");
+        dcvc::ConvKxKDesc d;
+        d.x = H(x); d.ldx = ldx; d.w = H(w); d.bias = H(bias); d.zeros = zero_page();
+        d.y = H(y); d.ldy = ldy; d.in_h = in_h; d.in_w = in_w; d.cin = cin; d.cout = cout;
+        d.ksize = ksize; d.stride = stride; d.pad = pad; d.n = n;
+        dcvc::conv_kxk(d, S(stream));
+    });
+}
+
+int dcvc_tconv2x2_b(const void* x, int ldx, const void* w, void* y, int ldy, int in_h, int in_w, int cin, int cout, int n,
+                    void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {x, w, y}, {in_h, in_w, cin, cout}, "tconv2x2_b");
+        dcvc::TConv2x2Desc d;
+        d.x = H(x); d.ldx = ldx; d.w = H(w); d.y = H(y); d.ldy = ldy;
+        d.in_h = in_h; d.in_w = in_w; d.cin = cin; d.cout = cout; d.n = n;
+        dcvc::tconv2x2(d, S(stream));
+    });
+}
+
+int dcvc_pad_unshuffle8_b(const void* x, int Hh, int W, int C3, void* out, int H8, int W8, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {x, out}, {Hh, W, C3, H8, W8}, "pad_unshuffle8_b");
+        if (H8 * 8 < Hh || W8 * 8 < W) throw std::invalid_argument("pad_unshuffle8_b: output smaller than the picture");
+        dcvc::pad_unshuffle8_b(H(x), Hh, W, C3, H(out), H8, W8, n, S(stream));
+    });
+}
+
+int dcvc_shuffle8_b(const void* in, int ldin, int H8, int W8, int C3, int clamp, void* out, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {in, out}, {H8, W8, C3}, "shuffle8_b");
+        if (ldin < C3 * 64) throw std::invalid_argument("shuffle8_b: ldin below 64 * C3");
+        dcvc::shuffle8_b(H(in), ldin, H8, W8, C3, clamp != 0, H(out), n, S(stream));
+    });
+}
+
+int dcvc_replicate_pad_b(const void* in, int ldin, int Hh, int W, int C, int pad_b, int pad_r, void* out, int ldout, int n,
+                         void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {in, out}, {Hh, W, C}, "replicate_pad_b");
+        if (pad_b < 0 || pad_r < 0 || C % 8 != 0 || ldin < C || ldout < C) {
+            throw std::invalid_argument("replicate_pad_b: negative padding, C not a multiple of 8 or ld below C");
+        }
+        dcvc::replicate_pad_b(H(in), ldin, Hh, W, C, pad_b, pad_r, H(out), ldout, n, S(stream));
+    });
+}
+
+int dcvc_crop_b(const void* in, int ldin, int Hin, int Win, void* out, int ldout, int Hh, int W, int C, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {in, out}, {Hin, Win, Hh, W, C}, "crop_b");
+        if (Hh > Hin || W > Win || C % 8 != 0 || ldin < C || ldout < C) {
+            throw std::invalid_argument("crop_b: crop larger than the input, C not a multiple of 8 or ld below C");
+        }
+        dcvc::crop_b(H(in), ldin, Hin, Win, H(out), ldout, Hh, W, C, n, S(stream));
+    });
 }
 
 int dcvc_pad_unshuffle8(const void* x, int Hh, int W, int C3, void* out, int H8, int W8, void* stream)

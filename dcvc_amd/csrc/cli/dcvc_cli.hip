@@ -31,6 +31,10 @@
 //               --calc-ssim 1: MS-SSIM of every picture on the GPU (dcvc_msssim; test_video.py:45-51 --calc_ssim), logged as
 //               ave_{i,p,all}_frame_msssim{,_y,_u,_v}; needs --ref and both sides >= 176 (chroma planes >= 88).
 //               --verbose-json 1: per-picture lists as the reference's --verbose_json writes them (common.py:90-98).
+//               --batch N (1..16, default 1): intra pictures N per codec call (dcvc_dmci_compress_batch / _decompress_batch,
+//               DESIGN.md 14). Encode: all-intra runs only (no --inter, or --intra-period 1); the file is byte-identical to
+//               --batch 1, a short last batch included. Decode: up to N consecutive I units of one size and one qp per call;
+//               outputs and log as with --batch 1 (test_time aside).
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -410,9 +414,24 @@ int bit_depth_arg(const Args& a, SrcType type)
     return static_cast<int>(v);
 }
 
+// --batch: 1 (the default) .. 16 pictures per intra call; refused before anything touches the device
+int batch_arg(const Args& a)
+{
+    if (!a.has("batch")) return 1;
+    const std::string s = a.str("batch");
+    char* end = nullptr;
+    const long v = strtol(s.c_str(), &end, 10);
+    if (s.empty() || *end != '\0' || v < 1 || v > 16) die("--batch must be in 1..16, got " + s);
+    return static_cast<int>(v);
+}
+
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
+    const int batch = batch_arg(a);
+    if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
+        die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
+    }
     const SrcType type = src_type(a.str("src-type", "yuv420"));
     const bool rgb = type != SrcType::Yuv420;
     const int depth = bit_depth_arg(a, type);
@@ -449,35 +468,70 @@ int encode(const Args& a)
     }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
-    DeviceBuffers b = make_buffers(g, delay);
+    DeviceBuffers b = make_buffers(g, std::max(delay, batch));
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
     const auto t0 = std::chrono::steady_clock::now();
+    // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx)
+    auto load_picture = [&]() {
+        if (type == SrcType::Png) {
+            if (!pngs.read(b.h_yuv, g)) die("short read");
+        } else if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) {
+            die("short read");
+        }
+        hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+    };
+    auto convert = [&](char* dst, int ldx) {
+        if (rgb) {
+            abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, b.st), "rgb_to_x");
+        } else if (g.hbd()) {
+            abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, dst, ldx, b.st), "yuv420p16_to_x");
+        } else {
+            abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, dst, ldx, b.st), "yuv420_to_x");
+        }
+        hip_ok(hipStreamSynchronize(b.st), "sync");      // the staging buffers are reused
+    };
+    auto put_unit = [&](bool intra, int qp, int ec, int reset, const std::vector<uint8_t>& pl) {
+        bool is_new = false;
+        const int sps_id = sps.id_for(g.H, g.W, is_new);
+        if (is_new) dcvc::stream::put_sps(out, sps_id, g.H, g.W);
+        dcvc::stream::put_ip(out, intra, sps_id, qp, ec, reset != 0, pl.data(), pl.size());
+    };
     int idx = 0;
     while (idx < frame_num) {
         const bool intra = is_intra_picture(idx, intra_period);
+        if (intra && batch > 1) {
+            // up to `batch` intra pictures in one call, each in its own slot [H][W][3]; the units go out in picture order
+            const int nb = std::min(batch, frame_num - idx);
+            const size_t slot = static_cast<size_t>(g.H) * g.W * 3 * 2, slot_hat = static_cast<size_t>(g.Hp) * g.Wp * 3 * 2;
+            for (int j = 0; j < nb; ++j) {
+                char* dst = static_cast<char*>(b.x) + slot * j;
+                load_picture();
+                convert(dst, 3);
+            }
+            int ecs[16];
+            abi_ok(dcvc_dmci_compress_batch(c.intra, nb, b.x, g.H, g.W, qp_i, pad_b, pad_r, b.x_hat, ecs, b.st), "intra compress");
+            for (int j = 0; j < nb; ++j) {
+                const long long nbytes = dcvc_dmci_get_stream_at(c.intra, j, nullptr, 0);
+                abi_ok(nbytes, "get_stream_at");
+                payload.resize(static_cast<size_t>(nbytes));
+                abi_ok(dcvc_dmci_get_stream_at(c.intra, j, payload.data(), payload.size()), "get_stream_at");
+                const char* xh = static_cast<const char*>(b.x_hat) + slot_hat * j;
+                if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
+                put_unit(true, qp_i, ecs[j], 0, payload);
+            }
+            idx += nb;
+            continue;
+        }
         const int want = intra ? 1 : std::min(delay, frame_num - idx);
         const int slots = intra ? 1 : delay;
         const int ldx = 3 * slots;
         for (int j = 0; j < slots; ++j) {
-            if (j < want) {          // a short last chunk repeats its final picture (test_video.py:104-110)
-                if (type == SrcType::Png) {
-                    if (!pngs.read(b.h_yuv, g)) die("short read");
-                } else if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) {
-                    die("short read");
-                }
-                hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
-            }
-            if (rgb) {
-                abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, nullptr, b.st), "rgb_to_x");
-            } else if (g.hbd()) {
-                abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, static_cast<char*>(b.x) + 6 * j, ldx,
-                                           b.st), "yuv420p16_to_x");
-            } else {
-                abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, static_cast<char*>(b.x) + 6 * j, ldx, b.st), "yuv420_to_x");
-            }
-            hip_ok(hipStreamSynchronize(b.st), "sync");      // the staging buffers are reused
+            char* dst = static_cast<char*>(b.x) + 6 * j;
+            if (j < want) load_picture();      // a short last chunk repeats its final picture (test_video.py:104-110)
+            convert(dst, ldx);
         }
         int ec = 0, reset = 0, qp = qp_i;
         long long nbytes = 0;
@@ -506,10 +560,7 @@ int encode(const Args& a)
                 abi_ok(dcvc_dmcht_get_stream(c.ht, payload.data(), payload.size()), "get_stream");
             }
         }
-        bool is_new = false;
-        const int sps_id = sps.id_for(g.H, g.W, is_new);
-        if (is_new) dcvc::stream::put_sps(out, sps_id, g.H, g.W);
-        dcvc::stream::put_ip(out, intra, sps_id, qp, ec, reset != 0, payload.data(), payload.size());
+        put_unit(intra, qp, ec, reset, payload);
         idx += want;
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
@@ -526,6 +577,7 @@ int encode(const Args& a)
 // ------------------------------------------------------------------------------------ decode
 int decode(const Args& a)
 {
+    const int batch = batch_arg(a);
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     std::vector<uint8_t> bin;
     {
@@ -602,7 +654,7 @@ int decode(const Args& a)
             }
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth);
-            b = make_buffers(g, c.frames_per_p, calc_ssim);
+            b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
@@ -613,7 +665,45 @@ int decode(const Args& a)
         rd.ip_remaining(qp, ec, reset, payload, n);
         const bool intra = nal == dcvc::stream::kIntra;
         int frames = 1;
-        if (intra) {
+        // bits of each picture's unit (an 8-picture chunk: all on its first picture); a new parameter set counts with the next unit
+        std::vector<double> unit_bits{8.0 * (rd.position() - unit_start) + pending_sps_bits};
+        pending_sps_bits = 0;
+        if (intra && batch > 1) {
+            // --batch: this and up to batch - 1 following I units of the same size and qp in one call (a parameter set, a P unit,
+            // another size or qp ends the group)
+            std::vector<const uint8_t*> pls{payload};
+            std::vector<size_t> sizes{n};
+            std::vector<int> ecs{ec};
+            while (static_cast<int>(pls.size()) < batch && decoded + static_cast<int>(pls.size()) < limit && !rd.at_end()) {
+                dcvc::stream::Reader peek = rd;
+                const size_t start = peek.position();
+                int nal2 = 0, sid2 = 0, qp2 = 0, ec2 = 0;
+                bool reset2 = false;
+                const uint8_t* pl2 = nullptr;
+                size_t n2 = 0;
+                try {
+                    peek.header(nal2, sid2);
+                    if (nal2 != dcvc::stream::kIntra) break;
+                    const dcvc::stream::SpsTable::Sps* s2 = sps.find(sid2);
+                    if (s2 == nullptr || s2->height != g.H || s2->width != g.W) break;
+                    peek.ip_remaining(qp2, ec2, reset2, pl2, n2);
+                } catch (const std::exception&) {
+                    break;              // a malformed unit: the single path below reports it
+                }
+                if (qp2 != qp) break;
+                rd = peek;
+                pls.push_back(pl2); sizes.push_back(n2); ecs.push_back(ec2);
+                unit_bits.push_back(8.0 * (rd.position() - start));
+            }
+            frames = static_cast<int>(pls.size());
+            abi_ok(dcvc_dmci_decompress_batch(c.intra, frames, pls.data(), sizes.data(), ecs.data(), qp, g.H, g.W, b.x_hat, b.st),
+                   "intra decompress");
+            for (int j = 0; j < frames; ++j) {
+                const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
+                if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, xh, g.Hp, g.Wp, 0, b.st), "add_ref");
+                if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, xh, g.Hp, g.Wp, 0, b.st), "add_ref");
+            }
+        } else if (intra) {
             abi_ok(dcvc_dmci_decompress(c.intra, payload, n, qp, g.H, g.W, ec, b.x_hat, b.st), "intra decompress");
             if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 0, b.st), "add_ref");
             if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 0, b.st), "add_ref");
@@ -625,8 +715,6 @@ int decode(const Args& a)
         } else {
             die("the stream holds P pictures but no inter model was given");
         }
-        const double unit_bits = 8.0 * (rd.position() - unit_start) + pending_sps_bits;
-        pending_sps_bits = 0;
         for (int j = 0; j < frames && decoded < limit; ++j) {
             const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
             char* y16 = static_cast<char*>(b.y16);
@@ -645,7 +733,7 @@ int decode(const Args& a)
                 uint8_t* sp = rgb || g.hbd() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
                 const bool got = png ? ref_pngs.read(sp, g) : fread(sp, 1, g.frame_bytes(), ref) == g.frame_bytes();
                 if (!got) {
-                    if (j > 0) { source_ended = true; break; }
+                    if (j > 0 && !intra) { source_ended = true; break; }      // (an I batch: as its pictures one by one)
                     die("reference file is shorter than the stream");
                 }
             }
@@ -728,7 +816,7 @@ int decode(const Args& a)
                 }
             }
             types.push_back(intra ? 0 : 1);
-            bits.push_back(j == 0 ? unit_bits : 0.0);
+            bits.push_back(j < static_cast<int>(unit_bits.size()) ? unit_bits[static_cast<size_t>(j)] : 0.0);
             ++decoded;
         }
     }

@@ -26,11 +26,24 @@ public:
     void decompress(const uint8_t* bits, size_t nbytes, int qp, int height, int width, int ec_parallel,
                     half_t* x_hat, hipStream_t stream);
 
+    // Not part of the reference surface: n (1..kMaxBatch) pictures of one size and one qp per call, every launch shared by
+    // all of them. x: n x [H][W][3] back to back; x_hat: n x [H16][W16][3]. Each picture's stream and
+    // ec_parallel are exactly what compress() gives for it (stream_at(i), ec_parallel_out[i]), and decompress_batch()
+    // reconstructs exactly what decompress() does.
+    static constexpr int kMaxBatch = 16;
+    void compress_batch(int n, const half_t* x, int height, int width, int qp, half_t* x_hat, int* ec_parallel_out,
+                        hipStream_t stream);
+    void decompress_batch(int n, const uint8_t* const* bits, const size_t* nbytes, const int* ec_parallel, int qp,
+                          int height, int width, half_t* x_hat, hipStream_t stream);
+    int last_batch() const { return m_last_n; }               // pictures of the last compress / compress_batch call
+    const std::vector<uint8_t>& stream_at(int i) const;        // stream i of that call
+
     // test hook: copies an internal tensor of the last call to the host. Returns the byte size.
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
 private:
     struct Geometry {
+        int N = 0;                  // pictures back to back in every buffer (a batch)
         int H = 0, W = 0;           // picture
         int H8 = 0, W8 = 0, H16 = 0, W16 = 0, H16p = 0, W16p = 0, H32 = 0, W32 = 0, H64 = 0, W64 = 0;
         int P8() const { return H8 * W8; }
@@ -41,7 +54,10 @@ private:
         bool padded() const { return H16p != H16 || W16p != W16; }
     };
 
-    void prepare(int height, int width);
+    void prepare(int height, int width, int n);
+    void compress_impl(int n, const half_t* x, int height, int width, int qp, half_t* x_hat, hipStream_t user);
+    void decompress_impl(int n, const uint8_t* const* bits, const size_t* nbytes, const int* ec_parallel, int qp,
+                         int height, int width, half_t* x_hat, hipStream_t user);
     void select_qp(int qp, hipStream_t st);
     // network stages
     void run_encoder(hipStream_t st);                       // U -> Y
@@ -98,6 +114,12 @@ private:
     Pinned<uint8_t> m_h_idx;
     Pinned<int8_t> m_h_dec;
     int m_ec_parallel = 1;
+    // batches: the streams and ec_parallel of pictures 1.. (picture 0's stream stays in m_enc, as a single call leaves it),
+    // and the rANS decoder state of every picture between the autoregressive steps
+    int m_last_n = 0;
+    std::vector<std::vector<uint8_t>> m_streams;
+    std::vector<int> m_ec_parallels;
+    std::vector<RansDecoder::StreamState> m_dec_states;
 };
 
 }  // namespace dcvc

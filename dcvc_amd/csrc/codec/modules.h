@@ -75,6 +75,9 @@ struct Scratch {
     // which of t1 / t2 holds dc.0's output: a block launch with its depthwise conv inside reads it from one plane and leaves the
     // NEXT block's in the other (DcbW::forward flips this with every such hand-over and resets it whenever a block computes its own dc.0)
     mutable int hand = 0;
+    // pictures back to back in every activation the modules see ([batch][H][W][ld], H x W per picture) and in these planes:
+    // launches cover all of them, launch choices follow ONE picture's geometry (the intra batches)
+    int batch = 1;
 };
 
 // ---------------------------------------------------------------- weights
@@ -158,7 +161,7 @@ struct SubpelW {
     size_t tmp_elems(int H, int W) const { return b ? static_cast<size_t>(H) * W * 4 * cout : 0; }
     // y: [2H][2W][cout]
     void forward(View x, View y, int H, int W, hipStream_t st, half_t* tmp = nullptr,
-                 const half_t* zeros = nullptr) const;
+                 const half_t* zeros = nullptr, int n = 1) const;      // n: pictures back to back (no bias only)
 };
 
 // layers.py:162-173: SubpelConv2x + DepthConvBlock

@@ -215,14 +215,15 @@ bool DcbW::feeds(const DcbW& next) const
 void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t st, bool shortcut,
                    const half_t* q_fused, const half_t* q_after, View alt, const DcbW* next, bool dc0_done, const FinCall* fin) const
 {
-    const int P = H * W;
+    const int P = H * W;                 // one picture: what the launch choices below follow
+    const int NP = P * s.batch;          // the pixels of the launches
     if (fin != nullptr && (next != nullptr || fin->w == nullptr || fin->w->conv.cin != c)) {
         throw std::invalid_argument("DepthConvBlock: a closing conv sits behind the LAST block of a chain and reads its output");
     }
     if ((next != nullptr && !feeds(*next)) || (dc0_done && (!core_fused() || has_adaptor))) {
         throw std::invalid_argument("DepthConvBlock: dc.0 hand-over between blocks that do not support it");
     }
-    if (static_cast<size_t>(P) * cdc > s.elems || static_cast<size_t>(P) * cffn > s.elems) {
+    if (static_cast<size_t>(NP) * cdc > s.elems || static_cast<size_t>(NP) * cffn > s.elems) {
         throw std::runtime_error("DepthConvBlock: scratch planes too small");
     }
     View in = x;
@@ -240,19 +241,19 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
     if (has_adaptor) {
         // the one-launch block (dcb_tail with dc.0 inside) reads its input's neighbours, so the adaptor output must not be
         // the block output: without a spare buffer from the caller it goes to the third scratch plane, which that launch leaves alone
-        if (alt.p == nullptr && tail && static_cast<size_t>(P) * c <= s.elems) alt = View(s.t3, c, c);
+        if (alt.p == nullptr && tail && static_cast<size_t>(NP) * c <= s.elems) alt = View(s.t3, c, c);
         const View a = (alt.p != nullptr && alt.p != y.p) ? View(alt.p, alt.ld, c) : y;
         if (packed_adaptor != nullptr && nsplit() && a.p != x.p) {
             // adaptor + dc.0 in ONE launch (kernels/dcb_pair8_kernel.h): the adaptor output stays in LDS as dc.0's operand
             DcbPairDesc d;
             d.x = x.p; d.ldx = x.ld; d.wa = packed_adaptor; d.ba = adaptor.b; d.w1 = packed_dc0; d.b1 = dc0.b;
-            d.y = a.p; d.ldy = a.ld; d.t1 = p1; d.ldt1 = cdc; d.pixels = P; d.cin = adaptor.cin; d.c = c; d.ci = cdc;
+            d.y = a.p; d.ldy = a.ld; d.t1 = p1; d.ldt1 = cdc; d.pixels = NP; d.cin = adaptor.cin; d.c = c; d.ci = cdc;
             dcb_pair(d, st);
             dc0_done = true;
         } else {
             Conv1x1Desc d;
             d.x = x.p; d.ldx = x.ld; d.w = adaptor.w; d.bias = adaptor.b;
-            d.y = a.p; d.ldy = a.ld; d.pixels = P; d.cin = adaptor.cin; d.cout = adaptor.cout;
+            d.y = a.p; d.ldy = a.ld; d.pixels = NP; d.cin = adaptor.cin; d.cout = adaptor.cout;
             conv1x1(d, st);
         }
         in = a;
@@ -263,7 +264,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
     if (!tail_dc0 && !dc0_done) {   // dc.0 + WSiLU
         Conv1x1Desc d;
         d.x = in.p; d.ldx = in.ld; d.w = dc0.w; d.bias = dc0.b; d.wsilu = true;
-        d.y = p1; d.ldy = cdc; d.pixels = P; d.cin = c; d.cout = cdc;
+        d.y = p1; d.ldy = cdc; d.pixels = NP; d.cin = c; d.cout = cdc;
         conv1x1(d, st);
     }
     if (tail) {
@@ -273,16 +274,18 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         d.t = p1; d.ldt = cdc; d.dw = dw; d.x = in.p; d.ldx = in.ld;
         d.w3 = dc3.w; d.b3 = dc3.b; d.w0 = ffn0.w; d.b0 = ffn0.b; d.w2 = ffn2.w; d.b2 = ffn2.b;
         d.q = q_fused; d.q2 = q_after; d.y = y.p; d.ldy = y.ld;
-        d.H = H; d.W = W; d.c = c; d.cdc = cdc; d.cffn = cffn; d.shortcut = shortcut;
+        d.H = H; d.W = W; d.c = c; d.cdc = cdc; d.cffn = cffn; d.shortcut = shortcut; d.n = s.batch;
         dcb_tail(d, st);
-        if (fin != nullptr) run_fin(*fin, y, P, st);
+        if (fin != nullptr) run_fin(*fin, y, NP, st);
         return;
     }
     // the narrow blocks take their depthwise conv into the block launch (dcb_nsplit8_kernel.h, DW): dc.0's output is read from one
     // scratch plane, the next block's written to the other
-    // (the kernel addresses dc.0's output with 32-bit byte offsets from its base)
-    const bool dw_inside = nsplit() && dcb_nsplit_dw_supported(c, cdc, P) && static_cast<long long>(P) * cdc * 2 < (1LL << 31);
-    if (!dw_inside) dwconv3x3(p1, cdc, dw, p2, cdc, H, W, cdc, st);
+    // (the kernel addresses dc.0's output with 32-bit byte offsets from its base). A batch takes the unfused pair, which
+    // computes the same bits: the kernel's halo rows know one picture
+    const bool dw_inside = s.batch == 1 && nsplit() && dcb_nsplit_dw_supported(c, cdc, P) &&
+                           static_cast<long long>(P) * cdc * 2 < (1LL << 31);
+    if (!dw_inside) dwconv3x3_b(p1, cdc, dw, p2, cdc, H, W, cdc, s.batch, st);
     if (nsplit()) {
         // [depthwise +] dc.3 + ffn.0 + ffn.2 (+ the next block's dc.0) in one launch, activations in LDS, weights per wave from L2
         DcbNsplitDesc d;
@@ -290,7 +293,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         if (dw_inside) { d.t1 = p1; d.wdw = dw; d.width = W; }
         else d.t2 = p2;
         d.wmain = packed_main; d.b3 = dc3.b; d.b0 = ffn0.b; d.b2 = ffn2.b;
-        d.q = q_fused; d.q2 = q_after; d.y = y.p; d.ldy = y.ld; d.pixels = P; d.c = c; d.ci = cdc; d.shortcut = shortcut;
+        d.q = q_fused; d.q2 = q_after; d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.c = c; d.ci = cdc; d.shortcut = shortcut;
         if (next != nullptr) {
             d.wnext = next->packed_dc0; d.b1n = next->dc0.b; d.t1n = dw_inside ? p2 : p1; d.ldt1 = next->cdc;
             if (dw_inside) s.hand ^= 1;
@@ -302,13 +305,13 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
             if (!fin->keep_block_output && !shortcut) d.y = nullptr;      // (with the block shortcut y may alias x: keep it simple)
         }
         dcb_nsplit(d, st);
-        if (fin != nullptr && !fin_inside) run_fin(*fin, y, P, st);
+        if (fin != nullptr && !fin_inside) run_fin(*fin, y, NP, st);
         return;
     }
     {   // dc.3 (+ folded depthwise bias) + shortcut
         Conv1x1Desc d;
         d.x = p2; d.ldx = cdc; d.w = dc3.w; d.bias = dc3.b; d.r1 = in.p; d.ldr1 = in.ld;
-        d.y = y.p; d.ldy = y.ld; d.pixels = P; d.cin = cdc; d.cout = c;
+        d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.cin = cdc; d.cout = c;
         conv1x1(d, st);
     }
     if (ffn_fused_supported(P, c, cffn) && ffn0.b != nullptr && ffn2.b != nullptr) {
@@ -317,15 +320,15 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         d.x = y.p; d.ldx = y.ld; d.w0 = ffn0.w; d.b0 = ffn0.b; d.w2 = ffn2.w; d.b2 = ffn2.b;
         if (shortcut) { d.r2 = in.p; d.ldr2 = in.ld; }
         d.q = q_fused; d.q2 = q_after;
-        d.y = y.p; d.ldy = y.ld; d.pixels = P; d.c = c; d.cffn = cffn;
+        d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.c = c; d.cffn = cffn;
         ffn_fused(d, st);
-        if (fin != nullptr) run_fin(*fin, y, P, st);
+        if (fin != nullptr) run_fin(*fin, y, NP, st);
         return;
     }
     {   // ffn.0 + WSiLU + chunk-add: the 4x expanded tensor never reaches HBM
         Conv1x1Desc d;
         d.x = y.p; d.ldx = y.ld; d.w = ffn0.w; d.bias = ffn0.b; d.wsilu = true; d.chunk_add = true;
-        d.y = s.t3; d.ldy = cffn; d.pixels = P; d.cin = c; d.cout = ffn0.cout;
+        d.y = s.t3; d.ldy = cffn; d.pixels = NP; d.cin = c; d.cout = ffn0.cout;
         conv1x1(d, st);
     }
     {   // ffn.2 + shortcut (+ block input when `shortcut`) (* quant)
@@ -333,10 +336,10 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         d.x = s.t3; d.ldx = cffn; d.w = ffn2.w; d.bias = ffn2.b; d.r1 = y.p; d.ldr1 = y.ld;
         if (shortcut) { d.r2 = in.p; d.ldr2 = in.ld; }
         d.q = q_fused; d.q2 = q_after;
-        d.y = y.p; d.ldy = y.ld; d.pixels = P; d.cin = cffn; d.cout = c;
+        d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.cin = cffn; d.cout = c;
         conv1x1(d, st);
     }
-    if (fin != nullptr) run_fin(*fin, y, P, st);
+    if (fin != nullptr) run_fin(*fin, y, NP, st);
 }
 
 void Stride2W::load(const ParamStore& ps, DeviceArena& mem, const std::string& p, bool with_shortcut)
@@ -362,10 +365,10 @@ void Stride2W::forward(View x, View tmp, View y, int H, int W, const half_t* zer
     ConvKxKDesc d;
     d.x = x.p; d.ldx = x.ld; d.w = w; d.bias = b; d.zeros = zeros;
     d.y = tmp.p; d.ldy = tmp.ld; d.in_h = H; d.in_w = W; d.cin = cin; d.cout = cout;
-    d.ksize = 2; d.stride = 2; d.pad = 0;
+    d.ksize = 2; d.stride = 2; d.pad = 0; d.n = s.batch;
     // a caller without a buffer to spare passes tmp = y: the block would run in place, and the one-launch form (dc.0 on the
     // halo of a patch) cannot. The third scratch plane is free in that form: the conv's output goes there instead
-    if (tmp.p == y.p && block.one_launch(H / 2, W / 2) && static_cast<size_t>(H / 2) * (W / 2) * cout <= s.elems) {
+    if (tmp.p == y.p && block.one_launch(H / 2, W / 2) && static_cast<size_t>(H / 2) * (W / 2) * cout * s.batch <= s.elems) {
         tmp = View(s.t3, cout, cout);
         d.y = tmp.p; d.ldy = tmp.ld;
     }
@@ -399,15 +402,16 @@ void SubpelW::load(const ParamStore& ps, DeviceArena& mem, const std::string& p)
     w = mem.upload(r);
 }
 
-void SubpelW::forward(View x, View y, int H, int W, hipStream_t st, half_t* tmp, const half_t* zeros) const
+void SubpelW::forward(View x, View y, int H, int W, hipStream_t st, half_t* tmp, const half_t* zeros, int n) const
 {
     if (b == nullptr) {
         TConv2x2Desc d;
         d.x = x.p; d.ldx = x.ld; d.w = w; d.y = y.p; d.ldy = y.ld;
-        d.in_h = H; d.in_w = W; d.cin = cin; d.cout = cout;
+        d.in_h = H; d.in_w = W; d.cin = cin; d.cout = cout; d.n = n;
         tconv2x2(d, st);
         return;
     }
+    if (n != 1) throw std::invalid_argument("biased SubpelConv2x takes one picture per launch");
     if (tmp == nullptr) throw std::invalid_argument("biased SubpelConv2x needs a temporary");
     if (k == 1) {
         Conv1x1Desc d;
@@ -434,10 +438,10 @@ void UpsampleW::load(const ParamStore& ps, DeviceArena& mem, const std::string& 
 void UpsampleW::forward(View x, View tmp, View y, int H, int W, const Scratch& s, hipStream_t st,
                         half_t* up_tmp, const half_t* zeros, const DcbW* next) const
 {
-    if (tmp.p == y.p && block.one_launch(2 * H, 2 * W) && static_cast<size_t>(4) * H * W * up.cout <= s.elems) {
+    if (tmp.p == y.p && block.one_launch(2 * H, 2 * W) && static_cast<size_t>(4) * H * W * up.cout * s.batch <= s.elems) {
         tmp = View(s.t3, up.cout, up.cout);      // (as Stride2W::forward: the one-launch block cannot run in place)
     }
-    up.forward(x, tmp, H, W, st, up_tmp, zeros);
+    up.forward(x, tmp, H, W, st, up_tmp, zeros, s.batch);
     block.forward(tmp, y, 2 * H, 2 * W, s, st, shortcut, nullptr, nullptr, View(), next);
 }
 

@@ -70,8 +70,9 @@ struct ConvGemmParams {
     int ldx, ldr1, ldr2, ldy;
     int M, N, K;          // output pixels, output channels (pre chunk-add), contraction length
     // spatial description (k x k convs and the transposed conv)
-    int in_h, in_w, out_h, out_w;   // input / output grid
+    int in_h, in_w, out_h, out_w;   // input / output grid (of one picture)
     int cin, ksize, stride, pad;
+    int pictures;                   // k x k convs: pictures back to back in x and y (M = pictures * out_h * out_w)
     int up_cout;                    // transposed conv: N = 4 * up_cout, channel tile n0 belongs to output pixel
                                     // (2y + dy, 2x + dx) with dy * 2 + dx = n0 / up_cout (a tile never straddles two of them)
     long long* timeline;            // optional [blocks][16] shader-clock stamps of wave 0 (tools/gemm_timeline.py)
@@ -89,13 +90,20 @@ __device__ __forceinline__ const half_t* x_row_ptr(const ConvGemmParams& p, int 
         const int tap = k0 / p.cin;
         const int c0 = k0 - tap * p.cin;
         const int ky = tap / p.ksize, kx = tap - ky * p.ksize;
-        const int oy = m / p.out_w, ox = m - oy * p.out_w;
+        int oy = m / p.out_w;
+        const int ox = m - oy * p.out_w;
+        const half_t* x = p.x;
+        if (p.pictures > 1) {       // a batch: the padding taps follow the picture's own rows
+            const int b = oy / p.out_h;
+            oy -= b * p.out_h;
+            x += static_cast<size_t>(b) * p.in_h * p.in_w * p.ldx;
+        }
         const int iy = oy * p.stride + ky - p.pad;
         const int ix = ox * p.stride + kx - p.pad;
         if (iy < 0 || iy >= p.in_h || ix < 0 || ix >= p.in_w) {
             return p.zeros;
         }
-        return p.x + (static_cast<size_t>(iy) * p.in_w + ix) * p.ldx + c0;
+        return x + (static_cast<size_t>(iy) * p.in_w + ix) * p.ldx + c0;
     }
 }
 
@@ -744,7 +752,9 @@ void conv_kxk(const ConvKxKDesc& d, hipStream_t stream)
     p.out_h = (d.in_h + 2 * d.pad - d.ksize) / d.stride + 1;
     p.out_w = (d.in_w + 2 * d.pad - d.ksize) / d.stride + 1;
     p.cin = d.cin; p.ksize = d.ksize; p.stride = d.stride; p.pad = d.pad;
-    p.M = p.out_h * p.out_w; p.N = d.cout; p.K = d.ksize * d.ksize * d.cin;
+    if (d.n < 1 || static_cast<long long>(d.n) * p.out_h * p.out_w > (1LL << 30)) throw std::invalid_argument("conv_kxk: batch size out of range");
+    p.pictures = d.n;
+    p.M = d.n * p.out_h * p.out_w; p.N = d.cout; p.K = d.ksize * d.ksize * d.cin;
     check_common(p);
     if (d.cin % BK != 0 || !d.zeros) {
         throw std::invalid_argument("conv_kxk: Cin must be a multiple of 64 and a zero page is required");
@@ -766,7 +776,9 @@ void tconv2x2(const TConv2x2Desc& d, hipStream_t stream)
     p.y = d.y;  p.ldy = d.ldy;
     p.in_h = d.in_h; p.in_w = d.in_w;
     p.up_cout = d.cout;
-    p.M = d.in_h * d.in_w; p.N = 4 * d.cout; p.K = d.cin;
+    // a batch of pictures back to back is one taller picture here: output rows 2y, 2y + 1 belong to input row y's picture
+    if (d.n < 1 || static_cast<long long>(d.n) * d.in_h * d.in_w > (1LL << 30)) throw std::invalid_argument("tconv2x2: batch size out of range");
+    p.M = d.n * d.in_h * d.in_w; p.N = 4 * d.cout; p.K = d.cin;
     check_common(p);
     launch<false, ACT_NONE, false, 0, false, true>(p, stream);
 }

@@ -72,10 +72,23 @@ struct TailParams {
 // DC0: dc.0 (1x1 + WSiLU) runs inside the launch too, on the 10 x 18 halo tile of the patch (192 rows
 // with padding: 1.4x the patch, dc.0 is the cheapest conv of the block), its output stays in LDS for
 // the depthwise: the whole DepthConvBlock behind an optional adaptor is ONE launch.
+// a batch: blockIdx.y = picture, H x W pixels each, back to back in t1, x and y (the halo stays in the picture)
+__device__ __forceinline__ TailParams at_picture(const TailParams& p, int b)
+{
+    TailParams q = p;
+    const size_t pix = static_cast<size_t>(b) * p.H * p.W;
+    q.t1 = p.t1 != nullptr ? p.t1 + pix * p.ldt : nullptr;
+    q.x += pix * p.ldx;
+    q.y += pix * p.ldy;
+    q.dbg_t1 = p.dbg_t1 != nullptr ? p.dbg_t1 + pix * p.CD : nullptr;
+    return q;
+}
+
 template <int NT2, bool DW, bool QUANT, bool DC0>
 __global__ void __launch_bounds__(NTHREADS)
-dcb_tail_kernel(const TailParams p)
+dcb_tail_kernel(const TailParams pk)
 {
+    const TailParams p = at_picture(pk, blockIdx.y);
     static_assert(!DC0 || DW, "dc.0 inside the launch feeds the depthwise");
     constexpr int HW_ = PW + 2;                      // halo tile: 10 x 18 pixels
     constexpr int HROWS = 192;                       // padded to 6 MFMA row tiles
@@ -547,7 +560,7 @@ dcb_tail_kernel(const TailParams p)
 }
 
 template <int NT2, bool DW, bool QUANT, bool DC0>
-void launch(const TailParams& p, hipStream_t stream)
+void launch(const TailParams& p, int pics, hipStream_t stream)
 {
     auto kern = dcb_tail_kernel<NT2, DW, QUANT, DC0>;
     static std::once_flag attr_once;      // lanes launch from several host threads
@@ -561,25 +574,25 @@ void launch(const TailParams& p, hipStream_t stream)
     // bench.py's roofline pass: [dc.0] + dc.3 + ffn.0 + ffn.2 as one record (family 2 in bits 28..30, ops.h)
     hipEvent_t ev0, ev1;
     const int kflop = (DC0 ? p.CD : 0) + p.CD + 5 * p.CF;
-    if (gemm_profile_slot(GemmLaunchInfo{p.H * p.W, C, kflop, 0x20000000, 0.f}, &ev0, &ev1)) {
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), smem_bytes, stream, ev0, ev1, 0, p);
+    if (gemm_profile_slot(GemmLaunchInfo{pics * p.H * p.W, C, kflop, 0x20000000, 0.f}, &ev0, &ev1)) {
+        hipExtLaunchKernelGGL(kern, dim3(grid, pics), dim3(NTHREADS), smem_bytes, stream, ev0, ev1, 0, p);
     } else {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), smem_bytes, stream, p);
+        hipLaunchKernelGGL(kern, dim3(grid, pics), dim3(NTHREADS), smem_bytes, stream, p);
     }
     hip_check(hipGetLastError(), "dcb_tail launch");
 }
 
 template <int NT2>
-void launch_variant(const TailParams& p, bool dw, hipStream_t stream)
+void launch_variant(const TailParams& p, bool dw, int pics, hipStream_t stream)
 {
     const bool quant = p.q != nullptr, dc0 = p.w1 != nullptr;
     if (dc0 && !dw) throw std::invalid_argument("dcb_tail: dc.0 inside the launch needs the depthwise weights");
-    if (dc0 && quant) launch<NT2, true, true, true>(p, stream);
-    else if (dc0) launch<NT2, true, false, true>(p, stream);
-    else if (dw && quant) launch<NT2, true, true, false>(p, stream);
-    else if (dw) launch<NT2, true, false, false>(p, stream);
-    else if (quant) launch<NT2, false, true, false>(p, stream);
-    else launch<NT2, false, false, false>(p, stream);
+    if (dc0 && quant) launch<NT2, true, true, true>(p, pics, stream);
+    else if (dc0) launch<NT2, true, false, true>(p, pics, stream);
+    else if (dw && quant) launch<NT2, true, true, false>(p, pics, stream);
+    else if (dw) launch<NT2, true, false, false>(p, pics, stream);
+    else if (quant) launch<NT2, false, true, false>(p, pics, stream);
+    else launch<NT2, false, false, false>(p, pics, stream);
 }
 
 bool shape_ok(int c, int cdc, int cffn)
@@ -632,8 +645,11 @@ void dcb_tail(const DcbTailDesc& d, hipStream_t stream)
     p.H = d.H; p.W = d.W; p.CD = d.cdc; p.CF = d.cffn; p.r2x = d.shortcut ? 1 : 0;
     p.wsilu = wsilu_table_device();
     p.dbg_t1 = g_dbg_t1;
-    if (d.c == 128) launch_variant<1>(p, d.dw != nullptr, stream);
-    else launch_variant<2>(p, d.dw != nullptr, stream);
+    if (d.n < 1 || d.n > 65535 || static_cast<long long>(d.n) * d.H * d.W > (1LL << 30)) {
+        throw std::invalid_argument("dcb_tail: batch size out of range");
+    }
+    if (d.c == 128) launch_variant<1>(p, d.dw != nullptr, d.n, stream);
+    else launch_variant<2>(p, d.dw != nullptr, d.n, stream);
 }
 
 }  // namespace dcvc

@@ -37,6 +37,9 @@ __global__ void __launch_bounds__(256)
 dwconv3x3_kernel(const half_t* __restrict__ x, int ldx, const half_t* __restrict__ wt,
                  half_t* __restrict__ y, int ldy, int H, int W, int C)
 {
+    // a batch: blockIdx.y = picture, H x W pixels each, back to back (the halo never crosses into the next picture)
+    x += static_cast<size_t>(blockIdx.y) * H * W * ldx;
+    y += static_cast<size_t>(blockIdx.y) * H * W * ldy;
     const int cv = C >> 3;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int strips = (H + RPT - 1) / RPT;
@@ -104,6 +107,8 @@ __global__ void __launch_bounds__(256)
 dwconv3x3_walk_kernel(const half_t* __restrict__ x, int ldx, const half_t* __restrict__ wt,
                       half_t* __restrict__ y, int ldy, int H, int W, int C)
 {
+    x += static_cast<size_t>(blockIdx.y) * H * W * ldx;      // (a batch: as dwconv3x3_kernel)
+    y += static_cast<size_t>(blockIdx.y) * H * W * ldy;
     const int cv = C >> 3;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int strips = (H + ROWS - 1) / ROWS;
@@ -181,33 +186,41 @@ int variant()
 }
 
 template <int ROWS, int AHEAD>
-void launch_walk(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C, hipStream_t stream)
+void launch_walk(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C, int pics,
+                 hipStream_t stream)
 {
     const long long n = static_cast<long long>((H + ROWS - 1) / ROWS) * W * (C / 8);
-    hipLaunchKernelGGL((dwconv3x3_walk_kernel<ROWS, AHEAD>), dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL((dwconv3x3_walk_kernel<ROWS, AHEAD>), dim3(static_cast<unsigned>((n + 255) / 256), pics), dim3(256), 0,
                        stream, x, ldx, wt, y, ldy, H, W, C);
     hip_check(hipGetLastError(), "dwconv3x3 launch");
 }
 
 }  // namespace
 
-void dwconv3x3(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C,
-               hipStream_t stream)
+void dwconv3x3_b(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C, int pics,
+                 hipStream_t stream)
 {
     if (C % 8 != 0) throw std::invalid_argument("dwconv3x3: C must be a multiple of 8");
+    if (pics < 1 || pics > 65535) throw std::invalid_argument("dwconv3x3: batch size out of range");
     switch (variant() >= 0 ? variant() : (C <= 128 ? 3 : 1)) {
-    case 1: return launch_walk<8, 2>(x, ldx, wt, y, ldy, H, W, C, stream);
-    case 2: return launch_walk<4, 1>(x, ldx, wt, y, ldy, H, W, C, stream);
-    case 3: return launch_walk<4, 2>(x, ldx, wt, y, ldy, H, W, C, stream);
-    case 4: return launch_walk<16, 1>(x, ldx, wt, y, ldy, H, W, C, stream);
-    case 5: return launch_walk<16, 2>(x, ldx, wt, y, ldy, H, W, C, stream);
-    case 6: return launch_walk<8, 3>(x, ldx, wt, y, ldy, H, W, C, stream);
+    case 1: return launch_walk<8, 2>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
+    case 2: return launch_walk<4, 1>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
+    case 3: return launch_walk<4, 2>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
+    case 4: return launch_walk<16, 1>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
+    case 5: return launch_walk<16, 2>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
+    case 6: return launch_walk<8, 3>(x, ldx, wt, y, ldy, H, W, C, pics, stream);
     default: break;
     }
     const long long n = static_cast<long long>((H + RPT - 1) / RPT) * W * (C / 8);
-    hipLaunchKernelGGL(dwconv3x3_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0,
+    hipLaunchKernelGGL(dwconv3x3_kernel, dim3(static_cast<unsigned>((n + 255) / 256), pics), dim3(256), 0,
                        stream, x, ldx, wt, y, ldy, H, W, C);
     hip_check(hipGetLastError(), "dwconv3x3 launch");
+}
+
+void dwconv3x3(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C,
+               hipStream_t stream)
+{
+    dwconv3x3_b(x, ldx, wt, y, ldy, H, W, C, 1, stream);
 }
 
 }  // namespace dcvc

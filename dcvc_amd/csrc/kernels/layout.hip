@@ -13,11 +13,16 @@ namespace dcvc {
 
 namespace {
 
+// The pad / shuffle / crop kernels take a batch of pictures back to back: blockIdx.y = picture, in_pic / out_pic = the
+// picture strides in elements (a single launch has one picture: blockIdx.y = 0).
+
 // out[h8][w8][c*64 + dy*8 + dx] = x[min(h8*8+dy, H-1)][min(w8*8+dx, W-1)][c]
 // one thread = one (pixel, c, dy): 8 consecutive dx -> 8 consecutive output channels (16 B store)
 __global__ void pad_unshuffle8_kernel(const half_t* __restrict__ x, int H, int W, int C3,
-                                      half_t* __restrict__ out, int H8, int W8, int ldout)
+                                      half_t* __restrict__ out, int H8, int W8, int ldout, long long in_pic, long long out_pic)
 {
+    x += blockIdx.y * in_pic;
+    out += blockIdx.y * out_pic;
     const int per_pix = C3 * 8;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H8 * W8 * per_pix) return;
@@ -38,8 +43,10 @@ __global__ void pad_unshuffle8_kernel(const half_t* __restrict__ x, int H, int W
 // out[h8*8+dy][w8*8+dx][c] = clamp(in[h8][w8][c*64 + dy*8 + dx])
 template <bool CLAMP>
 __global__ void shuffle8_kernel(const half_t* __restrict__ in, int ldin, int H8, int W8, int C3,
-                                half_t* __restrict__ out)
+                                half_t* __restrict__ out, long long in_pic, long long out_pic)
 {
+    in += blockIdx.y * in_pic;
+    out += blockIdx.y * out_pic;
     const int per_pix = C3 * 8;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H8 * W8 * per_pix) return;
@@ -77,8 +84,10 @@ __global__ void shuffle2_kernel(const half_t* __restrict__ in, int ldin, int H, 
 }
 
 __global__ void replicate_pad_kernel(const half_t* __restrict__ in, int ldin, int H, int W, int C,
-                                     int Ho, int Wo, half_t* __restrict__ out, int ldout)
+                                     int Ho, int Wo, half_t* __restrict__ out, int ldout, long long in_pic, long long out_pic)
 {
+    in += blockIdx.y * in_pic;
+    out += blockIdx.y * out_pic;
     const int cv = C >> 3;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Ho * Wo * cv) return;
@@ -91,8 +100,10 @@ __global__ void replicate_pad_kernel(const half_t* __restrict__ in, int ldin, in
 }
 
 __global__ void crop_kernel(const half_t* __restrict__ in, int ldin, int Win,
-                            half_t* __restrict__ out, int ldout, int H, int W, int C)
+                            half_t* __restrict__ out, int ldout, int H, int W, int C, long long in_pic, long long out_pic)
 {
+    in += blockIdx.y * in_pic;
+    out += blockIdx.y * out_pic;
     const int cv = C >> 3;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W * cv) return;
@@ -141,29 +152,49 @@ __global__ void scale_clamped_kernel(const half_t* __restrict__ x, int ldx, cons
     *reinterpret_cast<half8*>(y + static_cast<size_t>(pix) * ldy + c0) = o;
 }
 
-inline dim3 grid1d(long long n, int block = 256)
+inline dim3 grid1d(long long n, int block = 256, int pictures = 1)
 {
-    return dim3(static_cast<unsigned>((n + block - 1) / block));
+    return dim3(static_cast<unsigned>((n + block - 1) / block), static_cast<unsigned>(pictures));
+}
+
+void check_batch(int n, const char* what)
+{
+    if (n < 1 || n > 65535) throw std::invalid_argument(std::string(what) + ": batch size out of range");
 }
 
 }  // namespace
 
+void pad_unshuffle8_b(const half_t* x, int H, int W, int C3, half_t* out, int H8, int W8, int n, hipStream_t stream,
+                      int ldout)
+{
+    check_batch(n, "pad_unshuffle8");
+    if (ldout == 0) ldout = C3 * 64;
+    const long long cnt = static_cast<long long>(H8) * W8 * C3 * 8;
+    hipLaunchKernelGGL(pad_unshuffle8_kernel, grid1d(cnt, 256, n), dim3(256), 0, stream, x, H, W, C3, out, H8, W8, ldout,
+                       static_cast<long long>(H) * W * C3, static_cast<long long>(H8) * W8 * ldout);
+    hip_check(hipGetLastError(), "pad_unshuffle8 launch");
+}
+
 void pad_unshuffle8(const half_t* x, int H, int W, int C3, half_t* out, int H8, int W8,
                     hipStream_t stream, int ldout)
 {
-    if (ldout == 0) ldout = C3 * 64;
-    const long long n = static_cast<long long>(H8) * W8 * C3 * 8;
-    hipLaunchKernelGGL(pad_unshuffle8_kernel, grid1d(n), dim3(256), 0, stream, x, H, W, C3, out, H8, W8, ldout);
-    hip_check(hipGetLastError(), "pad_unshuffle8 launch");
+    pad_unshuffle8_b(x, H, W, C3, out, H8, W8, 1, stream, ldout);
+}
+
+void shuffle8_b(const half_t* in, int ldin, int H8, int W8, int C3, bool clamp, half_t* out, int n, hipStream_t stream)
+{
+    check_batch(n, "shuffle8");
+    const long long cnt = static_cast<long long>(H8) * W8 * C3 * 8;
+    const long long in_pic = static_cast<long long>(H8) * W8 * ldin, out_pic = static_cast<long long>(H8) * W8 * 64 * C3;
+    if (clamp) hipLaunchKernelGGL(shuffle8_kernel<true>, grid1d(cnt, 256, n), dim3(256), 0, stream, in, ldin, H8, W8, C3, out, in_pic, out_pic);
+    else       hipLaunchKernelGGL(shuffle8_kernel<false>, grid1d(cnt, 256, n), dim3(256), 0, stream, in, ldin, H8, W8, C3, out, in_pic, out_pic);
+    hip_check(hipGetLastError(), "shuffle8 launch");
 }
 
 void shuffle8(const half_t* in, int ldin, int H8, int W8, int C3, bool clamp, half_t* out,
               hipStream_t stream)
 {
-    const long long n = static_cast<long long>(H8) * W8 * C3 * 8;
-    if (clamp) hipLaunchKernelGGL(shuffle8_kernel<true>, grid1d(n), dim3(256), 0, stream, in, ldin, H8, W8, C3, out);
-    else       hipLaunchKernelGGL(shuffle8_kernel<false>, grid1d(n), dim3(256), 0, stream, in, ldin, H8, W8, C3, out);
-    hip_check(hipGetLastError(), "shuffle8 launch");
+    shuffle8_b(in, ldin, H8, W8, C3, clamp, out, 1, stream);
 }
 
 void shuffle2(const half_t* in, int ldin, int H, int W, int C, half_t* out, int ldout, hipStream_t stream)
@@ -173,21 +204,37 @@ void shuffle2(const half_t* in, int ldin, int H, int W, int C, half_t* out, int 
     hip_check(hipGetLastError(), "shuffle2 launch");
 }
 
+void replicate_pad_b(const half_t* in, int ldin, int H, int W, int C, int pad_b, int pad_r, half_t* out, int ldout, int n,
+                     hipStream_t stream)
+{
+    check_batch(n, "replicate_pad");
+    const int Ho = H + pad_b, Wo = W + pad_r;
+    const long long cnt = static_cast<long long>(Ho) * Wo * (C / 8);
+    hipLaunchKernelGGL(replicate_pad_kernel, grid1d(cnt, 256, n), dim3(256), 0, stream, in, ldin, H, W, C, Ho, Wo, out, ldout,
+                       static_cast<long long>(H) * W * ldin, static_cast<long long>(Ho) * Wo * ldout);
+    hip_check(hipGetLastError(), "replicate_pad launch");
+}
+
 void replicate_pad(const half_t* in, int ldin, int H, int W, int C, int pad_b, int pad_r,
                    half_t* out, int ldout, hipStream_t stream)
 {
-    const int Ho = H + pad_b, Wo = W + pad_r;
-    const long long n = static_cast<long long>(Ho) * Wo * (C / 8);
-    hipLaunchKernelGGL(replicate_pad_kernel, grid1d(n), dim3(256), 0, stream, in, ldin, H, W, C, Ho, Wo, out, ldout);
-    hip_check(hipGetLastError(), "replicate_pad launch");
+    replicate_pad_b(in, ldin, H, W, C, pad_b, pad_r, out, ldout, 1, stream);
+}
+
+void crop_b(const half_t* in, int ldin, int Hin, int Win, half_t* out, int ldout, int H, int W, int C, int n,
+            hipStream_t stream)
+{
+    check_batch(n, "crop");
+    const long long cnt = static_cast<long long>(H) * W * (C / 8);
+    hipLaunchKernelGGL(crop_kernel, grid1d(cnt, 256, n), dim3(256), 0, stream, in, ldin, Win, out, ldout, H, W, C,
+                       static_cast<long long>(Hin) * Win * ldin, static_cast<long long>(H) * W * ldout);
+    hip_check(hipGetLastError(), "crop launch");
 }
 
 void crop(const half_t* in, int ldin, int Win, half_t* out, int ldout, int H, int W, int C,
           hipStream_t stream)
 {
-    const long long n = static_cast<long long>(H) * W * (C / 8);
-    hipLaunchKernelGGL(crop_kernel, grid1d(n), dim3(256), 0, stream, in, ldin, Win, out, ldout, H, W, C);
-    hip_check(hipGetLastError(), "crop launch");
+    crop_b(in, ldin, H, Win, out, ldout, H, W, C, 1, stream);      // (one picture: its height is never read)
 }
 
 void mul_channel(const half_t* x, int ldx, const half_t* q, half_t* y, int ldy, int pixels, int C,

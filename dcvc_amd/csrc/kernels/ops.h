@@ -133,6 +133,9 @@ struct ConvKxKDesc {
     const half_t* zeros = nullptr;              // >= 128 B of zeros
     half_t* y = nullptr; int ldy = 0;           // [out_h][out_w][ldy]
     int in_h = 0, in_w = 0, cin = 0, cout = 0, ksize = 0, stride = 1, pad = 0;
+    // batch: n pictures back to back in x ([n][in_h][in_w][ldx]) and y ([n][out_h][out_w][ldy]); in_h / out_h are per picture,
+    // the padding taps follow each picture's own rows. n = 1: one picture, the launch of before
+    int n = 1;
 };
 void conv_kxk(const ConvKxKDesc& d, hipStream_t stream);
 
@@ -141,6 +144,7 @@ struct TConv2x2Desc {
     const half_t* w = nullptr;                  // [4 = dy*2+dx][cout][cin]
     half_t* y = nullptr; int ldy = 0;           // [2 in_h][2 in_w][ldy]
     int in_h = 0, in_w = 0, cin = 0, cout = 0;
+    int n = 1;                                  // n pictures back to back (no overlap: stacking them is the same layout)
 };
 void tconv2x2(const TConv2x2Desc& d, hipStream_t stream);
 
@@ -189,6 +193,7 @@ struct DcbTailDesc {
     half_t* y = nullptr; int ldy = 0;
     int H = 0, W = 0, c = 0, cdc = 0, cffn = 0;
     bool shortcut = false;                      // ffn.2 also adds x (block-level shortcut)
+    int n = 1;                                  // n pictures of H x W back to back in t, x and y (the halo stays in each picture)
 };
 // shape supported AND enough 8x16 patches to fill the chip; DCVC_DCB_TAIL=0 / 2 = never / whenever possible
 bool dcb_tail_supported(int H, int W, int c, int cdc, int cffn);
@@ -203,6 +208,9 @@ void dcb_tail_debug_buffer(half_t* device_buffer);
 // reference folds the bias into the next 1x1, layers_proxy.cpp:175-178)
 void dwconv3x3(const half_t* x, int ldx, const half_t* wt /* [9][C] */, half_t* y, int ldy,
                int H, int W, int C, hipStream_t stream);
+// n pictures of H x W back to back in x and y ([n][H][W][ld]); the zero padding follows each picture's own rows
+void dwconv3x3_b(const half_t* x, int ldx, const half_t* wt, half_t* y, int ldy, int H, int W, int C, int n,
+                 hipStream_t stream);
 
 // ---------------------------------------------------------------- layout kernels (layout.hip)
 // x: [H][W][C3] (channels_last view of [1, C3, H, W]); out: [H8][W8][C3*64] with pixel stride
@@ -221,6 +229,15 @@ void replicate_pad(const half_t* in, int ldin, int H, int W, int C, int pad_b, i
 // crop: in [Hin][Win][C] -> out [H][W][C]
 void crop(const half_t* in, int ldin, int Win, half_t* out, int ldout, int H, int W, int C,
           hipStream_t stream);
+// Batched forms (intra batches): n pictures back to back on both sides, each with the per-picture geometry
+// of the single form; n = 1 is the single launch. crop_b also needs the input picture's height.
+void pad_unshuffle8_b(const half_t* x, int H, int W, int C3, half_t* out, int H8, int W8, int n, hipStream_t stream,
+                      int ldout = 0);
+void shuffle8_b(const half_t* in, int ldin, int H8, int W8, int C3, bool clamp, half_t* out, int n, hipStream_t stream);
+void replicate_pad_b(const half_t* in, int ldin, int H, int W, int C, int pad_b, int pad_r, half_t* out, int ldout, int n,
+                     hipStream_t stream);
+void crop_b(const half_t* in, int ldin, int Hin, int Win, half_t* out, int ldout, int H, int W, int C, int n,
+            hipStream_t stream);
 // y = x * q[c] (fp16 multiply, may be in place)
 void mul_channel(const half_t* x, int ldx, const half_t* q, half_t* y, int ldy, int pixels, int C,
                  hipStream_t stream);
@@ -324,6 +341,9 @@ struct YStepEnc {
     int H = 0, W = 0, C = 0, step = 0;
     float skip_thres = 0.f;
     bool first = false;                                // step 0 initialises y_hat_acc (copy, not add)
+    // n pictures of H x W back to back in every operand: y / scales / means / y_hat_acc [n][P][ld], sym [n][P*C/4],
+    // cond [n][P*C/32], block_count [n][symbol_blocks(P*C/4)]. The masks follow each picture's own (y, x).
+    int n = 1;
 };
 void y_step_enc(const YStepEnc& d, hipStream_t stream);
 
@@ -335,6 +355,7 @@ struct YStepDecIndex {
     int32_t* block_count = nullptr;
     int H = 0, W = 0, C = 0, step = 0;
     float skip_thres = 0.f;
+    int n = 1;                                         // n pictures, laid out as YStepEnc's
 };
 void y_step_dec_index(const YStepDecIndex& d, hipStream_t stream);
 
@@ -342,6 +363,11 @@ void y_step_dec_index(const YStepDecIndex& d, hipStream_t stream);
 // base = total[0..slot) summed; total[slot] receives this step's kept count.
 void compact(const void* in, int elem_bytes, const uint8_t* cond, const int32_t* block_count,
              int count, void* out, int32_t* totals, int slot, hipStream_t stream);
+// n pictures of `count` elements each (in [n][count], cond [n][count/8], block_count [n][symbol_blocks(count)]), each
+// compacted into its own region: picture b writes out + b * out_stride (elements) and totals + b * totals_stride (int32s),
+// with the base of its own totals[0..slot). count must be a multiple of 8.
+void compact_b(const void* in, int elem_bytes, const uint8_t* cond, const int32_t* block_count, int count, void* out,
+               long long out_stride, int32_t* totals, int totals_stride, int slot, int n, hipStream_t stream);
 
 // Decoder: scatter decoded int8 symbols back (zeros where skipped), add the mean of the active
 // group and accumulate into y_hat_so_far (restore_y_4x*, stream.cu:757-844).
@@ -354,6 +380,11 @@ struct YStepDecRestore {
     half_t* y_hat_acc = nullptr; int ldacc = 0;
     int H = 0, W = 0, C = 0, step = 0;
     bool first = false;
+    // n pictures, laid out as YStepEnc's; picture b's symbols start at decoded + b * decoded_stride and its totals at
+    // totals + b * totals_stride
+    int n = 1;
+    long long decoded_stride = 0;
+    int totals_stride = 0;
 };
 void y_step_dec_restore(const YStepDecRestore& d, hipStream_t stream);
 

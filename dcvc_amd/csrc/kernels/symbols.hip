@@ -115,10 +115,48 @@ __device__ __forceinline__ int block_sum_256(int v, int* lds)
     return s;
 }
 
+// ----------------------------------------------------------------- batches
+// A batch of pictures runs as a 2-D grid: blockIdx.x = the 2048-element block inside the picture, blockIdx.y = the picture.
+// Each picture's operands start at its own offset, so every block sees exactly what it sees in a single launch: the masks
+// follow the picture's own (y, x), block counts and compaction regions are the picture's own.
+__device__ __forceinline__ size_t pic_pixels(int H, int W)
+{
+    return static_cast<size_t>(blockIdx.y) * H * W;
+}
+
+__device__ __forceinline__ YStepEnc at_picture(const YStepEnc& d)
+{
+    YStepEnc e = d;
+    const size_t pix = pic_pixels(d.H, d.W), sym = pix * (d.C >> 2);
+    e.y += pix * d.ldy; e.scales += pix * d.lds; e.means += pix * d.ldm; e.y_hat_acc += pix * d.ldacc;
+    e.sym += sym; e.cond += sym >> 3; e.block_count += static_cast<size_t>(blockIdx.y) * gridDim.x;
+    return e;
+}
+
+__device__ __forceinline__ YStepDecIndex at_picture(const YStepDecIndex& d)
+{
+    YStepDecIndex e = d;
+    const size_t pix = pic_pixels(d.H, d.W), sym = pix * (d.C >> 2);
+    e.scales += pix * d.lds;
+    e.index += sym; e.cond += sym >> 3; e.block_count += static_cast<size_t>(blockIdx.y) * gridDim.x;
+    return e;
+}
+
+__device__ __forceinline__ YStepDecRestore at_picture(const YStepDecRestore& d)
+{
+    YStepDecRestore e = d;
+    const size_t pix = pic_pixels(d.H, d.W), sym = pix * (d.C >> 2);
+    e.decoded += blockIdx.y * d.decoded_stride; e.totals += static_cast<size_t>(blockIdx.y) * d.totals_stride;
+    e.cond += sym >> 3; e.block_count += static_cast<size_t>(blockIdx.y) * gridDim.x;
+    e.means += pix * d.ldm; e.y_hat_acc += pix * d.ldacc;
+    return e;
+}
+
 // ----------------------------------------------------------------- encoder step
 __global__ void __launch_bounds__(kBlockThreads)
-y_step_enc_kernel(const YStepEnc d, const LutView lutv, const half_t thres)
+y_step_enc_kernel(const YStepEnc dk, const LutView lutv, const half_t thres)
 {
+    const YStepEnc d = at_picture(dk);
     __shared__ int lds[4];
     const int cq = d.C >> 2;
     const int total = d.H * d.W * cq;
@@ -173,8 +211,9 @@ y_step_enc_kernel(const YStepEnc d, const LutView lutv, const half_t thres)
 
 // ----------------------------------------------------------------- decoder index step
 __global__ void __launch_bounds__(kBlockThreads)
-y_step_dec_index_kernel(const YStepDecIndex d, const LutView lutv, const half_t thres)
+y_step_dec_index_kernel(const YStepDecIndex dk, const LutView lutv, const half_t thres)
 {
+    const YStepDecIndex d = at_picture(dk);
     __shared__ int lds[4];
     const int cq = d.C >> 2;
     const int total = d.H * d.W * cq;
@@ -233,8 +272,14 @@ template <typename T>
 __global__ void __launch_bounds__(kBlockThreads)
 compact_kernel(const T* __restrict__ in, const uint8_t* __restrict__ cond,
                const int32_t* __restrict__ block_count, int count, T* __restrict__ out,
-               int32_t* totals, int slot)
+               int32_t* totals, int slot, long long out_stride, int totals_stride)
 {
+    // a batch (blockIdx.y = picture): each picture of `count` elements into its own region
+    in += static_cast<size_t>(blockIdx.y) * count;
+    cond += (static_cast<size_t>(blockIdx.y) * count) >> 3;
+    block_count += static_cast<size_t>(blockIdx.y) * gridDim.x;
+    out += blockIdx.y * out_stride;
+    totals += static_cast<size_t>(blockIdx.y) * totals_stride;
     __shared__ int lds[4];
     const int e0 = (blockIdx.x * kBlockThreads + threadIdx.x) * kElemsPerThread;
     unsigned flags = 0;
@@ -253,8 +298,9 @@ compact_kernel(const T* __restrict__ in, const uint8_t* __restrict__ cond,
 }
 
 __global__ void __launch_bounds__(kBlockThreads)
-y_step_dec_restore_kernel(const YStepDecRestore d)
+y_step_dec_restore_kernel(const YStepDecRestore dk)
 {
+    const YStepDecRestore d = at_picture(dk);
     __shared__ int lds[4];
     const int cq = d.C >> 2;
     const int total = d.H * d.W * cq;
@@ -477,6 +523,11 @@ int grid_for(int count)
     return (count + kBlockElems - 1) / kBlockElems;
 }
 
+void check_pictures(int n, const char* what)
+{
+    if (n < 1 || n > 65535) throw std::invalid_argument(std::string(what) + ": batch size out of range");
+}
+
 }  // namespace
 
 void symbols_init()
@@ -492,8 +543,9 @@ int symbol_blocks(int count)
 void y_step_enc(const YStepEnc& d, hipStream_t stream)
 {
     if (d.C % 32 != 0) throw std::invalid_argument("y_step_enc: C must be a multiple of 32");
+    check_pictures(d.n, "y_step_enc");
     const int count = d.H * d.W * (d.C / 4);
-    hipLaunchKernelGGL(y_step_enc_kernel, dim3(grid_for(count)), dim3(kBlockThreads), 0, stream, d,
+    hipLaunchKernelGGL(y_step_enc_kernel, dim3(grid_for(count), d.n), dim3(kBlockThreads), 0, stream, d,
                        lut_view(), static_cast<half_t>(d.skip_thres));
     hip_check(hipGetLastError(), "y_step_enc launch");
 }
@@ -501,8 +553,9 @@ void y_step_enc(const YStepEnc& d, hipStream_t stream)
 void y_step_dec_index(const YStepDecIndex& d, hipStream_t stream)
 {
     if (d.C % 32 != 0) throw std::invalid_argument("y_step_dec_index: C must be a multiple of 32");
+    check_pictures(d.n, "y_step_dec_index");
     const int count = d.H * d.W * (d.C / 4);
-    hipLaunchKernelGGL(y_step_dec_index_kernel, dim3(grid_for(count)), dim3(kBlockThreads), 0, stream,
+    hipLaunchKernelGGL(y_step_dec_index_kernel, dim3(grid_for(count), d.n), dim3(kBlockThreads), 0, stream,
                        d, lut_view(), static_cast<half_t>(d.skip_thres));
     hip_check(hipGetLastError(), "y_step_dec_index launch");
 }
@@ -510,15 +563,23 @@ void y_step_dec_index(const YStepDecIndex& d, hipStream_t stream)
 void compact(const void* in, int elem_bytes, const uint8_t* cond, const int32_t* block_count,
              int count, void* out, int32_t* totals, int slot, hipStream_t stream)
 {
-    const dim3 grid(grid_for(count)), block(kBlockThreads);
+    compact_b(in, elem_bytes, cond, block_count, count, out, 0, totals, 0, slot, 1, stream);
+}
+
+void compact_b(const void* in, int elem_bytes, const uint8_t* cond, const int32_t* block_count, int count, void* out,
+               long long out_stride, int32_t* totals, int totals_stride, int slot, int n, hipStream_t stream)
+{
+    check_pictures(n, "compact");
+    if (n > 1 && count % 8 != 0) throw std::invalid_argument("compact: a batch needs a multiple of 8 elements per picture");
+    const dim3 grid(grid_for(count), n), block(kBlockThreads);
     if (elem_bytes == 2) {
         hipLaunchKernelGGL(compact_kernel<int16_t>, grid, block, 0, stream,
                            static_cast<const int16_t*>(in), cond, block_count, count,
-                           static_cast<int16_t*>(out), totals, slot);
+                           static_cast<int16_t*>(out), totals, slot, out_stride, totals_stride);
     } else if (elem_bytes == 1) {
         hipLaunchKernelGGL(compact_kernel<uint8_t>, grid, block, 0, stream,
                            static_cast<const uint8_t*>(in), cond, block_count, count,
-                           static_cast<uint8_t*>(out), totals, slot);
+                           static_cast<uint8_t*>(out), totals, slot, out_stride, totals_stride);
     } else {
         throw std::invalid_argument("compact: element size must be 1 or 2 bytes");
     }
@@ -527,8 +588,9 @@ void compact(const void* in, int elem_bytes, const uint8_t* cond, const int32_t*
 
 void y_step_dec_restore(const YStepDecRestore& d, hipStream_t stream)
 {
+    check_pictures(d.n, "y_step_dec_restore");
     const int count = d.H * d.W * (d.C / 4);
-    hipLaunchKernelGGL(y_step_dec_restore_kernel, dim3(grid_for(count)), dim3(kBlockThreads), 0,
+    hipLaunchKernelGGL(y_step_dec_restore_kernel, dim3(grid_for(count), d.n), dim3(kBlockThreads), 0,
                        stream, d);
     hip_check(hipGetLastError(), "y_step_dec_restore launch");
 }

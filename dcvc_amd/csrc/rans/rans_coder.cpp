@@ -649,6 +649,12 @@ void RansDecoder::set_parallel(int n)
     m_n = n;
 }
 
+void RansDecoder::swap_state(StreamState& s)
+{
+    for (int i = 0; i < kMaxEcParallel; ++i) std::swap(m_sub[i], s.sub[i]);
+    std::swap(m_n, s.n);
+}
+
 void RansDecoder::set_stream(const uint8_t* data, size_t size)
 {
     const int n = m_n;

@@ -137,6 +137,17 @@ private:
         const uint8_t* end = nullptr;
         uint32_t state = 0;
     };
+
+public:
+    // The position in one stream: several streams decode in turns on one decoder (and its tables and threads) by
+    // swapping their states in and out. A swap moves the byte buffers, so the read positions stay valid.
+    struct StreamState {
+        Sub sub[kMaxEcParallel];
+        int n = 1;
+    };
+    void swap_state(StreamState& s);
+
+private:
     CdfTable m_tab[2];
     Sub m_sub[kMaxEcParallel];
     int m_n = 1;

@@ -60,6 +60,12 @@ _F = dict(
     decompress=_lib.fn("dcvc_dmci_decompress", _ci, [_vp, _vp, ctypes.c_size_t, _ci, _ci, _ci, _ci, _vp, _vp]),
     use_graphs=_lib.fn("dcvc_dmci_set_use_graphs", _ci, [_vp, _ci]),
     debug_read=_lib.fn("dcvc_dmci_debug_read", ctypes.c_int64, [_vp, ctypes.c_char_p, _vp, ctypes.c_size_t, _vp]),
+    compress_batch=_lib.fn("dcvc_dmci_compress_batch", _ci,
+                           [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _vp, ctypes.POINTER(_ci), _vp]),
+    get_stream_at=_lib.fn("dcvc_dmci_get_stream_at", ctypes.c_int64, [_vp, _ci, _vp, ctypes.c_size_t]),
+    decompress_batch=_lib.fn("dcvc_dmci_decompress_batch", _ci,
+                             [_vp, _ci, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_ci), _ci,
+                              _ci, _ci, _vp, _vp]),
 )
 
 _SET_PARAM_ARGS = [_vp, _ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_vp), ctypes.POINTER(_ci),
@@ -208,6 +214,50 @@ class DMCIProxy(_Proxy):
                                     int(entropy_coder_parallel), ctypes.c_void_p(x_hat.data_ptr()),
                                     _stream_ptr()))
         return x_hat
+
+    # ---- extras, not part of the reference surface: intra batches
+    MAX_BATCH = 16
+
+    def compress_batch(self, x, qp, padding_b, padding_r):
+        """x: [N, 3, H, W] fp16 CUDA (1 <= N <= 16), one qp for all -> list of N (bit stream, x_hat [1, 3, H16, W16],
+        ec_parallel), each exactly what compress() gives for that picture alone. The x_hat are views of one fresh tensor."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected an [N, 3, H, W] tensor, got %s" % (tuple(x.shape),))
+        if x.dtype != torch.float16 or not x.is_cuda:
+            raise ValueError("expected a CUDA fp16 tensor")
+        n, height, width = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        x = x.contiguous(memory_format=torch.channels_last)
+        h16, w16 = (height + 15) // 16 * 16, (width + 15) // 16 * 16
+        x_hat = torch.empty((n, 3, h16, w16), dtype=torch.float16, device=x.device).contiguous(
+            memory_format=torch.channels_last)
+        ec = (_ci * max(1, n))()
+        _lib.check(_F["compress_batch"](self._h, n, ctypes.c_void_p(x.data_ptr()), height, width, int(qp), int(padding_b),
+                                        int(padding_r), ctypes.c_void_p(x_hat.data_ptr()), ec, _stream_ptr()))
+        out = []
+        for i in range(n):
+            size = _lib.check(_F["get_stream_at"](self._h, i, None, 0))
+            bs = np.empty(size, dtype=np.uint8)
+            _lib.check(_F["get_stream_at"](self._h, i, bs.ctypes.data_as(_vp), size))
+            out.append((bs, x_hat[i:i + 1], int(ec[i])))
+        return out
+
+    def decompress_batch(self, bit_streams, qp, height, width, entropy_coder_parallels):
+        """N streams of one size and one qp -> x_hat [N, 3, H16, W16] (a fresh tensor), picture i exactly what
+        decompress() gives for stream i."""
+        streams = [np.ascontiguousarray(b, dtype=np.uint8) for b in bit_streams]
+        n = len(streams)
+        if len(entropy_coder_parallels) != n:
+            raise ValueError("one ec_parallel per stream")
+        device = torch.device("cuda", torch.cuda.current_device())
+        h16, w16 = (int(height) + 15) // 16 * 16, (int(width) + 15) // 16 * 16
+        x_hat = torch.empty((max(1, n), 3, h16, w16), dtype=torch.float16, device=device).contiguous(
+            memory_format=torch.channels_last)
+        ptrs = (_vp * max(1, n))(*[s.ctypes.data for s in streams])
+        sizes = (ctypes.c_size_t * max(1, n))(*[s.size for s in streams])
+        ecs = (_ci * max(1, n))(*[int(e) for e in entropy_coder_parallels])
+        _lib.check(_F["decompress_batch"](self._h, n, ptrs, sizes, ecs, int(qp), int(height), int(width),
+                                          ctypes.c_void_p(x_hat.data_ptr()), _stream_ptr()))
+        return x_hat[:n]
 
 
 class DMCLDProxy(_Proxy):

@@ -69,6 +69,20 @@ int dcvc_dmci_decompress(dcvc_dmci* c, const uint8_t* bit_stream, size_t nbytes,
 
 /* Not part of the reference surface: 1 = replay the stages as hipGraphs (default), 0 = eager. */
 int dcvc_dmci_set_use_graphs(dcvc_dmci* c, int on);
+
+/* Not part of the reference surface: intra batches. n (1..16) pictures of one size and one qp per call, every
+ * launch shared by all of them. x: n x [height][width][3] back to back; x_hat: n x [ceil16(height)][ceil16(width)][3] back
+ * to back; ec_parallel_out[i] receives picture i's ec_parallel. Picture i's stream (dcvc_dmci_get_stream_at) and
+ * reconstruction are byte- and bit-identical to what dcvc_dmci_compress gives for it alone. Returns 0. */
+int dcvc_dmci_compress_batch(dcvc_dmci* c, int n, const void* x, int height, int width, int qp, int padding_b,
+                             int padding_r, void* x_hat, int* ec_parallel_out, void* stream);
+/* Not part of the reference surface: stream i (0 <= i < n) of the last compress / compress_batch call (a single call has
+ * n = 1: index 0 is dcvc_dmci_get_stream's stream). Size query (dst == NULL) or copy of at most cap bytes; returns the size. */
+int64_t dcvc_dmci_get_stream_at(dcvc_dmci* c, int i, uint8_t* dst, size_t cap);
+/* Not part of the reference surface: n (1..16) streams of one size and one qp; x_hat as dcvc_dmci_compress_batch's. Each
+ * picture's reconstruction is bit-identical to dcvc_dmci_decompress of its stream. ec_parallel[i] in 1..8. */
+int dcvc_dmci_decompress_batch(dcvc_dmci* c, int n, const uint8_t* const* streams, const size_t* nbytes,
+                               const int* ec_parallel, int qp, int height, int width, void* x_hat, void* stream);
 /* Test hook: copy an internal tensor of the last call ("y", "y_hat", "z_i8", "params",
  * "unshuffled", "features", "totals", "symbols") to host memory; returns its size in bytes. */
 int64_t dcvc_dmci_debug_read(dcvc_dmci* c, const char* name, void* dst, size_t cap, void* stream);

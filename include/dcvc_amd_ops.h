@@ -61,6 +61,21 @@ int dcvc_crop(const void* in, int ldin, int Win, void* out, int ldout, int H, in
 int dcvc_mul_channel(const void* x, int ldx, const void* q, void* y, int ldy, int pixels, int C,
                      void* stream);
 
+/* Not part of the reference surface: batched forms for the intra batches. n (1..16) pictures back to back
+ * on both sides, each with the per-picture geometry of the single form above; n = 1 is the single launch. The halo,
+ * padding and edge replication of every picture stay inside it. crop_b also takes the input picture's height Hin.
+ * conv_kxk_b / tconv2x2_b: in_h is one picture's height. */
+int dcvc_dwconv3x3_b(const void* x, int ldx, const void* w, void* y, int ldy, int H, int W, int C, int n, void* stream);
+int dcvc_conv_kxk_b(const void* x, int ldx, const void* w, const void* bias, void* y, int ldy, int in_h, int in_w, int cin,
+                    int cout, int ksize, int stride, int pad, int n, void* stream);
+int dcvc_tconv2x2_b(const void* x, int ldx, const void* w, void* y, int ldy, int in_h, int in_w, int cin, int cout, int n,
+                    void* stream);
+int dcvc_pad_unshuffle8_b(const void* x, int H, int W, int C3, void* out, int H8, int W8, int n, void* stream);
+int dcvc_shuffle8_b(const void* in, int ldin, int H8, int W8, int C3, int clamp, void* out, int n, void* stream);
+int dcvc_replicate_pad_b(const void* in, int ldin, int H, int W, int C, int pad_b, int pad_r, void* out, int ldout, int n,
+                         void* stream);
+int dcvc_crop_b(const void* in, int ldin, int Hin, int Win, void* out, int ldout, int H, int W, int C, int n, void* stream);
+
 /* ffn.0 + ffn.2 of a DepthConvBlock in one launch (layers_proxy.cpp:84-98: conv1x1_bias_wsilu_chunk_add
  * followed by conv1x1_bias_shortcut[2][_with_quant] with the block-internal tensor as first residual):
  *   out = W2 * chunk_add(WSiLU(W0 * x + b0)) + b2 + x [+ r2] [* q], rounded to fp16, [* q2].

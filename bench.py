@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - DCVC-UF 1080p YUV420 encode + decode throughput on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--workload intra|ld|hts|htl] [--resolution 3840x2160]
+  python bench.py --gpus N --steps K --warmup W [--workload intra|ld|hts|htl] [--resolution 3840x2160] [--full]
   N > 1: either under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
   LOCAL_RANK / WORLD_SIZE in the environment), or plainly `python bench.py --gpus N ...`: without WORLD_SIZE the
   process re-launches itself under torch.distributed.run, one rank per GPU over RCCL (launch_ranks()).
@@ -24,7 +24,10 @@ Other modes:
                 (RCCL point-to-point: north_star's context exchange); time / bytes per hand-off, bit-exact continuation
   --fanout      ONE hierarchical stream, the 8 reconstruction heads of a chunk spread over the ranks
 
-The JSON line (rank 0) carries, besides the driver contract:
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line
+(rank 0) with the driver contract's fields, the loop and the coded rate of the K steps. Everything else is measured with --full,
+behind the K timed steps, and the line then also carries:
+  closure_ok                every rank's decoder output against its encoder's, one step per rate point, behind the timed regions
   encode_fps / decode_fps   SURVEY 8d's metric, measured the reference's way (test_video.py:261-265,
                             321-325, 380-388; test_compress_time.py:60-69): device synchronised, events
                             around every compress / decompress call, the first 4 calls dropped,
@@ -107,20 +110,25 @@ def parse_args():
                    help="ld / hts / htl: ONE running GOP whose temporal state moves to the next rank every K coded units "
                         "(RCCL point-to-point; north_star's context exchange). Reports pictures/s, time and bytes per hand-off "
                         "and whether the stream continued bit-exactly")
+    p.add_argument("--full", action="store_true",
+                   help="behind the K timed steps, everything else the line can report: `sustained`, `closure_ok`, encode_fps / "
+                        "decode_fps, `pipelined`, `other_workloads`, `uhd`, `resolutions`, `roofline`, `cpu_baseline` (the --no-* "
+                        "switches and --min-seconds below take single blocks out again). Without it a run sets up, warms up, times "
+                        "the K steps, writes --dump-outputs and prints the line's headline fields")
     p.add_argument("--no-pipeline", action="store_true",
-                   help="skip the `pipelined` blocks (encoder and decoder objects as a two-stage pipeline on prioritised streams)")
+                   help="--full: skip the `pipelined` blocks (encoder and decoder objects as a two-stage pipeline on prioritised streams)")
     p.add_argument("--one-codec", action="store_true", help="(the default since round 5; kept for old command lines)")
     p.add_argument("--two-codecs", action="store_true", help="(kept for old command lines: the two-object loop is `pipelined`)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip the short runs of the other three workloads")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    p.add_argument("--no-roofline", action="store_true", help="--full: skip `roofline`")
+    p.add_argument("--no-extras", action="store_true", help="--full: skip the short runs of the other three workloads")
     p.add_argument("--resolution", default=None, help="WxH of the synthetic pictures (default 1920x1080; 3840x2160 = configs[4], "
                                                       "the default of --sweep64)")
-    p.add_argument("--no-uhd", action="store_true", help="skip the short 3840x2160 runs of the default line")
+    p.add_argument("--no-uhd", action="store_true", help="--full: skip the short 3840x2160 runs")
     p.add_argument("--no-resolutions", action="store_true",
-                   help="skip the short 1280x720 / 832x480 runs of the default line (the reference's other tuned sizes)")
+                   help="--full: skip the short 1280x720 / 832x480 runs (the reference's other tuned sizes)")
     p.add_argument("--min-seconds", type=float, default=2.0,
-                   help="length of the `sustained` region behind the K timed steps (0 = none)")
+                   help="--full: length of the `sustained` region behind the K timed steps (0 = none)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="after the K timed steps, write what the last of them returned (compress and decompress results, rank 0) "
                         "as DIR/<name>.npy: float32, integers float64, at most 64 MB in all - an array beyond its share is "
@@ -831,6 +839,38 @@ def common_fields(env, fps, elapsed, steps, scaling, metric, config):
                             "plugin_policy": getattr(sys.modules.get("inference_extensions_cuda"), "hw_queue_policy", None)}}
 
 
+def headline_fields(env, work, fanout, elapsed, nbytes):
+    """rank 0's line for the K timed steps of run_default(): the driver contract's fields, the loop and the coded rate"""
+    args, world = env.args, env.world
+    height, width = args.height, args.width
+    fps = (1 if fanout else world) * args.steps * work.frames / elapsed
+    res = "%dx%d" % (width, height)
+    one_object = args.workload == "intra"
+    loop_text = ("one call after the other from one thread: compress, then decompress (%s), no host synchronisation between steps"
+                 % ("ONE codec object codes and decodes, as the reference harness uses its i_frame_net" if one_object
+                    else "separate encoder / decoder objects, the decoder sees only the bytes"))
+    out = common_fields(
+        env, fps, elapsed, args.steps, "strong" if fanout else "weak",
+        "%s YUV420 %s encode+decode pictures per second (%s, real rANS bit streams, q_index in {0,16,32,48,63}; sequential loop: "
+        "compress then decompress per picture)" % ("1080p" if (height, width) == (1080, 1920) else res,
+                                                   "intra" if args.workload == "intra" else "inter", NAMES[args.workload]),
+        {"workload": ("%s " + res + " YUV420, ONE stream over all ranks (rank 0 codes, feature_p broadcast, reconstruction "
+                      "heads fanned out), " if fanout else "%s " + res + " YUV420 on 1xMI355X per rank, ") % NAMES[args.workload]
+                     + "q_index cycling {0,16,32,48,63}, skip_thres 0.15, one step = compress + decompress of %d "
+                       "picture(s)" % work.frames,
+         "sharding": "recon-head fan-out" if fanout else "independent streams (sharding.shard_range)",
+         "codec_objects": "one" if one_object else "separate encoder / decoder",
+         "loop": "sequential",
+         "pictures_per_step": work.frames, "resolution": res})
+    out.update({
+        "full": bool(args.full),
+        "loop": loop_text,
+        "bytes_per_picture": nbytes / args.steps / work.frames,
+        "bpp": 8.0 * nbytes / args.steps / work.frames / (height * width),
+    })
+    return out
+
+
 def run_default(env, make_work):
     """configs[1] / configs[2]: independent streams, one per rank (or --fanout: one hierarchical stream over all ranks)."""
     args, rank, world, dist, device = env.args, env.rank, env.world, env.dist, env.device
@@ -864,6 +904,13 @@ def run_default(env, make_work):
     if args.dump_outputs and rank == 0:         # before the next codec call overwrites the proxy-owned outputs
         shapes = dump_outputs(args.dump_outputs, *work.last_step)
         print("bench.py: step %d's outputs in %s: %s" % (args.warmup + args.steps - 1, args.dump_outputs, shapes), file=sys.stderr)
+    if not args.full:
+        if rank != 0:
+            return None
+        out = headline_fields(env, work, fanout, elapsed, nbytes)
+        out["fps_method"] = "value: K steps of the sequential loop between device synchronisations (nothing else is measured in " \
+                            "this run; --full adds the rest of the line behind the K steps)"
+        return out
 
     # the same loop for >= --min-seconds: the K-step region of a short driver run lasts a fraction of a second
     sustained = None
@@ -892,25 +939,7 @@ def run_default(env, make_work):
         te, td = call_times(work, cursor, ncalls)
     if rank != 0:
         return None
-    fps = (1 if fanout else world) * args.steps * work.frames / elapsed
-    res = "%dx%d" % (width, height)
-    one_object = args.workload == "intra"
-    loop_text = ("one call after the other from one thread: compress, then decompress (%s), no host synchronisation between steps"
-                 % ("ONE codec object codes and decodes, as the reference harness uses its i_frame_net" if one_object
-                    else "separate encoder / decoder objects, the decoder sees only the bytes"))
-    out = common_fields(
-        env, fps, elapsed, args.steps, "strong" if fanout else "weak",
-        "%s YUV420 %s encode+decode pictures per second (%s, real rANS bit streams, q_index in {0,16,32,48,63}; sequential loop: "
-        "compress then decompress per picture)" % ("1080p" if (height, width) == (1080, 1920) else res,
-                                                   "intra" if args.workload == "intra" else "inter", NAMES[args.workload]),
-        {"workload": ("%s " + res + " YUV420, ONE stream over all ranks (rank 0 codes, feature_p broadcast, reconstruction "
-                      "heads fanned out), " if fanout else "%s " + res + " YUV420 on 1xMI355X per rank, ") % NAMES[args.workload]
-                     + "q_index cycling {0,16,32,48,63}, skip_thres 0.15, one step = compress + decompress of %d "
-                       "picture(s)" % work.frames,
-         "sharding": "recon-head fan-out" if fanout else "independent streams (sharding.shard_range)",
-         "codec_objects": "one" if one_object else "separate encoder / decoder",
-         "loop": "sequential",
-         "pictures_per_step": work.frames, "resolution": res})
+    out = headline_fields(env, work, fanout, elapsed, nbytes)
     out.update({
         "fps_method": "value: K steps of the sequential loop between device synchronisations; encode_fps / decode_fps: the "
                       "reference's loop (events around each call on a synchronised device, first %d calls dropped, rank 0), "
@@ -919,9 +948,6 @@ def run_default(env, make_work):
                              "the two-stage pipelines on objects of their own (priority streams); phase B: the per-call event loops "
                              "(encode_fps / decode_fps) and the event-stamped roofline passes on the objects of A1 - no timing event "
                              "and no priority stream exists in the process while a plain loop is measured",
-        "loop": loop_text,
-        "bytes_per_picture": nbytes / args.steps / work.frames,
-        "bpp": 8.0 * nbytes / args.steps / work.frames / (height * width),
         "closure_ok": closure,
     })
     if sustained is not None:

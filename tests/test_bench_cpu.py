@@ -198,7 +198,7 @@ def _run(monkeypatch, capsys, argv):
 
 
 def test_one_json_line_with_the_contract_fields(fake_gpu, monkeypatch, capsys):
-    d = _run(monkeypatch, capsys, ["--steps", "7", "--warmup", "2", "--min-seconds", "0.3"])
+    d = _run(monkeypatch, capsys, ["--full", "--steps", "7", "--warmup", "2", "--min-seconds", "0.3"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "encode_fps", "decode_fps",
                 "other_workloads", "sustained", "uhd", "pipelined", "box", "loop"):
@@ -236,7 +236,7 @@ def test_one_json_line_with_the_contract_fields(fake_gpu, monkeypatch, capsys):
 
 
 def test_timed_region_runs_exactly_k_steps(fake_gpu, monkeypatch, capsys):
-    d = _run(monkeypatch, capsys, ["--steps", "5", "--warmup", "3", "--no-extras", "--no-roofline", "--no-cpu-baseline",
+    d = _run(monkeypatch, capsys, ["--full", "--steps", "5", "--warmup", "3", "--no-extras", "--no-roofline", "--no-cpu-baseline",
                                    "--min-seconds", "0"])
     w = _FakeWork.made[0]
     timed_and_warm = [c for c in w.calls if c[0] == "c" and c[1] < 8]
@@ -260,7 +260,7 @@ class _FakeOutputs(_FakeWork):
 def test_dump_outputs_holds_the_last_timed_step(fake_gpu, monkeypatch, capsys, tmp_path):
     import numpy as np
     monkeypatch.setattr(bench, "IntraWorkload", _FakeOutputs)
-    _run(monkeypatch, capsys, ["--steps", "5", "--warmup", "3", "--no-extras", "--no-roofline", "--no-cpu-baseline",
+    _run(monkeypatch, capsys, ["--full", "--steps", "5", "--warmup", "3", "--no-extras", "--no-roofline", "--no-cpu-baseline",
                                "--min-seconds", "0.1", "--dump-outputs", str(tmp_path)])
     assert len([c for c in _FakeOutputs.made[0].calls if c[0] == "c"]) > 8       # codec calls after the timed steps
     got = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
@@ -294,6 +294,56 @@ def test_dump_outputs_samples_beyond_the_budget(monkeypatch, tmp_path):
     assert np.all(np.diff(a["compress_x_hat.npy"]) > 0) and np.array_equal(a["decompress_x_hat.npy"], a["compress_x_hat.npy"] + 1)
 
 
+def test_a_plain_run_times_the_k_steps_and_nothing_else(fake_gpu, monkeypatch, capsys, tmp_path):
+    """without --full: set-up, the W warm-up steps, the K timed steps, --dump-outputs and the line - no codec call behind the
+    K steps, no other codec object, no roofline, CPU baseline or rate sweep; the contract's fields say what --full's say"""
+    import numpy as np
+    skipped = []
+    monkeypatch.setattr(bench, "roofline", lambda work, n=5: skipped.append("roofline"))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda net, device: skipped.append("cpu_baseline"))
+    monkeypatch.setattr(bench, "sweep64_block", lambda env, kind, h, w, units: skipped.append("sweep64"))
+    monkeypatch.setattr(bench, "IntraWorkload", _FakeOutputs)
+    d = _run(monkeypatch, capsys, ["--steps", "5", "--warmup", "3", "--dump-outputs", str(tmp_path)])
+    assert skipped == [] and len(_FakeOutputs.made) == 1
+    assert _FakeOutputs.made[0].calls == [(k, i) for i in range(3 + 5) for k in ("c", "d")]
+    assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 3 and d["n_gpus"] == 1
+    assert d["value"] == pytest.approx(5 / (d["ms_per_step"] * 5 / 1e3), rel=1e-6) and d["ms_per_step"] > 11.0
+    for key in ("sustained", "closure_ok", "encode_fps", "decode_fps", "pipelined", "other_workloads", "uhd", "resolutions",
+                "roofline", "cpu_baseline", "measurement_order"):
+        assert key not in d and key not in d["config"], key
+    got = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert (got["compress_x_hat"] == 3 + 5 - 1).all() and (got["decompress_x_hat_0"] == 3 + 5 - 1).all()
+    full = _run(monkeypatch, capsys, ["--full", "--steps", "5", "--warmup", "3", "--no-extras", "--min-seconds", "0"])
+    assert full["full"] is True and "closure_ok" in full and "encode_fps" in full
+    for key in ("metric", "unit", "higher_is_better", "dtype", "scaling", "loop", "data"):
+        assert d[key] == full[key], key
+    assert d["config"] == {k: v for k, v in full["config"].items() if k not in ("encode_fps", "decode_fps")}
+
+
+@pytest.mark.parametrize("rank", [0, 1])
+def test_a_plain_rank_of_a_two_gpu_launch(fake_gpu, monkeypatch, capsys, rank):
+    """without --full every rank codes its share of the 2 K steps and stops: one max over ranks (the K steps), no closure vote"""
+    fake = _FakeDist(rank, 2)
+    monkeypatch.setitem(sys.modules, "torch.distributed", fake)
+    monkeypatch.setattr(torch, "distributed", fake, raising=False)
+    monkeypatch.setattr(torch, "tensor", lambda data, dtype=None, device=None: torch.as_tensor(data, dtype=dtype))
+    monkeypatch.setenv("RANK", str(rank))
+    monkeypatch.setenv("LOCAL_RANK", str(rank))
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1"])
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    w = _FakeWork.made[0]
+    assert [c[1] for c in w.calls if c[0] == "c"] == [0] + [1 + 4 * rank + i for i in range(4)]
+    assert fake.reduced == 1 and not hasattr(fake, "closure_votes") and len(_FakeWork.made) == 1
+    if rank == 1:
+        assert lines == []
+        return
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "closure_ok" not in d and "sustained" not in d
+    assert d["value"] == pytest.approx(2 * 4 / (d["ms_per_step"] * 4 / 1e3), rel=1e-6)
+
+
 def test_steps_must_be_positive(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit):
@@ -322,7 +372,7 @@ def test_reset_cadence_of_the_inter_workloads():
 
 
 def test_inter_workload_line(fake_gpu, monkeypatch, capsys):
-    d = _run(monkeypatch, capsys, ["--steps", "6", "--warmup", "1", "--workload", "hts", "--no-extras", "--min-seconds", "0"])
+    d = _run(monkeypatch, capsys, ["--full", "--steps", "6", "--warmup", "1", "--workload", "hts", "--no-extras", "--min-seconds", "0"])
     assert d["config"]["pictures_per_step"] == 8 and "HT-S" in d["metric"]
     assert d["value"] == pytest.approx(8 * 6 / (d["ms_per_step"] * 6 / 1e3), rel=1e-6)
     assert "cpu_baseline" not in d                        # the CPU baseline belongs to the headline workload
@@ -343,7 +393,7 @@ def test_inter_workload_line(fake_gpu, monkeypatch, capsys):
 
 
 def test_no_pipeline_switch(fake_gpu, monkeypatch, capsys):
-    d = _run(monkeypatch, capsys, ["--steps", "3", "--warmup", "1", "--workload", "ld", "--no-extras", "--min-seconds", "0",
+    d = _run(monkeypatch, capsys, ["--full", "--steps", "3", "--warmup", "1", "--workload", "ld", "--no-extras", "--min-seconds", "0",
                                    "--no-pipeline"])
     assert "pipelined" not in d and "one call after the other" in d["loop"] and d["ms_per_step"] > 11.0
     assert len(_FakeWork.made) == 1
@@ -404,7 +454,8 @@ def test_one_rank_of_a_two_gpu_launch(fake_gpu, monkeypatch, capsys, rank):
     monkeypatch.setenv("RANK", str(rank))
     monkeypatch.setenv("LOCAL_RANK", str(rank))
     monkeypatch.setenv("WORLD_SIZE", "2")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline", "--min-seconds", "0.1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline",
+                                      "--min-seconds", "0.1"])
     bench.main()
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     w = _FakeWork.made[0]
@@ -433,7 +484,8 @@ def test_fan_out_line(fake_gpu, monkeypatch, capsys):
     monkeypatch.setenv("RANK", "0")
     monkeypatch.setenv("LOCAL_RANK", "0")
     monkeypatch.setenv("WORLD_SIZE", "2")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--workload", "hts", "--fanout", "--steps", "3", "--warmup", "1", "--min-seconds", "0"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--gpus", "2", "--workload", "hts", "--fanout", "--steps", "3", "--warmup", "1",
+                                      "--min-seconds", "0"])
     bench.main()
     d = json.loads([l for l in capsys.readouterr().out.splitlines() if l.strip()][0])
     assert d["scaling"] == "strong" and d["n_gpus"] == 2 and d["config"]["sharding"] == "recon-head fan-out"
@@ -524,7 +576,7 @@ def test_gpus_flag_spawns_the_ranks_itself():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_launch_child.py")
-    res = subprocess.run([sys.executable, child, "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline", "--min-seconds", "0.2"],
+    res = subprocess.run([sys.executable, child, "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-roofline", "--min-seconds", "0.2"],
                          env=env, capture_output=True, text=True, timeout=280)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip().startswith("{")]

@@ -1,4 +1,4 @@
-"""bench.py's multi-rank launch path with the REAL codec on a 1-GPU box (-m gpu).
+"""bench.py's multi-rank launch path with the REAL codec on a 1-GPU box (-m gpu), and its plain one-GPU run.
 
 `python bench.py --gpus 2` re-launches itself under torch.distributed.run (bench.launch_ranks); here both ranks are
 pinned to cuda:0 (DCVC_BENCH_ONE_DEVICE=1) and talk over gloo (DCVC_BENCH_BACKEND=gloo): real sharding
@@ -31,12 +31,27 @@ def _bench(*argv):
 
 @pytest.mark.timeout(900)
 def test_two_ranks_code_their_own_pictures():
-    d = _bench("--gpus", "2", "--steps", "4", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-roofline",
+    d = _bench("--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-roofline",
                "--min-seconds", "0")
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["scaling"] == "weak"
     assert d["closure_ok"] is True                     # MIN over both ranks' own codec objects
     assert d["value"] > 0 and d["bytes_per_picture"] > 1000
     assert d["value"] == pytest.approx(2 * 4 / (d["ms_per_step"] * 4 / 1e3), rel=1e-6)
+
+
+@pytest.mark.timeout(900)
+def test_a_plain_run_reports_the_timed_steps(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line of the K steps and nothing behind them, and
+    --dump-outputs holds the last timed step"""
+    import numpy as np
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 3 and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["bytes_per_picture"] > 1000 and d["unit"] == "frames/s"
+    assert d["value"] == pytest.approx(3 / (d["ms_per_step"] * 3 / 1e3), rel=1e-6)
+    assert not {"closure_ok", "encode_fps", "sustained", "pipelined", "other_workloads", "roofline", "cpu_baseline"} & set(d)
+    x = np.load(tmp_path / "compress_x_hat.npy")
+    assert np.array_equal(x, np.load(tmp_path / "decompress_x_hat.npy")) and np.isfinite(x).all()
+    assert np.load(tmp_path / "compress_bit_stream.npy").size > 1000
 
 
 @pytest.mark.timeout(900)

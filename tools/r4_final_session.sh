@@ -25,7 +25,7 @@ cp $O/r04_hbm_traffic.json profiles/r04_hbm_traffic.json
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/r04_test_gpu.log
 tail -4 $O/r04_test_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.log
-timeout 900 python bench.py > $O/r04_bench_line.json 2> $O/r04_bench.err
+timeout 900 python bench.py --full > $O/r04_bench_line.json 2> $O/r04_bench.err
 tail -1 $O/r04_bench_line.json | cut -c1-600
 tail -2 $O/r04_bench.err
 # block bench, every shape: this build (8 waves) and the same sources dispatching to the 4-wave kernel (tools/_bin/w4.so =
@@ -57,6 +57,6 @@ cat $O/r04_block_clocks.txt
 ( for i in $(seq 1 40); do echo "== $(date +%s.%N)"; rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power \(W\)|sclk"; sleep 0.25; done ) > $O/r04_smi_during_bench.txt 2>&1 &
 SMI=$!
 sleep 1
-timeout 600 python bench.py --steps 100 --min-seconds 8 --no-extras --no-cpu-baseline --no-roofline > $O/r04_bench_sustained.json 2> /dev/null
+timeout 600 python bench.py --full --steps 100 --min-seconds 8 --no-extras --no-cpu-baseline --no-roofline > $O/r04_bench_sustained.json 2> /dev/null
 wait $SMI
 grep -E "Power \(W\)" $O/r04_smi_during_bench.txt | sort | uniq -c | sort -rn | head -5

@@ -31,7 +31,7 @@ cp $O/r05_hbm_traffic.json profiles/r05_hbm_traffic.json
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -25 > $O/r05_test_gpu.log
 tail -6 $O/r05_test_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.log
-timeout 900 python bench.py > $O/r05_bench_line.json 2> $O/r05_bench.err
+timeout 900 python bench.py --full > $O/r05_bench_line.json 2> $O/r05_bench.err
 tail -c 400 $O/r05_bench_line.json
 tail -2 $O/r05_bench.err
 cd /tmp

@@ -20,7 +20,7 @@ for m in sliding ahead deep; do
 done
 cat $O/dwconv_ab.txt
 timeout 900 python -m pytest tests/test_kernels_gpu.py -m gpu -q -x -k "dwconv" -s 2>&1 | grep -v "^$" | tail -8 | tee $O/tests_dwconv.log
-A="--steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-pipeline --min-seconds 2"
+A="--full --steps 40 --warmup 5 --no-extras --no-cpu-baseline --no-pipeline --min-seconds 2"
 for m in sliding deep; do
   DCVC_DWCONV_MODE=$m timeout 300 python bench.py $A > $O/intra_dw_$m.json 2> $O/intra_dw_$m.err
   python - <<EOF
@@ -30,7 +30,7 @@ print("intra, dwconv $m: value %.1f sustained %.1f enc %.1f dec %.1f closure %s"
 EOF
 done 2>&1 | tee $O/intra_dw.txt
 for w in htl hts; do
-  timeout 300 python bench.py --workload $w --steps 48 --warmup 12 --no-extras --no-cpu-baseline --no-roofline --min-seconds 2 > $O/alone_$w.json 2> $O/alone_$w.err
+  timeout 300 python bench.py --full --workload $w --steps 48 --warmup 12 --no-extras --no-cpu-baseline --no-roofline --min-seconds 2 > $O/alone_$w.json 2> $O/alone_$w.err
   python - <<EOF
 import json
 d = json.load(open("$O/alone_$w.json"))
@@ -40,7 +40,7 @@ done 2>&1 | tee $O/alone.txt
 timeout 1500 python -m pytest tests/test_qsweep_gpu.py tests/test_bench_gpu.py tests/test_fullsize_gpu.py -m gpu -q -x -k "all_64 or order_covers or hand_a_running or rate_sweep or tolerance or qends_1920 or 3840x2160_q" -s > $O/tests_new.log 2>&1
 echo "tests rc $?" >> $O/tests_new.log
 tail -25 $O/tests_new.log
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err
 echo "bench rc $?"
 python - <<EOF
 import json

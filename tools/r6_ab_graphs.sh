@@ -1,5 +1,5 @@
 set -x
-B="python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --min-seconds 0"
+B="python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --min-seconds 0"
 for w in ld hts; do
 for g in 0 1; do
   DCVC_BENCH_GRAPHS=$g $B --workload $w 2>/dev/null | python -c "

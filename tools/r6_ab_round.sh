@@ -2,7 +2,7 @@
 # round 6 against round 5 on ONE box in ONE session: bench.py's sequential loop with round 5's library (tools/_bin/r05.so =
 # tools/build_variant.sh r05 --rev 6d43745, loaded through DCVC_LIB; the build / ABI check of this tree is skipped for it: it
 # lacks the round-6 entry points) and with this tree's, interleaved, two passes
-ARGS="--steps 60 --warmup 10 --no-cpu-baseline --no-uhd --no-resolutions --no-extras --no-roofline --no-pipeline --min-seconds 0"
+ARGS="--full --steps 60 --warmup 10 --no-cpu-baseline --no-uhd --no-resolutions --no-extras --no-roofline --no-pipeline --min-seconds 0"
 for pass in 1 2; do
 for w in intra ld hts htl; do
 for l in r05 r06; do

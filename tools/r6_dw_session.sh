@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_kernels_gpu.py -x -q -m gpu -k "depthwis
 if [ "$1" != "quick" ]; then
   timeout 1500 python -m pytest tests -x -q -m gpu > $O/test_gpu.log 2>&1; tail -3 $O/test_gpu.log
 fi
-B="python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --no-resolutions --min-seconds 0"
+B="python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --no-resolutions --min-seconds 0"
 for pass in 1 2 3; do
 for w in ld; do
 for g in 0 1; do

@@ -35,7 +35,7 @@ cat $O/r06_block_counters.txt
 timeout 2400 python -m pytest tests -m gpu -q -rs 2>&1 | tail -25 > $O/r06_test_gpu.log
 tail -6 $O/r06_test_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.log
-timeout 900 python bench.py > $O/r06_bench_line.json 2> $O/r06_bench.err
+timeout 900 python bench.py --full > $O/r06_bench_line.json 2> $O/r06_bench.err
 tail -c 600 $O/r06_bench_line.json
 tail -2 $O/r06_bench.err
 cd /tmp
@@ -50,13 +50,13 @@ done
 cd $R
 # per-shape timing of the contraction launches (bench.py's event-stamped pass)
 for w in ld intra hts htl; do
-  DCVC_BENCH_SHAPES=$O/r06_gemm_shapes_$w.csv timeout 300 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-uhd --no-resolutions --no-extras --no-pipeline --min-seconds 0 > /dev/null 2>&1
+  DCVC_BENCH_SHAPES=$O/r06_gemm_shapes_$w.csv timeout 300 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-uhd --no-resolutions --no-extras --no-pipeline --min-seconds 0 > /dev/null 2>&1
 done
 # round 6 against round 5's library on this box (tools/_bin/r05.so, when it travelled with the tree)
 if [ -f tools/_bin/r05.so ]; then bash tools/r6_ab_round.sh 2>/dev/null | grep "^pass" > $O/r06_round_ab_closing.txt; cat $O/r06_round_ab_closing.txt; fi
 # round 6, last session: the depthwise conv inside the (256, 128) / (384, 192) block launches - the LD codec with and without on this box
 # (fps, kernel trace), the launch under core_bench with its in-kernel stamps, the issue-rate probe behind its arithmetic
-B2="python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --no-resolutions --min-seconds 0"
+B2="python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-uhd --no-extras --no-roofline --no-pipeline --no-resolutions --min-seconds 0"
 for pass in 1 2 3; do for g in 0 1; do
   DCVC_NSPLIT_DW=$g timeout 300 $B2 --workload ld 2>/dev/null | python -c "
 import json,sys

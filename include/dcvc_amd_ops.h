@@ -42,7 +42,9 @@ int dcvc_conv_kxk(const void* x, int ldx, const void* w, const void* bias, void*
                   int in_h, int in_w, int cin, int cout, int ksize, int stride, int pad,
                   void* stream);
 
-/* def_cutlass.h:39-40 transposed_conv: 2x2, stride 2, no bias. w: [4 = dy*2+dx][cout][cin]. */
+/* def_cutlass.h:39-40 transposed_conv: 2x2, stride 2, no bias. w: [4 = dy*2+dx][cout][cin].
+ * cout must be a multiple of 128 (a channel tile of the one launch must not straddle two output pixels): cout = 192 and
+ * other such widths are rejected with an error, not computed (tests/test_gemm_matrix_gpu.py). */
 int dcvc_tconv2x2(const void* x, int ldx, const void* w, void* y, int ldy,
                   int in_h, int in_w, int cin, int cout, void* stream);
 

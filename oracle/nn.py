@@ -35,6 +35,14 @@ def mfma16(c, a16, b16):
     return np.float32(_lib().orc_mfma16(ctypes.c_float(float(c)), _p(a16), _p(b16)))
 
 
+def wsilu(v):
+    """WSiLU of float32 values exactly as the epilogues evaluate it (arith.h wsilu_spec): float32 in, float32 out."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    out = np.empty_like(v)
+    _lib().orc_wsilu(_p(v), _p(out), ctypes.c_int64(v.size))
+    return out
+
+
 def conv1x1(x, w, bias=None, r1=None, r2=None, q=None, q2=None, wsilu=False, chunk_add=False):
     """x [..., K] fp16, w [N, K]; returns [..., N] (or N/4 with chunk_add) fp16."""
     lead = x.shape[:-1]

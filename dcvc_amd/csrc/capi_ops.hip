@@ -490,6 +490,25 @@ int dcvc_dcb_tail(const void* w1, const void* b1, const void* t, int ldt, const 
     });
 }
 
+int dcvc_dcb_tail_b(const void* w1, const void* b1, const void* t, int ldt, const void* dw, const void* x, int ldx,
+                    const void* w3, const void* b3,
+                    const void* w0, const void* b0, const void* w2, const void* b2, const void* q, const void* q2,
+                    void* y, int ldy, int Hh, int W, int c, int cdc, int cffn, int shortcut, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_b(n, {w1 != nullptr ? w1 : t, x, w3, b3, w0, b0, w2, b2, y}, {Hh, W, c, cdc, cffn}, "dcb_tail_b");
+        if (w1 != nullptr && (b1 == nullptr || dw == nullptr)) throw std::invalid_argument("dcb_tail_b: dc.0 inside needs its bias and the depthwise taps");
+        if (ldx < c || ldy < c || (w1 == nullptr && ldt < cdc)) throw std::invalid_argument("dcb_tail_b: leading dimensions below the channel counts");
+        if (w1 != nullptr && x == y) throw std::invalid_argument("dcb_tail_b with dc.0 inside cannot run in place");
+        dcvc::kernels_init();
+        dcvc::DcbTailDesc d;
+        d.w1 = H(w1); d.b1 = H(b1); d.t = H(t); d.ldt = ldt; d.dw = H(dw); d.x = H(x); d.ldx = ldx; d.w3 = H(w3); d.b3 = H(b3);
+        d.w0 = H(w0); d.b0 = H(b0); d.w2 = H(w2); d.b2 = H(b2); d.q = H(q); d.q2 = H(q2);
+        d.y = H(y); d.ldy = ldy; d.H = Hh; d.W = W; d.c = c; d.cdc = cdc; d.cffn = cffn; d.shortcut = shortcut != 0; d.n = n;
+        dcvc::dcb_tail(d, S(stream));
+    });
+}
+
 int dcvc_scale_clamped(const void* x, int ldx, const void* q, int ldq, void* y, int ldy, int pixels,
                        int C, int reciprocal, void* stream)
 {

@@ -317,9 +317,11 @@ void launch_pair(const PairParams& p, hipStream_t stream)
     const int tiles = (p.M + 32 * PXT - 1) / (32 * PXT);
     const int grid = tiles < cus ? tiles : cus;
     hipEvent_t ev0, ev1;
-    // bench.py's roofline pass: 2 M C kflop = the launch's FLOPs (family 6 in bits 28..31, ops.h)
+    // bench.py's roofline pass: 2 M C kflop = the launch's FLOPs (family 6 in bits 28..31 | inner width | input width << 12 |
+    // 64-pixel workgroups << 25, ops.h)
     const int kflop = CIN + CI;
-    if (gemm_profile_slot(GemmLaunchInfo{p.M, C, kflop, 0x60000000, 0.f}, &ev0, &ev1)) {
+    constexpr int variant = 0x60000000 | CI | (CIN << 12) | ((PXT == 2 ? 1 : 0) << 25);
+    if (gemm_profile_slot(GemmLaunchInfo{p.M, C, kflop, variant, 0.f}, &ev0, &ev1)) {
         hipExtLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), smem, stream, ev0, ev1, 0, p);
     } else {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), smem, stream, p);

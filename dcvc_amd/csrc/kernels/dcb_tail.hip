@@ -571,10 +571,12 @@ void launch(const TailParams& p, int pics, hipStream_t stream)
                   "hipFuncSetAttribute(dcb_tail)");
     });
     const int grid = ((p.H + PH - 1) / PH) * ((p.W + PW - 1) / PW);
-    // bench.py's roofline pass: [dc.0] + dc.3 + ffn.0 + ffn.2 as one record (family 2 in bits 28..30, ops.h)
+    // bench.py's roofline pass: [dc.0] + dc.3 + ffn.0 + ffn.2 as one record (family 2 in bits 28..31 | block width |
+    // depthwise conv << 24 | quant << 26 | dc.0 inside << 27, ops.h)
     hipEvent_t ev0, ev1;
     const int kflop = (DC0 ? p.CD : 0) + p.CD + 5 * p.CF;
-    if (gemm_profile_slot(GemmLaunchInfo{pics * p.H * p.W, C, kflop, 0x20000000, 0.f}, &ev0, &ev1)) {
+    constexpr int variant = 0x20000000 | C | ((DW ? 1 : 0) << 24) | ((QUANT ? 1 : 0) << 26) | ((DC0 ? 1 : 0) << 27);
+    if (gemm_profile_slot(GemmLaunchInfo{pics * p.H * p.W, C, kflop, variant, 0.f}, &ev0, &ev1)) {
         hipExtLaunchKernelGGL(kern, dim3(grid, pics), dim3(NTHREADS), smem_bytes, stream, ev0, ev1, 0, p);
     } else {
         hipLaunchKernelGGL(kern, dim3(grid, pics), dim3(NTHREADS), smem_bytes, stream, p);

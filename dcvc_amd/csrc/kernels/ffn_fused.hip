@@ -343,8 +343,11 @@ void launch(const FfnParams& p, hipStream_t stream)
         hip_check(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes),
                   "hipFuncSetAttribute(ffn_fused)");
     });
-    hipEvent_t ev0, ev1;      // bench.py's roofline pass: ffn.0 + ffn.2 as one record (family 3 in bits 28..30, ops.h)
-    if (gemm_profile_slot(GemmLaunchInfo{p.M, p.C, 5 * p.CF, 0x30000000, 0.f}, &ev0, &ev1)) {
+    // bench.py's roofline pass: ffn.0 + ffn.2 as one record (family 3 in bits 28..31 | block width | quant << 26 |
+    // second residual << 27, ops.h)
+    hipEvent_t ev0, ev1;
+    constexpr int variant = 0x30000000 | NT2 * 128 | ((QUANT ? 1 : 0) << 26) | ((RES2 ? 1 : 0) << 27);
+    if (gemm_profile_slot(GemmLaunchInfo{p.M, p.C, 5 * p.CF, variant, 0.f}, &ev0, &ev1)) {
         hipExtLaunchKernelGGL(kern, dim3((p.M + BM - 1) / BM), dim3(NTHREADS), smem_bytes, stream, ev0, ev1, 0, p);
     } else {
         hipLaunchKernelGGL(kern, dim3((p.M + BM - 1) / BM), dim3(NTHREADS), smem_bytes, stream, p);

@@ -41,6 +41,13 @@ size_t gemm_profile_launches(GemmLaunchInfo* out, size_t cap);
 // info.K is chosen such that 2 * M * N * K is the launch's FLOP count; variant bits 28..31 name the kernel
 // family: 0 conv_gemm, 2 dcb_tail, 3 ffn_fused, 4 dcb_nsplit, 5 dcb_nsplit8 (its variant also carries the inner width in bits
 // 0..11 and the NEXT slot - 0, 1 = next dc.0, NN = closing conv - in bits 12..23), 6 dcb_pair8 (8 was round 2's dcb_core).
+// Bits 0..27 name the instantiation that ran; every field keeps the place it has in any family that carries it:
+//   bits 0..11   inner width (dcb_nsplit8, dcb_pair8) or block width C (dcb_tail, ffn_fused)
+//   bits 12..23  dcb_nsplit8: the NEXT slot as above; dcb_pair8: the adaptor's input width CIN
+//   bit 24       the depthwise conv runs inside (dcb_nsplit8, dcb_tail)
+//   bit 25       64-pixel workgroups (dcb_nsplit8, dcb_pair8; 0 = 32 pixels)
+//   bit 26       fused quant scale q (dcb_tail, ffn_fused)
+//   bit 27       dcb_tail: dc.0 inside the launch; ffn_fused: second residual r2
 bool gemm_profile_slot(const GemmLaunchInfo& info, hipEvent_t* start, hipEvent_t* stop);
 // Tuning aid: when non-null, wave 0 of every workgroup of the following contraction launches
 // writes up to 16 shader-clock stamps (kernel entry, prologue issued, start of k-steps 0..7, main

@@ -164,6 +164,13 @@ int dcvc_dcb_tail(const void* w1, const void* b1, const void* t, int ldt, const 
                   const void* w3, const void* b3,
                   const void* w0, const void* b0, const void* w2, const void* b2, const void* q, const void* q2,
                   void* y, int ldy, int H, int W, int c, int cdc, int cffn, int shortcut, void* stream);
+/* Batched form of dcvc_dcb_tail (intra batches): n (1..16) pictures of H x W back to back in t, x and y, each with its own
+ * halo (the depthwise conv and dc.0 inside never read a neighbouring picture). Refuses, like the other _b forms, n outside
+ * 1..16, null operands, non-positive sizes and leading dimensions below the channel counts. */
+int dcvc_dcb_tail_b(const void* w1, const void* b1, const void* t, int ldt, const void* dw, const void* x, int ldx,
+                    const void* w3, const void* b3,
+                    const void* w0, const void* b0, const void* w2, const void* b2, const void* q, const void* q2,
+                    void* y, int ldy, int H, int W, int c, int cdc, int cffn, int shortcut, int n, void* stream);
 
 /* Debugging aid (no reference counterpart): device buffer [H*W][cdc] that receives dc.0's output from
  * the following dcvc_dcb_tail launches with dc.0 inside; NULL = off. */

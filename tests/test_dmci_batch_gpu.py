@@ -138,6 +138,22 @@ def test_kernel_b_refusals():
     assert f(_p(x), 64, _p(x), _p(x), 64, 0, 4, 64, 2, _stream()) < 0
     f = _fn("dcvc_crop_b", [_vp, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _vp])
     assert f(_p(x), 64, 4, 4, _p(x), 64, 5, 4, 64, 2, _stream()) < 0      # crop taller than its input
+    f = _fn("dcvc_dcb_tail_b", [_vp, _vp, _vp, _ci, _vp, _vp, _ci] + [_vp] * 9 + [_ci] * 8 + [_vp])
+    z = torch.zeros((2 * 16, 512), dtype=torch.half, device="cuda")
+    y = torch.full((2 * 16, 256), 7.0, dtype=torch.half, device="cuda")
+    ws = [_p(z)] * 6                       # w3, b3, w0, b0, w2, b2
+
+    def tail_b(n, t=_p(z), x=_p(z), ldx=256, Hh=4, w1=None, b1=None, dw=None):
+        return f(w1, b1, t, 128, dw, x, ldx, *ws, None, None, _p(y), 256, Hh, 4, 256, 128, 128, 0, n, _stream())
+    for n in (0, 17):
+        assert tail_b(n) < 0
+    assert tail_b(2, t=None) < 0                                            # neither dc.0's output nor its weights
+    assert tail_b(2, x=None) < 0
+    assert tail_b(2, Hh=0) < 0
+    assert tail_b(2, ldx=128) < 0                                           # leading dimension below c
+    assert tail_b(2, w1=_p(z), b1=_p(z)) < 0                                # dc.0 inside without the depthwise taps
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
 
 
 # ------------------------------------------------------------------------------------------------ codec

@@ -10,6 +10,8 @@
 
 struct dcvc_dmci {
     dcvc::DmciCodec codec;
+    int64_t est_kept[dcvc::DmciCodec::kMaxBatch] = {};      // y symbols of the pictures of the last size probe
+    int est_n = 0;
 };
 
 struct dcvc_dmcld {
@@ -146,6 +148,41 @@ int dcvc_dmci_decompress_batch(dcvc_dmci* c, int n, const uint8_t* const* stream
         c->codec.decompress_batch(n, streams, nbytes, ec_parallel, qp, height, width, static_cast<dcvc::half_t*>(x_hat),
                                   static_cast<hipStream_t>(stream));
     });
+}
+
+int dcvc_dmci_estimate_bits_batch(dcvc_dmci* c, int n, const void* x, int height, int width, int qp, int padding_b,
+                                  int padding_r, int64_t* out_units, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_batch(c, n);
+        if (x == nullptr || out_units == nullptr) throw std::invalid_argument("estimate_bits: null picture or result pointer");
+        check_padding16(height, width, padding_b, padding_r);
+        c->est_n = 0;
+        c->codec.estimate_bits(n, static_cast<const dcvc::half_t*>(x), height, width, qp, out_units, c->est_kept,
+                               static_cast<hipStream_t>(stream));
+        c->est_n = n;
+    });
+}
+
+int dcvc_dmci_estimate_bits(dcvc_dmci* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                            int64_t* out_units, void* stream)
+{
+    return dcvc_dmci_estimate_bits_batch(c, 1, x, height, width, qp, padding_b, padding_r, out_units, stream);
+}
+
+int64_t dcvc_dmci_estimate_symbols(dcvc_dmci* c, int i)
+{
+    int64_t n = -1;
+    const int rc = dcvc::guarded([&] {
+        if (c == nullptr || i < 0 || i >= c->est_n) throw std::invalid_argument("estimate_symbols: no such picture in the last size probe");
+        n = c->est_kept[i];
+    });
+    return rc < 0 ? rc : n;
+}
+
+int dcvc_ec_parallel_for(int64_t symbols)
+{
+    return dcvc::ec_parallel_for(symbols > 0x7fffffff ? 0x7fffffff : static_cast<int>(symbols < 0 ? 0 : symbols));
 }
 
 int dcvc_dmci_set_use_graphs(dcvc_dmci* c, int on)

@@ -6,6 +6,7 @@
 #include <stdexcept>
 #include "dcvc_amd_ops.h"
 #include "kernels/ops.h"
+#include "rans/code_length.h"
 
 namespace {
 
@@ -804,5 +805,52 @@ long long dcvc_gemm_profile_launches(void* records, long long cap)
     return n;
 }
 
+// ---- code length (host tables: rans/code_length.cpp; sums: kernels/code_length.hip)
+int dcvc_code_length_table(const int32_t* cdfs, int num_cdf, int stride, const int32_t* cdf_sizes, int cols, uint32_t* out)
+{
+    return dcvc::guarded([&] { dcvc::code_length_table(cdfs, num_cdf, stride, cdf_sizes, cols, out); });
+}
+
+uint32_t dcvc_code_length_cost(int freq, int bypass_groups)
+{
+    return dcvc::code_length_cost(freq, bypass_groups);
+}
+
+long long dcvc_predicted_stream_bytes(long long y_units, long long z_units, int ec_parallel)
+{
+    long long n = -1;
+    dcvc::guarded([&] { n = dcvc::predicted_stream_bytes(y_units, z_units, ec_parallel); });
+    return n;
+}
+
+int dcvc_code_length_y(const void* sym, long long sym_stride, const void* cond, long long cond_stride, const void* totals,
+                       int totals_stride, int n_totals, int count, const void* table, int num_cdf, void* out, int n,
+                       void* stream)
+{
+    return dcvc::guarded([&] {
+        if (n < 1 || n > 65535 || out == nullptr) throw std::invalid_argument("code_length_y: bad batch size or null output");
+        dcvc::CodeLengthY d;
+        d.sym = static_cast<const int16_t*>(sym); d.sym_stride = sym_stride;
+        d.cond = static_cast<const uint8_t*>(cond); d.cond_stride = cond_stride;
+        d.totals = static_cast<const int32_t*>(totals); d.totals_stride = totals_stride; d.n_totals = n_totals;
+        d.count = count; d.table = static_cast<const uint32_t*>(table); d.num_cdf = num_cdf;
+        d.out = static_cast<unsigned long long*>(out); d.out_stride = 2; d.kept_slot = 1; d.n = n;
+        dcvc::hip_check(hipMemsetAsync(out, 0, sizeof(unsigned long long) * 2 * n, S(stream)), "hipMemsetAsync(code length)");
+        dcvc::code_length_y(d, S(stream));
+    });
+}
+
+int dcvc_code_length_z(const void* z, int count, int ch, const void* table, void* out, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        if (n < 1 || n > 65535 || out == nullptr) throw std::invalid_argument("code_length_z: bad batch size or null output");
+        dcvc::CodeLengthZ d;
+        d.z = static_cast<const int8_t*>(z); d.count = count; d.ch = ch;
+        d.table = static_cast<const uint32_t*>(table);
+        d.out = static_cast<unsigned long long*>(out); d.out_stride = 1; d.n = n;
+        dcvc::hip_check(hipMemsetAsync(out, 0, sizeof(unsigned long long) * n, S(stream)), "hipMemsetAsync(code length)");
+        dcvc::code_length_z(d, S(stream));
+    });
+}
 
 }  // extern "C"

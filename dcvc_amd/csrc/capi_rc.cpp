@@ -1,0 +1,68 @@
+// C ABI of the rate control (include/dcvc_amd_rc.h).
+#include "capi_common.h"
+#include "codec/rate_control.h"
+#include "dcvc_amd_rc.h"
+
+#include <stdexcept>
+
+struct dcvc_rc {
+    dcvc::TargetBpp ctl;
+};
+
+extern "C" {
+
+dcvc_rc* dcvc_rc_create(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus,
+                        int qp_min, int qp_max, double slope)
+{
+    dcvc_rc* rc = nullptr;
+    dcvc::guarded([&] {
+        rc = new dcvc_rc{dcvc::TargetBpp(target_bpp, pixels_per_picture, qp0, horizon, intra_bonus, qp_min, qp_max, slope)};
+    });
+    return rc;
+}
+
+void dcvc_rc_destroy(dcvc_rc* rc)
+{
+    delete rc;
+}
+
+int dcvc_rc_next_qp(const dcvc_rc* rc, int is_intra)
+{
+    int qp = -1;
+    const int e = dcvc::guarded([&] {
+        if (rc == nullptr) throw std::invalid_argument("null rate controller");
+        qp = rc->ctl.next_qp(is_intra != 0);
+    });
+    return e < 0 ? e : qp;
+}
+
+int dcvc_rc_update(dcvc_rc* rc, double bits, int pictures, int is_intra)
+{
+    return dcvc::guarded([&] {
+        if (rc == nullptr) throw std::invalid_argument("null rate controller");
+        rc->ctl.update(bits, pictures, is_intra != 0);
+    });
+}
+
+double dcvc_rc_state_qp(const dcvc_rc* rc)
+{
+    return rc ? rc->ctl.qp() : -1.0;
+}
+
+int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int qp_min, int qp_max,
+                               int* probes)
+{
+    int qp = -1;
+    const int e = dcvc::guarded([&] {
+        if (estimate == nullptr) throw std::invalid_argument("pick_qp_for_budget: null estimate");
+        qp = dcvc::pick_qp_for_budget([&](int q) { return estimate(q, user); }, budget_bits, qp_min, qp_max, probes);
+    });
+    return e < 0 ? e : qp;
+}
+
+int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits)
+{
+    return dcvc::intra_budget_bits(target_bpp, pixels_per_picture, k, spent_bits);
+}
+
+}  // extern "C"

@@ -9,6 +9,7 @@
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
+//               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16]
 //               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
@@ -35,6 +36,16 @@
 //               DESIGN.md 14). Encode: all-intra runs only (no --inter, or --intra-period 1); the file is byte-identical to
 //               --batch 1, a short last batch included. Decode: up to N consecutive I units of one size and one qp per call;
 //               outputs and log as with --batch 1 (test_time aside).
+//               --target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json] (encode):
+//               code to an average of B bits per pixel instead of a constant q_index. All-intra runs (no
+//               --inter, or --intra-period 1): every picture gets the largest q_index in [--qp-min, --qp-max] whose
+//               predicted stream fits its budget B W H (k + 1) - bits spent (at least a quarter of one picture's share),
+//               found by bisection on the size probe (dcvc_dmci_estimate_bits, at most 7 probes), then one compress at
+//               that q_index; --qp-i is unused. Runs with an inter model: the one-pass feedback controller
+//               (dcvc_amd_rc.h, rate_control.TargetBpp; --qp-i is its start value, I pictures get --rc-intra-bonus steps),
+//               no probes. --qp-p and --batch above 1 are refused with --target-bpp. --rc-log: per coded unit {type, qp,
+//               probes, predicted_bytes, bytes} and the totals. The container carries every unit's q_index: decode
+//               needs no option.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -43,6 +54,7 @@
 #include "dcvc_amd_image.h"
 #include "dcvc_amd_ops.h"
 #include "dcvc_amd_rans.h"
+#include "dcvc_amd_rc.h"
 #include "stream/container.h"
 
 #include <hip/hip_runtime.h>
@@ -425,10 +437,65 @@ int batch_arg(const Args& a)
     return static_cast<int>(v);
 }
 
+// --target-bpp and its companions, refused before anything touches the device
+struct RateArgs {
+    bool on = false;
+    double target_bpp = 0;
+    int qp_min = 0, qp_max = 63, horizon = 8, intra_bonus = 0;
+    std::string log;
+};
+
+int int_arg(const Args& a, const std::string& key, int def, int lo, int hi)
+{
+    if (!a.has(key)) return def;
+    const std::string s = a.str(key);
+    char* end = nullptr;
+    const long v = strtol(s.c_str(), &end, 10);
+    if (s.empty() || *end != '\0' || v < lo || v > hi) {
+        die("--" + key + " must be in " + std::to_string(lo) + ".." + std::to_string(hi) + ", got " + s);
+    }
+    return static_cast<int>(v);
+}
+
+RateArgs rate_args(const Args& a, int batch)
+{
+    RateArgs r;
+    if (!a.has("target-bpp")) {
+        for (const char* k : {"qp-min", "qp-max", "rc-horizon", "rc-intra-bonus", "rc-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --target-bpp");
+        }
+        return r;
+    }
+    r.on = true;
+    const std::string s = a.str("target-bpp");
+    char* end = nullptr;
+    r.target_bpp = strtod(s.c_str(), &end);
+    if (s.empty() || *end != '\0' || !std::isfinite(r.target_bpp) || !(r.target_bpp > 0)) {
+        die("--target-bpp must be a positive number of bits per pixel, got " + s);
+    }
+    if (batch > 1) die("--target-bpp cannot be combined with --batch above 1: a batch has one q_index");
+    if (a.has("qp-p")) die("--target-bpp cannot be combined with --qp-p: the controller chooses the q_index of the P units");
+    r.qp_min = int_arg(a, "qp-min", 0, 0, 63);
+    r.qp_max = int_arg(a, "qp-max", 63, 0, 63);
+    if (r.qp_min > r.qp_max) die("--qp-min " + std::to_string(r.qp_min) + " is above --qp-max " + std::to_string(r.qp_max));
+    r.horizon = int_arg(a, "rc-horizon", 8, 1, 1 << 20);
+    r.intra_bonus = int_arg(a, "rc-intra-bonus", 0, -63, 63);
+    r.log = a.str("rc-log");
+    return r;
+}
+
+// one coded unit in --rc-log
+struct RateUnit {
+    bool intra = false;
+    int qp = 0, probes = 0;
+    long long predicted_bytes = -1, bytes = 0;      // -1: no prediction (the feedback loop does not probe)
+};
+
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
     const int batch = batch_arg(a);
+    const RateArgs rate = rate_args(a, batch);
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
     }
@@ -498,6 +565,32 @@ int encode(const Args& a)
         if (is_new) dcvc::stream::put_sps(out, sps_id, g.H, g.W);
         dcvc::stream::put_ip(out, intra, sps_id, qp, ec, reset != 0, pl.data(), pl.size());
     };
+    // --target-bpp: all-intra runs search the q_index of every picture on the size probe, runs with an inter model follow the
+    // feedback controller (rate_control.code_sequence with TargetBpp)
+    const bool rate_search = rate.on && intra_period == 1;
+    const double pixels = static_cast<double>(g.H) * g.W;
+    dcvc_rc* ctl = nullptr;
+    if (rate.on && !rate_search) {
+        ctl = dcvc_rc_create(rate.target_bpp, pixels, qp_i, rate.horizon, rate.intra_bonus, rate.qp_min, rate.qp_max, 0.049);
+        if (!ctl) die(std::string("rate control: ") + dcvc_last_error());
+    }
+    std::vector<RateUnit> rate_units;
+    long long spent_bits = 0;
+    struct Probe {
+        dcvc_dmci* codec; const void* x; int H, W, pad_b, pad_r; void* st;
+        std::map<int, long long> bytes;                // predicted stream bytes of every q_index probed
+    };
+    auto probe_bits = [](int qp, void* user) -> int64_t {
+        Probe& p = *static_cast<Probe*>(user);
+        int64_t units[2];
+        if (dcvc_dmci_estimate_bits(p.codec, p.x, p.H, p.W, qp, p.pad_b, p.pad_r, units, p.st) < 0) return -1;
+        const int64_t kept = dcvc_dmci_estimate_symbols(p.codec, 0);
+        if (kept < 0) return -1;
+        const long long bytes = dcvc_predicted_stream_bytes(units[0], units[1], dcvc_ec_parallel_for(kept));
+        if (bytes < 0) return -1;
+        p.bytes[qp] = bytes;
+        return 8 * bytes;
+    };
     int idx = 0;
     while (idx < frame_num) {
         const bool intra = is_intra_picture(idx, intra_period);
@@ -535,8 +628,20 @@ int encode(const Args& a)
         }
         int ec = 0, reset = 0, qp = qp_i;
         long long nbytes = 0;
+        RateUnit ru;
+        ru.intra = intra;
+        if (rate_search) {
+            Probe p{c.intra, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
+            const int64_t budget = dcvc_rc_intra_budget_bits(rate.target_bpp, pixels, idx, spent_bits);
+            qp = dcvc_rc_pick_qp_for_budget(probe_bits, &p, budget, rate.qp_min, rate.qp_max, &ru.probes);
+            abi_ok(qp, "size probe");
+            ru.predicted_bytes = p.bytes.at(qp);
+        } else if (ctl) {
+            qp = dcvc_rc_next_qp(ctl, intra ? 1 : 0);
+            abi_ok(qp, "rate control");
+        }
         if (intra) {
-            ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, qp_i, pad_b, pad_r, b.x_hat, b.st);
+            ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, qp, pad_b, pad_r, b.x_hat, b.st);
             abi_ok(ec, "intra compress");
             nbytes = dcvc_dmci_get_stream(c.intra, nullptr, 0);
             payload.resize(static_cast<size_t>(nbytes));
@@ -544,7 +649,7 @@ int encode(const Args& a)
             if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
             if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
         } else {
-            qp = qp_p;
+            if (!ctl) qp = qp_p;
             reset = (reset_interval > 0 && (idx + delay) % reset_interval == 1) ? 1 : 0;
             if (c.ld) {
                 ec = dcvc_dmcld_compress(c.ld, b.x, g.H, g.W, qp, reset, pad_b, pad_r, b.st);
@@ -561,10 +666,40 @@ int encode(const Args& a)
             }
         }
         put_unit(intra, qp, ec, reset, payload);
+        if (rate.on) {
+            if (ctl) abi_ok(dcvc_rc_update(ctl, 8.0 * payload.size(), want, intra ? 1 : 0), "rate control");
+            spent_bits += 8LL * static_cast<long long>(payload.size());
+            ru.qp = qp;
+            ru.bytes = static_cast<long long>(payload.size());
+            rate_units.push_back(ru);
+        }
         idx += want;
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
     if (in) fclose(in);
+    if (ctl) dcvc_rc_destroy(ctl);
+    if (rate.on) {
+        const double achieved = static_cast<double>(spent_bits) / (static_cast<double>(frame_num) * pixels);
+        printf("rate control: target %.4f bpp, coded %.4f bpp in %zu units\n", rate.target_bpp, achieved, rate_units.size());
+        if (!rate.log.empty()) {
+            std::string js = "{\"target_bpp\": " + jnum(rate.target_bpp) + ", \"achieved_bpp\": " + jnum(achieved) +
+                             ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) +
+                             ", \"pictures\": " + std::to_string(frame_num) + ", \"qp_min\": " + std::to_string(rate.qp_min) +
+                             ", \"qp_max\": " + std::to_string(rate.qp_max) + ", \"mode\": \"" +
+                             (rate_search ? "probe" : "feedback") + "\", \"units\": [";
+            for (size_t i = 0; i < rate_units.size(); ++i) {
+                const RateUnit& u = rate_units[i];
+                js += std::string(i ? ", " : "") + "{\"type\": \"" + (u.intra ? "I" : "P") + "\", \"qp\": " + std::to_string(u.qp) +
+                      ", \"probes\": " + std::to_string(u.probes) + ", \"predicted_bytes\": " +
+                      (u.predicted_bytes < 0 ? std::string("null") : std::to_string(u.predicted_bytes)) +
+                      ", \"bytes\": " + std::to_string(u.bytes) + "}";
+            }
+            js += "]}\n";
+            FILE* lf = fopen(rate.log.c_str(), "wb");
+            if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + rate.log);
+            fclose(lf);
+        }
+    }
     FILE* of = fopen(a.str("o").c_str(), "wb");
     if (!of || fwrite(out.data(), 1, out.size(), of) != out.size()) die("cannot write " + a.str("o"));
     fclose(of);

@@ -35,6 +35,13 @@ public:
                         hipStream_t stream);
     void decompress_batch(int n, const uint8_t* const* bits, const size_t* nbytes, const int* ec_parallel, int qp,
                           int height, int width, half_t* x_hat, hipStream_t stream);
+    // Not part of the reference surface either: what compress() would spend on n pictures at this qp, without coding them
+    // (DESIGN.md 15). Runs compress()'s first stage - the same launches, the same graph - and sums the code length of the
+    // symbols on the device (kernels/code_length.hip): no symbol copy, no rANS, no reconstruction. Picture i:
+    // units[2 i] = y, units[2 i + 1] = z, in 2^-16 bit (rans/code_length.h); kept[i] = y symbols that would be coded
+    // (-> ec_parallel_for). Streams, reconstructions and states of earlier and later calls are what they are without it.
+    void estimate_bits(int n, const half_t* x, int height, int width, int qp, int64_t* units, int64_t* kept,
+                       hipStream_t stream);
     int last_batch() const { return m_last_n; }               // pictures of the last compress / compress_batch call
     const std::vector<uint8_t>& stream_at(int i) const;        // stream i of that call
 
@@ -90,6 +97,12 @@ private:
     DcbW m_dec1[12], m_dec2;
     float m_skip_thres = 0.f;
     bool m_has_params = false;
+    // code-length tables (estimate_bits): y [m_cl_y_num][256], z [m_cl_z_num][128], and the sums of a call
+    // [kMaxBatch][3] = {y units, y symbols, z units}
+    const uint32_t *m_cl_y = nullptr, *m_cl_z = nullptr;
+    int m_cl_y_num = 0, m_cl_z_num = 0;
+    unsigned long long* m_cl_sums = nullptr;
+    Pinned<unsigned long long> m_h_cl;
 
     // ---- per-resolution buffers
     Geometry m_g;

@@ -4,6 +4,8 @@
 // device->host transfer of the compacted symbols of all four steps.
 #include "codec/dmci.h"
 
+#include "rans/code_length.h"
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +68,23 @@ void DmciCodec::set_param(const ParamStore& ps, float skip_thres)
     m_dec2.load(ps, m_wmem, "dec.dec_2.");
 
     load_cdf_tables(ps);
+    {   // what the coder will spend on every symbol under these CDFs, for estimate_bits (rans/code_length.h)
+        auto upload = [&](const char* name_cdf, const char* name_len, int cols, int& num) {
+            const HostTensor& c = ps.at(name_cdf);
+            const HostTensor& l = ps.at(name_len);
+            num = static_cast<int>(l.numel());
+            std::vector<uint32_t> host(static_cast<size_t>(num) * cols);
+            code_length_table(c.i.data(), num, static_cast<int>(c.numel() / num), l.i.data(), cols, host.data());
+            void* dev = m_wmem.alloc(host.size() * sizeof(uint32_t));
+            hip_check(hipMemcpy(dev, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D code-length table");
+            return static_cast<const uint32_t*>(dev);
+        };
+        m_cl_z = upload("bit_estimator_z.quantized_cdf", "bit_estimator_z.cdf_length", kCodeLengthZCols, m_cl_z_num);
+        m_cl_y = upload("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", kCodeLengthYCols, m_cl_y_num);
+        if (m_cl_y_num > 256) throw std::invalid_argument("DMCI: more than 256 Gaussian CDFs");
+        m_cl_sums = static_cast<unsigned long long*>(m_wmem.alloc(sizeof(unsigned long long) * 3 * kMaxBatch));
+        m_h_cl.reserve(3 * kMaxBatch);
+    }
     m_has_params = true;
 }
 
@@ -292,6 +311,42 @@ void DmciCodec::compress_impl(int n, const half_t* x, int height, int width, int
     leave(user);
     wait_job();
     m_last_n = n;
+}
+
+// ------------------------------------------------------------------------------------ size probe
+void DmciCodec::estimate_bits(int n, const half_t* x, int height, int width, int qp, int64_t* units, int64_t* kept,
+                              hipStream_t user)
+{
+    if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMCI estimate_bits: qp must be in [0, 63]");
+    prepare(height, width, n);
+    if ((qp + 1) * kChZ > m_cl_z_num) throw std::invalid_argument("DMCI estimate_bits: no z CDFs for this qp");
+    const Geometry& g = m_g;
+    hipStream_t st = enter(user);
+    select_qp(qp, st);
+    pad_unshuffle8_b(x, height, width, 3, m_U, g.H8, g.W8, n, st);
+    run_stage(kEnc0, st, [&] { enc_stage0(st); });          // the graph compress() replays; nothing below is part of it
+    const long long nq = static_cast<long long>(g.P16()) * (kChY / 4);
+    hip_check(hipMemsetAsync(m_cl_sums, 0, sizeof(unsigned long long) * 3 * n, st), "hipMemsetAsync(code length)");
+    CodeLengthY dy;
+    dy.sym = m_COMP; dy.sym_stride = 4 * nq;
+    dy.totals = m_TOTALS; dy.totals_stride = 4; dy.n_totals = 4;
+    dy.count = static_cast<int>(4 * nq);
+    dy.table = m_cl_y; dy.num_cdf = m_cl_y_num;
+    dy.out = m_cl_sums; dy.out_stride = 3; dy.kept_slot = 1; dy.n = n;
+    code_length_y(dy, st);
+    CodeLengthZ dz;
+    dz.z = m_ZI8; dz.count = g.P64() * kChZ; dz.ch = kChZ;
+    dz.table = m_cl_z + static_cast<size_t>(qp) * kChZ * kCodeLengthZCols;
+    dz.out = m_cl_sums + 2; dz.out_stride = 3; dz.n = n;
+    code_length_z(dz, st);
+    hip_check(hipMemcpyAsync(m_h_cl.get(), m_cl_sums, sizeof(unsigned long long) * 3 * n, hipMemcpyDeviceToHost, st), "D2H code length");
+    hip_check(hipStreamSynchronize(st), "sync");
+    leave(user);
+    for (int b = 0; b < n; ++b) {
+        units[2 * b] = static_cast<int64_t>(m_h_cl[3 * b]);
+        units[2 * b + 1] = static_cast<int64_t>(m_h_cl[3 * b + 2]);
+        if (kept) kept[b] = static_cast<int64_t>(m_h_cl[3 * b + 1]);
+    }
 }
 
 void DmciCodec::entropy_encode(int qp)

@@ -1,0 +1,79 @@
+// See rate_control.h; dcvc_amd/rate_control.py has the reasoning behind every step of the controller.
+#include "codec/rate_control.h"
+
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+
+namespace dcvc {
+
+TargetBpp::TargetBpp(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus, int qp_min,
+                     int qp_max, double slope)
+    : m_target_bits(target_bpp * pixels_per_picture), m_qp(qp0), m_slope(slope), m_horizon(std::max(1, horizon)),
+      m_intra_bonus(intra_bonus), m_qp_min(qp_min), m_qp_max(qp_max)
+{
+    if (!(target_bpp > 0) || !(pixels_per_picture > 0)) {
+        throw std::invalid_argument("target_bpp and pixels_per_picture must be positive");
+    }
+}
+
+int TargetBpp::next_qp(bool is_intra) const
+{
+    const double q = m_qp + (is_intra ? m_intra_bonus : 0);
+    const double r = std::rint(q);                                  // half to even, as Python's round()
+    return static_cast<int>(std::min<double>(m_qp_max, std::max<double>(m_qp_min, r)));
+}
+
+void TargetBpp::update(double bits, int pictures, bool is_intra)
+{
+    if (pictures <= 0) return;
+    m_spent += bits;
+    m_pictures += pictures;
+    double per_picture = std::max(bits / pictures, 1.0);
+    const int used_qp = next_qp(is_intra);
+    if (!is_intra) {
+        if (m_has_last && used_qp != m_last_qp) {
+            const double s = (std::log2(per_picture) - m_last_log) / (used_qp - m_last_qp);
+            if (0.005 < s && s < 0.5) m_slope = 0.75 * m_slope + 0.25 * s;
+        }
+        m_has_last = true;
+        m_last_qp = used_qp;
+        m_last_log = std::log2(per_picture);
+    }
+    const double budget = m_target_bits * (m_pictures + m_horizon) - m_spent;
+    const double want = std::max(budget / m_horizon, m_target_bits / 64.0);
+    if (is_intra) {
+        if (!m_has_last) return;
+        per_picture = std::pow(2.0, m_last_log + m_slope * (m_qp - m_last_qp));
+    }
+    const double step = (std::log2(want) - std::log2(per_picture)) / m_slope;
+    m_qp += std::min(m_max_step, std::max(-m_max_step, step));
+    m_qp = std::min(static_cast<double>(m_qp_max), std::max(static_cast<double>(m_qp_min), m_qp));
+}
+
+int pick_qp_for_budget(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int qp_min, int qp_max, int* probes)
+{
+    if (qp_min > qp_max) throw std::invalid_argument("pick_qp_for_budget: qp_min above qp_max");
+    int lo = qp_min - 1, hi = qp_max + 1, count = 0;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;             // (lo + hi) floored, lo may be -1
+        const int64_t bits = estimate(mid);
+        ++count;
+        if (bits < 0) {
+            if (probes) *probes = count;
+            throw std::runtime_error("pick_qp_for_budget: the size probe failed");
+        }
+        if (bits <= budget_bits) lo = mid; else hi = mid;
+    }
+    if (probes) *probes = count;
+    return lo < qp_min ? qp_min : lo;
+}
+
+int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits)
+{
+    const double share = target_bpp * pixels_per_picture;
+    const double budget = std::max(share * (k + 1) - static_cast<double>(spent_bits), share / 4.0);
+    return static_cast<int64_t>(std::floor(budget));
+}
+
+}  // namespace dcvc

@@ -1,0 +1,40 @@
+// Rate control of the native tool: the one-pass feedback controller of dcvc_amd/rate_control.py (TargetBpp) and the
+// search for the largest q_index whose predicted stream fits a budget, on top of a size probe. Plain host code; the
+// Python module is the restatement the tests compare with, so the arithmetic here follows it operation for operation
+// (double, rint where Python's round() rounds half to even).
+#pragma once
+
+#include <cstdint>
+#include <functional>
+
+namespace dcvc {
+
+class TargetBpp {
+public:
+    TargetBpp(double target_bpp, double pixels_per_picture, double qp0 = 32, int horizon = 8, int intra_bonus = 0,
+              int qp_min = 0, int qp_max = 63, double slope = 0.049);
+    int next_qp(bool is_intra) const;
+    void update(double bits, int pictures, bool is_intra);
+    double qp() const { return m_qp; }
+    double spent() const { return m_spent; }
+    int pictures() const { return m_pictures; }
+
+private:
+    double m_target_bits, m_qp, m_slope, m_max_step = 4.0, m_spent = 0.0;
+    int m_horizon, m_intra_bonus, m_qp_min, m_qp_max, m_pictures = 0;
+    bool m_has_last = false;
+    int m_last_qp = 0;
+    double m_last_log = 0.0;
+};
+
+// Bisection over the q_index. estimate(qp) = predicted bits of the stream at qp (negative = failure, passed on).
+// lo = qp_min - 1 counts as fitting, hi = qp_max + 1 as not; while hi - lo > 1: mid = (lo + hi) / 2 (floor), probed,
+// lo = mid if estimate(mid) <= budget_bits, else hi = mid. Returns lo, or qp_min when lo never moved; at most
+// ceil(log2(qp_max - qp_min + 2)) probes. probes (may be null) receives their number.
+int pick_qp_for_budget(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int qp_min, int qp_max, int* probes);
+
+// Budget of picture k (0-based) of an all-intra run towards target_bpp: what the k + 1 pictures may take together minus what
+// the first k took, floored at a quarter of one picture's share. floor() of the double value.
+int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);
+
+}  // namespace dcvc

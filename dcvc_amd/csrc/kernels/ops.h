@@ -455,4 +455,34 @@ struct MaskStepDec {
 };
 void mask_step_dec(const MaskStepDec& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- code length (code_length.hip)
+// Sum of the cost-table entries (rans/code_length.h, units of 2^-16 bit) of the symbols of n pictures: the ideal length
+// of the stream the host coder would build from them. Integer sums, so exact and the same on every run. The sums are
+// ADDED to out (unsigned 64-bit, device memory): the caller zeroes it.
+struct CodeLengthY {
+    const int16_t* sym = nullptr;           // (q << 8) + cdf index, as y_step_enc writes them; 16-byte aligned
+    long long sym_stride = 0;               // picture b's symbols start at sym + b * sym_stride (a multiple of 8)
+    const uint8_t* cond = nullptr;          // keep bits of the uncompacted layout (bit i of byte e / 8), picture b at
+    long long cond_stride = 0;              //   cond + b * cond_stride; nullptr: every symbol counts (compacted layout)
+    const int32_t* totals = nullptr;        // device-side counts: picture b holds totals[b * totals_stride + 0 .. n_totals)
+    int totals_stride = 0, n_totals = 0;    //   summed symbols (compacted layout); nullptr: `count` symbols
+    int count = 0;                          // symbols per picture, or with totals the most a picture can hold
+    const uint32_t* table = nullptr;        // [num_cdf][256], column uint8(q)
+    int num_cdf = 0;                        // a symbol whose index is not below it counts nothing
+    unsigned long long* out = nullptr;      // picture b: out[b * out_stride] += cost, out[b * out_stride + kept_slot] += symbols
+    int out_stride = 1, kept_slot = -1;     //   counted (kept_slot < 0: not written)
+    int n = 1;
+};
+void code_length_y(const CodeLengthY& d, hipStream_t stream);
+
+struct CodeLengthZ {
+    const int8_t* z = nullptr;              // [n][count], values in [-64, 63]; symbol i is coded with row i % ch
+    int count = 0, ch = 1;
+    const uint32_t* table = nullptr;        // [ch][128] rows of the selected q_index, column z + 64
+    unsigned long long* out = nullptr;      // picture b: out[b * out_stride] += cost
+    int out_stride = 1;
+    int n = 1;
+};
+void code_length_z(const CodeLengthZ& d, hipStream_t stream);
+
 }  // namespace dcvc

@@ -211,6 +211,13 @@ class DMCI(CompressionModel):
             np.frombuffer(bit_stream, dtype=np.uint8), qp, sps["height"], sps["width"], ec_part)
         return {"x_hat": x_hat}
 
+    # not in the reference: the size probe - what compress() would spend, without coding
+    def estimate_bits(self, x, qp, padding_b, padding_r):
+        return self._ensure_proxy().estimate_bits(x, qp, padding_b, padding_r)
+
+    def estimate_bits_batch(self, x, qp, padding_b, padding_r):
+        return self._ensure_proxy().estimate_bits_batch(x, qp, padding_b, padding_r)
+
 
 class DMC(CompressionModel):
     """video_model_ld.py:191-308 (inference subset): the low-delay inter model. The temporal

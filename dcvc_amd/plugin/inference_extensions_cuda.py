@@ -66,6 +66,11 @@ _F = dict(
     decompress_batch=_lib.fn("dcvc_dmci_decompress_batch", _ci,
                              [_vp, _ci, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_ci), _ci,
                               _ci, _ci, _vp, _vp]),
+    estimate_bits=_lib.fn("dcvc_dmci_estimate_bits", _ci,
+                          [_vp, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
+    estimate_bits_batch=_lib.fn("dcvc_dmci_estimate_bits_batch", _ci,
+                                [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
+    estimate_symbols=_lib.fn("dcvc_dmci_estimate_symbols", ctypes.c_int64, [_vp, _ci]),
 )
 
 _SET_PARAM_ARGS = [_vp, _ci, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_vp), ctypes.POINTER(_ci),
@@ -258,6 +263,34 @@ class DMCIProxy(_Proxy):
         _lib.check(_F["decompress_batch"](self._h, n, ptrs, sizes, ecs, int(qp), int(height), int(width),
                                           ctypes.c_void_p(x_hat.data_ptr()), _stream_ptr()))
         return x_hat[:n]
+
+
+    # ---- extras, not part of the reference surface: the size probe
+    def estimate_bits(self, x, qp, padding_b, padding_r):
+        """What compress(x, qp, ...) would spend, without coding: -> (y_units, z_units, symbols), the ideal code length
+        of y and z in 2^-16 bit (exact integers) and the y symbols that would be coded. With
+        rate_control.predicted_stream_bytes(y_units, z_units, rate_control.ec_parallel_for(symbols)) that predicts
+        len(stream). Later and earlier compress / decompress calls give what they give without it."""
+        x, xp = _nhwc_ptr(x, 3)
+        units = (ctypes.c_int64 * 2)()
+        _lib.check(_F["estimate_bits"](self._h, xp, int(x.shape[2]), int(x.shape[3]), int(qp), int(padding_b),
+                                       int(padding_r), units, _stream_ptr()))
+        return int(units[0]), int(units[1]), int(_lib.check(_F["estimate_symbols"](self._h, 0)))
+
+    def estimate_bits_batch(self, x, qp, padding_b, padding_r):
+        """x: [N, 3, H, W] fp16 CUDA (1 <= N <= 16) -> list of N (y_units, z_units, symbols), each what estimate_bits()
+        gives for that picture alone."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected an [N, 3, H, W] tensor, got %s" % (tuple(x.shape),))
+        if x.dtype != torch.float16 or not x.is_cuda:
+            raise ValueError("expected a CUDA fp16 tensor")
+        n, height, width = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        x = x.contiguous(memory_format=torch.channels_last)
+        units = (ctypes.c_int64 * (2 * max(1, n)))()
+        _lib.check(_F["estimate_bits_batch"](self._h, n, ctypes.c_void_p(x.data_ptr()), height, width, int(qp),
+                                             int(padding_b), int(padding_r), units, _stream_ptr()))
+        return [(int(units[2 * i]), int(units[2 * i + 1]), int(_lib.check(_F["estimate_symbols"](self._h, i))))
+                for i in range(n)]
 
 
 class DMCLDProxy(_Proxy):

@@ -6,8 +6,9 @@ The reference harness codes a whole sequence with ONE q_index per rate point (te
 changes it from picture to picture. This module is the encoder-side hook for that: a controller object the coding
 loop asks for the q_index of the next coded unit and tells the bits the unit took, plus `code_sequence`, the
 loop of test_video.py:204-257 (picture types, reset rule, chunk padding) with the q_index taken from the
-controller instead of a constant. The native tool (csrc/cli/dcvc_cli.hip) keeps the reference's constant
---qp-i / --qp-p; this is the Python-surface hook.
+controller instead of a constant. The native tool (csrc/cli/dcvc_cli.hip) codes with the reference's constant
+--qp-i / --qp-p unless it is given --target-bpp; then it runs the same controller natively (csrc/codec/rate_control.cpp),
+or, in all-intra runs, the budget search at the end of this module on the GPU size probe.
 
 In DCVC-UF a HIGHER q_index means finer quantisation = more bits (q 0 .. 63).
 """
@@ -118,3 +119,60 @@ def code_sequence(frame_count, frames_per_p, code_intra, code_inter, controller,
         units.append((False, qp, reset, payload))
         idx += frames_per_p
     return units
+
+
+# ---- coding to a budget on a size probe. The native tool has the same functions
+# (csrc/codec/rate_control.cpp, include/dcvc_amd_rc.h); the tests hold the two against each other probe for probe.
+
+CODE_LENGTH_UNIT = 1 << 16          # size probes count in 2^-16 bit (csrc/rans/code_length.h)
+MIN_SYMBOLS_PER_STREAM = 32768      # def_const.h:18
+
+
+def ec_parallel_for(symbols):
+    """sub-streams of a picture with that many coded y symbols (dmc_common.cpp:31-35)"""
+    return min(8, max(1, int(symbols) // MIN_SYMBOLS_PER_STREAM))
+
+
+def stream_fixed_bits(ec_parallel):
+    """What the stream format adds to the coded symbols: every sub-stream ends with its 32-bit coder state, and a
+    container of three or more sub-streams starts with n // 2 - 1 + n % 2 32-bit offsets."""
+    n = int(ec_parallel)
+    if not 1 <= n <= 8:
+        raise ValueError("ec_parallel must be in [1, 8]")
+    return 32 * n + 32 * (0 if n == 1 else n // 2 - 1 + n % 2)
+
+
+def predicted_stream_bytes(y_units, z_units, ec_parallel):
+    """ideal code length (2^-16 bit) -> predicted len(stream): the fixed bits on top, rounded up to bytes"""
+    units = int(y_units) + int(z_units) + stream_fixed_bits(ec_parallel) * CODE_LENGTH_UNIT
+    return (units + 8 * CODE_LENGTH_UNIT - 1) // (8 * CODE_LENGTH_UNIT)
+
+
+def pick_qp_for_budget(estimate, budget_bits, qp_min=0, qp_max=63, trace=None):
+    """Largest q_index whose predicted stream fits `budget_bits`, by bisection on estimate(qp) -> predicted bits.
+
+    lo = qp_min - 1 counts as fitting, hi = qp_max + 1 as not; while hi - lo > 1: mid = (lo + hi) // 2 is probed,
+    lo = mid if it fits, else hi = mid. The answer is lo, or qp_min when lo never moved: at most
+    ceil(log2(qp_max - qp_min + 2)) probes. On a size curve that rises with the q_index that is the largest q_index that
+    fits; on any curve it ends with "lo fits, lo + 1 was probed and does not". `trace`, a list, receives (qp, bits) of every
+    probe."""
+    if qp_min > qp_max:
+        raise ValueError("qp_min above qp_max")
+    lo, hi = qp_min - 1, qp_max + 1
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        bits = int(estimate(mid))
+        if trace is not None:
+            trace.append((mid, bits))
+        if bits <= budget_bits:
+            lo = mid
+        else:
+            hi = mid
+    return qp_min if lo < qp_min else lo
+
+
+def intra_budget_bits(target_bpp, pixels_per_picture, k, spent_bits):
+    """Budget of picture k (0-based) of an all-intra run: what k + 1 pictures may take together minus what the first k
+    took, floored at a quarter of one picture's share."""
+    share = float(target_bpp) * pixels_per_picture
+    return int(math.floor(max(share * (k + 1) - float(spent_bits), share / 4.0)))

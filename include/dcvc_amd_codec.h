@@ -83,6 +83,23 @@ int64_t dcvc_dmci_get_stream_at(dcvc_dmci* c, int i, uint8_t* dst, size_t cap);
  * picture's reconstruction is bit-identical to dcvc_dmci_decompress of its stream. ec_parallel[i] in 1..8. */
 int dcvc_dmci_decompress_batch(dcvc_dmci* c, int n, const uint8_t* const* streams, const size_t* nbytes,
                                const int* ec_parallel, int qp, int height, int width, void* x_hat, void* stream);
+/* Not part of the reference surface: the size probe. What dcvc_dmci_compress would spend on the picture at
+ * this qp, without coding it: the first stage of compress (the same launches and graph), then the code length of the
+ * symbols summed on the device (dcvc_code_length_y / _z of dcvc_amd_ops.h) and ONE small device-to-host copy - no symbol
+ * copy, no rANS, no reconstruction. out_units[0] = y, out_units[1] = z, ideal code length in units of 2^-16 bit (exact
+ * integers). The call blocks until the sums are on the host. It changes nothing that a later or earlier compress /
+ * decompress gives: a following dcvc_dmci_compress returns the bytes and the x_hat it returns without the probe.
+ * The batch form (n in 1..16): out_units[2 i], [2 i + 1] of picture i, each what the single form gives for it.
+ * dcvc_dmci_estimate_symbols: the y symbols of picture i of the last probe that would be coded (the skipped ones are
+ * not), so that ec_parallel = dcvc_ec_parallel_for(symbols) and
+ * dcvc_predicted_stream_bytes(out_units[0], out_units[1], ec_parallel) (dcvc_amd_ops.h) predicts the stream's length. */
+int dcvc_dmci_estimate_bits(dcvc_dmci* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                            int64_t* out_units, void* stream);
+int dcvc_dmci_estimate_bits_batch(dcvc_dmci* c, int n, const void* x, int height, int width, int qp, int padding_b,
+                                  int padding_r, int64_t* out_units, void* stream);
+int64_t dcvc_dmci_estimate_symbols(dcvc_dmci* c, int i);
+/* sub-streams compress uses for a picture with that many coded y symbols (dmc_common.cpp:31-35) */
+int dcvc_ec_parallel_for(int64_t symbols);
 /* Test hook: copy an internal tensor of the last call ("y", "y_hat", "z_i8", "params",
  * "unshuffled", "features", "totals", "symbols") to host memory; returns its size in bytes. */
 int64_t dcvc_dmci_debug_read(dcvc_dmci* c, const char* name, void* dst, size_t cap, void* stream);

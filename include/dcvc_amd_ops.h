@@ -306,6 +306,33 @@ int dcvc_gemm_profile_collect(double* ms, double* flops, long long* launches);
 /* per-launch records {int M, N, K, variant; float ms}; returns the number of launches recorded */
 long long dcvc_gemm_profile_launches(void* records, long long cap);
 
+/* Code length (no reference counterpart): what the host rANS coder will spend on symbols, from tables, in units of
+ * 2^-16 bit. A value coded with frequency f out of 2^16 costs rint(65536 * (16 - log2(f))) (double arithmetic); an
+ * escaped one (value >= cdf_len - 2) costs the escape value's frequency plus 2 bits for each of its bypass groups
+ * (raw groups + 1 count group + raw groups / 3 continuation groups), exactly as the coder emits them.
+ *   dcvc_code_length_cost: one entry from a frequency (1 .. 65536) and a bypass group count; 0xFFFFFFFF = not codable.
+ *   dcvc_code_length_table (host memory, no GPU): the table of a CDF family as given to dcvc_rans_*_set_cdf
+ *     (cdfs [num_cdf][stride], cdf_sizes [num_cdf]) -> out [num_cdf][cols]; cols = 256: column uint8(symbol), symbol an
+ *     int8 (the y family); cols = 128: column symbol + 64, symbol in [-64, 63] (the z family).
+ *   dcvc_predicted_stream_bytes: ideal length -> bytes of the stream of ec_parallel (1 .. 8) sub-streams: 32 bits of
+ *     final coder state per sub-stream and the 32-bit offsets in front of 3 or more sub-streams are added, then
+ *     rounded up to bytes. */
+uint32_t dcvc_code_length_cost(int freq, int bypass_groups);
+int dcvc_code_length_table(const int32_t* cdfs, int num_cdf, int stride, const int32_t* cdf_sizes, int cols, uint32_t* out);
+long long dcvc_predicted_stream_bytes(long long y_units, long long z_units, int ec_parallel);
+/* The sums on the device, n pictures per call (picture = blockIdx.y). Integer sums: exact, the same on every run.
+ *   y: sym int16 (q << 8) + cdf index as dcvc_y_step_enc writes them, 16-byte aligned, picture b at sym + b * sym_stride
+ *     (elements, a multiple of 8). cond: keep bits of the uncompacted layout (bit e % 8 of byte e / 8; picture b at
+ *     cond + b * cond_stride bytes) or NULL = every symbol counts (compacted layout). totals: device int32 counts, picture
+ *     b's symbol count = sum of totals[b * totals_stride + 0 .. n_totals) capped at `count`, or NULL = `count` symbols.
+ *     table: device uint32 [num_cdf][256]. out: device uint64 [n][2] = {units, symbols counted}, zeroed by the call.
+ *   z: int8 [n][count] in [-64, 63], symbol i coded with row i % ch of table (device uint32 [ch][128], the rows of the
+ *     selected q_index). out: device uint64 [n] units, zeroed by the call. */
+int dcvc_code_length_y(const void* sym, long long sym_stride, const void* cond, long long cond_stride, const void* totals,
+                       int totals_stride, int n_totals, int count, const void* table, int num_cdf, void* out, int n,
+                       void* stream);
+int dcvc_code_length_z(const void* z, int count, int ch, const void* table, void* out, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,43 @@
+/* Rate control of the dcvc tool (no reference counterpart): the one-pass controller towards a target rate and the
+ * q_index search on a size probe. Host code only, no GPU. dcvc_amd/rate_control.py is the same arithmetic in Python
+ * (TargetBpp, pick_qp_for_budget, intra_budget_bits); the two are tested against each other.
+ *
+ * Errors: a negative return code, message through dcvc_last_error() (dcvc_amd_ops.h). */
+#ifndef DCVC_AMD_RC_H
+#define DCVC_AMD_RC_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct dcvc_rc dcvc_rc;
+
+/* rate_control.TargetBpp(target_bpp, pixels_per_picture, qp0, horizon, intra_bonus, qp_min, qp_max, slope); NULL on
+ * a non-positive target or picture size. */
+dcvc_rc* dcvc_rc_create(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus,
+                        int qp_min, int qp_max, double slope);
+void dcvc_rc_destroy(dcvc_rc* rc);
+/* q_index of the next coded unit (an I picture gets intra_bonus steps on top) */
+int dcvc_rc_next_qp(const dcvc_rc* rc, int is_intra);
+/* the unit took `bits` for `pictures` pictures */
+int dcvc_rc_update(dcvc_rc* rc, double bits, int pictures, int is_intra);
+double dcvc_rc_state_qp(const dcvc_rc* rc);      /* the controller's fractional q_index */
+
+/* Largest q_index in [qp_min, qp_max] whose predicted stream fits budget_bits, by bisection on
+ * estimate(qp, user) = predicted bits (negative = failure): lo = qp_min - 1 (fits), hi = qp_max + 1 (does not); while
+ * hi - lo > 1: mid = floor((lo + hi) / 2) is probed, lo = mid if it fits (estimate <= budget_bits), else hi = mid.
+ * Returns lo, or qp_min when nothing fits; at most ceil(log2(qp_max - qp_min + 2)) probes, their number in *probes
+ * (may be NULL). Negative on failure. */
+typedef int64_t (*dcvc_rc_estimate_fn)(int qp, void* user);
+int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int qp_min, int qp_max,
+                               int* probes);
+/* Budget of picture k (0-based) of an all-intra run: floor(max(target_bpp * pixels * (k + 1) - spent_bits,
+ * target_bpp * pixels / 4)) in double arithmetic. */
+int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DCVC_AMD_RC_H */

@@ -16,11 +16,13 @@ struct dcvc_dmci {
 
 struct dcvc_dmcld {
     dcvc::DmcLdCodec codec;
+    int64_t est_kept = -1;      // y symbols of the last size probe
 };
 
 struct dcvc_dmcht {
     explicit dcvc_dmcht(bool is_hts) : codec(is_hts) {}
     dcvc::DmcHtCodec codec;
+    int64_t est_kept = -1;
 };
 
 namespace {
@@ -258,6 +260,30 @@ int dcvc_dmcld_decompress(dcvc_dmcld* c, const uint8_t* bit_stream, size_t nbyte
     });
 }
 
+int dcvc_dmcld_estimate_bits(dcvc_dmcld* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                             int64_t* out_units, void* stream)
+{
+    return dcvc::guarded([&] {
+        if (c == nullptr || x == nullptr || out_units == nullptr) throw std::invalid_argument("estimate_bits: null codec, picture or result pointer");
+        check_padding16(height, width, padding_b, padding_r);
+        c->est_kept = -1;
+        int64_t kept = 0;
+        c->codec.estimate_bits(static_cast<const dcvc::half_t*>(x), height, width, qp, out_units, &kept,
+                               static_cast<hipStream_t>(stream));
+        c->est_kept = kept;
+    });
+}
+
+int64_t dcvc_dmcld_estimate_symbols(dcvc_dmcld* c)
+{
+    int64_t n = -1;
+    const int rc = dcvc::guarded([&] {
+        if (c == nullptr || c->est_kept < 0) throw std::invalid_argument("estimate_symbols: no size probe yet");
+        n = c->est_kept;
+    });
+    return rc < 0 ? rc : n;
+}
+
 int64_t dcvc_dmcld_export_state(dcvc_dmcld* c, void* dst, size_t cap, void* stream)
 {
     int64_t n = -1;
@@ -343,6 +369,30 @@ int dcvc_dmcht_decompress(dcvc_dmcht* c, const uint8_t* bit_stream, size_t nbyte
         c->codec.decompress(bit_stream, nbytes, qp, height, width, ec_parallel, reset_feature_memory != 0,
                             static_cast<dcvc::half_t*>(x_hat), static_cast<hipStream_t>(stream));
     });
+}
+
+int dcvc_dmcht_estimate_bits(dcvc_dmcht* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                             int64_t* out_units, void* stream)
+{
+    return dcvc::guarded([&] {
+        if (c == nullptr || x == nullptr || out_units == nullptr) throw std::invalid_argument("estimate_bits: null codec, picture or result pointer");
+        check_padding16(height, width, padding_b, padding_r);
+        c->est_kept = -1;
+        int64_t kept = 0;
+        c->codec.estimate_bits(static_cast<const dcvc::half_t*>(x), height, width, qp, out_units, &kept,
+                               static_cast<hipStream_t>(stream));
+        c->est_kept = kept;
+    });
+}
+
+int64_t dcvc_dmcht_estimate_symbols(dcvc_dmcht* c)
+{
+    int64_t n = -1;
+    const int rc = dcvc::guarded([&] {
+        if (c == nullptr || c->est_kept < 0) throw std::invalid_argument("estimate_symbols: no size probe yet");
+        n = c->est_kept;
+    });
+    return rc < 0 ? rc : n;
 }
 
 int64_t dcvc_dmcht_export_state(dcvc_dmcht* c, void* dst, size_t cap, void* stream)

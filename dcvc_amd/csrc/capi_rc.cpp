@@ -60,6 +60,27 @@ int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t
     return e < 0 ? e : qp;
 }
 
+int dcvc_rc_pick_qp_near(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int start, int qp_min, int qp_max,
+                         int* probes)
+{
+    int qp = -1;
+    const int e = dcvc::guarded([&] {
+        if (estimate == nullptr) throw std::invalid_argument("pick_qp_near: null estimate");
+        qp = dcvc::pick_qp_near([&](int q) { return estimate(q, user); }, budget_bits, start, qp_min, qp_max, probes);
+    });
+    return e < 0 ? e : qp;
+}
+
+int64_t dcvc_rc_unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits, int horizon,
+                                 int n)
+{
+    int64_t bits = -1;
+    const int e = dcvc::guarded([&] {
+        bits = dcvc::unit_budget_bits(target_bpp, pixels_per_picture, pictures_coded, spent_bits, horizon, n);
+    });
+    return e < 0 ? e : bits;
+}
+
 int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits)
 {
     return dcvc::intra_budget_bits(target_bpp, pixels_per_picture, k, spent_bits);

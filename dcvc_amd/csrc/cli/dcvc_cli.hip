@@ -9,7 +9,8 @@
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
-//               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]]
+//               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
+//                [--rc-mode feedback|probe]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16]
 //               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
@@ -43,9 +44,20 @@
 //               found by bisection on the size probe (dcvc_dmci_estimate_bits, at most 7 probes), then one compress at
 //               that q_index; --qp-i is unused. Runs with an inter model: the one-pass feedback controller
 //               (dcvc_amd_rc.h, rate_control.TargetBpp; --qp-i is its start value, I pictures get --rc-intra-bonus steps),
-//               no probes. --qp-p and --batch above 1 are refused with --target-bpp. --rc-log: per coded unit {type, qp,
-//               probes, predicted_bytes, bytes} and the totals. The container carries every unit's q_index: decode
-//               needs no option.
+//               no probes - or, with --rc-mode probe, the search below. --qp-p and --batch above 1 are refused with
+//               --target-bpp. --rc-log: per coded unit {type, qp, probes, predicted_bytes, bytes} and the totals. The
+//               container carries every unit's q_index: decode needs no option.
+//               --rc-mode feedback|probe (encode, needs --target-bpp; default feedback = the controller above, byte for byte):
+//               probe, with an inter model, bounds every P unit instead of steering the average. A P unit of n existing
+//               pictures gets floor(want n) bits, want = max((B W H (pictures coded + horizon) - bits spent) / horizon,
+//               B W H / 64) - what the controller steers towards (dcvc_rc_unit_budget_bits) - and the largest q_index in
+//               [--qp-min, --qp-max] whose predicted stream fits, searched on the inter model's size probe
+//               (dcvc_dmcld_estimate_bits / dcvc_dmcht_estimate_bits: the first stage of compress, the temporal state
+//               untouched) from the previous P unit's q_index (--qp-i for the first): gallop, then bisection
+//               (dcvc_rc_pick_qp_near; 2 probes when the q_index stays, at most 12). I pictures are not probed: they take
+//               that start value plus --rc-intra-bonus, and their bits count as spent. --rc-log: "mode": "probe", P units
+//               with probes >= 1 and predicted_bytes, I units with probes 0 and null. All-intra runs ignore the flag (they
+//               probe already); the stream format and the decoder do not change.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -443,6 +455,7 @@ struct RateArgs {
     double target_bpp = 0;
     int qp_min = 0, qp_max = 63, horizon = 8, intra_bonus = 0;
     std::string log;
+    bool probe = false;      // --rc-mode probe: P units searched on the inter model's size probe
 };
 
 int int_arg(const Args& a, const std::string& key, int def, int lo, int hi)
@@ -461,7 +474,7 @@ RateArgs rate_args(const Args& a, int batch)
 {
     RateArgs r;
     if (!a.has("target-bpp")) {
-        for (const char* k : {"qp-min", "qp-max", "rc-horizon", "rc-intra-bonus", "rc-log"}) {
+        for (const char* k : {"qp-min", "qp-max", "rc-horizon", "rc-intra-bonus", "rc-log", "rc-mode"}) {
             if (a.has(k)) die(std::string("--") + k + " needs --target-bpp");
         }
         return r;
@@ -481,6 +494,9 @@ RateArgs rate_args(const Args& a, int batch)
     r.horizon = int_arg(a, "rc-horizon", 8, 1, 1 << 20);
     r.intra_bonus = int_arg(a, "rc-intra-bonus", 0, -63, 63);
     r.log = a.str("rc-log");
+    const std::string mode = a.str("rc-mode", "feedback");
+    if (mode != "feedback" && mode != "probe") die("--rc-mode must be feedback or probe, got " + mode);
+    r.probe = mode == "probe";
     return r;
 }
 
@@ -569,8 +585,11 @@ int encode(const Args& a)
     // feedback controller (rate_control.code_sequence with TargetBpp)
     const bool rate_search = rate.on && intra_period == 1;
     const double pixels = static_cast<double>(g.H) * g.W;
+    // ... or, with --rc-mode probe, search every P unit's q_index on the inter model's probe (rate_control.code_sequence_probed)
+    const bool rate_probe = rate.on && !rate_search && rate.probe;
+    int start_q = qp_i, pictures_coded = 0;
     dcvc_rc* ctl = nullptr;
-    if (rate.on && !rate_search) {
+    if (rate.on && !rate_search && !rate_probe) {
         ctl = dcvc_rc_create(rate.target_bpp, pixels, qp_i, rate.horizon, rate.intra_bonus, rate.qp_min, rate.qp_max, 0.049);
         if (!ctl) die(std::string("rate control: ") + dcvc_last_error());
     }
@@ -585,6 +604,23 @@ int encode(const Args& a)
         int64_t units[2];
         if (dcvc_dmci_estimate_bits(p.codec, p.x, p.H, p.W, qp, p.pad_b, p.pad_r, units, p.st) < 0) return -1;
         const int64_t kept = dcvc_dmci_estimate_symbols(p.codec, 0);
+        if (kept < 0) return -1;
+        const long long bytes = dcvc_predicted_stream_bytes(units[0], units[1], dcvc_ec_parallel_for(kept));
+        if (bytes < 0) return -1;
+        p.bytes[qp] = bytes;
+        return 8 * bytes;
+    };
+    struct InterProbe {
+        dcvc_dmcld* ld; dcvc_dmcht* ht; const void* x; int H, W, pad_b, pad_r; void* st;
+        std::map<int, long long> bytes;
+    };
+    auto inter_probe_bits = [](int qp, void* user) -> int64_t {
+        InterProbe& p = *static_cast<InterProbe*>(user);
+        int64_t units[2];
+        const int rc = p.ld ? dcvc_dmcld_estimate_bits(p.ld, p.x, p.H, p.W, qp, p.pad_b, p.pad_r, units, p.st)
+                            : dcvc_dmcht_estimate_bits(p.ht, p.x, p.H, p.W, qp, p.pad_b, p.pad_r, units, p.st);
+        if (rc < 0) return -1;
+        const int64_t kept = p.ld ? dcvc_dmcld_estimate_symbols(p.ld) : dcvc_dmcht_estimate_symbols(p.ht);
         if (kept < 0) return -1;
         const long long bytes = dcvc_predicted_stream_bytes(units[0], units[1], dcvc_ec_parallel_for(kept));
         if (bytes < 0) return -1;
@@ -639,6 +675,16 @@ int encode(const Args& a)
         } else if (ctl) {
             qp = dcvc_rc_next_qp(ctl, intra ? 1 : 0);
             abi_ok(qp, "rate control");
+        } else if (rate_probe && intra) {
+            qp = std::min(rate.qp_max, std::max(rate.qp_min, start_q + rate.intra_bonus));
+        } else if (rate_probe) {
+            InterProbe p{c.ld, c.ht, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
+            const int64_t budget = dcvc_rc_unit_budget_bits(rate.target_bpp, pixels, pictures_coded, spent_bits, rate.horizon, want);
+            abi_ok(budget, "rate control");
+            qp = dcvc_rc_pick_qp_near(inter_probe_bits, &p, budget, start_q, rate.qp_min, rate.qp_max, &ru.probes);
+            abi_ok(qp, "size probe");
+            ru.predicted_bytes = p.bytes.at(qp);
+            start_q = qp;
         }
         if (intra) {
             ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, qp, pad_b, pad_r, b.x_hat, b.st);
@@ -649,7 +695,7 @@ int encode(const Args& a)
             if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
             if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
         } else {
-            if (!ctl) qp = qp_p;
+            if (!ctl && !rate_probe) qp = qp_p;
             reset = (reset_interval > 0 && (idx + delay) % reset_interval == 1) ? 1 : 0;
             if (c.ld) {
                 ec = dcvc_dmcld_compress(c.ld, b.x, g.H, g.W, qp, reset, pad_b, pad_r, b.st);
@@ -669,6 +715,7 @@ int encode(const Args& a)
         if (rate.on) {
             if (ctl) abi_ok(dcvc_rc_update(ctl, 8.0 * payload.size(), want, intra ? 1 : 0), "rate control");
             spent_bits += 8LL * static_cast<long long>(payload.size());
+            pictures_coded += want;
             ru.qp = qp;
             ru.bytes = static_cast<long long>(payload.size());
             rate_units.push_back(ru);
@@ -686,7 +733,7 @@ int encode(const Args& a)
                              ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) +
                              ", \"pictures\": " + std::to_string(frame_num) + ", \"qp_min\": " + std::to_string(rate.qp_min) +
                              ", \"qp_max\": " + std::to_string(rate.qp_max) + ", \"mode\": \"" +
-                             (rate_search ? "probe" : "feedback") + "\", \"units\": [";
+                             (rate_search || rate_probe ? "probe" : "feedback") + "\", \"units\": [";
             for (size_t i = 0; i < rate_units.size(); ++i) {
                 const RateUnit& u = rate_units[i];
                 js += std::string(i ? ", " : "") + "{\"type\": \"" + (u.intra ? "I" : "P") + "\", \"qp\": " + std::to_string(u.qp) +

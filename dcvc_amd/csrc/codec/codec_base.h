@@ -106,6 +106,16 @@ protected:
     };
     static void copy_qp_rows(std::initializer_list<QpRow> rows, int qp, hipStream_t st);
 
+    // Size probe of the inter codecs. set_param: what the coder spends on every symbol under this model's
+    // CDFs (rans/code_length.h), on the device. probe_code_length: behind the encoder's first stage, the code length of
+    // the compacted y symbols (`count` at most, the `n_totals` device totals say how many) and of the z rows of `qp`,
+    // summed on the device; ONE small copy to the host, and the call blocks for it. units = {y, z} in 2^-16 bit.
+    // DmciCodec (dmci.hip, set_param / estimate_bits) keeps a private copy of this table setup and sums buffer, which its
+    // batched probe indexes per picture: a change to the tables or the sums layout goes into both until DMCI moves here.
+    void upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z);
+    void probe_code_length(const int16_t* comp, int count, const int32_t* totals, int n_totals, const int8_t* z, int nz,
+                           int qp, int64_t units[2], int64_t* kept, hipStream_t st);
+
     RansEncoder m_enc;
     RansDecoder m_dec;
     hipStream_t m_io_stream = nullptr;    // D2H / H2D of symbols, high priority
@@ -114,6 +124,11 @@ protected:
     bool m_use_graphs = true;
 
 private:
+    const uint32_t *m_cl_y = nullptr, *m_cl_z = nullptr;
+    int m_cl_y_num = 0, m_cl_z_num = 0, m_cl_ch_z = 0;
+    unsigned long long* m_cl_sums = nullptr;      // y units, y symbols, z units
+    Pinned<unsigned long long> m_h_cl;
+
     void worker_loop();
 
     struct GraphSlot {

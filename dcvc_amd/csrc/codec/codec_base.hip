@@ -1,6 +1,8 @@
 // See codec_base.h.
 #include "codec/codec_base.h"
 
+#include "rans/code_length.h"
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -186,6 +188,51 @@ void CodecBase::load_cdf_tables(const ParamStore& ps)
     };
     cdf("bit_estimator_z.quantized_cdf", "bit_estimator_z.cdf_length", 0);
     cdf("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", 1);
+}
+
+void CodecBase::upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z)
+{
+    auto upload = [&](const char* name_cdf, const char* name_len, int cols, int& num) {
+        const HostTensor& c = ps.at(name_cdf);
+        const HostTensor& l = ps.at(name_len);
+        num = static_cast<int>(l.numel());
+        std::vector<uint32_t> host(static_cast<size_t>(num) * cols);
+        code_length_table(c.i.data(), num, static_cast<int>(c.numel() / num), l.i.data(), cols, host.data());
+        void* dev = mem.alloc(host.size() * sizeof(uint32_t));
+        hip_check(hipMemcpy(dev, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D code-length table");
+        return static_cast<const uint32_t*>(dev);
+    };
+    m_cl_z = upload("bit_estimator_z.quantized_cdf", "bit_estimator_z.cdf_length", kCodeLengthZCols, m_cl_z_num);
+    m_cl_y = upload("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", kCodeLengthYCols, m_cl_y_num);
+    if (m_cl_y_num > 256) throw std::invalid_argument("more than 256 Gaussian CDFs");
+    m_cl_ch_z = ch_z;
+    m_cl_sums = static_cast<unsigned long long*>(mem.alloc(sizeof(unsigned long long) * 3));
+    m_h_cl.reserve(3);
+}
+
+void CodecBase::probe_code_length(const int16_t* comp, int count, const int32_t* totals, int n_totals, const int8_t* z, int nz,
+                                  int qp, int64_t units[2], int64_t* kept, hipStream_t st)
+{
+    if (m_cl_sums == nullptr) throw std::runtime_error("estimate_bits: set_param() has not been called");
+    if (qp < 0 || (qp + 1) * m_cl_ch_z > m_cl_z_num) throw std::invalid_argument("estimate_bits: no z CDFs for this qp");
+    hip_check(hipMemsetAsync(m_cl_sums, 0, sizeof(unsigned long long) * 3, st), "hipMemsetAsync(code length)");
+    CodeLengthY dy;
+    dy.sym = comp;
+    dy.totals = totals; dy.totals_stride = 4; dy.n_totals = n_totals;
+    dy.count = count;
+    dy.table = m_cl_y; dy.num_cdf = m_cl_y_num;
+    dy.out = m_cl_sums; dy.out_stride = 3; dy.kept_slot = 1;
+    code_length_y(dy, st);
+    CodeLengthZ dz;
+    dz.z = z; dz.count = nz; dz.ch = m_cl_ch_z;
+    dz.table = m_cl_z + static_cast<size_t>(qp) * m_cl_ch_z * kCodeLengthZCols;
+    dz.out = m_cl_sums + 2; dz.out_stride = 3;
+    code_length_z(dz, st);
+    hip_check(hipMemcpyAsync(m_h_cl.get(), m_cl_sums, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost, st), "D2H code length");
+    hip_check(hipStreamSynchronize(st), "sync");
+    units[0] = static_cast<int64_t>(m_h_cl[0]);
+    units[1] = static_cast<int64_t>(m_h_cl[2]);
+    if (kept) *kept = static_cast<int64_t>(m_h_cl[1]);
 }
 
 const half_t* CodecBase::upload_qp_table(const ParamStore& ps, DeviceArena& mem, const char* name, int ch)

@@ -38,6 +38,9 @@ public:
     void decompress(const uint8_t* bits, size_t nbytes, int qp, int height, int width, int ec_parallel,
                     bool reset_feature_memory, half_t* x_hat, hipStream_t stream);
 
+    // Not in the reference: the size probe, as DmcLdCodec::estimate_bits. x as for compress.
+    void estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept, hipStream_t stream);
+
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
     // Temporal state (reference feature, memory | feature_p, ctx + validity flags) as one flat DEVICE
@@ -85,6 +88,7 @@ private:
     void run_recon_head(half_t* x_hat, hipStream_t st);   // feature_p -> 8 pictures + FI
     void run_recon_reset(hipStream_t st);             // feature_p -> FI (picture 7's head only)
     void enc_entropy_stage(hipStream_t st);
+    void enc_stage0(hipStream_t st);                  // x, ctx, memory -> symbols, totals, z: all compress() codes
     void entropy_encode(int qp);                      // worker thread
 
     const bool m_hts;

@@ -81,6 +81,7 @@ void DmcHtCodec::set_param(const ParamStore& ps, float skip_thres)
     }
     if (m_sp3.conv.cout != (m_hts ? kChY : 2 * kChY)) throw std::invalid_argument("unexpected y_spatial_prior.conv.3 width");
     load_cdf_tables(ps);
+    upload_code_length_tables(ps, m_wmem, kChZ);      // for estimate_bits
     m_has_params = true;
     m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
 }
@@ -350,6 +351,16 @@ void DmcHtCodec::enc_entropy_stage(hipStream_t st)
     scale_clamped(m_CATSP, 2 * kChY, m_COMMON, ldc, m_CATSP, 2 * kChY, g.P16(), kChY, false, st);
 }
 
+void DmcHtCodec::enc_stage0(hipStream_t st)
+{
+    run_encoder(st);
+    run_hyper_encoder(st);
+    run_tpe(st);
+    run_common(st);
+    run_reduction(st);
+    enc_entropy_stage(st);
+}
+
 int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool reset, hipStream_t user)
 {
     prepare(height, width);
@@ -361,14 +372,7 @@ int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool re
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8(x, height, width, 3 * kFrames, m_CATE, g.H8, g.W8, st, kChSrc + kChD);
-    run_stage(kEnc0, st, [&] {
-        run_encoder(st);
-        run_hyper_encoder(st);
-        run_tpe(st);
-        run_common(st);
-        run_reduction(st);
-        enc_entropy_stage(st);
-    });
+    run_stage(kEnc0, st, [&] { enc_stage0(st); });
     submit(st, [this, qp] { entropy_encode(qp); });
     run_stage(kEnc1 + (reset ? 1 : 0), st, [&] {
         run_decoder(st);
@@ -384,6 +388,31 @@ int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool re
     m_has_feature_p = true;
     wait_job();
     return m_ec_parallel;
+}
+
+// ------------------------------------------------------------------------------------ size probe
+void DmcHtCodec::estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept,
+                               hipStream_t user)
+{
+    // every refusal comes before anything is touched: prepare() with another size would drop the temporal state
+    if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMC-HT estimate_bits: qp must be in [0, 63]");
+    if (!m_has_params || !m_enc_ready) {
+        throw std::runtime_error("DMC-HT estimate_bits: no reference feature "
+                                 "(call add_ref_feature_from_frame(frame, true) first)");
+    }
+    if (height <= 0 || width <= 0 || ceil_div(height, 16) * 2 != m_g.H8 || ceil_div(width, 16) * 2 != m_g.W8) {
+        throw std::invalid_argument("DMC-HT estimate_bits: the picture size is not the one of the temporal state");
+    }
+    const Geometry& g = m_g;
+    hipStream_t st = enter(user);
+    select_qp(qp, st);
+    pad_unshuffle8(x, height, width, 3 * kFrames, m_CATE, g.H8, g.W8, st, kChSrc + kChD);
+    // the stage compress() runs (and, with graphs, the graph it replays). It reads memory and ctx and writes neither:
+    // run_tpe derives its input and the temporal parameters into buffers of their own.
+    run_stage(kEnc0, st, [&] { enc_stage0(st); });
+    // HT-S: all symbols behind one total; HT-L: the four groups back to back, four totals
+    probe_code_length(m_COMP, g.P16() * kChY, m_TOTALS, m_hts ? 1 : 4, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
+    leave(user);
 }
 
 void DmcHtCodec::entropy_encode(int qp)

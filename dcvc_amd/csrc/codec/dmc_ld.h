@@ -32,6 +32,13 @@ public:
     void decompress(const uint8_t* bits, size_t nbytes, int qp, int height, int width, int ec_parallel,
                     bool reset_feature_memory, half_t* x_hat, hipStream_t stream);
 
+    // Not in the reference: the size probe. What compress(x, qp, ...) would spend, without coding: the first
+    // stage of compress (the same launches, the same graph), then the code lengths summed on the device. units = {y, z}
+    // in 2^-16 bit, kept (may be null) = the y symbols that would be coded. Neither the temporal state nor the stream of
+    // the last compress changes. Refused, with nothing touched: qp outside 0..63, no encoder-side reference, a picture size
+    // other than the temporal state's.
+    void estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept, hipStream_t stream);
+
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
     // Temporal state as one flat DEVICE buffer (reference feature, memory | feature_p, ctx, temporal
@@ -63,10 +70,11 @@ private:
     void run_tpe(hipStream_t st);                     // memory -> temporal params
     void run_encoder(hipStream_t st);                 // [x unshuffled | ctx] -> Y
     void run_hyper_encoder(hipStream_t st);           // Y -> z, z_hat
-    void run_priors(hipStream_t st);                  // z_hat, temporal -> common params
+    void run_priors(hipStream_t st);                  // z_hat, temporal -> common params (the temporal prior is only read)
     void run_spatial_prior(hipStream_t st);           // [y_hat | common] -> means of step 1
     void run_decoder(hipStream_t st);                 // y_hat, ctx -> feature_p
     void run_recon_head(half_t* x_hat, hipStream_t st);   // feature_p -> FI (+ x_hat)
+    void enc_stage0(hipStream_t st);                  // x, ctx, temporal -> symbols, totals, z: all compress() codes
     void entropy_encode(int qp);                      // worker thread
 
     // ---- parameters
@@ -107,7 +115,8 @@ private:
     half_t *m_Z1 = nullptr, *m_Z2 = nullptr, *m_Z3 = nullptr, *m_ZH = nullptr;
     int8_t* m_ZI8 = nullptr;
     half_t *m_H1 = nullptr, *m_H2 = nullptr, *m_HP = nullptr;
-    half_t* m_CATPF = nullptr;   // [P16][384] hyper params | temporal params
+    half_t* m_TP = nullptr;      // [P16][256] temporal params: state, written by run_tpe alone
+    half_t* m_PF = nullptr;      // [P16][384] hyper params | temporal params * q_feature: the fusion chain, in place
     half_t* m_CATSP = nullptr;   // [P16][512] y_hat | q_dec | scales | means
     half_t* m_SPT = nullptr;     // [P16][256]
     half_t* m_MEANS1 = nullptr;  // [P16][128]

@@ -74,6 +74,7 @@ void DmcLdCodec::set_param(const ParamStore& ps, float skip_thres)
     chain(m_rh, 3, "recon_head.conv.");
     m_rh_head.load(ps, m_wmem, "recon_head.head.");
     load_cdf_tables(ps);
+    upload_code_length_tables(ps, m_wmem, kChZ);      // for estimate_bits
     m_has_params = true;
     m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
 }
@@ -108,7 +109,8 @@ void DmcLdCodec::prepare(int height, int width)
     m_Z1 = H(P16p * kChZ); m_Z2 = H(P32 * kChZ); m_Z3 = H(P64 * kChZ); m_ZH = H(P64 * kChZ);
     m_ZI8 = static_cast<int8_t*>(m_bmem.alloc(P64 * kChZ));
     m_H1 = H(P32 * kChZ); m_H2 = H(P16p * kChZ); m_HP = H(P16p * kChY);
-    m_CATPF = H(P16 * 3 * kChY);
+    m_TP = H(P16 * 2 * kChY);
+    m_PF = H(P16 * 3 * kChY);
     m_CATSP = H(P16 * 4 * kChY);
     m_SPT = H(P16 * 2 * kChY);
     m_MEANS1 = H(P16 * kChY);
@@ -161,7 +163,7 @@ void DmcLdCodec::run_fe(hipStream_t st, bool dc0_done)
 
 void DmcLdCodec::run_tpe(hipStream_t st)
 {
-    const View out(m_CATPF + kChY, 3 * kChY, 2 * kChY);
+    const View out(m_TP, 2 * kChY, 2 * kChY);
     m_tpe.forward(View(m_CATM, kChM + kChD, kChM), out, out, m_g.H8, m_g.W8, m_zeros, m_s, st);
 }
 
@@ -202,9 +204,11 @@ void DmcLdCodec::run_priors(hipStream_t st)
     m_hdec1.forward(h1, h2, h2, g.H32, g.W32, m_s, st);
     m_hdec2.forward(h2, View(m_HP, kChY, kChY), g.H16p, g.W16p, m_s, st);
     // crop_hyper_params -> first third of the fusion input (dmc_ld_proxy.cpp:437-438)
-    crop(m_HP, kChY, g.W16p, m_CATPF, 3 * kChY, g.H16, g.W16, kChY, st);
-    mul_channel(m_CATPF + kChY, 3 * kChY, m_cur_q_feature, m_CATPF + kChY, 3 * kChY, g.P16(), 2 * kChY, st);
-    const View pf(m_CATPF, 3 * kChY, 3 * kChY);
+    crop(m_HP, kChY, g.W16p, m_PF, 3 * kChY, g.H16, g.W16, kChY, st);
+    // the temporal prior is state (the previous picture's last stage left it, export_state carries it): it is scaled INTO
+    // the fusion input, which the chain then overwrites, and stays as it is - a size probe reads it any number of times
+    mul_channel(m_TP, 2 * kChY, m_cur_q_feature, m_PF + kChY, 3 * kChY, g.P16(), 2 * kChY, st);
+    const View pf(m_PF, 3 * kChY, 3 * kChY);
     // y_prior_fusion: three (384, 192) blocks in place, each launch with dc.0 of the next inside, the last one with
     // y_prior_fusion.conv.3 -> (q_dec | scales | means) behind y_hat in the spatial-prior input
     const FinCall fin(m_fus3, m_CATSP + kChY, 4 * kChY);
@@ -273,24 +277,7 @@ int DmcLdCodec::compress(const half_t* x, int height, int width, int qp, bool re
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8(x, height, width, 3, m_CATD + 64, g.H8, g.W8, st, kChD + kChM);   // x varies: outside the graph
-    run_stage(kEnc0, st, [&] {
-        run_encoder(st);
-        run_hyper_encoder(st);
-        run_priors(st);
-        MaskStepEnc d;
-        d.y = m_Y; d.ldy = kChY;
-        d.q_dec = m_CATSP + kChY; d.ldq = 4 * kChY;
-        d.scales = m_CATSP + 2 * kChY; d.lds = 4 * kChY;
-        d.means = m_CATSP + 3 * kChY; d.ldm = 4 * kChY;
-        d.y_hat = m_CATSP; d.ldh = 4 * kChY;
-        d.sym = m_SYM; d.cond = m_COND; d.block_count = m_CNT;
-        d.H = g.H16; d.W = g.W16; d.C = kChY; d.step = 0; d.skip_thres = m_skip_thres;
-        mask_step_enc(d, st);
-        run_spatial_prior(st);
-        d.means = m_MEANS1; d.ldm = kChY; d.step = 1;
-        mask_step_enc(d, st);
-        compact(m_SYM, 2, m_COND, m_CNT, g.P16() * kChY, m_COMP, m_TOTALS, 0, st);
-    });
+    run_stage(kEnc0, st, [&] { enc_stage0(st); });
     submit(st, [this, qp] { entropy_encode(qp); });
     // decoder + temporal state update run on the GPU while the worker entropy-codes on the host
     run_stage(kEnc1 + (reset ? 1 : 0), st, [&] {
@@ -308,6 +295,51 @@ int DmcLdCodec::compress(const half_t* x, int height, int width, int qp, bool re
     m_has_feature_p = true;
     wait_job();
     return m_ec_parallel;
+}
+
+// ------------------------------------------------------------------------------------ size probe
+void DmcLdCodec::enc_stage0(hipStream_t st)
+{
+    const Geometry& g = m_g;
+    run_encoder(st);
+    run_hyper_encoder(st);
+    run_priors(st);
+    MaskStepEnc d;
+    d.y = m_Y; d.ldy = kChY;
+    d.q_dec = m_CATSP + kChY; d.ldq = 4 * kChY;
+    d.scales = m_CATSP + 2 * kChY; d.lds = 4 * kChY;
+    d.means = m_CATSP + 3 * kChY; d.ldm = 4 * kChY;
+    d.y_hat = m_CATSP; d.ldh = 4 * kChY;
+    d.sym = m_SYM; d.cond = m_COND; d.block_count = m_CNT;
+    d.H = g.H16; d.W = g.W16; d.C = kChY; d.step = 0; d.skip_thres = m_skip_thres;
+    mask_step_enc(d, st);
+    run_spatial_prior(st);
+    d.means = m_MEANS1; d.ldm = kChY; d.step = 1;
+    mask_step_enc(d, st);
+    compact(m_SYM, 2, m_COND, m_CNT, g.P16() * kChY, m_COMP, m_TOTALS, 0, st);
+}
+
+void DmcLdCodec::estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept,
+                               hipStream_t user)
+{
+    // every refusal comes before anything is touched: prepare() with another size would drop the temporal state
+    if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMC-LD estimate_bits: qp must be in [0, 63]");
+    if (!m_has_params || !m_enc_ready) {
+        throw std::runtime_error("DMC-LD estimate_bits: no reference feature "
+                                 "(call add_ref_feature_from_frame(frame, true) first)");
+    }
+    if (height <= 0 || width <= 0 || ceil_div(height, 16) * 2 != m_g.H8 || ceil_div(width, 16) * 2 != m_g.W8) {
+        throw std::invalid_argument("DMC-LD estimate_bits: the picture size is not the one of the temporal state");
+    }
+    const Geometry& g = m_g;
+    hipStream_t st = enter(user);
+    select_qp(qp, st);
+    pad_unshuffle8(x, height, width, 3, m_CATD + 64, g.H8, g.W8, st, kChD + kChM);
+    // the stage compress() runs (and, with graphs, the graph it replays). It reads the temporal state - ctx, the temporal
+    // prior - and writes none of it; what it leaves in the scratch buffers the next call's first stage overwrites.
+    run_stage(kEnc0, st, [&] { enc_stage0(st); });
+    probe_code_length(m_COMP, g.P16() * kChY, m_TOTALS, 1, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
+    leave(user);
 }
 
 void DmcLdCodec::entropy_encode(int qp)
@@ -450,7 +482,7 @@ size_t DmcLdCodec::export_state(void* dst, size_t cap, hipStream_t user)
     // ctx and the temporal prior are channel slices of wider buffers: dense copies
     hip_check(hipMemcpy2DAsync(out, 2 * kChM, m_CATD + kChD, 2 * (kChD + kChM), 2 * kChM, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
     out += 2 * n_ctx;
-    hip_check(hipMemcpy2DAsync(out, 4 * kChY, m_CATPF + kChY, 6 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
+    hip_check(hipMemcpy2DAsync(out, 4 * kChY, m_TP, 4 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
     leave(user);
     return bytes;
 }
@@ -481,7 +513,7 @@ void DmcLdCodec::import_state(const void* src, size_t bytes, int height, int wid
     get(m_CATM, n_catm);
     hip_check(hipMemcpy2DAsync(m_CATD + kChD, 2 * (kChD + kChM), in, 2 * kChM, 2 * kChM, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
     in += 2 * n_ctx;
-    hip_check(hipMemcpy2DAsync(m_CATPF + kChY, 6 * kChY, in, 4 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
+    hip_check(hipMemcpy2DAsync(m_TP, 4 * kChY, in, 4 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
     leave(user);
     m_has_ref = h.flags & 1u; m_enc_ready = h.flags & 2u; m_memory_has_value = h.flags & 4u; m_has_feature_p = h.flags & 8u;
 }
@@ -503,7 +535,7 @@ size_t DmcLdCodec::debug_read(const std::string& name, void* dst, size_t cap, hi
     else if (name == "memory") view(m_CATM, g.P8(), kChM, kChM + kChD, 2);
     else if (name == "feature_p") view(m_CATM + kChM, g.P8(), kChD, kChM + kChD, 2);
     else if (name == "ctx") view(m_CATD + kChD, g.P8(), kChM, kChD + kChM, 2);
-    else if (name == "temporal") view(m_CATPF + kChY, g.P16(), 2 * kChY, 3 * kChY, 2);
+    else if (name == "temporal") view(m_TP, g.P16(), 2 * kChY, 2 * kChY, 2);
     else if (name == "feature_i") view(m_FI, g.P8(), kChSrc, kChSrc, 2);
     else if (name == "symbols") view(m_COMP, 1, g.P16() * kChY, g.P16() * kChY, 2);
     else if (name == "totals") view(m_TOTALS, 1, 4, 4, 4);

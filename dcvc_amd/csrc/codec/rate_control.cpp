@@ -69,6 +69,59 @@ int pick_qp_for_budget(const std::function<int64_t(int)>& estimate, int64_t budg
     return lo < qp_min ? qp_min : lo;
 }
 
+int pick_qp_near(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int start, int qp_min, int qp_max, int* probes)
+{
+    if (qp_min > qp_max) throw std::invalid_argument("pick_qp_near: qp_min above qp_max");
+    int count = 0;
+    auto fits = [&](int qp) {
+        const int64_t bits = estimate(qp);
+        ++count;
+        if (probes) *probes = count;
+        if (bits < 0) throw std::runtime_error("pick_qp_near: the size probe failed");
+        return bits <= budget_bits;
+    };
+    if (probes) *probes = 0;
+    const int s = std::min(qp_max, std::max(qp_min, start));
+    int lo = qp_min - 1, hi = qp_max + 1, step = 1;
+    if (fits(s)) {
+        lo = s;
+        while (lo < qp_max) {
+            const int q = std::min(lo + step, qp_max);
+            if (!fits(q)) {
+                hi = q;
+                break;
+            }
+            lo = q;
+            step *= 2;
+        }
+    } else {
+        hi = s;
+        while (hi > qp_min) {
+            const int q = std::max(hi - step, qp_min);
+            if (fits(q)) {
+                lo = q;
+                break;
+            }
+            hi = q;
+            step *= 2;
+        }
+    }
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (fits(mid)) lo = mid; else hi = mid;
+    }
+    return lo < qp_min ? qp_min : lo;
+}
+
+int64_t unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits, int horizon, int n)
+{
+    if (horizon < 1 || n < 0) throw std::invalid_argument("unit_budget_bits: horizon must be positive, n not negative");
+    const double share = target_bpp * pixels_per_picture;
+    const double budget = share * (pictures_coded + horizon) - static_cast<double>(spent_bits);
+    const double want = std::max(budget / horizon, share / 64.0);
+    return static_cast<int64_t>(std::floor(want * n));
+}
+
 int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits)
 {
     const double share = target_bpp * pixels_per_picture;

@@ -33,6 +33,19 @@ private:
 // ceil(log2(qp_max - qp_min + 2)) probes. probes (may be null) receives their number.
 int pick_qp_for_budget(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int qp_min, int qp_max, int* probes);
 
+// The same answer from a start value, for P units whose neighbours have neighbouring size curves. s = start clamped to the
+// range is probed. It fits: gallop upward - min(lo + step, qp_max) with step = 1, 2, 4, ... from lo = s, lo moving to every
+// value that fits - to the first value that does not fit (hi) or until lo = qp_max. It does not: gallop downward from hi = s -
+// max(hi - step, qp_min), hi moving to every value that does not fit - to the first value that fits (lo) or until hi = qp_min.
+// Then the bisection of pick_qp_for_budget on (lo, hi). No q_index is probed twice; 2 probes when the answer is start, at
+// most 2 ceil(log2(qp_max - qp_min + 2)) + 1 in any range (12 over 0 .. 63).
+int pick_qp_near(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int start, int qp_min, int qp_max, int* probes);
+
+// Budget of a P unit of n pictures in a run towards target_bpp, from what TargetBpp::update aims at: with share =
+// target_bpp * pixels_per_picture, want = max((share * (pictures_coded + horizon) - spent_bits) / horizon, share / 64) bits
+// per picture; floor(want * n) in double arithmetic.
+int64_t unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits, int horizon, int n);
+
 // Budget of picture k (0-based) of an all-intra run towards target_bpp: what the k + 1 pictures may take together minus what
 // the first k took, floored at a quarter of one picture's share. floor() of the double value.
 int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);

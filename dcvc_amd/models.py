@@ -243,6 +243,11 @@ class DMC(CompressionModel):
             bool(reset_feature_memory))
         return {"x_hat": x_hat}
 
+    # not in the reference: the size probe - what compress() would spend against the temporal state the
+    # proxy holds, without coding and without advancing that state -> (y_units, z_units, symbols)
+    def estimate_bits(self, x, qp, padding_b, padding_r):
+        return self._ensure_proxy().estimate_bits(x, qp, padding_b, padding_r)
+
 
 class DMCHT(DMC):
     """video_model_ht.py:320-470 (inference subset): the hierarchical inter models, 8 pictures per

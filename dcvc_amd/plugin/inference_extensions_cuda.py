@@ -88,6 +88,9 @@ _LD = dict(
     export_state=_lib.fn("dcvc_dmcld_export_state", ctypes.c_int64, [_vp, _vp, ctypes.c_size_t, _vp]),
     import_state=_lib.fn("dcvc_dmcld_import_state", _ci, [_vp, _vp, ctypes.c_size_t, _ci, _ci, _vp]),
     debug_read=_lib.fn("dcvc_dmcld_debug_read", ctypes.c_int64, [_vp, ctypes.c_char_p, _vp, ctypes.c_size_t, _vp]),
+    estimate_bits=_lib.fn("dcvc_dmcld_estimate_bits", _ci,
+                          [_vp, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
+    estimate_symbols=_lib.fn("dcvc_dmcld_estimate_symbols", ctypes.c_int64, [_vp]),
 )
 
 _HT = dict(
@@ -107,6 +110,9 @@ _HT = dict(
     import_feature=_lib.fn("dcvc_dmcht_import_feature", _ci, [_vp, _vp, ctypes.c_size_t, _ci, _ci, _vp]),
     run_recon_heads=_lib.fn("dcvc_dmcht_run_recon_heads", _ci, [_vp, ctypes.c_uint, _vp, _vp]),
     debug_read=_lib.fn("dcvc_dmcht_debug_read", ctypes.c_int64, [_vp, ctypes.c_char_p, _vp, ctypes.c_size_t, _vp]),
+    estimate_bits=_lib.fn("dcvc_dmcht_estimate_bits", _ci,
+                          [_vp, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
+    estimate_symbols=_lib.fn("dcvc_dmcht_estimate_symbols", ctypes.c_int64, [_vp]),
 )
 
 _DTYPES = {torch.float16: 0, torch.float32: 1, torch.int32: 2}
@@ -321,6 +327,18 @@ class DMCLDProxy(_Proxy):
         return x_hat
 
 
+def _estimate_bits_inter(self, x, qp, padding_b, padding_r):
+    """Not part of the reference surface: the size probe. What compress(x, qp, reset, ...) would spend
+    against the temporal state the object holds, without coding: -> (y_units, z_units, symbols) as
+    DMCIProxy.estimate_bits. x is what compress takes (HT: the [1, 24, H, W] chunk). The temporal state and the stream of
+    the last compress stay as they are."""
+    x, xp = _nhwc_ptr(x, 3 * getattr(self, "FRAMES", 1))
+    units = (ctypes.c_int64 * 2)()
+    _lib.check(self._FN["estimate_bits"](self._h, xp, int(x.shape[2]), int(x.shape[3]), int(qp), int(padding_b),
+                                         int(padding_r), units, _stream_ptr()))
+    return int(units[0]), int(units[1]), int(_lib.check(self._FN["estimate_symbols"](self._h)))
+
+
 def _export_state(self):
     """-> uint8 CUDA tensor holding the temporal state (send it with torch.distributed.send)."""
     n = _lib.check(self._FN["export_state"](self._h, None, 0, _stream_ptr()))
@@ -338,6 +356,7 @@ def _import_state(self, state, height, width):
 
 
 DMCLDProxy.export_state = _export_state
+DMCLDProxy.estimate_bits = _estimate_bits_inter
 DMCLDProxy.import_state = _import_state
 
 
@@ -416,6 +435,7 @@ class _DMCHTProxy(_Proxy):
 
 
 _DMCHTProxy.export_state = _export_state
+_DMCHTProxy.estimate_bits = _estimate_bits_inter
 _DMCHTProxy.import_state = _import_state
 
 

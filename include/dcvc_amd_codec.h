@@ -136,6 +136,17 @@ int dcvc_dmcld_decompress(dcvc_dmcld* c, const uint8_t* bit_stream, size_t nbyte
                           int width, int ec_parallel, int reset_feature_memory, void* x_hat,
                           void* stream);
 
+/* Not part of the reference surface: the size probe, as dcvc_dmci_estimate_bits. What dcvc_dmcld_compress
+ * would spend on the picture at this qp against the temporal state the object holds, without coding it: the first stage
+ * of compress (the same launches and graph), the code lengths summed on the device, one small device-to-host copy.
+ * out_units[0] = y, out_units[1] = z in 2^-16 bit; dcvc_dmcld_estimate_symbols = the y symbols of the last probe that
+ * would be coded. The temporal state, the stream of the last compress and everything a later compress gives stay as they
+ * are. Refused, with nothing touched: qp outside 0..63, no encoder-side reference (add_ref with apply_adaptor != 0, or a
+ * compress), a picture size other than the temporal state's. */
+int dcvc_dmcld_estimate_bits(dcvc_dmcld* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                             int64_t* out_units, void* stream);
+int64_t dcvc_dmcld_estimate_symbols(dcvc_dmcld* c);
+
 /* Not part of the reference surface - hand-off of a GOP to another GPU (north_star: temporal
  * context exchanged point-to-point over xGMI): the temporal state (reference feature, memory,
  * last decoded feature, context, temporal prior, validity flags) as ONE flat device buffer that
@@ -173,6 +184,10 @@ int64_t dcvc_dmcht_get_stream(dcvc_dmcht* c, uint8_t* dst, size_t cap);
 int dcvc_dmcht_decompress(dcvc_dmcht* c, const uint8_t* bit_stream, size_t nbytes, int qp, int height,
                           int width, int ec_parallel, int reset_feature_memory, void* x_hat,
                           void* stream);
+/* Not part of the reference surface: the size probe of a chunk, as dcvc_dmcld_estimate_bits (x as for compress) */
+int dcvc_dmcht_estimate_bits(dcvc_dmcht* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
+                             int64_t* out_units, void* stream);
+int64_t dcvc_dmcht_estimate_symbols(dcvc_dmcht* c);
 /* GOP hand-off between GPUs, as dcvc_dmcld_export_state / _import_state */
 int64_t dcvc_dmcht_export_state(dcvc_dmcht* c, void* dst, size_t cap, void* stream);
 int dcvc_dmcht_import_state(dcvc_dmcht* c, const void* src, size_t bytes, int height, int width, void* stream);

@@ -33,6 +33,20 @@ double dcvc_rc_state_qp(const dcvc_rc* rc);      /* the controller's fractional 
 typedef int64_t (*dcvc_rc_estimate_fn)(int qp, void* user);
 int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int qp_min, int qp_max,
                                int* probes);
+/* The same answer as dcvc_rc_pick_qp_for_budget on a size curve that rises with the q_index, from a start value (the
+ * q_index of the previous P unit): s = start clamped to [qp_min, qp_max] is probed; if it fits, min(lo + step, qp_max) with
+ * step = 1, 2, 4, ... is probed from lo = s upward, lo moving to every value that fits, until one does not (hi) or
+ * lo = qp_max; if it does not, max(hi - step, qp_min) from hi = s downward until one fits (lo) or hi = qp_min; then the
+ * bisection above on (lo, hi). Ends like it: lo fits or is qp_min - 1, lo + 1 was probed and does not fit or is
+ * qp_max + 1; returns lo, or qp_min when nothing fits. No q_index is probed twice; 2 probes when the answer is start, at
+ * most 4 within 2 of it, at most 2 ceil(log2(qp_max - qp_min + 2)) + 1 (12 over 0 .. 63). */
+int dcvc_rc_pick_qp_near(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int start, int qp_min, int qp_max,
+                         int* probes);
+/* Budget of a P unit of n pictures: share = target_bpp * pixels, want = max((share * (pictures_coded + horizon) -
+ * spent_bits) / horizon, share / 64) (what dcvc_rc_update steers towards), floor(want * n), in double arithmetic.
+ * Negative on failure (horizon < 1, n < 0). */
+int64_t dcvc_rc_unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits,
+                                 int horizon, int n);
 /* Budget of picture k (0-based) of an all-intra run: floor(max(target_bpp * pixels * (k + 1) - spent_bits,
  * target_bpp * pixels / 4)) in double arithmetic. */
 int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);

@@ -638,6 +638,16 @@ int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, 
     });
 }
 
+int dcvc_luma_sad(const void* x, int ldx, int H_, int W_, const void* prev_luma8, void* luma8_out, void* sad_out, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::LumaSadDesc d;
+        d.x = H(x); d.ldx = ldx; d.H = H_; d.W = W_;
+        d.prev = static_cast<const uint8_t*>(prev_luma8); d.luma = static_cast<uint8_t*>(luma8_out); d.sad = sad_out;
+        dcvc::luma_sad(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_mask_step_enc(void* y, int ldy, const void* q_dec, int ldq, const void* scales, int lds,
                        const void* means, int ldm, void* y_hat, int ldh, void* sym, void* cond,
                        void* block_count, void* compact_out, void* totals, int Hh, int W, int C,

@@ -9,6 +9,10 @@ struct dcvc_rc {
     dcvc::TargetBpp ctl;
 };
 
+struct dcvc_scd {
+    dcvc::SceneCut scd;
+};
+
 extern "C" {
 
 dcvc_rc* dcvc_rc_create(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus,
@@ -84,6 +88,38 @@ int64_t dcvc_rc_unit_budget_bits(double target_bpp, double pixels_per_picture, i
 int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits)
 {
     return dcvc::intra_budget_bits(target_bpp, pixels_per_picture, k, spent_bits);
+}
+
+dcvc_scd* dcvc_scd_create(double threshold, int min_gap, long long pixels)
+{
+    dcvc_scd* s = nullptr;
+    dcvc::guarded([&] { s = new dcvc_scd{dcvc::SceneCut(threshold, min_gap, pixels)}; });
+    return s;
+}
+
+void dcvc_scd_destroy(dcvc_scd* s)
+{
+    delete s;
+}
+
+int dcvc_scd_push(dcvc_scd* s, int idx, long long sad, int scheduled_intra)
+{
+    int intra = 0;
+    const int e = dcvc::guarded([&] {
+        if (s == nullptr) throw std::invalid_argument("null scene-cut detector");
+        intra = s->scd.push(idx, sad, scheduled_intra != 0) ? 1 : 0;
+    });
+    return e < 0 ? e : intra;
+}
+
+int dcvc_scd_last(const dcvc_scd* s, double* mafd, double* score, int* detected)
+{
+    return dcvc::guarded([&] {
+        if (s == nullptr) throw std::invalid_argument("null scene-cut detector");
+        if (mafd) *mafd = s->scd.mafd();
+        if (score) *score = s->scd.score();
+        if (detected) *detected = s->scd.detected() ? 1 : 0;
+    });
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
+//               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16]
 //               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
@@ -58,6 +59,17 @@
 //               that start value plus --rc-intra-bonus, and their bits count as spent. --rc-log: "mode": "probe", P units
 //               with probes >= 1 and predicted_bytes, I units with probes 0 and null. All-intra runs ignore the flag (they
 //               probe already); the stream format and the decoder do not change.
+//               --scene-cut T [--scene-min-gap G] [--scene-log log.json] (encode, one-picture inter model = LD): an I picture
+//               where the source changes scene. Every source picture is converted first and measured on
+//               the device (dcvc_luma_sad: 8-bit luma of x, sum of absolute differences against the previous picture);
+//               dcvc_scd_push (dcvc_amd_rc.h) scores it - mafd = 100 sad / (256 W H), score = mafd - the mafd of the last
+//               pair that was no cut - and a picture with score >= T (percent of full range; 5 is a reasonable start) at least
+//               G (default 8) pictures after the previous I picture is coded as one, on the path of any other I picture.
+//               --intra-period and the reset rule stay index-based; with --target-bpp the controller (or the probe mode)
+//               sees the final type. --scene-log: {threshold, min_gap, width, height, pictures: [{idx, sad, mafd, score,
+//               detected, type, reason: "first" | "period" | "cut" | null}]}. Refused: all-intra runs, --batch above 1, and
+//               the 8-picture models (HT-S / HT-L): a P unit there always holds 8 pictures and the container has no picture
+//               count, so a chunk cannot be cut short at a scene change. The stream format and the decoder do not change.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -168,6 +180,18 @@ WeightFile load_weights(const std::string& path)
     return w;
 }
 
+// the kind field of a .dcvw file's header alone (load_weights checks the rest)
+int weight_kind(const std::string& path)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) die("cannot open " + path);
+    char head[12];
+    if (!f.read(head, sizeof(head)) || std::memcmp(head, "DCVW1\0\0\0", 8) != 0) die(path + " is not a .dcvw file");
+    uint32_t kind;
+    std::memcpy(&kind, head + 8, 4);
+    return static_cast<int>(kind);
+}
+
 // ------------------------------------------------------------------------------------ codecs
 struct Codecs {
     dcvc_dmci* intra = nullptr;
@@ -253,10 +277,13 @@ struct DeviceBuffers {
     void* sse_ws = nullptr;        // dcvc_sse_ws's workspace
     long long sse_ws_bytes = 0;
     uint8_t* h_src = nullptr;      // pinned: the source picture (RGB or high-bit-depth --ref)
+    uint8_t* luma8[2] = {nullptr, nullptr};      // --scene-cut: the 8-bit luma of this picture and of the previous one, in turn
+    unsigned long long* sad = nullptr;           // --scene-cut: dcvc_luma_sad's sum
+    unsigned long long* h_sad = nullptr;         // pinned
     hipStream_t st = nullptr;
 };
 
-DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false)
+DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false, bool scene = false)
 {
     DeviceBuffers b;
     hip_ok(hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking), "hipStreamCreate");
@@ -282,6 +309,11 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false)
                                : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.H / 2, g.W / 2));
         hip_ok(hipMalloc(&b.sse_ws, static_cast<size_t>(b.sse_ws_bytes)), "hipMalloc");
     }
+    if (scene) {
+        for (uint8_t*& p : b.luma8) hip_ok(hipMalloc(&p, g.y_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&b.sad, sizeof(unsigned long long)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_sad), sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc");
+    }
     return b;
 }
 
@@ -289,12 +321,14 @@ void free_buffers(DeviceBuffers& b)
 {
     if (b.st) hip_ok(hipStreamSynchronize(b.st), "sync");
     for (void* d : {static_cast<void*>(b.yuv8), b.x, b.x_hat, b.y16, static_cast<void*>(b.out8), static_cast<void*>(b.src8),
-                    static_cast<void*>(b.ssim), static_cast<void*>(b.sse), b.sse_ws}) {
+                    static_cast<void*>(b.ssim), static_cast<void*>(b.sse), b.sse_ws, static_cast<void*>(b.luma8[0]),
+                    static_cast<void*>(b.luma8[1]), static_cast<void*>(b.sad)}) {
         if (d) hip_ok(hipFree(d), "hipFree");
     }
     if (b.h_ssim) hip_ok(hipHostFree(b.h_ssim), "hipHostFree");
     if (b.h_sse) hip_ok(hipHostFree(b.h_sse), "hipHostFree");
     if (b.h_src) hip_ok(hipHostFree(b.h_src), "hipHostFree");
+    if (b.h_sad) hip_ok(hipHostFree(b.h_sad), "hipHostFree");
     if (b.h_yuv) hip_ok(hipHostFree(b.h_yuv), "hipHostFree");
     if (b.h_p16) hip_ok(hipHostFree(b.h_p16), "hipHostFree");
     if (b.st) hip_ok(hipStreamDestroy(b.st), "hipStreamDestroy");
@@ -500,6 +534,47 @@ RateArgs rate_args(const Args& a, int batch)
     return r;
 }
 
+// --scene-cut and its companions; what the flags alone decide is refused before a model is loaded
+struct SceneArgs {
+    bool on = false;
+    double threshold = 0;
+    int min_gap = 8;
+    std::string log;
+};
+
+SceneArgs scene_args(const Args& a, int batch)
+{
+    SceneArgs sc;
+    if (!a.has("scene-cut")) {
+        for (const char* k : {"scene-min-gap", "scene-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --scene-cut");
+        }
+        return sc;
+    }
+    sc.on = true;
+    const std::string s = a.str("scene-cut");
+    char* end = nullptr;
+    sc.threshold = strtod(s.c_str(), &end);
+    if (s.empty() || *end != '\0' || !std::isfinite(sc.threshold) || !(sc.threshold > 0) || sc.threshold > 100) {
+        die("--scene-cut must be a threshold in (0, 100] (percent of full range; 5 is a reasonable start), got " + s);
+    }
+    sc.min_gap = int_arg(a, "scene-min-gap", 8, 1, 1 << 30);
+    if (batch > 1) die("--scene-cut cannot be combined with --batch above 1: a batch holds I pictures only");
+    if (!a.has("inter") || a.num("intra-period", -1) == 1) {
+        die("--scene-cut is for runs with P pictures: an all-intra run (no --inter, or --intra-period 1) has an I picture at every cut");
+    }
+    sc.log = a.str("scene-log");
+    return sc;
+}
+
+// one source picture in --scene-log
+struct ScenePicture {
+    long long sad = 0;
+    double mafd = 0, score = 0;
+    bool detected = false, intra = false;
+    const char* reason = nullptr;      // "first", "period", "cut"
+};
+
 // one coded unit in --rc-log
 struct RateUnit {
     bool intra = false;
@@ -511,6 +586,7 @@ struct RateUnit {
 int encode(const Args& a)
 {
     const int batch = batch_arg(a);
+    const SceneArgs scene = scene_args(a, batch);
     const RateArgs rate = rate_args(a, batch);
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
@@ -531,6 +607,13 @@ int encode(const Args& a)
         die("--src-type rgb24 needs -W and -H");
     }
     const Geometry g = geometry(pic_h, pic_w, rgb, depth);
+    if (scene.on) {
+        const int kind = weight_kind(a.str("inter"));      // from the file's header, before either model is built
+        if (kind == 2 || kind == 3) {
+            die("--scene-cut needs a one-picture inter model (LD): " + a.str("inter") + " codes chunks of 8 pictures, a P unit "
+                "always holds 8 and the container has no picture count, so a chunk cannot be cut short at a scene change");
+        }
+    }
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     const bool force_intra = !c.has_inter();
     const int intra_period = force_intra ? 1 : a.num("intra-period", -1);
@@ -551,7 +634,7 @@ int encode(const Args& a)
     }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
-    DeviceBuffers b = make_buffers(g, std::max(delay, batch));
+    DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
@@ -565,13 +648,21 @@ int encode(const Args& a)
         }
         hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
     };
-    auto convert = [&](char* dst, int ldx) {
+    // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
+    int luma_turn = 0;
+    auto convert = [&](char* dst, int ldx, bool measure = false, bool has_prev = false) {
         if (rgb) {
             abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, b.st), "rgb_to_x");
         } else if (g.hbd()) {
             abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, dst, ldx, b.st), "yuv420p16_to_x");
         } else {
             abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, dst, ldx, b.st), "yuv420_to_x");
+        }
+        if (measure) {
+            abi_ok(dcvc_luma_sad(dst, ldx, g.H, g.W, has_prev ? b.luma8[luma_turn ^ 1] : nullptr, b.luma8[luma_turn], b.sad, b.st),
+                   "luma_sad");
+            hip_ok(hipMemcpyAsync(b.h_sad, b.sad, sizeof(unsigned long long), hipMemcpyDeviceToHost, b.st), "D2H");
+            luma_turn ^= 1;
         }
         hip_ok(hipStreamSynchronize(b.st), "sync");      // the staging buffers are reused
     };
@@ -627,9 +718,32 @@ int encode(const Args& a)
         p.bytes[qp] = bytes;
         return 8 * bytes;
     };
+    // --scene-cut: every picture is converted and measured before its type is known (one-picture units: I and P share
+    // the x layout, ldx == 3); the detector may turn a scheduled P picture into an I picture, never the other way
+    dcvc_scd* scd = nullptr;
+    std::vector<ScenePicture> scene_pictures;
+    if (scene.on) {
+        scd = dcvc_scd_create(scene.threshold, scene.min_gap, static_cast<long long>(g.H) * g.W);
+        if (!scd) die(std::string("scene cut: ") + dcvc_last_error());
+    }
     int idx = 0;
     while (idx < frame_num) {
-        const bool intra = is_intra_picture(idx, intra_period);
+        bool intra = is_intra_picture(idx, intra_period);
+        if (scd) {
+            load_picture();
+            convert(static_cast<char*>(b.x), 3, true, idx > 0);
+            ScenePicture sp;
+            sp.sad = idx > 0 ? static_cast<long long>(*b.h_sad) : 0;
+            const int as_intra = dcvc_scd_push(scd, idx, sp.sad, intra ? 1 : 0);
+            abi_ok(as_intra, "scene cut");
+            int detected = 0;
+            abi_ok(dcvc_scd_last(scd, &sp.mafd, &sp.score, &detected), "scene cut");
+            sp.detected = detected != 0;
+            sp.reason = intra ? (idx == 0 ? "first" : "period") : (as_intra ? "cut" : nullptr);
+            intra = as_intra != 0;
+            sp.intra = intra;
+            scene_pictures.push_back(sp);
+        }
         if (intra && batch > 1) {
             // up to `batch` intra pictures in one call, each in its own slot [H][W][3]; the units go out in picture order
             const int nb = std::min(batch, frame_num - idx);
@@ -657,7 +771,7 @@ int encode(const Args& a)
         const int want = intra ? 1 : std::min(delay, frame_num - idx);
         const int slots = intra ? 1 : delay;
         const int ldx = 3 * slots;
-        for (int j = 0; j < slots; ++j) {
+        for (int j = 0; j < slots && !scd; ++j) {
             char* dst = static_cast<char*>(b.x) + 6 * j;
             if (j < want) load_picture();      // a short last chunk repeats its final picture (test_video.py:104-110)
             convert(dst, ldx);
@@ -725,6 +839,28 @@ int encode(const Args& a)
     hip_ok(hipStreamSynchronize(b.st), "sync");
     if (in) fclose(in);
     if (ctl) dcvc_rc_destroy(ctl);
+    if (scd) {
+        dcvc_scd_destroy(scd);
+        int cuts = 0;
+        for (const ScenePicture& sp : scene_pictures) cuts += sp.reason && std::strcmp(sp.reason, "cut") == 0;
+        printf("scene cut: threshold %s, min gap %d, %d of %zu pictures coded as I pictures at a cut\n", jnum(scene.threshold).c_str(),
+               scene.min_gap, cuts, scene_pictures.size());
+        if (!scene.log.empty()) {
+            std::string js = "{\"threshold\": " + jnum(scene.threshold) + ", \"min_gap\": " + std::to_string(scene.min_gap) +
+                             ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) + ", \"pictures\": [";
+            for (size_t i = 0; i < scene_pictures.size(); ++i) {
+                const ScenePicture& sp = scene_pictures[i];
+                js += std::string(i ? ", " : "") + "{\"idx\": " + std::to_string(i) + ", \"sad\": " + std::to_string(sp.sad) +
+                      ", \"mafd\": " + jnum(sp.mafd) + ", \"score\": " + jnum(sp.score) + ", \"detected\": " +
+                      (sp.detected ? "true" : "false") + ", \"type\": \"" + (sp.intra ? "I" : "P") + "\", \"reason\": " +
+                      (sp.reason ? "\"" + std::string(sp.reason) + "\"" : std::string("null")) + "}";
+            }
+            js += "]}\n";
+            FILE* lf = fopen(scene.log.c_str(), "wb");
+            if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + scene.log);
+            fclose(lf);
+        }
+    }
     if (rate.on) {
         const double achieved = static_cast<double>(spent_bits) / (static_cast<double>(frame_num) * pixels);
         printf("rate control: target %.4f bpp, coded %.4f bpp in %zu units\n", rate.target_bpp, achieved, rate_units.size());

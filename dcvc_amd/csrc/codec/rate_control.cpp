@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <stdexcept>
+#include <string>
 
 namespace dcvc {
 
@@ -127,6 +128,44 @@ int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, i
     const double share = target_bpp * pixels_per_picture;
     const double budget = std::max(share * (k + 1) - static_cast<double>(spent_bits), share / 4.0);
     return static_cast<int64_t>(std::floor(budget));
+}
+
+SceneCut::SceneCut(double threshold, int min_gap, long long pixels) : m_threshold(threshold), m_min_gap(min_gap), m_pixels(pixels)
+{
+    if (!std::isfinite(threshold) || !(threshold > 0.0) || threshold > 100.0) {
+        throw std::invalid_argument("scene cut: the threshold must be in (0, 100] (percent of full range)");
+    }
+    if (min_gap < 1) throw std::invalid_argument("scene cut: min_gap must be at least 1");
+    if (pixels < 1) throw std::invalid_argument("scene cut: pixels must be at least 1");
+}
+
+bool SceneCut::push(int idx, long long sad, bool scheduled_intra)
+{
+    if (idx != m_next) {
+        throw std::invalid_argument("scene cut: picture " + std::to_string(idx) + " pushed, " + std::to_string(m_next) + " is next");
+    }
+    if (idx > 0 && (sad < 0 || sad / 255 > m_pixels || (sad / 255 == m_pixels && sad % 255 != 0))) {      // sad > 255 * pixels
+        throw std::invalid_argument("scene cut: sad " + std::to_string(sad) + " is outside [0, 255 * pixels]");
+    }
+    m_next = idx + 1;
+    if (idx == 0) {
+        m_mafd = m_score = 0.0;
+        m_detected = false;
+    } else {
+        m_mafd = 100.0 * static_cast<double>(sad) / (256.0 * static_cast<double>(m_pixels));
+        m_score = m_has_base ? m_mafd - m_base : 0.0;
+        m_detected = m_score >= m_threshold;
+        if (!m_detected) {
+            m_base = m_mafd;
+            m_has_base = true;
+        }
+    }
+    const bool intra = scheduled_intra || (m_detected && (!m_has_intra || idx - m_last_intra >= m_min_gap));
+    if (intra) {
+        m_last_intra = idx;
+        m_has_intra = true;
+    }
+    return intra;
 }
 
 }  // namespace dcvc

@@ -50,4 +50,27 @@ int64_t unit_budget_bits(double target_bpp, double pixels_per_picture, int pictu
 // the first k took, floored at a quarter of one picture's share. floor() of the double value.
 int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);
 
+// Scene-cut decisions of dcvc encode --scene-cut (dcvc_amd/scene.py SceneCut is the restatement). Pictures
+// are pushed in source order with the luma SAD against their predecessor (dcvc_luma_sad). mafd = 100.0 * sad /
+// (256.0 * pixels) in double, in this operation order; score = mafd - base, base = the mafd of the most recent pair that
+// was not detected (no base yet: score 0, and the pair becomes the base); detected = score >= threshold. A detected pair
+// leaves the base alone, so the picture after a cut is measured against the motion before it, not against the spike.
+class SceneCut {
+public:
+    SceneCut(double threshold, int min_gap, long long pixels);      // threshold in (0, 100], min_gap >= 1, pixels >= 1
+    // true: code picture idx as an I picture - it is scheduled as one, or it is detected and at least min_gap pictures
+    // after the last picture this returned true for (none yet: far enough). idx must follow the previous one (0 first);
+    // sad in [0, 255 * pixels], ignored for idx 0. A refused push (std::invalid_argument) changes nothing.
+    bool push(int idx, long long sad, bool scheduled_intra);
+    double mafd() const { return m_mafd; }
+    double score() const { return m_score; }
+    bool detected() const { return m_detected; }
+
+private:
+    double m_threshold, m_base = 0.0, m_mafd = 0.0, m_score = 0.0;
+    int m_min_gap, m_next = 0, m_last_intra = 0;
+    long long m_pixels;
+    bool m_has_base = false, m_has_intra = false, m_detected = false;
+};
+
 }  // namespace dcvc

@@ -324,6 +324,21 @@ void sse_validate(const SseDesc& d);             // throws std::invalid_argument
 size_t sse_workspace_bytes(int n_planes, int H, int W);
 void sse(const SseDesc& d, void* workspace, hipStream_t stream);
 
+// ---------------------------------------------------------------- scene-cut measurement (scene.hip)
+// x fp16, pixel (r, c) at x + (r W + c) ldx (all ldx halfs of a pixel readable), luma in channel 0 -> luma u8 [H][W] =
+// clamp(rintf((float(x0) + 0.5f) * 255.f), 0, 255) and *sad (one device uint64) = sum |luma - prev| over the plane, an
+// exact integer; prev null: *sad = 0. At most two launches, no host synchronisation.
+constexpr int kLumaSadMaxSide = 16384;
+struct LumaSadDesc {
+    const half_t* x = nullptr; int ldx = 3;
+    int H = 0, W = 0;
+    const uint8_t* prev = nullptr;
+    uint8_t* luma = nullptr;
+    void* sad = nullptr;
+};
+void luma_sad_validate(const LumaSadDesc& d);    // throws std::invalid_argument for what luma_sad() refuses
+void luma_sad(const LumaSadDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -91,19 +91,25 @@ class TargetBpp:
 
 
 def code_sequence(frame_count, frames_per_p, code_intra, code_inter, controller, intra_period=-1, reset_interval=32,
-                  force_intra=False):
+                  force_intra=False, intra_at=None):
     """The encode loop of test_video.py:204-257 with the q_index from `controller`.
 
     code_intra(frame_idx, qp) -> bytes-like          one I picture
     code_inter(frame_idx, n, qp, reset) -> bytes-like a P unit of frames_per_p pictures starting at frame_idx, of which
                                                       the first n exist in the source (the caller pads the rest by
                                                       repeating the last picture, test_video.py:104-110)
+    intra_at(frame_idx, scheduled) -> bool            optional (dcvc encode --scene-cut, scene.SceneCut.push behind it): asked
+                                                      once for every picture a unit starts with, in coding order, with the
+                                                      index-based decision; its answer is the picture's type. None: the
+                                                      index-based decision stands.
     Returns [(is_intra, qp, reset, payload)] in coding order - what write_ip stores per unit."""
     units, idx = [], 0
     while idx < frame_count:
         # test_video.py:204-213: frame 0; every frame when intra_period == 1 (or --force_intra); with intra_period > 1
         # every frame with index % intra_period == 1 other than frame 1
         intra = idx == 0 or force_intra or intra_period == 1 or (intra_period > 1 and idx != 1 and idx % intra_period == 1)
+        if intra_at is not None:
+            intra = bool(intra_at(idx, intra))
         if intra:
             qp = controller.next_qp(True)
             payload = code_intra(idx, qp)
@@ -233,7 +239,7 @@ def unit_budget_bits(target_bpp, pixels_per_picture, pictures_coded, spent_bits,
 
 def code_sequence_probed(frame_count, frames_per_p, code_intra, code_inter, probe_inter, target_bpp, pixels_per_picture,
                          qp_i=32, horizon=8, intra_bonus=0, qp_min=0, qp_max=63, intra_period=-1, reset_interval=32,
-                         force_intra=False, log=None):
+                         force_intra=False, log=None, intra_at=None):
     """code_sequence with every P unit's q_index searched on the size probe of the inter model (dcvc encode --rc-mode
     probe): the largest q_index whose predicted stream fits the unit's budget.
 
@@ -242,11 +248,13 @@ def code_sequence_probed(frame_count, frames_per_p, code_intra, code_inter, prob
     P unit of n existing pictures: pick_qp_near on the probe with the budget unit_budget_bits(...), start = the q_index
     of the previous P unit (qp_i for the first). I picture: start + intra_bonus clamped to the range, not probed; its bits
     count in what is spent. `log`, a list, receives per unit {type, qp, probes, predicted_bits, budget_bits, trace}.
-    Returns what code_sequence returns."""
+    `intra_at` as in code_sequence. Returns what code_sequence returns."""
     units, idx = [], 0
     start, spent, pictures = int(qp_i), 0, 0
     while idx < frame_count:
         intra = idx == 0 or force_intra or intra_period == 1 or (intra_period > 1 and idx != 1 and idx % intra_period == 1)
+        if intra_at is not None:
+            intra = bool(intra_at(idx, intra))
         if intra:
             qp = min(qp_max, max(qp_min, start + int(intra_bonus)))
             payload = code_intra(idx, qp)

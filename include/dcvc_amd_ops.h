@@ -245,6 +245,16 @@ long long dcvc_sse_workspace_bytes(int n_planes, int H, int W);
 int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W, int row_stride,
                 long long plane_stride, double* out, void* workspace, long long workspace_bytes, void* stream);
 
+/* The measurement behind scene-cut detection (no reference counterpart). x: the codec's input as
+ * dcvc_yuv420_to_x, dcvc_yuv420p16_to_x and dcvc_rgb_to_x write it - fp16, pixel (r, c) at x + (r W + c) ldx halfs, luma in
+ * channel 0 - so every source type is served. Per pixel L = clamp(rintf((float(x0) + 0.5f) * 255.f), 0, 255) in fp32, half
+ * to even (an 8-bit source's luma sample, exactly).
+ *   luma8_out: u8 [H][W] = L. sad_out: one uint64 on the device, 8-byte aligned = sum |L - prev_luma8| over H W pixels, an
+ *   exact integer and the same bits on every run; prev_luma8 (u8 [H][W]) NULL: 0. Whatever *sad_out held is overwritten.
+ * At most two launches on `stream`, no host synchronisation. Refused before anything is enqueued: NULL x, luma8_out or
+ * sad_out; H, W or ldx below 1; a side above 16384; luma8_out == prev_luma8. */
+int dcvc_luma_sad(const void* x, int ldx, int H, int W, const void* prev_luma8, void* luma8_out, void* sad_out, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

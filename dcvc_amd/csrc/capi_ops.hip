@@ -584,6 +584,30 @@ int dcvc_msssim_range(const void* src, int src_dtype, const void* rec, int rec_d
     });
 }
 
+long long dcvc_msssim_workspace_bytes(int n_planes, int H_, int W_)
+{
+    if (n_planes < 1 || n_planes > 65535 || H_ < 88 || W_ < 88) return 0;
+    return static_cast<long long>(dcvc::msssim_workspace_bytes(n_planes, H_, W_));
+}
+
+int dcvc_msssim_range_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
+                         long long plane_stride, double data_range, double* out, void* workspace, long long workspace_bytes, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::MsssimDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        d.data_range = data_range;
+        dcvc::msssim_validate(d);
+        if (workspace == nullptr || workspace_bytes < 0 ||
+            static_cast<unsigned long long>(workspace_bytes) < dcvc::msssim_workspace_bytes(n_planes, H_, W_)) {
+            throw std::invalid_argument("msssim: workspace missing or smaller than dcvc_msssim_workspace_bytes");
+        }
+        if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) throw std::invalid_argument("msssim: the workspace must be 16-byte aligned");
+        dcvc::msssim(d, workspace, S(stream));
+    });
+}
+
 int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H_, int W_,
                   void* x, int ldx, void* planar, void* stream)
 {
@@ -645,6 +669,47 @@ int dcvc_luma_sad(const void* x, int ldx, int H_, int W_, const void* prev_luma8
         d.x = H(x); d.ldx = ldx; d.H = H_; d.W = W_;
         d.prev = static_cast<const uint8_t*>(prev_luma8); d.luma = static_cast<uint8_t*>(luma8_out); d.sad = sad_out;
         dcvc::luma_sad(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_resample_ntaps(int n_in, int n_out) { return dcvc::resample_ntaps(n_in, n_out); }
+
+int dcvc_resample_taps(int n_in, int n_out, int16_t* coef, int32_t* first)
+{
+    return dcvc::guarded([&] { dcvc::resample_taps(n_in, n_out, coef, first); });
+}
+
+int dcvc_resample_plan_create(int in_h, int in_w, int out_h, int out_w, void** plan)
+{
+    return dcvc::guarded([&] {
+        if (plan == nullptr) throw std::invalid_argument("resample: null plan pointer");
+        *plan = nullptr;
+        *plan = dcvc::resample_plan_create(in_h, in_w, out_h, out_w);
+    });
+}
+
+int dcvc_resample_plan_free(void* plan)
+{
+    return dcvc::guarded([&] { dcvc::resample_plan_free(static_cast<dcvc::ResamplePlan*>(plan)); });
+}
+
+long long dcvc_resample_workspace_bytes(const void* plan, int n_planes)
+{
+    if (plan == nullptr || n_planes < 1 || n_planes > 65535) return 0;
+    return static_cast<long long>(dcvc::resample_workspace_bytes(*static_cast<const dcvc::ResamplePlan*>(plan), n_planes));
+}
+
+int dcvc_resample_planes(const void* plan, const void* src, int src_dtype, int src_row_stride, long long src_plane_stride, void* dst,
+                         int dst_dtype, int dst_row_stride, long long dst_plane_stride, int n_planes, int max_val, void* workspace,
+                         long long workspace_bytes, void* stream)
+{
+    return dcvc::guarded([&] {
+        if (plan == nullptr) throw std::invalid_argument("resample: null plan");
+        dcvc::ResampleDesc d;
+        d.src = src; d.src_dtype = src_dtype; d.src_row_stride = src_row_stride; d.src_plane_stride = src_plane_stride;
+        d.dst = dst; d.dst_dtype = dst_dtype; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.n_planes = n_planes; d.max_val = max_val; d.workspace = workspace; d.workspace_bytes = workspace_bytes;
+        dcvc::resample_planes(*static_cast<const dcvc::ResamplePlan*>(plan), d, S(stream));      // validates before it enqueues anything
     });
 }
 

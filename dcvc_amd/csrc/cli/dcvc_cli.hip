@@ -11,9 +11,9 @@
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
-//               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]]
+//               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16]
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
 //               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
 //               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
@@ -70,6 +70,17 @@
 //               detected, type, reason: "first" | "period" | "cut" | null}]}. Refused: all-intra runs, --batch above 1, and
 //               the 8-picture models (HT-S / HT-L): a P unit there always holds 8 pictures and the container has no picture
 //               count, so a chunk cannot be cut short at a scene change. The stream format and the decoder do not change.
+//               --scale WxH (encode, yuv420): code the clip at W x H instead of the source's -W x -H. The uploaded
+//               u8 / u16 planes are resampled on the device (dcvc_resample_planes, integer Lanczos-3: Y in one call, U and V
+//               in one call, every plane on its own with the centre-aligned rule) before dcvc_yuv420_to_x / _yuv420p16_to_x
+//               read them; the parameter set carries W x H and everything behind - --batch, --target-bpp, --scene-cut -
+//               sees a clip of that size. W and H positive and even, each side's ratio in [1/8, 8]; the source size gives
+//               the file of a run without the flag. RGB sources are not resampled yet.
+//               --out-size WxH (decode, yuv420): the reconstruction's integer samples (what -o writes at the coded size) are
+//               resampled on the device to W x H; -o, --ref (the original clip), PSNR (dcvc_sse_ws on the u8 / u16 output
+//               samples against the reference's) and --calc-ssim (dcvc_msssim_range_ws on the same planes) work
+//               at that size, frame_pixel_num and the bpp figures count its pixels, and the log gains coded_width and
+//               coded_height.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -567,6 +578,132 @@ SceneArgs scene_args(const Args& a, int batch)
     return sc;
 }
 
+// "WxH" of --scale / --out-size: two positive even decimal numbers, nothing else
+bool parse_size(const std::string& s, int& w, int& h)
+{
+    const size_t x = s.find('x');
+    if (x == std::string::npos || x == 0 || x + 1 >= s.size()) return false;
+    long v[2];
+    const std::string part[2] = {s.substr(0, x), s.substr(x + 1)};
+    for (int i = 0; i < 2; ++i) {
+        if (part[i].size() > 6 || part[i].find_first_not_of("0123456789") != std::string::npos) return false;
+        v[i] = strtol(part[i].c_str(), nullptr, 10);
+        if (v[i] < 2 || (v[i] & 1)) return false;
+    }
+    w = static_cast<int>(v[0]); h = static_cast<int>(v[1]);
+    return true;
+}
+
+// --scale (encode) / --out-size (decode): what the flag alone decides is refused before a model is loaded
+struct SizeArg {
+    bool on = false;
+    int W = 0, H = 0;
+};
+
+SizeArg size_arg(const Args& a, const char* key)
+{
+    SizeArg z;
+    if (!a.has(key)) return z;
+    const std::string flag = std::string("--") + key;
+    const std::string type = a.str("src-type", "yuv420");
+    if (type == "rgb24" || type == "png") die(flag + " is for --src-type yuv420: RGB sources are not resampled yet");
+    if (!parse_size(a.str(key), z.W, z.H)) die(flag + " must be WxH with both sides positive and even, got " + a.str(key));
+    z.on = true;
+    return z;
+}
+
+// each side's ratio in [1/8, 8] (dcvc_resample_ntaps is host code: no device is touched)
+void check_ratio(const char* flag, int from_w, int from_h, int to_w, int to_h)
+{
+    if (dcvc_resample_ntaps(from_w, to_w) < 0 || dcvc_resample_ntaps(from_h, to_h) < 0) {
+        die(std::string(flag) + ": each side's ratio must lie in [1/8, 8], got " + std::to_string(from_w) + "x" + std::to_string(from_h) +
+            " -> " + std::to_string(to_w) + "x" + std::to_string(to_h));
+    }
+}
+
+// the YUV420 planes of one picture at another size on the device: Y in one call, U and V in one call
+struct Resampler {
+    void* plan_y = nullptr;
+    void* plan_c = nullptr;
+    void* ws = nullptr;
+    long long ws_bytes = 0;
+    int from_h = 0, from_w = 0, to_h = 0, to_w = 0, bit_depth = 8;
+    void create(int fh, int fw, int th, int tw, int depth)
+    {
+        from_h = fh; from_w = fw; to_h = th; to_w = tw; bit_depth = depth;
+        abi_ok(dcvc_resample_plan_create(fh, fw, th, tw, &plan_y), "resample plan");
+        abi_ok(dcvc_resample_plan_create(fh / 2, fw / 2, th / 2, tw / 2, &plan_c), "resample plan");
+        ws_bytes = std::max(dcvc_resample_workspace_bytes(plan_y, 1), dcvc_resample_workspace_bytes(plan_c, 2));
+        hip_ok(hipMalloc(&ws, static_cast<size_t>(ws_bytes)), "hipMalloc");
+    }
+    // src / dst: the planes Y [h][w], U, V [h/2][w/2] back to back, u8 or u16 by the bit depth
+    void run(const uint8_t* src, uint8_t* dst, hipStream_t st) const
+    {
+        const int es = bit_depth > 8 ? 2 : 1, dt = bit_depth > 8 ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8, max_val = (1 << bit_depth) - 1;
+        const long long fy = static_cast<long long>(from_h) * from_w, ty = static_cast<long long>(to_h) * to_w;
+        abi_ok(dcvc_resample_planes(plan_y, src, dt, from_w, fy, dst, dt, to_w, ty, 1, max_val, ws, ws_bytes, st), "resample (Y)");
+        abi_ok(dcvc_resample_planes(plan_c, src + fy * es, dt, from_w / 2, fy / 4, dst + ty * es, dt, to_w / 2, ty / 4, 2, max_val, ws,
+                                    ws_bytes, st), "resample (U, V)");
+    }
+    void destroy()
+    {
+        if (ws) hip_ok(hipFree(ws), "hipFree");
+        abi_ok(dcvc_resample_plan_free(plan_y), "resample plan");
+        abi_ok(dcvc_resample_plan_free(plan_c), "resample plan");
+        *this = Resampler{};
+    }
+};
+
+// --out-size: the output picture on the device and what measures it against the reference, all at the output size
+struct ScaledOut {
+    Resampler rs;
+    uint8_t* out = nullptr;        // the resampled reconstruction: u8 or u16 planes
+    uint8_t* ref = nullptr;        // the reference picture's planes
+    uint8_t* h_out = nullptr;      // pinned
+    uint8_t* h_ref = nullptr;      // pinned
+    double* sse = nullptr;
+    double* h_sse = nullptr;       // pinned
+    double* ssim = nullptr;
+    double* h_ssim = nullptr;      // pinned
+    void* sse_ws = nullptr;
+    long long sse_ws_bytes = 0;
+    void* ssim_ws = nullptr;       // dcvc_msssim_range_ws's workspace: Y, then U and V, one after the other
+    long long ssim_ws_bytes = 0;
+    void create(const Geometry& from, const Geometry& to, bool has_ref, bool calc_ssim)
+    {
+        destroy();                 // a stream may switch parameter sets
+        rs.create(from.H, from.W, to.H, to.W, to.bit_depth);
+        hip_ok(hipMalloc(&out, to.frame_bytes()), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), to.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        if (has_ref) {
+            hip_ok(hipMalloc(&ref, to.frame_bytes()), "hipMalloc");
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_ref), to.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+            hip_ok(hipMalloc(&sse, 3 * sizeof(double)), "hipMalloc");
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+            sse_ws_bytes = std::max(dcvc_sse_workspace_bytes(1, to.H, to.W), dcvc_sse_workspace_bytes(2, to.H / 2, to.W / 2));
+            hip_ok(hipMalloc(&sse_ws, static_cast<size_t>(sse_ws_bytes)), "hipMalloc");
+        }
+        if (calc_ssim) {
+            hip_ok(hipMalloc(&ssim, 3 * sizeof(double)), "hipMalloc");
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_ssim), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+            ssim_ws_bytes = std::max(dcvc_msssim_workspace_bytes(1, to.H, to.W), dcvc_msssim_workspace_bytes(2, to.H / 2, to.W / 2));
+            hip_ok(hipMalloc(&ssim_ws, static_cast<size_t>(ssim_ws_bytes)), "hipMalloc");
+        }
+    }
+    void destroy()
+    {
+        if (rs.plan_y) rs.destroy();
+        for (void* d : {static_cast<void*>(out), static_cast<void*>(ref), static_cast<void*>(sse), static_cast<void*>(ssim), sse_ws,
+                        ssim_ws}) {
+            if (d) hip_ok(hipFree(d), "hipFree");
+        }
+        for (void* h : {static_cast<void*>(h_out), static_cast<void*>(h_ref), static_cast<void*>(h_sse), static_cast<void*>(h_ssim)}) {
+            if (h) hip_ok(hipHostFree(h), "hipHostFree");
+        }
+        *this = ScaledOut{};
+    }
+};
+
 // one source picture in --scene-log
 struct ScenePicture {
     long long sad = 0;
@@ -594,6 +731,7 @@ int encode(const Args& a)
     const SrcType type = src_type(a.str("src-type", "yuv420"));
     const bool rgb = type != SrcType::Yuv420;
     const int depth = bit_depth_arg(a, type);
+    const SizeArg scale = size_arg(a, "scale");
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     PngDir pngs;
     if (type == SrcType::Png) {
@@ -606,7 +744,10 @@ int encode(const Args& a)
     } else if (rgb && (!a.has("W") || !a.has("H"))) {
         die("--src-type rgb24 needs -W and -H");
     }
-    const Geometry g = geometry(pic_h, pic_w, rgb, depth);
+    // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
+    const Geometry gs = geometry(pic_h, pic_w, rgb, depth);
+    if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
+    const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
     if (scene.on) {
         const int kind = weight_kind(a.str("inter"));      // from the file's header, before either model is built
         if (kind == 2 || kind == 3) {
@@ -629,18 +770,33 @@ int encode(const Args& a)
         in = fopen(a.str("i").c_str(), "rb");
         if (!in) die("cannot open " + a.str("i"));
         fseek(in, 0, SEEK_END);
-        total = ftell(in) / static_cast<long long>(g.frame_bytes());
+        total = ftell(in) / static_cast<long long>(gs.frame_bytes());
         fseek(in, 0, SEEK_SET);
     }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
     DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
+    // --scale: the source picture's own staging, pinned and on the device, in front of b.yuv8
+    Resampler rs;
+    uint8_t* h_full = nullptr;
+    uint8_t* d_full = nullptr;
+    if (scale.on) {
+        rs.create(gs.H, gs.W, g.H, g.W, depth);
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_full), gs.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        hip_ok(hipMalloc(&d_full, gs.frame_bytes()), "hipMalloc");
+    }
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
     const auto t0 = std::chrono::steady_clock::now();
     // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx)
     auto load_picture = [&]() {
+        if (scale.on) {
+            if (fread(h_full, 1, gs.frame_bytes(), in) != gs.frame_bytes()) die("short read");
+            hip_ok(hipMemcpyAsync(d_full, h_full, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            rs.run(d_full, b.yuv8, b.st);
+            return;
+        }
         if (type == SrcType::Png) {
             if (!pngs.read(b.h_yuv, g)) die("short read");
         } else if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) {
@@ -838,6 +994,11 @@ int encode(const Args& a)
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
     if (in) fclose(in);
+    if (scale.on) {
+        rs.destroy();
+        hip_ok(hipHostFree(h_full), "hipHostFree");
+        hip_ok(hipFree(d_full), "hipFree");
+    }
     if (ctl) dcvc_rc_destroy(ctl);
     if (scd) {
         dcvc_scd_destroy(scd);
@@ -896,6 +1057,12 @@ int encode(const Args& a)
 int decode(const Args& a)
 {
     const int batch = batch_arg(a);
+    const SizeArg out_size = size_arg(a, "out-size");
+    // MS-SSIM's size floor holds at the size that is measured
+    if (out_size.on && a.num("calc-ssim", 0) != 0 && (out_size.H < 176 || out_size.W < 176)) {
+        die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), --out-size is " +
+            std::to_string(out_size.W) + "x" + std::to_string(out_size.H));
+    }
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     std::vector<uint8_t> bin;
     {
@@ -931,6 +1098,10 @@ int decode(const Args& a)
     DeviceBuffers b;
     bool have_buffers = false;
     std::vector<uint8_t> src;
+    // --out-size: the output pictures' geometry and their buffers, beside the coded size's (which follow the stream)
+    Geometry go;
+    ScaledOut so;
+    if (out_size.on) go = geometry(out_size.H, out_size.W, false, depth);
     // log (src/utils/common.py:46-116)
     std::vector<int> types;
     std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v, ssim, ssim_y, ssim_u, ssim_v;
@@ -966,13 +1137,15 @@ int decode(const Args& a)
                 die("--calc-ssim needs both picture sides >= 88 (MS-SSIM of the R, G and B planes), the stream holds " +
                     std::to_string(s->width) + "x" + std::to_string(s->height));
             }
-            if (calc_ssim && !rgb && (s->height < 176 || s->width < 176)) {
+            if (calc_ssim && !rgb && !out_size.on && (s->height < 176 || s->width < 176)) {
                 die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), the "
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
+            if (out_size.on) check_ratio("--out-size", s->width, s->height, go.W, go.H);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth);
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
+            if (out_size.on) so.create(g, go, has_ref, calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
@@ -1041,9 +1214,57 @@ int decode(const Args& a)
                 abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_rgb");
             } else if (g.hbd()) {
                 // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
-                abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_yuv420p16");
+                abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, has_rec || out_size.on ? b.out8 : nullptr, b.st),
+                       "x_to_yuv420p16");
             } else {
                 abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
+            }
+            if (out_size.on) {
+                // b.out8 holds the integer samples -o would write at the coded size: resample them, then the output picture is
+                // written and measured at its own size, sample against sample (the source first, as below)
+                const size_t ny = go.y_bytes(), nc = ny / 4, es = go.hbd() ? 2 : 1;
+                if (has_ref && fread(so.h_ref, 1, go.frame_bytes(), ref) != go.frame_bytes()) {
+                    if (j > 0 && !intra) { source_ended = true; break; }
+                    die("reference file is shorter than the stream");
+                }
+                so.rs.run(b.out8, so.out, b.st);
+                if (has_rec) hip_ok(hipMemcpyAsync(so.h_out, so.out, go.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (has_ref) {
+                    const int dt = go.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+                    const double peak = static_cast<double>((1 << go.bit_depth) - 1);
+                    hip_ok(hipMemcpyAsync(so.ref, so.h_ref, go.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                    abi_ok(dcvc_sse_ws(so.ref, dt, so.out, dt, 1, go.H, go.W, go.W, static_cast<long long>(ny), so.sse, so.sse_ws,
+                                       so.sse_ws_bytes, b.st), "sse (Y)");
+                    abi_ok(dcvc_sse_ws(so.ref + ny * es, dt, so.out + ny * es, dt, 2, go.H / 2, go.W / 2, go.W / 2, static_cast<long long>(nc),
+                                       so.sse + 1, so.sse_ws, so.sse_ws_bytes, b.st), "sse (U, V)");
+                    hip_ok(hipMemcpyAsync(so.h_sse, so.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                    if (calc_ssim) {
+                        // data_range 255 gives dcvc_msssim's bits; the workspace is the tool's own, as for the sums
+                        abi_ok(dcvc_msssim_range_ws(so.ref, dt, so.out, dt, 1, go.H, go.W, go.W, static_cast<long long>(ny), peak, so.ssim,
+                                                    so.ssim_ws, so.ssim_ws_bytes, b.st), "msssim (Y)");
+                        abi_ok(dcvc_msssim_range_ws(so.ref + ny * es, dt, so.out + ny * es, dt, 2, go.H / 2, go.W / 2, go.W / 2,
+                                                    static_cast<long long>(nc), peak, so.ssim + 1, so.ssim_ws, so.ssim_ws_bytes, b.st),
+                               "msssim (U, V)");
+                    }
+                    if (calc_ssim) hip_ok(hipMemcpyAsync(so.h_ssim, so.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                    hip_ok(hipStreamSynchronize(b.st), "sync");
+                    const double py = psnr_of_sse(so.h_sse[0], static_cast<double>(ny), peak);
+                    const double pu = psnr_of_sse(so.h_sse[1], static_cast<double>(nc), peak);
+                    const double pv = psnr_of_sse(so.h_sse[2], static_cast<double>(nc), peak);
+                    psnr.push_back((6 * py + pu + pv) / 8); psnr_y.push_back(py); psnr_u.push_back(pu); psnr_v.push_back(pv);
+                    if (calc_ssim) {
+                        const double sy = so.h_ssim[0], su = so.h_ssim[1], sv = so.h_ssim[2];
+                        ssim.push_back((6 * sy + su + sv) / 8); ssim_y.push_back(sy); ssim_u.push_back(su); ssim_v.push_back(sv);
+                    }
+                }
+                if (has_rec) {
+                    hip_ok(hipStreamSynchronize(b.st), "sync");
+                    if (fwrite(so.h_out, 1, go.frame_bytes(), rec) != go.frame_bytes()) die("short write");
+                }
+                types.push_back(intra ? 0 : 1);
+                bits.push_back(j < static_cast<int>(unit_bits.size()) ? unit_bits[static_cast<size_t>(j)] : 0.0);
+                ++decoded;
+                continue;
             }
             // the source first: when it ends inside a chunk, the remaining pictures of the chunk are the encoder's
             // padding (repeats of the final picture) and must reach neither the log nor rec.yuv
@@ -1139,14 +1360,20 @@ int decode(const Args& a)
         }
     }
     if (have_buffers) free_buffers(b);
+    so.destroy();
     if (rec) fclose(rec);
     if (ref) fclose(ref);
     const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    printf("decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
+    if (out_size.on) {
+        printf("decoded %d pictures (%dx%d, output at %dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, go.W, go.H,
+               decoded / secs);
+    } else {
+        printf("decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
+    }
     if (a.has("json")) {
         if (psnr.size() != types.size()) die("--json needs --ref (PSNR per picture)");
-        const double px = static_cast<double>(g.H) * g.W;
+        const double px = out_size.on ? static_cast<double>(go.H) * go.W : static_cast<double>(g.H) * g.W;
         double ib = 0, pb = 0, ip[4] = {0, 0, 0, 0}, pp[4] = {0, 0, 0, 0};
         int ni = 0, np = 0;
         for (size_t i = 0; i < types.size(); ++i) {
@@ -1160,6 +1387,7 @@ int decode(const Args& a)
         if (!jf) die("cannot write " + a.str("json"));
         const char* sfx[4] = {"", "_y", "_u", "_v"};
         fprintf(jf, "{\n  \"arith_policy\": %d,\n  \"frame_pixel_num\": %.0f,\n  \"i_frame_num\": %d,\n  \"p_frame_num\": %d,\n", dcvc_arith_policy_version(), px, ni, np);
+        if (out_size.on) fprintf(jf, "  \"coded_width\": %d,\n  \"coded_height\": %d,\n", g.W, g.H);
         fprintf(jf, "  \"ave_i_frame_bpp\": %.9g,\n  \"ave_p_frame_bpp\": %.9g,\n", ni ? ib / ni / px : 0.0, np ? pb / np / px : 0.0);
         if (rgb) {
             // 17 digits, as Python's json writes a float (the YUV log keeps its 9)

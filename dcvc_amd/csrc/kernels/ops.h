@@ -339,6 +339,36 @@ struct LumaSadDesc {
 void luma_sad_validate(const LumaSadDesc& d);    // throws std::invalid_argument for what luma_sad() refuses
 void luma_sad(const LumaSadDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- resampling (resample.hip)
+// Planes of u8 / u16 samples at another size: separable integer Lanczos-3, horizontal pass then vertical pass through an
+// intermediate plane of clamped samples (the filter is stated at the head of resample.hip).
+constexpr int kResampleMaxSide = 16384;
+constexpr int kResampleMaxRatio = 8;             // each side's ratio lies in [1/8, 8]
+constexpr int kResampleMaxTaps = 48;
+int resample_ntaps(int n_in, int n_out);         // host; -1 for a length outside 1..kResampleMaxSide or a ratio outside [1/8, 8]
+// host: coef [n_out][T] (every row sums to 4096), first [n_out]; throws std::invalid_argument for what resample_ntaps refuses
+void resample_taps(int n_in, int n_out, int16_t* coef, int32_t* first);
+struct ResamplePlan {
+    int in_h = 0, in_w = 0, out_h = 0, out_w = 0;
+    int taps_w = 0, taps_h = 0;
+    int span_w = 0;                              // samples of a horizontal tile's row segment in LDS (a multiple of 16)
+    void* tables = nullptr;                      // the device allocation behind the four tables
+    const int16_t* coef_w = nullptr; const int32_t* first_w = nullptr;
+    const int16_t* coef_h = nullptr; const int32_t* first_h = nullptr;
+};
+ResamplePlan* resample_plan_create(int in_h, int in_w, int out_h, int out_w);     // tables onto the current device (synchronous)
+void resample_plan_free(ResamplePlan* p);
+unsigned long long resample_workspace_bytes(const ResamplePlan& p, int n_planes);
+struct ResampleDesc {
+    const void* src = nullptr; int src_dtype = kSampleU8; int src_row_stride = 0; long long src_plane_stride = 0;
+    void* dst = nullptr; int dst_dtype = kSampleU8; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int n_planes = 1, max_val = 255;
+    void* workspace = nullptr; long long workspace_bytes = 0;
+};
+void resample_validate(const ResamplePlan& p, const ResampleDesc& d);     // throws std::invalid_argument for what is refused
+// two launches on `stream`: validates first, allocates nothing, never waits for the host
+void resample_planes(const ResamplePlan& p, const ResampleDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -218,6 +218,13 @@ int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, 
  * fp64 (metrics.py calc_msssim's data_range argument). data_range = 255 gives dcvc_msssim's bits; data_range <= 0 -> error. */
 int dcvc_msssim_range(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W,
                       int row_stride, long long plane_stride, double data_range, double* out, void* stream);
+/* dcvc_msssim_range on a caller-owned workspace of at least dcvc_msssim_workspace_bytes(n_planes, H, W) bytes (device memory,
+ * 16-byte aligned, not touched by other work until the call's launches have run on `stream`): nothing is allocated, for a
+ * caller that measures picture after picture, as dcvc_sse_ws is to dcvc_sse. The same bits as dcvc_msssim_range (and, at
+ * data_range = 255, as dcvc_msssim). dcvc_msssim_workspace_bytes is 0 for what dcvc_msssim refuses. */
+long long dcvc_msssim_workspace_bytes(int n_planes, int H, int W);
+int dcvc_msssim_range_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H, int W, int row_stride,
+                         long long plane_stride, double data_range, double* out, void* workspace, long long workspace_bytes, void* stream);
 
 /* RGB pictures on the device (BT.709: Kr, Kg, Kb = 0.2126, 0.7152, 0.0722; transforms.py:10-14). Every step rounds as the
  * reference's torch op on a GPU does: one fp32 operation each, and a tensor divided by a scalar is a * fp32(1 / b).
@@ -254,6 +261,37 @@ int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, 
  * At most two launches on `stream`, no host synchronisation. Refused before anything is enqueued: NULL x, luma8_out or
  * sad_out; H, W or ldx below 1; a side above 16384; luma8_out == prev_luma8. */
 int dcvc_luma_sad(const void* x, int ldx, int H, int W, const void* prev_luma8, void* luma8_out, void* sad_out, void* stream);
+
+/* Planes of integer samples at another size (no reference counterpart): a separable Lanczos-3 filter with
+ * 12-bit integer coefficients, every output sample defined exactly. One 1-D pass n_in -> n_out, the tables in IEEE double:
+ *   scale = n_in / n_out, fs = max(1, scale), support = 3 fs, T = 2 ceil(support) taps for every output of the pass;
+ *   output j: centre = (j + 0.5) scale - 0.5, first = floor(centre - support) + 1, w[k] = L((first + k - centre) / fs) with
+ *   L(t) = sinc(t) sinc(t / 3) for |t| < 3, else 0; c[k] = rint(w[k] * 4096 / sum w); 4096 - sum c is added to the largest
+ *   c[k] (the first one on a tie), so every row sums to 4096 (4097 occurs);
+ *   out[j] = clamp((sum_k c[k] in[clamp(first + k, 0, n_in - 1)] + 2048) >> 12, 0, max_val), an arithmetic shift.
+ * A plane is filtered horizontally into an intermediate plane of clamped samples, then vertically. n_in == n_out copies.
+ * Lengths are 1..16384 and each ratio lies in [1/8, 8] (T <= 48); anything else is refused.
+ *   dcvc_resample_ntaps: host only; T, or -1 for what is refused.
+ *   dcvc_resample_taps:  host only, no GPU; coef [n_out][T] int16, first [n_out] int32.
+ *   dcvc_resample_plan_create: the tables of in_h x in_w -> out_h x out_w onto the current device, once (synchronous);
+ *   dcvc_resample_plan_free releases them (NULL is fine).
+ *   dcvc_resample_workspace_bytes: the intermediate planes of a call with n_planes planes (either sample type); 0 for bad
+ *   arguments.
+ *   dcvc_resample_planes: n_planes planes src [in_h][in_w] -> dst [out_h][out_w], every plane on its own. Sample types are
+ *   DCVC_SAMPLE_U8 or DCVC_SAMPLE_U16, equal on both sides; strides in samples (plane strides are not read for one plane);
+ *   max_val = 255, or 2^bit_depth - 1 for u16. Two launches on `stream`: nothing is allocated and nothing waits for the
+ *   host, and the workspace is the caller's until they have run. Refused before anything is enqueued: NULL operands; another
+ *   sample type or two different ones; max_val outside 1..255 (u8) / 1..65535 (u16); a row stride below the width or a plane
+ *   stride below the plane; n_planes outside 1..65535; a workspace below dcvc_resample_workspace_bytes; dst or the workspace
+ *   overlapping src, or the workspace overlapping dst. */
+int dcvc_resample_ntaps(int n_in, int n_out);
+int dcvc_resample_taps(int n_in, int n_out, int16_t* coef, int32_t* first);
+int dcvc_resample_plan_create(int in_h, int in_w, int out_h, int out_w, void** plan);
+int dcvc_resample_plan_free(void* plan);
+long long dcvc_resample_workspace_bytes(const void* plan, int n_planes);
+int dcvc_resample_planes(const void* plan, const void* src, int src_dtype, int src_row_stride, long long src_plane_stride, void* dst,
+                         int dst_dtype, int dst_row_stride, long long dst_plane_stride, int n_planes, int max_val, void* workspace,
+                         long long workspace_bytes, void* stream);
 
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */

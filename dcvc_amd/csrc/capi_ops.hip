@@ -78,7 +78,7 @@ int dcvc_dwconv3x3(const void* x, int ldx, const void* w, void* y, int ldy, int 
     return dcvc::guarded([&] { dcvc::dwconv3x3(H(x), ldx, H(w), H(y), ldy, Hh, W, C, S(stream)); });
 }
 
-// ---- batched forms (intra batches): argument checks before any launch
+// ---- argument checks before any launch, shared by the single and the batched forms of an entry point
 namespace {
 
 void check_b(int n, std::initializer_list<const void*> ptrs, std::initializer_list<int> dims, const char* what)
@@ -90,6 +90,83 @@ void check_b(int n, std::initializer_list<const void*> ptrs, std::initializer_li
     for (int d : dims) {
         if (d <= 0) throw std::invalid_argument(std::string(what) + ": sizes must be positive");
     }
+}
+
+[[noreturn]] void refuse(const char* what, const char* why)
+{
+    throw std::invalid_argument(std::string(what) + ": " + why);
+}
+
+// an operand whose rows the kernel reads or writes 16 bytes at a time: [pixels][ld] halves, `C` of them used
+struct Rows {
+    const void* p;
+    int ld;
+};
+
+void check_rows(std::initializer_list<Rows> rows, int C, const char* what)
+{
+    if (C % 8 != 0) refuse(what, "C must be a multiple of 8");
+    for (const Rows& r : rows) {
+        if (r.ld < C) refuse(what, "leading dimension below C");
+        if (r.ld % 8 != 0 || (reinterpret_cast<uintptr_t>(r.p) & 15) != 0) {
+            refuse(what, "16-byte accesses: pointers must be 16-byte aligned and leading dimensions multiples of 8");
+        }
+    }
+}
+
+void check_aligned(std::initializer_list<const void*> ptrs, unsigned bytes, const char* what)
+{
+    for (const void* p : ptrs) {
+        if ((reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0) refuse(what, "misaligned pointer");
+    }
+}
+
+void check_pad_unshuffle8(const void* x, int Hh, int W, int C3, const void* out, int ldout, int H8, int W8, int n, const char* what)
+{
+    check_b(n, {x, out}, {Hh, W, C3, H8, W8}, what);
+    if (H8 * 8 < Hh || W8 * 8 < W) refuse(what, "output smaller than the picture");
+    check_rows({{out, ldout}}, 64 * C3, what);
+}
+
+void check_shuffle8(const void* in, int ldin, int H8, int W8, int C3, const void* out, int n, const char* what)
+{
+    check_b(n, {in, out}, {H8, W8, C3}, what);
+    if (ldin < C3 * 64) refuse(what, "ldin below 64 * C3");
+    check_rows({{in, ldin}}, 64 * C3, what);
+}
+
+void check_replicate_pad(const void* in, int ldin, int Hh, int W, int C, int pad_b, int pad_r, const void* out, int ldout, int n,
+                         const char* what)
+{
+    check_b(n, {in, out}, {Hh, W, C}, what);
+    if (pad_b < 0 || pad_r < 0 || C % 8 != 0 || ldin < C || ldout < C) {
+        refuse(what, "negative padding, C not a multiple of 8 or ld below C");
+    }
+    check_rows({{in, ldin}, {out, ldout}}, C, what);
+}
+
+void check_crop(const void* in, int ldin, int Hin, int Win, const void* out, int ldout, int Hh, int W, int C, int n, const char* what)
+{
+    check_b(n, {in, out}, {Hin, Win, Hh, W, C}, what);
+    if (Hh > Hin || W > Win || C % 8 != 0 || ldin < C || ldout < C) {
+        refuse(what, "crop larger than the input, C not a multiple of 8 or ld below C");
+    }
+    check_rows({{in, ldin}, {out, ldout}}, C, what);
+}
+
+// the 4-step symbol kernels: C/4 symbols per pixel in runs of 8, every picture of a batch the same size
+void check_y_step(int n, int Hh, int W, int C, int step, int slot, const char* what)
+{
+    if (Hh <= 0 || W <= 0 || C <= 0) refuse(what, "sizes must be positive");
+    if (C % 32 != 0) refuse(what, "C must be a multiple of 32");
+    if (step < 0 || step > 3 || slot < 0 || slot > 3) refuse(what, "step and slot must be in 0..3");
+    if (static_cast<long long>(Hh) * W * C * n >= (1LL << 31)) refuse(what, "more than 2^31 elements");
+}
+
+void check_strides(int n, long long data_stride, int totals_stride, const char* what)
+{
+    if (n > 1 && (data_stride <= 0 || totals_stride <= 0)) refuse(what, "a batch needs positive picture strides");
+    if (data_stride < 0 || totals_stride < 0) refuse(what, "negative picture stride");
 }
 
 }  // namespace
@@ -132,8 +209,7 @@ int dcvc_tconv2x2_b(const void* x, int ldx, const void* w, void* y, int ldy, int
 int dcvc_pad_unshuffle8_b(const void* x, int Hh, int W, int C3, void* out, int H8, int W8, int n, void* stream)
 {
     return dcvc::guarded([&] {
-        check_b(n, {x, out}, {Hh, W, C3, H8, W8}, "pad_unshuffle8_b");
-        if (H8 * 8 < Hh || W8 * 8 < W) throw std::invalid_argument("pad_unshuffle8_b: output smaller than the picture");
+        check_pad_unshuffle8(x, Hh, W, C3, out, 64 * C3, H8, W8, n, "pad_unshuffle8_b");
         dcvc::pad_unshuffle8_b(H(x), Hh, W, C3, H(out), H8, W8, n, S(stream));
     });
 }
@@ -141,8 +217,7 @@ int dcvc_pad_unshuffle8_b(const void* x, int Hh, int W, int C3, void* out, int H
 int dcvc_shuffle8_b(const void* in, int ldin, int H8, int W8, int C3, int clamp, void* out, int n, void* stream)
 {
     return dcvc::guarded([&] {
-        check_b(n, {in, out}, {H8, W8, C3}, "shuffle8_b");
-        if (ldin < C3 * 64) throw std::invalid_argument("shuffle8_b: ldin below 64 * C3");
+        check_shuffle8(in, ldin, H8, W8, C3, out, n, "shuffle8_b");
         dcvc::shuffle8_b(H(in), ldin, H8, W8, C3, clamp != 0, H(out), n, S(stream));
     });
 }
@@ -151,10 +226,7 @@ int dcvc_replicate_pad_b(const void* in, int ldin, int Hh, int W, int C, int pad
                          void* stream)
 {
     return dcvc::guarded([&] {
-        check_b(n, {in, out}, {Hh, W, C}, "replicate_pad_b");
-        if (pad_b < 0 || pad_r < 0 || C % 8 != 0 || ldin < C || ldout < C) {
-            throw std::invalid_argument("replicate_pad_b: negative padding, C not a multiple of 8 or ld below C");
-        }
+        check_replicate_pad(in, ldin, Hh, W, C, pad_b, pad_r, out, ldout, n, "replicate_pad_b");
         dcvc::replicate_pad_b(H(in), ldin, Hh, W, C, pad_b, pad_r, H(out), ldout, n, S(stream));
     });
 }
@@ -162,46 +234,70 @@ int dcvc_replicate_pad_b(const void* in, int ldin, int Hh, int W, int C, int pad
 int dcvc_crop_b(const void* in, int ldin, int Hin, int Win, void* out, int ldout, int Hh, int W, int C, int n, void* stream)
 {
     return dcvc::guarded([&] {
-        check_b(n, {in, out}, {Hin, Win, Hh, W, C}, "crop_b");
-        if (Hh > Hin || W > Win || C % 8 != 0 || ldin < C || ldout < C) {
-            throw std::invalid_argument("crop_b: crop larger than the input, C not a multiple of 8 or ld below C");
-        }
+        check_crop(in, ldin, Hin, Win, out, ldout, Hh, W, C, n, "crop_b");
         dcvc::crop_b(H(in), ldin, Hin, Win, H(out), ldout, Hh, W, C, n, S(stream));
     });
 }
 
 int dcvc_pad_unshuffle8(const void* x, int Hh, int W, int C3, void* out, int H8, int W8, void* stream)
 {
-    return dcvc::guarded([&] { dcvc::pad_unshuffle8(H(x), Hh, W, C3, H(out), H8, W8, S(stream)); });
+    return dcvc::guarded([&] {
+        check_pad_unshuffle8(x, Hh, W, C3, out, 64 * C3, H8, W8, 1, "pad_unshuffle8");
+        dcvc::pad_unshuffle8(H(x), Hh, W, C3, H(out), H8, W8, S(stream));
+    });
+}
+
+int dcvc_pad_unshuffle8_ld(const void* x, int Hh, int W, int C3, void* out, int ldout, int H8, int W8, void* stream)
+{
+    return dcvc::guarded([&] {
+        check_pad_unshuffle8(x, Hh, W, C3, out, ldout, H8, W8, 1, "pad_unshuffle8_ld");
+        dcvc::pad_unshuffle8(H(x), Hh, W, C3, H(out), H8, W8, S(stream), ldout);
+    });
 }
 
 int dcvc_shuffle8(const void* in, int ldin, int H8, int W8, int C3, int clamp, void* out, void* stream)
 {
-    return dcvc::guarded([&] { dcvc::shuffle8(H(in), ldin, H8, W8, C3, clamp != 0, H(out), S(stream)); });
+    return dcvc::guarded([&] {
+        check_shuffle8(in, ldin, H8, W8, C3, out, 1, "shuffle8");
+        dcvc::shuffle8(H(in), ldin, H8, W8, C3, clamp != 0, H(out), S(stream));
+    });
 }
 
 int dcvc_shuffle2(const void* in, int ldin, int Hh, int W, int C, void* out, int ldout, void* stream)
 {
-    return dcvc::guarded([&] { dcvc::shuffle2(H(in), ldin, Hh, W, C, H(out), ldout, S(stream)); });
+    return dcvc::guarded([&] {
+        check_b(1, {in, out}, {Hh, W, C}, "shuffle2");
+        if (ldin < 4 * C) refuse("shuffle2", "ldin below 4 * C");
+        check_rows({{out, ldout}}, C, "shuffle2");
+        dcvc::shuffle2(H(in), ldin, Hh, W, C, H(out), ldout, S(stream));
+    });
 }
 
 int dcvc_replicate_pad(const void* in, int ldin, int Hh, int W, int C, int pad_b, int pad_r,
                        void* out, int ldout, void* stream)
 {
     return dcvc::guarded([&] {
+        check_replicate_pad(in, ldin, Hh, W, C, pad_b, pad_r, out, ldout, 1, "replicate_pad");
         dcvc::replicate_pad(H(in), ldin, Hh, W, C, pad_b, pad_r, H(out), ldout, S(stream));
     });
 }
 
 int dcvc_crop(const void* in, int ldin, int Win, void* out, int ldout, int Hh, int W, int C, void* stream)
 {
-    return dcvc::guarded([&] { dcvc::crop(H(in), ldin, Win, H(out), ldout, Hh, W, C, S(stream)); });
+    return dcvc::guarded([&] {
+        check_crop(in, ldin, Hh, Win, out, ldout, Hh, W, C, 1, "crop");       // (one picture: its height is never read)
+        dcvc::crop(H(in), ldin, Win, H(out), ldout, Hh, W, C, S(stream));
+    });
 }
 
 int dcvc_mul_channel(const void* x, int ldx, const void* q, void* y, int ldy, int pixels, int C,
                      void* stream)
 {
-    return dcvc::guarded([&] { dcvc::mul_channel(H(x), ldx, H(q), H(y), ldy, pixels, C, S(stream)); });
+    return dcvc::guarded([&] {
+        check_b(1, {x, q, y}, {pixels, C}, "mul_channel");
+        check_rows({{x, ldx}, {q, C}, {y, ldy}}, C, "mul_channel");
+        dcvc::mul_channel(H(x), ldx, H(q), H(y), ldy, pixels, C, S(stream));
+    });
 }
 
 int dcvc_ffn_fused(const void* x, int ldx, const void* w0, const void* b0, const void* w2, const void* b2,
@@ -514,6 +610,8 @@ int dcvc_scale_clamped(const void* x, int ldx, const void* q, int ldq, void* y, 
                        int C, int reciprocal, void* stream)
 {
     return dcvc::guarded([&] {
+        check_b(1, {x, q, y}, {pixels, C}, "scale_clamped");
+        check_rows({{x, ldx}, {q, ldq}, {y, ldy}}, C, "scale_clamped");
         dcvc::scale_clamped(H(x), ldx, H(q), ldq, H(y), ldy, pixels, C, reciprocal != 0, S(stream));
     });
 }
@@ -789,13 +887,19 @@ int dcvc_dcb_nsplit_dw_hook(const void* t1, const void* wdw, int width)
 int dcvc_round_z(const void* z, void* z_hat, void* z_i8, int count, void* stream)
 {
     return dcvc::guarded([&] {
+        check_b(1, {z, z_hat, z_i8}, {count}, "round_z");
+        check_aligned({z, z_hat}, 2, "round_z");
         dcvc::round_z(H(z), H(z_hat), static_cast<int8_t*>(z_i8), count, S(stream));
     });
 }
 
 int dcvc_int8_to_half(const void* in, void* out, int count, void* stream)
 {
-    return dcvc::guarded([&] { dcvc::int8_to_half(static_cast<const int8_t*>(in), H(out), count, S(stream)); });
+    return dcvc::guarded([&] {
+        check_b(1, {in, out}, {count}, "int8_to_half");
+        check_aligned({out}, 2, "int8_to_half");
+        dcvc::int8_to_half(static_cast<const int8_t*>(in), H(out), count, S(stream));
+    });
 }
 
 int dcvc_symbol_blocks(int count)
@@ -803,22 +907,92 @@ int dcvc_symbol_blocks(int count)
     return dcvc::symbol_blocks(count);
 }
 
+namespace {
+
+void y_step_enc_n(const char* what, const void* y, int ldy, const void* scales, int lds, const void* means, int ldm, void* y_hat_acc,
+                  int ldacc, void* sym, void* cond, void* block_count, void* compact_out, long long out_stride, void* totals,
+                  int totals_stride, int slot, int Hh, int W, int C, int step, float skip_thres, int n, void* stream)
+{
+    check_b(n, {y, scales, means, y_hat_acc, sym, cond, block_count, compact_out, totals}, {Hh, W, C}, what);
+    check_y_step(n, Hh, W, C, step, slot, what);
+    check_rows({{y, ldy}, {scales, lds}, {means, ldm}, {y_hat_acc, ldacc}}, C, what);
+    check_aligned({sym}, 16, what);
+    check_aligned({block_count, totals}, 4, what);
+    check_aligned({compact_out}, 2, what);
+    check_strides(n, out_stride, totals_stride, what);
+    dcvc::symbols_init();
+    dcvc::YStepEnc d;
+    d.y = H(y); d.ldy = ldy; d.scales = H(scales); d.lds = lds; d.means = H(means); d.ldm = ldm;
+    d.y_hat_acc = H(y_hat_acc); d.ldacc = ldacc;
+    d.sym = static_cast<int16_t*>(sym); d.cond = static_cast<uint8_t*>(cond);
+    d.block_count = static_cast<int32_t*>(block_count);
+    d.H = Hh; d.W = W; d.C = C; d.step = step; d.skip_thres = skip_thres; d.first = (step == 0); d.n = n;
+    dcvc::y_step_enc(d, S(stream));
+    dcvc::compact_b(sym, 2, d.cond, d.block_count, Hh * W * (C / 4), compact_out, out_stride, static_cast<int32_t*>(totals),
+                    totals_stride, slot, n, S(stream));
+}
+
+void y_step_dec_index_n(const char* what, const void* scales, int lds, void* index, void* cond, void* block_count, void* compact_out,
+                        long long out_stride, void* totals, int totals_stride, int slot, int Hh, int W, int C, int step,
+                        float skip_thres, int n, void* stream)
+{
+    check_b(n, {scales, index, cond, block_count, compact_out, totals}, {Hh, W, C}, what);
+    check_y_step(n, Hh, W, C, step, slot, what);
+    check_rows({{scales, lds}}, C, what);
+    check_aligned({index}, 8, what);
+    check_aligned({block_count, totals}, 4, what);
+    check_strides(n, out_stride, totals_stride, what);
+    dcvc::symbols_init();
+    dcvc::YStepDecIndex d;
+    d.scales = H(scales); d.lds = lds;
+    d.index = static_cast<uint8_t*>(index); d.cond = static_cast<uint8_t*>(cond);
+    d.block_count = static_cast<int32_t*>(block_count);
+    d.H = Hh; d.W = W; d.C = C; d.step = step; d.skip_thres = skip_thres; d.n = n;
+    dcvc::y_step_dec_index(d, S(stream));
+    dcvc::compact_b(index, 1, d.cond, d.block_count, Hh * W * (C / 4), compact_out, out_stride, static_cast<int32_t*>(totals),
+                    totals_stride, slot, n, S(stream));
+}
+
+void y_step_dec_restore_n(const char* what, const void* decoded, long long decoded_stride, const void* cond, const void* block_count,
+                          const void* totals, int totals_stride, int slot, const void* means, int ldm, void* y_hat_acc, int ldacc,
+                          int Hh, int W, int C, int step, int n, void* stream)
+{
+    check_b(n, {decoded, cond, block_count, totals, means, y_hat_acc}, {Hh, W, C}, what);
+    check_y_step(n, Hh, W, C, step, slot, what);
+    check_rows({{means, ldm}, {y_hat_acc, ldacc}}, C, what);
+    check_aligned({block_count, totals}, 4, what);
+    check_strides(n, decoded_stride, totals_stride, what);
+    dcvc::YStepDecRestore d;
+    d.decoded = static_cast<const int8_t*>(decoded);
+    d.cond = static_cast<const uint8_t*>(cond);
+    d.block_count = static_cast<const int32_t*>(block_count);
+    d.totals = static_cast<const int32_t*>(totals); d.slot = slot;
+    d.means = H(means); d.ldm = ldm; d.y_hat_acc = H(y_hat_acc); d.ldacc = ldacc;
+    d.H = Hh; d.W = W; d.C = C; d.step = step; d.first = (step == 0);
+    d.n = n; d.decoded_stride = decoded_stride; d.totals_stride = totals_stride;
+    dcvc::y_step_dec_restore(d, S(stream));
+}
+
+}  // namespace
+
 int dcvc_y_step_enc(const void* y, int ldy, const void* scales, int lds, const void* means, int ldm,
                     void* y_hat_acc, int ldacc, void* sym, void* cond, void* block_count,
                     void* compact_out, void* totals, int Hh, int W, int C, int step,
                     float skip_thres, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::symbols_init();
-        dcvc::YStepEnc d;
-        d.y = H(y); d.ldy = ldy; d.scales = H(scales); d.lds = lds; d.means = H(means); d.ldm = ldm;
-        d.y_hat_acc = H(y_hat_acc); d.ldacc = ldacc;
-        d.sym = static_cast<int16_t*>(sym); d.cond = static_cast<uint8_t*>(cond);
-        d.block_count = static_cast<int32_t*>(block_count);
-        d.H = Hh; d.W = W; d.C = C; d.step = step; d.skip_thres = skip_thres; d.first = (step == 0);
-        dcvc::y_step_enc(d, S(stream));
-        dcvc::compact(sym, 2, d.cond, d.block_count, Hh * W * (C / 4), compact_out,
-                      static_cast<int32_t*>(totals), step, S(stream));
+        y_step_enc_n("y_step_enc", y, ldy, scales, lds, means, ldm, y_hat_acc, ldacc, sym, cond, block_count, compact_out, 0, totals,
+                     0, step, Hh, W, C, step, skip_thres, 1, stream);
+    });
+}
+
+int dcvc_y_step_enc_b(const void* y, int ldy, const void* scales, int lds, const void* means, int ldm, void* y_hat_acc, int ldacc,
+                      void* sym, void* cond, void* block_count, void* compact_out, long long out_stride, void* totals,
+                      int totals_stride, int slot, int Hh, int W, int C, int step, float skip_thres, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        y_step_enc_n("y_step_enc_b", y, ldy, scales, lds, means, ldm, y_hat_acc, ldacc, sym, cond, block_count, compact_out,
+                     out_stride, totals, totals_stride, slot, Hh, W, C, step, skip_thres, n, stream);
     });
 }
 
@@ -827,15 +1001,18 @@ int dcvc_y_step_dec_index(const void* scales, int lds, void* index, void* cond, 
                           float skip_thres, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::symbols_init();
-        dcvc::YStepDecIndex d;
-        d.scales = H(scales); d.lds = lds;
-        d.index = static_cast<uint8_t*>(index); d.cond = static_cast<uint8_t*>(cond);
-        d.block_count = static_cast<int32_t*>(block_count);
-        d.H = Hh; d.W = W; d.C = C; d.step = step; d.skip_thres = skip_thres;
-        dcvc::y_step_dec_index(d, S(stream));
-        dcvc::compact(index, 1, d.cond, d.block_count, Hh * W * (C / 4), compact_out,
-                      static_cast<int32_t*>(totals), step, S(stream));
+        y_step_dec_index_n("y_step_dec_index", scales, lds, index, cond, block_count, compact_out, 0, totals, 0, step, Hh, W, C,
+                           step, skip_thres, 1, stream);
+    });
+}
+
+int dcvc_y_step_dec_index_b(const void* scales, int lds, void* index, void* cond, void* block_count, void* compact_out,
+                            long long out_stride, void* totals, int totals_stride, int slot, int Hh, int W, int C, int step,
+                            float skip_thres, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        y_step_dec_index_n("y_step_dec_index_b", scales, lds, index, cond, block_count, compact_out, out_stride, totals,
+                           totals_stride, slot, Hh, W, C, step, skip_thres, n, stream);
     });
 }
 
@@ -844,14 +1021,18 @@ int dcvc_y_step_dec_restore(const void* decoded, const void* cond, const void* b
                             int ldacc, int Hh, int W, int C, int step, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::YStepDecRestore d;
-        d.decoded = static_cast<const int8_t*>(decoded);
-        d.cond = static_cast<const uint8_t*>(cond);
-        d.block_count = static_cast<const int32_t*>(block_count);
-        d.totals = static_cast<const int32_t*>(totals); d.slot = step;
-        d.means = H(means); d.ldm = ldm; d.y_hat_acc = H(y_hat_acc); d.ldacc = ldacc;
-        d.H = Hh; d.W = W; d.C = C; d.step = step; d.first = (step == 0);
-        dcvc::y_step_dec_restore(d, S(stream));
+        y_step_dec_restore_n("y_step_dec_restore", decoded, 0, cond, block_count, totals, 0, step, means, ldm, y_hat_acc, ldacc,
+                             Hh, W, C, step, 1, stream);
+    });
+}
+
+int dcvc_y_step_dec_restore_b(const void* decoded, long long decoded_stride, const void* cond, const void* block_count,
+                              const void* totals, int totals_stride, int slot, const void* means, int ldm, void* y_hat_acc,
+                              int ldacc, int Hh, int W, int C, int step, int n, void* stream)
+{
+    return dcvc::guarded([&] {
+        y_step_dec_restore_n("y_step_dec_restore_b", decoded, decoded_stride, cond, block_count, totals, totals_stride, slot, means,
+                             ldm, y_hat_acc, ldacc, Hh, W, C, step, n, stream);
     });
 }
 

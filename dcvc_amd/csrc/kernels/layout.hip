@@ -240,6 +240,7 @@ void crop(const half_t* in, int ldin, int Win, half_t* out, int ldout, int H, in
 void mul_channel(const half_t* x, int ldx, const half_t* q, half_t* y, int ldy, int pixels, int C,
                  hipStream_t stream)
 {
+    if (C % 8 != 0) throw std::invalid_argument("mul_channel: C must be a multiple of 8");
     const long long n = static_cast<long long>(pixels) * (C / 8);
     hipLaunchKernelGGL(mul_channel_kernel, grid1d(n), dim3(256), 0, stream, x, ldx, q, y, ldy, pixels, C);
     hip_check(hipGetLastError(), "mul_channel launch");

@@ -588,6 +588,7 @@ void compact_b(const void* in, int elem_bytes, const uint8_t* cond, const int32_
 
 void y_step_dec_restore(const YStepDecRestore& d, hipStream_t stream)
 {
+    if (d.C % 32 != 0) throw std::invalid_argument("y_step_dec_restore: C must be a multiple of 32");
     check_pictures(d.n, "y_step_dec_restore");
     const int count = d.H * d.W * (d.C / 4);
     hipLaunchKernelGGL(y_step_dec_restore_kernel, dim3(grid_for(count), d.n), dim3(kBlockThreads), 0,

@@ -62,6 +62,13 @@ int dcvc_replicate_pad(const void* in, int ldin, int H, int W, int C, int pad_b,
 int dcvc_crop(const void* in, int ldin, int Win, void* out, int ldout, int H, int W, int C, void* stream);
 int dcvc_mul_channel(const void* x, int ldx, const void* q, void* y, int ldy, int pixels, int C,
                      void* stream);
+/* pad_unshuffle8 into a wider row: out [H8][W8][ldout], ldout >= 64 * C3 (the inter codecs write the source picture into a
+ * channel slice of a concatenation buffer this way) */
+int dcvc_pad_unshuffle8_ld(const void* x, int H, int W, int C3, void* out, int ldout, int H8, int W8, void* stream);
+/* Every entry of this group and its batched form below refuse, before any launch (return < 0, dcvc_last_error names the
+ * entry): null pointers, sizes <= 0, C not a multiple of 8, a leading dimension below the channel count, negative padding,
+ * an output smaller than the picture and, on every side that the kernel moves 16 bytes at a time, a pointer that is not
+ * 16-byte aligned or a leading dimension that is not a multiple of 8. */
 
 /* Not part of the reference surface: batched forms for the intra batches. n (1..16) pictures back to back
  * on both sides, each with the per-picture geometry of the single form above; n = 1 is the single launch. The halo,
@@ -324,6 +331,22 @@ int dcvc_y_step_dec_index(const void* scales, int lds, void* index, void* cond, 
 int dcvc_y_step_dec_restore(const void* decoded, const void* cond, const void* block_count,
                             const void* totals, const void* means, int ldm,
                             void* y_hat_acc, int ldacc, int H, int W, int C, int step, void* stream);
+/* Batched forms of the three (not part of the reference surface): n (1..16) pictures of H x W back to back in
+ * every operand - y / scales / means / y_hat_acc [n][P][ld], sym and index [n][P*C/4], cond [n][P*C/32], block_count
+ * [n][dcvc_symbol_blocks(P*C/4)] - the masks following each picture's own (row, column). Picture b compacts into
+ * compact_out + b * out_stride (elements) with its counts in totals + b * totals_stride (int32s): this step's count goes to
+ * totals[slot] and its output starts sum(totals[0..slot)) elements into the picture's region. The restore reads picture b's
+ * symbols from decoded + b * decoded_stride in the same way. The single forms above are n = 1, slot = step. C must be a
+ * multiple of 32; the argument checks are those of the layout group. */
+int dcvc_y_step_enc_b(const void* y, int ldy, const void* scales, int lds, const void* means, int ldm, void* y_hat_acc, int ldacc,
+                      void* sym, void* cond, void* block_count, void* compact_out, long long out_stride, void* totals,
+                      int totals_stride, int slot, int H, int W, int C, int step, float skip_thres, int n, void* stream);
+int dcvc_y_step_dec_index_b(const void* scales, int lds, void* index, void* cond, void* block_count, void* compact_out,
+                            long long out_stride, void* totals, int totals_stride, int slot, int H, int W, int C, int step,
+                            float skip_thres, int n, void* stream);
+int dcvc_y_step_dec_restore_b(const void* decoded, long long decoded_stride, const void* cond, const void* block_count,
+                              const void* totals, int totals_stride, int slot, const void* means, int ldm, void* y_hat_acc,
+                              int ldacc, int H, int W, int C, int step, int n, void* stream);
 
 /* The inter models' full-tensor masked steps (nsteps = 2: LD checkerboard x channel halves,
  * dmc_ld_proxy.cpp:672-683; nsteps = 4: HT-S channel-group x 2x2-position masks,

@@ -1,7 +1,8 @@
 """Intra batches on a real MI355X (-m gpu): N pictures per DMCI call give exactly what N single calls give.
 
   * kernels: every batched `_b` entry point of include/dcvc_amd_ops.h equals N single launches bit for bit, on per-picture
-    geometries with odd row counts (H16 = 45, H64 = 17, H = 15), where stacking the pictures as one taller one would not;
+    geometries with odd row counts (H16 = 45, H64 = 17, H = 15), where stacking the pictures as one taller one would not
+    (the symbol steps' dcvc_y_step_enc_b / _dec_index_b / _dec_restore_b: tests/test_symbols_edges_gpu.py::test_batches);
   * codec: DMCIProxy.compress_batch gives the streams, ec_parallel and x_hat of single compress() calls on a fresh object,
     decompress_batch the x_hat of single decompress() calls; with and without graphs, skip_thres 0 and 0.15; a single call
     behind a batch call gives what a fresh object gives;

@@ -649,6 +649,25 @@ int dcvc_x_to_yuv420p16(const void* x_hat, int row_pixels, int H_, int W_, int b
     });
 }
 
+long long dcvc_pix_picture_samples(int fmt, int H_, int W_)
+{
+    long long n = -1;
+    const int rc = dcvc::guarded([&] { n = dcvc::pix_picture_samples(fmt, H_, W_); });
+    return rc < 0 ? rc : n;
+}
+
+int dcvc_pix_to_x(const void* src, int fmt, int bit_depth, int H_, int W_, void* x, int ldx, void* planar, void* stream)
+{
+    return dcvc::guarded([&] { dcvc::pix_to_x(src, fmt, bit_depth, H_, W_, H(x), ldx, planar, S(stream)); });
+}
+
+int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H_, int W_, int fmt, int bit_depth, void* dist32, void* out, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::x_to_pix(H(x_hat), row_pixels, H_, W_, fmt, bit_depth, static_cast<float*>(dist32), out, S(stream));
+    });
+}
+
 int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_,
                 int row_stride, long long plane_stride, double* out, void* stream)
 {

@@ -1,4 +1,5 @@
-// dcvc - standalone DCVC-UF encoder / decoder for 8- to 16-bit YUV420 and 8-bit RGB pictures on an MI355X.
+// dcvc - standalone DCVC-UF encoder / decoder for 8- to 16-bit YUV (4:2:0, 4:2:2, 4:4:4, NV12 / P010, Y4M) and 8-bit RGB pictures on
+// an MI355X.
 //
 // The codec without the research harness: what test_video.py:166-399 (run_one_point_with_stream)
 // does around the plugin - read YUV420 frames or RGB pictures, code them picture by picture into the reference's
@@ -8,13 +9,14 @@
 // planes and are converted on the device (frame_io.hip, rgb_io.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
-//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] -o out.bin
+//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
-//               --bit-depth (yuv420 only; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
+//               [--fps N:D]
+//               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
 //               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
 //               stream does not carry it: decode with the depth the source had. PSNR per plane is 10 log10(max_val^2 / mse)
@@ -28,6 +30,20 @@
 //               366-370); the log then holds the RGB PSNR (dcvc_sse, calc_psnr over 3 H W samples) and, with --calc-ssim,
 //               the mean of the three planes' MS-SSIM (calc_msssim_rgb), without _y / _u / _v keys. Both sides must be
 //               even, and >= 88 for --calc-ssim.
+//               --src-type yuv422 | yuv444 | nv12 | p010, each with --bit-depth 8|9..16 (p010 = nv12 --bit-depth 10):
+//               4:2:2 and 4:4:4 planar pictures (Y, Cb, Cr planes; u16 samples LSB-aligned as yuv4xxp10le) and NV12 (Y, then
+//               interleaved Cb Cr rows; above 8 bits the value sits in the high bits, P010 / P012 / P016) for -i (encode),
+//               --ref and -o. One picture path at every depth: dcvc_pix_to_x into x or the chunk slot; on decode
+//               dcvc_x_to_pix writes fp32 distortion planes and the output samples, PSNR per plane from dcvc_sse_ws (the
+//               source's planar samples against those planes, peak = max_val), --calc-ssim from dcvc_msssim_range_ws
+//               (every plane's sides >= 88). The log is the YUV420 log: (6 Y + U + V) / 8 for every format,
+//               frame_pixel_num = H W. --scale / --out-size are refused for them: not resampled yet.
+//               A -i, --ref or -o name ending in .y4m is a YUV4MPEG2 file (a file without the magic is refused). Encode:
+//               the header supplies -W -H, the source type and the bit depth, flags that disagree are refused; a C420*
+//               file takes the yuv420 path (its stream equals the raw file's). Decode: the flags, or - with both absent -
+//               the header of --ref *.y4m; -o *.y4m gets a header from the stream's size, the rate from --fps N:D (default:
+//               --ref's rate, else 25:1) and FRAME in front of each picture; nv12 / p010 cannot be written as Y4M. A Y4M
+//               file that ends inside a picture is refused. Chroma siting is ignored.
 //               (the container carries no picture count: the last chunk of an 8-picture model is padded by repeating
 //               the final picture, test_video.py:104-110 - give -n, or --ref whose length then trims the output, as the
 //               reference's maximum_read = min(g_frame_delay, frame_num - decoded) does)
@@ -249,14 +265,20 @@ struct Geometry {
     int H = 0, W = 0, Hp = 0, Wp = 0;      // picture, padded to multiples of 16
     bool rgb = false;                      // 8-bit RGB pictures (--src-type rgb24 / png) instead of YUV420
     int bit_depth = 8;                     // YUV420: 9..16 = uint16 samples (--bit-depth)
+    // --src-type yuv422 / yuv444 / nv12 / p010: a DCVC_PIX_* layout at any depth, on the picture path of dcvc_pix_to_x /
+    // dcvc_x_to_pix; -1: YUV420 planes or RGB on the paths that were here before
+    int pix_fmt = -1;
+    bool pix() const { return pix_fmt >= 0; }
     bool hbd() const { return bit_depth > 8; }
+    int Hc() const { return pix_fmt == DCVC_PIX_YUV422P || pix_fmt == DCVC_PIX_YUV444P ? H : H / 2; }      // a chroma plane's sides
+    int Wc() const { return pix_fmt == DCVC_PIX_YUV444P ? W : W / 2; }
     size_t y_bytes() const { return static_cast<size_t>(H) * W; }                 // samples of the Y plane
-    size_t uv_bytes() const { return static_cast<size_t>(H / 2) * (W / 2) * 2; } // samples of the U and V planes
-    // one picture: u8 or u16 YUV420 planes, or packed RGB (u8 planes [3][H][W] on the device)
+    size_t uv_bytes() const { return static_cast<size_t>(Hc()) * Wc() * 2; }      // samples of the U and V planes
+    // one picture: u8 or u16 YUV planes (NV12: interleaved chroma), or packed RGB (u8 planes [3][H][W] on the device)
     size_t frame_bytes() const { return rgb ? 3 * y_bytes() : (y_bytes() + uv_bytes()) * (hbd() ? 2 : 1); }
 };
 
-Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8)
+Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8, int pix_fmt = -1)
 {
     if (rgb && (H <= 0 || W <= 0 || (H & 1) || (W & 1))) {
         die("picture size must be positive and even (RGB pictures are coded as YUV420 is: even sides), got " +
@@ -267,6 +289,7 @@ Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8)
     g.H = H; g.W = W; g.Hp = (H + 15) / 16 * 16; g.Wp = (W + 15) / 16 * 16;
     g.rgb = rgb;
     g.bit_depth = bit_depth;
+    g.pix_fmt = pix_fmt;
     return g;
 }
 
@@ -287,6 +310,8 @@ struct DeviceBuffers {
     double* h_sse = nullptr;       // pinned
     void* sse_ws = nullptr;        // dcvc_sse_ws's workspace
     long long sse_ws_bytes = 0;
+    void* ssim_ws = nullptr;       // dcvc_msssim_range_ws's workspace (the other chroma formats)
+    long long ssim_ws_bytes = 0;
     uint8_t* h_src = nullptr;      // pinned: the source picture (RGB or high-bit-depth --ref)
     uint8_t* luma8[2] = {nullptr, nullptr};      // --scene-cut: the 8-bit luma of this picture and of the previous one, in turn
     unsigned long long* sad = nullptr;           // --scene-cut: dcvc_luma_sad's sum
@@ -301,7 +326,8 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false, boo
     hip_ok(hipMalloc(&b.yuv8, g.frame_bytes()), "hipMalloc");
     hip_ok(hipMalloc(&b.x, static_cast<size_t>(g.H) * g.W * 3 * frames * 2), "hipMalloc");
     hip_ok(hipMalloc(&b.x_hat, static_cast<size_t>(frames) * g.Hp * g.Wp * 3 * 2), "hipMalloc");
-    hip_ok(hipMalloc(&b.y16, g.frame_bytes() * 2), "hipMalloc");
+    // fp16 planes, or fp32 ones at a high bit depth; the other chroma formats: fp32 planes at every depth
+    hip_ok(hipMalloc(&b.y16, g.pix() ? (g.y_bytes() + g.uv_bytes()) * 4 : g.frame_bytes() * 2), "hipMalloc");
     hip_ok(hipMalloc(&b.out8, g.frame_bytes()), "hipMalloc");
     hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_yuv), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
     hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_p16), g.frame_bytes() * 2, hipHostMallocDefault), "hipHostMalloc");
@@ -310,15 +336,19 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false, boo
         hip_ok(hipMalloc(&b.ssim, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_ssim), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
     }
-    if (g.rgb || g.hbd()) {
+    if (g.rgb || g.hbd() || g.pix()) {
         if (!b.src8) hip_ok(hipMalloc(&b.src8, g.frame_bytes()), "hipMalloc");
         hip_ok(hipMalloc(&b.sse, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b.h_src), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
         // RGB: one call over the three planes; YUV420: Y, then U and V, one after the other on the same workspace
         b.sse_ws_bytes = g.rgb ? dcvc_sse_workspace_bytes(3, g.H, g.W)
-                               : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.H / 2, g.W / 2));
+                               : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.Hc(), g.Wc()));
         hip_ok(hipMalloc(&b.sse_ws, static_cast<size_t>(b.sse_ws_bytes)), "hipMalloc");
+    }
+    if (ssim && g.pix()) {
+        b.ssim_ws_bytes = std::max(dcvc_msssim_workspace_bytes(1, g.H, g.W), dcvc_msssim_workspace_bytes(2, g.Hc(), g.Wc()));
+        hip_ok(hipMalloc(&b.ssim_ws, static_cast<size_t>(b.ssim_ws_bytes)), "hipMalloc");
     }
     if (scene) {
         for (uint8_t*& p : b.luma8) hip_ok(hipMalloc(&p, g.y_bytes()), "hipMalloc");
@@ -332,7 +362,7 @@ void free_buffers(DeviceBuffers& b)
 {
     if (b.st) hip_ok(hipStreamSynchronize(b.st), "sync");
     for (void* d : {static_cast<void*>(b.yuv8), b.x, b.x_hat, b.y16, static_cast<void*>(b.out8), static_cast<void*>(b.src8),
-                    static_cast<void*>(b.ssim), static_cast<void*>(b.sse), b.sse_ws, static_cast<void*>(b.luma8[0]),
+                    static_cast<void*>(b.ssim), static_cast<void*>(b.sse), b.sse_ws, b.ssim_ws, static_cast<void*>(b.luma8[0]),
                     static_cast<void*>(b.luma8[1]), static_cast<void*>(b.sad)}) {
         if (d) hip_ok(hipFree(d), "hipFree");
     }
@@ -418,15 +448,102 @@ PngDir png_dir(const std::string& dir)
     die(dir + ": unknown image naming convention (im1.png or im00001.png expected)");
 }
 
-enum class SrcType { Yuv420, Rgb24, Png };
+enum class SrcType { Yuv420, Rgb24, Png, Yuv422, Yuv444, Nv12 };
 
 SrcType src_type(const std::string& s)
 {
     if (s == "yuv420") return SrcType::Yuv420;
     if (s == "rgb24") return SrcType::Rgb24;
     if (s == "png") return SrcType::Png;
-    die("unknown --src-type " + s + " (yuv420, rgb24 or png)");
+    if (s == "yuv422") return SrcType::Yuv422;
+    if (s == "yuv444") return SrcType::Yuv444;
+    if (s == "nv12" || s == "p010") return SrcType::Nv12;      // p010 = nv12 --bit-depth 10 (bit_depth_arg)
+    die("unknown --src-type " + s + " (yuv420, yuv422, yuv444, nv12, p010, rgb24 or png)");
 }
+
+// the DCVC_PIX_* layout of the types that take the picture path of dcvc_pix_to_x / dcvc_x_to_pix; -1 for the others
+int pix_fmt_of(SrcType t)
+{
+    return t == SrcType::Yuv422 ? DCVC_PIX_YUV422P : t == SrcType::Yuv444 ? DCVC_PIX_YUV444P : t == SrcType::Nv12 ? DCVC_PIX_NV12 : -1;
+}
+
+bool is_y4m_name(const std::string& path) { return path.size() >= 4 && path.compare(path.size() - 4, 4, ".y4m") == 0; }
+
+// A file of pictures back to back: raw, or Y4M (a name ending in .y4m: one header line, then a "FRAME...\n" line in front of
+// every picture; a file without the magic is refused).
+struct PictureFile {
+    FILE* f = nullptr;
+    std::string path;
+    bool y4m = false;
+    dcvc_y4m_info info{};
+    void open(const std::string& p)
+    {
+        path = p;
+        f = fopen(p.c_str(), "rb");
+        if (!f) die("cannot open " + p);
+        if (!is_y4m_name(p)) return;
+        y4m = true;
+        char head[1024];
+        const size_t n = fread(head, 1, sizeof(head), f);
+        if (dcvc_y4m_parse_header(head, n, &info) < 0) die(p + " is no Y4M file: " + dcvc_last_error());
+        fseek(f, static_cast<long>(info.header_bytes), SEEK_SET);
+    }
+    // the "FRAME...\n" line at the file position; false at the end of the file
+    bool frame_line()
+    {
+        char line[1024];
+        const long at = ftell(f);
+        const size_t n = fread(line, 1, sizeof(line), f);
+        if (n == 0) return false;
+        const int len = dcvc_y4m_frame_header_bytes(line, n);
+        if (len < 0) die(path + ": no FRAME line where a picture should start (" + dcvc_last_error() + ")");
+        fseek(f, at + len, SEEK_SET);
+        return true;
+    }
+    // pictures in the file; a Y4M file that ends inside a picture is refused. The position is left at the first picture.
+    long long count(size_t frame_bytes)
+    {
+        fseek(f, 0, SEEK_END);
+        const long long size = ftell(f);
+        long long n = 0;
+        if (!y4m) {
+            n = size / static_cast<long long>(frame_bytes);
+        } else {
+            fseek(f, static_cast<long>(info.header_bytes), SEEK_SET);
+            while (frame_line()) {
+                if (ftell(f) + static_cast<long long>(frame_bytes) > size) {
+                    die(path + " ends inside picture " + std::to_string(n + 1) + " (" + std::to_string(frame_bytes) + " bytes each)");
+                }
+                fseek(f, static_cast<long>(frame_bytes), SEEK_CUR);
+                ++n;
+            }
+        }
+        fseek(f, y4m ? static_cast<long>(info.header_bytes) : 0, SEEK_SET);
+        return n;
+    }
+    // the next picture; false when the file has ended (a Y4M file inside a picture: refused)
+    bool read(uint8_t* buf, size_t frame_bytes)
+    {
+        if (y4m && !frame_line()) return false;
+        const size_t got = fread(buf, 1, frame_bytes, f);
+        if (y4m && got != frame_bytes) die(path + " ends inside a picture");
+        return got == frame_bytes;
+    }
+    void close()
+    {
+        if (f) fclose(f);
+        f = nullptr;
+    }
+};
+
+// what a Y4M header says against the flags: explicit -W / -H / --src-type / --bit-depth that disagree are refused
+struct Y4mSource {
+    SrcType type = SrcType::Yuv420;
+    int depth = 8;
+};
+
+struct Args;
+Y4mSource y4m_source(const PictureFile& pf, const Args& a, bool check_size);
 
 // a JSON number as Python's json.dump writes it: NaN and the infinities as NaN / Infinity / -Infinity, else 17 digits
 std::string jnum(double v)
@@ -471,16 +588,55 @@ bool is_intra_picture(int idx, int intra_period)
     return intra_period > 1 && idx != 1 && idx % intra_period == 1;
 }
 
-// --bit-depth: 8 (the default, u8 samples) or 9..16 (u16 samples), YUV420 sources only
+// --bit-depth: 8 (the default, u8 samples) or 9..16 (u16 samples), YUV sources only; --src-type p010 is nv12 at 10 bits
 int bit_depth_arg(const Args& a, SrcType type)
 {
-    if (!a.has("bit-depth")) return 8;
+    const bool p010 = a.str("src-type") == "p010";
+    if (!a.has("bit-depth")) return p010 ? 10 : 8;
     const std::string s = a.str("bit-depth");
-    if (type != SrcType::Yuv420) die("--bit-depth is for --src-type yuv420 only (RGB sources are 8-bit)");
+    if (type == SrcType::Rgb24 || type == SrcType::Png) die("--bit-depth is for --src-type yuv420 only (RGB sources are 8-bit)");
     char* end = nullptr;
     const long v = strtol(s.c_str(), &end, 10);
     if (s.empty() || *end != '\0' || v < 8 || v > 16) die("--bit-depth must be 8 or 9..16, got " + s);
+    if (p010 && v != 10) die("--src-type p010 is nv12 at 10 bits: --bit-depth " + s + " disagrees (use --src-type nv12 --bit-depth " + s + ")");
     return static_cast<int>(v);
+}
+
+const char* src_type_name(SrcType t)
+{
+    return t == SrcType::Yuv420 ? "yuv420" : t == SrcType::Yuv422 ? "yuv422" : t == SrcType::Yuv444 ? "yuv444" : t == SrcType::Nv12 ? "nv12" :
+           t == SrcType::Rgb24 ? "rgb24" : "png";
+}
+
+Y4mSource y4m_source(const PictureFile& pf, const Args& a, bool check_size)
+{
+    Y4mSource y;
+    y.type = pf.info.pix_fmt == DCVC_PIX_YUV422P ? SrcType::Yuv422 : pf.info.pix_fmt == DCVC_PIX_YUV444P ? SrcType::Yuv444 : SrcType::Yuv420;
+    y.depth = pf.info.bit_depth;
+    const std::string what = pf.path + " holds " + std::to_string(pf.info.width) + "x" + std::to_string(pf.info.height) + " " +
+                             src_type_name(y.type) + " pictures of " + std::to_string(y.depth) + " bits";
+    if (check_size && ((a.has("W") && a.num("W", 0) != pf.info.width) || (a.has("H") && a.num("H", 0) != pf.info.height))) {
+        die(what + ", not the -W x -H given");
+    }
+    if (a.has("src-type") && src_type(a.str("src-type")) != y.type) die(what + ", not --src-type " + a.str("src-type"));
+    if ((a.has("bit-depth") || a.str("src-type") == "p010") && bit_depth_arg(a, y.type) != y.depth) die(what + ", not the --bit-depth given");
+    return y;
+}
+
+// --fps N:D (decode, -o *.y4m): the rate the Y4M header states
+bool fps_arg(const Args& a, int& num, int& den)
+{
+    if (!a.has("fps")) return false;
+    const std::string s = a.str("fps");
+    const size_t c = s.find(':');
+    const std::string part[2] = {s.substr(0, c), c == std::string::npos ? std::string() : s.substr(c + 1)};
+    for (const std::string& p : part) {
+        if (p.empty() || p.size() > 9 || p.find_first_not_of("0123456789") != std::string::npos || atoi(p.c_str()) <= 0) {
+            die("--fps must be N:D with two positive numbers, got " + s);
+        }
+    }
+    num = atoi(part[0].c_str()); den = atoi(part[1].c_str());
+    return true;
 }
 
 // --batch: 1 (the default) .. 16 pictures per intra call; refused before anything touches the device
@@ -607,6 +763,9 @@ SizeArg size_arg(const Args& a, const char* key)
     const std::string flag = std::string("--") + key;
     const std::string type = a.str("src-type", "yuv420");
     if (type == "rgb24" || type == "png") die(flag + " is for --src-type yuv420: RGB sources are not resampled yet");
+    if (type == "yuv422" || type == "yuv444" || type == "nv12" || type == "p010") {
+        die(flag + " is for --src-type yuv420: " + type + " sources are not resampled yet");
+    }
     if (!parse_size(a.str(key), z.W, z.H)) die(flag + " must be WxH with both sides positive and even, got " + a.str(key));
     z.on = true;
     return z;
@@ -728,11 +887,22 @@ int encode(const Args& a)
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
     }
-    const SrcType type = src_type(a.str("src-type", "yuv420"));
-    const bool rgb = type != SrcType::Yuv420;
-    const int depth = bit_depth_arg(a, type);
+    SrcType type = src_type(a.str("src-type", "yuv420"));
+    int depth = bit_depth_arg(a, type);
     const SizeArg scale = size_arg(a, "scale");
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
+    // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
+    PictureFile src_file;
+    if (is_y4m_name(a.str("i"))) {
+        src_file.open(a.str("i"));
+        const Y4mSource y = y4m_source(src_file, a, true);
+        type = y.type; depth = y.depth;
+        pic_w = src_file.info.width; pic_h = src_file.info.height;
+        if (scale.on && pix_fmt_of(type) >= 0) {
+            die(std::string("--scale is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
+        }
+    }
+    const bool rgb = type == SrcType::Rgb24 || type == SrcType::Png;
     PngDir pngs;
     if (type == SrcType::Png) {
         // the size of the first picture; -W / -H, when given, must agree with it
@@ -745,7 +915,7 @@ int encode(const Args& a)
         die("--src-type rgb24 needs -W and -H");
     }
     // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
-    const Geometry gs = geometry(pic_h, pic_w, rgb, depth);
+    const Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type));
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
     if (scene.on) {
@@ -762,16 +932,12 @@ int encode(const Args& a)
     const int qp_i = a.num("qp-i", 32), qp_p = a.num("qp-p", qp_i);
     const int delay = c.frames_per_p;
     if (intra_period > 1 && intra_period % delay != 0) die("intra period must be a multiple of the chunk size");
-    FILE* in = nullptr;
     long long total = 0;
     if (type == SrcType::Png) {
         total = pngs.count();
     } else {
-        in = fopen(a.str("i").c_str(), "rb");
-        if (!in) die("cannot open " + a.str("i"));
-        fseek(in, 0, SEEK_END);
-        total = ftell(in) / static_cast<long long>(gs.frame_bytes());
-        fseek(in, 0, SEEK_SET);
+        if (!src_file.f) src_file.open(a.str("i"));
+        total = src_file.count(gs.frame_bytes());
     }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
@@ -792,14 +958,14 @@ int encode(const Args& a)
     // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx)
     auto load_picture = [&]() {
         if (scale.on) {
-            if (fread(h_full, 1, gs.frame_bytes(), in) != gs.frame_bytes()) die("short read");
+            if (!src_file.read(h_full, gs.frame_bytes())) die("short read");
             hip_ok(hipMemcpyAsync(d_full, h_full, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
             rs.run(d_full, b.yuv8, b.st);
             return;
         }
         if (type == SrcType::Png) {
             if (!pngs.read(b.h_yuv, g)) die("short read");
-        } else if (fread(b.h_yuv, 1, g.frame_bytes(), in) != g.frame_bytes()) {
+        } else if (!src_file.read(b.h_yuv, g.frame_bytes())) {
             die("short read");
         }
         hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
@@ -809,6 +975,8 @@ int encode(const Args& a)
     auto convert = [&](char* dst, int ldx, bool measure = false, bool has_prev = false) {
         if (rgb) {
             abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, b.st), "rgb_to_x");
+        } else if (g.pix()) {
+            abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, dst, ldx, nullptr, b.st), "pix_to_x");
         } else if (g.hbd()) {
             abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, dst, ldx, b.st), "yuv420p16_to_x");
         } else {
@@ -993,7 +1161,7 @@ int encode(const Args& a)
         idx += want;
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
-    if (in) fclose(in);
+    src_file.close();
     if (scale.on) {
         rs.destroy();
         hip_ok(hipHostFree(h_full), "hipHostFree");
@@ -1063,6 +1231,16 @@ int decode(const Args& a)
         die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), --out-size is " +
             std::to_string(out_size.W) + "x" + std::to_string(out_size.H));
     }
+    // -o *.y4m: what the flags alone decide is refused before a model is loaded
+    const bool rec_y4m = a.has("o") && is_y4m_name(a.str("o"));
+    int fps_num = 25, fps_den = 1;
+    const bool has_fps = fps_arg(a, fps_num, fps_den);
+    if (has_fps && !rec_y4m) die("--fps is the rate in the header of -o *.y4m");
+    if (rec_y4m) {
+        const std::string t = a.str("src-type");
+        if (t == "nv12" || t == "p010") die("-o " + a.str("o") + ": Y4M has no tag for interleaved chroma (--src-type " + t + "); write a raw file");
+        if (t == "rgb24" || t == "png") die("-o " + a.str("o") + ": a Y4M file holds YUV pictures, not --src-type " + t);
+    }
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     std::vector<uint8_t> bin;
     {
@@ -1072,15 +1250,45 @@ int decode(const Args& a)
         f.seekg(0);
         f.read(reinterpret_cast<char*>(bin.data()), static_cast<std::streamsize>(bin.size()));
     }
-    const SrcType type = src_type(a.str("src-type", "yuv420"));
-    const bool rgb = type != SrcType::Yuv420, png = type == SrcType::Png;
-    const int depth = bit_depth_arg(a, type);
+    SrcType type = src_type(a.str("src-type", "yuv420"));
+    int depth = bit_depth_arg(a, type);
     const bool has_rec = a.has("o"), has_ref = a.has("ref");
-    // raw files (yuv420, rgb24), or directories of PNG pictures
+    const bool png = type == SrcType::Png;
+    // raw or Y4M files (the YUV types, rgb24), or directories of PNG pictures. --ref *.y4m: its header supplies the source
+    // type and the bit depth when the flags do not, and must agree with them when they do
+    PictureFile ref_file;
+    if (has_ref && !png) {
+        ref_file.open(a.str("ref"));
+        if (ref_file.y4m) {
+            const Y4mSource y = y4m_source(ref_file, a, false);
+            type = y.type; depth = y.depth;
+            if (!has_fps) { fps_num = ref_file.info.fps_num; fps_den = ref_file.info.fps_den; }
+        }
+    }
+    const bool rgb = type == SrcType::Rgb24 || type == SrcType::Png;
+    const int pix_fmt = pix_fmt_of(type);
+    if (out_size.on && pix_fmt >= 0) {
+        die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
+    }
     FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
-    FILE* ref = has_ref && !png ? fopen(a.str("ref").c_str(), "rb") : nullptr;
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
-    if (has_ref && !png && !ref) die("cannot open " + a.str("ref"));
+    // -o *.y4m: the header once the first picture's size is known, then a FRAME line in front of every picture
+    bool rec_header_done = false;
+    auto rec_frame = [&](const Geometry& og) {
+        if (!rec_y4m) return;
+        if (!rec_header_done) {
+            dcvc_y4m_info hi{};
+            hi.width = og.W; hi.height = og.H; hi.fps_num = fps_num; hi.fps_den = fps_den;
+            hi.pix_fmt = og.pix() ? og.pix_fmt : DCVC_PIX_YUV420P;
+            hi.bit_depth = og.bit_depth;
+            char line[256];
+            const int n = dcvc_y4m_write_header(line, sizeof(line), &hi);
+            abi_ok(n, "y4m header");
+            if (fwrite(line, 1, static_cast<size_t>(n), rec) != static_cast<size_t>(n)) die("short write");
+            rec_header_done = true;
+        }
+        if (fwrite("FRAME\n", 1, 6, rec) != 6) die("short write");
+    };
     PngDir ref_pngs, rec_pngs;
     if (png && has_ref) ref_pngs = png_dir(a.str("ref"));
     if (png && has_rec) {
@@ -1137,13 +1345,27 @@ int decode(const Args& a)
                 die("--calc-ssim needs both picture sides >= 88 (MS-SSIM of the R, G and B planes), the stream holds " +
                     std::to_string(s->width) + "x" + std::to_string(s->height));
             }
-            if (calc_ssim && !rgb && !out_size.on && (s->height < 176 || s->width < 176)) {
+            if (calc_ssim && pix_fmt >= 0) {
+                const Geometry t = geometry(s->height, s->width, false, depth, pix_fmt);
+                if (t.H < 88 || t.W < 88 || t.Hc() < 88 || t.Wc() < 88) {
+                    die("--calc-ssim needs the sides of every plane >= 88 (MS-SSIM of the Y, Cb and Cr planes), the stream holds " +
+                        std::to_string(s->width) + "x" + std::to_string(s->height) + " with " + std::to_string(t.Wc()) + "x" +
+                        std::to_string(t.Hc()) + " chroma planes");
+                }
+            }
+            if (ref_file.y4m && (ref_file.info.width != (out_size.on ? out_size.W : s->width) ||
+                                 ref_file.info.height != (out_size.on ? out_size.H : s->height))) {
+                die(ref_file.path + " holds " + std::to_string(ref_file.info.width) + "x" + std::to_string(ref_file.info.height) +
+                    " pictures, the output is " + std::to_string(out_size.on ? out_size.W : s->width) + "x" +
+                    std::to_string(out_size.on ? out_size.H : s->height));
+            }
+            if (calc_ssim && !rgb && pix_fmt < 0 && !out_size.on && (s->height < 176 || s->width < 176)) {
                 die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), the "
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             if (out_size.on) check_ratio("--out-size", s->width, s->height, go.W, go.H);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
-            g = geometry(s->height, s->width, rgb, depth);
+            g = geometry(s->height, s->width, rgb, depth, pix_fmt);
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
             if (out_size.on) so.create(g, go, has_ref, calc_ssim);
             src.resize(g.frame_bytes());
@@ -1212,6 +1434,9 @@ int decode(const Args& a)
             if (rgb) {
                 // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
                 abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_rgb");
+            } else if (g.pix()) {
+                // fp32 distortion planes [H][W] + [2][Hc][Wc] in y16, the output samples in file layout in out8
+                abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_pix");
             } else if (g.hbd()) {
                 // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
                 abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, has_rec || out_size.on ? b.out8 : nullptr, b.st),
@@ -1223,7 +1448,7 @@ int decode(const Args& a)
                 // b.out8 holds the integer samples -o would write at the coded size: resample them, then the output picture is
                 // written and measured at its own size, sample against sample (the source first, as below)
                 const size_t ny = go.y_bytes(), nc = ny / 4, es = go.hbd() ? 2 : 1;
-                if (has_ref && fread(so.h_ref, 1, go.frame_bytes(), ref) != go.frame_bytes()) {
+                if (has_ref && !ref_file.read(so.h_ref, go.frame_bytes())) {
                     if (j > 0 && !intra) { source_ended = true; break; }
                     die("reference file is shorter than the stream");
                 }
@@ -1259,6 +1484,7 @@ int decode(const Args& a)
                 }
                 if (has_rec) {
                     hip_ok(hipStreamSynchronize(b.st), "sync");
+                    rec_frame(go);
                     if (fwrite(so.h_out, 1, go.frame_bytes(), rec) != go.frame_bytes()) die("short write");
                 }
                 types.push_back(intra ? 0 : 1);
@@ -1269,8 +1495,8 @@ int decode(const Args& a)
             // the source first: when it ends inside a chunk, the remaining pictures of the chunk are the encoder's
             // padding (repeats of the final picture) and must reach neither the log nor rec.yuv
             if (has_ref) {
-                uint8_t* sp = rgb || g.hbd() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
-                const bool got = png ? ref_pngs.read(sp, g) : fread(sp, 1, g.frame_bytes(), ref) == g.frame_bytes();
+                uint8_t* sp = rgb || g.hbd() || g.pix() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
+                const bool got = png ? ref_pngs.read(sp, g) : ref_file.read(sp, g.frame_bytes());
                 if (!got) {
                     if (j > 0 && !intra) { source_ended = true; break; }      // (an I batch: as its pictures one by one)
                     die("reference file is shorter than the stream");
@@ -1281,8 +1507,9 @@ int decode(const Args& a)
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 if (png) {
                     abi_ok(dcvc_png_write_rgb(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
-                } else if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) {
-                    die("short write");
+                } else {
+                    rec_frame(g);
+                    if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) die("short write");
                 }
             }
             if (has_ref && rgb) {
@@ -1304,6 +1531,38 @@ int decode(const Args& a)
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 psnr.push_back(psnr_of_sse((b.h_sse[0] + b.h_sse[1]) + b.h_sse[2], 3.0 * static_cast<double>(plane)));
                 if (calc_ssim) ssim.push_back(((0.0 + b.h_ssim[0]) + b.h_ssim[1] + b.h_ssim[2]) / 3);    // calc_msssim_rgb
+            } else if (has_ref && g.pix()) {
+                // the other chroma formats, at every depth: the source as LSB-aligned planar samples (dcvc_pix_to_x's planar
+                // output, from the pinned picture) against dcvc_x_to_pix's fp32 planes, summed and measured on the device
+                const size_t ny = g.y_bytes(), nc = static_cast<size_t>(g.Hc()) * g.Wc(), es = g.hbd() ? 2 : 1;
+                const int dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+                const double peak = static_cast<double>((1 << g.bit_depth) - 1);
+                const uint8_t* src_uv = b.src8 + ny * es;
+                const char* dist_uv = y16 + ny * 4;
+                hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, nullptr, 3, b.src8, b.st), "pix_to_x (planar source)");
+                abi_ok(dcvc_sse_ws(b.src8, dt, y16, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), b.sse, b.sse_ws,
+                                   b.sse_ws_bytes, b.st), "sse (Y)");
+                abi_ok(dcvc_sse_ws(src_uv, dt, dist_uv, DCVC_SAMPLE_F32, 2, g.Hc(), g.Wc(), g.Wc(), static_cast<long long>(nc), b.sse + 1,
+                                   b.sse_ws, b.sse_ws_bytes, b.st), "sse (U, V)");
+                hip_ok(hipMemcpyAsync(b.h_sse, b.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (calc_ssim) {
+                    abi_ok(dcvc_msssim_range_ws(b.src8, dt, y16, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), peak, b.ssim,
+                                                b.ssim_ws, b.ssim_ws_bytes, b.st), "msssim (Y)");
+                    abi_ok(dcvc_msssim_range_ws(src_uv, dt, dist_uv, DCVC_SAMPLE_F32, 2, g.Hc(), g.Wc(), g.Wc(), static_cast<long long>(nc), peak,
+                                                b.ssim + 1, b.ssim_ws, b.ssim_ws_bytes, b.st), "msssim (U, V)");
+                    hip_ok(hipMemcpyAsync(b.h_ssim, b.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                }
+                hip_ok(hipStreamSynchronize(b.st), "sync");
+                const double py = psnr_of_sse(b.h_sse[0], static_cast<double>(ny), peak);
+                const double pu = psnr_of_sse(b.h_sse[1], static_cast<double>(nc), peak);
+                const double pv = psnr_of_sse(b.h_sse[2], static_cast<double>(nc), peak);
+                // (6 Y + U + V) / 8 for every format: this tool's convention beyond 4:2:0, where the reference defines it
+                psnr.push_back((6 * py + pu + pv) / 8); psnr_y.push_back(py); psnr_u.push_back(pu); psnr_v.push_back(pv);
+                if (calc_ssim) {
+                    const double sy = b.h_ssim[0], su = b.h_ssim[1], sv = b.h_ssim[2];
+                    ssim.push_back((6 * sy + su + sv) / 8); ssim_y.push_back(sy); ssim_u.push_back(su); ssim_v.push_back(sv);
+                }
             } else if (has_ref && g.hbd()) {
                 // as the RGB branch: sums of squares and MS-SSIM on the device from the pinned source, data range max_val
                 const size_t ny = g.y_bytes(), nc = ny / 4;
@@ -1362,7 +1621,7 @@ int decode(const Args& a)
     if (have_buffers) free_buffers(b);
     so.destroy();
     if (rec) fclose(rec);
-    if (ref) fclose(ref);
+    ref_file.close();
     const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (out_size.on) {

@@ -274,6 +274,20 @@ void yuv420p16_to_x(const uint16_t* y, const uint16_t* uv, int H, int W, int bit
 // half to even, all three planes: DCVC-FM's YUVWriter). Null outputs are skipped.
 void x_to_yuv420p16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* yuv, hipStream_t stream);
 
+// ---------------------------------------------------------------- other chroma formats (frame_io_fmt.hip)
+// One picture in file layout - Y [H][W], then Cb / Cr as planes [2][Hc][Wc] or, for NV12, interleaved [Hc][Wc][2] - of 8-bit
+// (u8) or 9..16-bit (u16: LSB-aligned in the planar formats, in the high bits for NV12 = P010 / P012 / P016) samples.
+constexpr int kPixYuv420p = 0, kPixYuv422p = 1, kPixYuv444p = 2, kPixNv12 = 3;      // DCVC_PIX_*
+// samples of one picture; throws for an unknown format or sides that are not positive and even
+long long pix_picture_samples(int fmt, int H, int W);
+// -> x fp16 at pixel stride ldx (yuv420_to_x's / yuv420p16_to_x's arithmetic per sample, nearest-neighbour chroma) and / or
+// `planar`: the picture as LSB-aligned planar samples (Y, Cb, Cr at the format's subsampling). One of the two may be null.
+void pix_to_x(const void* src, int fmt, int bit_depth, int H, int W, half_t* x, int ldx, void* planar, hipStream_t stream);
+// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as planar fp32 distortion planes [H][W] + [2][Hc][Wc] and / or
+// the samples in file layout (rint, half to even; the 4:2:0 layouts at 8 bits truncate Cb / Cr as x_to_yuv420 does). Chroma:
+// the mean of the 1, 2 or 2 x 2 luma positions of fp16(x_hat + 0.5), summed in fp32 and rounded to fp16 once.
+void x_to_pix(const half_t* x, int row_pixels, int H, int W, int fmt, int bit_depth, float* dist, void* out, hipStream_t stream);
+
 // ---------------------------------------------------------------- MS-SSIM (msssim.hip)
 // metrics.py:27-91 calc_msssim of n_planes pairs of H x W planes (u8 or fp16 samples in 0..255; src and rec share row_stride
 // and plane_stride, in samples), fp64 after the load; out[plane] (device, fp64). The workspace (msssim_workspace_bytes) holds the

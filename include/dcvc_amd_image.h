@@ -1,4 +1,4 @@
-/* dcvc_amd_image.h - PNG pictures as packed 8-bit RGB (RGB24) in host memory.
+/* dcvc_amd_image.h - picture files on the host: PNG pictures as packed 8-bit RGB (RGB24), and YUV4MPEG2 (.y4m) headers (below).
  *
  * The reference reads and writes its RGB test sequences as PNG files through PIL (src/utils/video_reader.py:10-45
  * PNGReader: Image.open(path).convert('RGB'); src/utils/video_writer.py:9-30 PNGWriter: Image.fromarray(rgb).save(path)).
@@ -27,6 +27,23 @@ int dcvc_png_info(const char* path, int* width, int* height);
 int dcvc_png_read_rgb(const char* path, void* rgb, size_t capacity, int* width, int* height);
 /* writes packed [height][width][3] u8 as a PNG file */
 int dcvc_png_write_rgb(const char* path, const void* rgb, int width, int height);
+
+/* YUV4MPEG2 (.y4m) headers, host only; the pictures behind them are raw planar samples (DCVC_PIX_* layouts of
+ * include/dcvc_amd_ops.h, LSB-aligned u16 little-endian above 8 bits), each behind a "FRAME" line.
+ *   accepted: "YUV4MPEG2", then the fields W H F I A C X in any order up to '\n' within 1024 bytes. C420jpeg | C420mpeg2 |
+ *             C420paldv | C420 (also when C is absent), C422, C444 and C4xxpN for N in 9..16; Ip, I? or no I field. A and X
+ *             are skipped; F absent or 0:0 reads as 25:1. Chroma siting (jpeg / mpeg2 / paldv) is ignored: chroma is
+ *             up-sampled nearest-neighbour whatever the file says.
+ *   refused, naming the offending field: interlaced It | Ib | Im; Cmono*, C411, C444alpha and unknown tags; unknown fields;
+ *             non-positive or odd sides; a missing W or H.
+ * pix_fmt is a DCVC_PIX_* value, header_bytes the length of the header line with its '\n'. */
+typedef struct { int width, height, fps_num, fps_den, pix_fmt, bit_depth; long long header_bytes; } dcvc_y4m_info;
+int dcvc_y4m_parse_header(const void* bytes, size_t n, dcvc_y4m_info* out);
+/* length of a "FRAME...\n" line (parameters included), < 0 if it is none */
+int dcvc_y4m_frame_header_bytes(const void* bytes, size_t n);
+/* writes "YUV4MPEG2 W.. H.. F..:.. Ip C..\n" (8-bit 4:2:0 as C420jpeg; header_bytes is not read); returns the bytes written.
+ * DCVC_PIX_NV12 is refused: Y4M has no tag for it. */
+int dcvc_y4m_write_header(char* dst, size_t cap, const dcvc_y4m_info* info);
 
 #ifdef __cplusplus
 }

@@ -210,6 +210,37 @@ int dcvc_yuv420p16_to_x(const void* y, const void* uv, int H, int W, int bit_dep
  *   NULL = skip. */
 int dcvc_x_to_yuv420p16(const void* x_hat, int row_pixels, int H, int W, int bit_depth, void* dist32, void* yuv16, void* stream);
 
+/* Other chroma formats (no reference counterpart beyond the arithmetic above: the same per-sample rules on other layouts).
+ * One picture is contiguous, in file layout: Y [H][W], then Cb and Cr as planes [2][Hc][Wc] or, for DCVC_PIX_NV12,
+ * interleaved [Hc][Wc][2]; Hc = H except for the two 4:2:0 layouts (H / 2), Wc = W for 4:4:4, else W / 2. bit_depth 8: u8
+ * samples, max_val = 255; 9..16: u16 little-endian, max_val = 2^b - 1, LSB-aligned in the planar formats (yuv4xxp10le) and in
+ * the high b bits for DCVC_PIX_NV12 (P010 / P012 / P016). H and W are positive and even for every format: odd 4:4:4 sides are
+ * out of scope. Pictures whose H ceil(W / 8) does not fit a 32-bit thread index are refused ("picture too large"). */
+#define DCVC_PIX_YUV420P 0
+#define DCVC_PIX_YUV422P 1
+#define DCVC_PIX_YUV444P 2
+#define DCVC_PIX_NV12    3
+/* samples per picture, H W + 2 Hc Wc; < 0 for a bad argument (host only) */
+long long dcvc_pix_picture_samples(int fmt, int H, int W);
+/*   src (device) -> x fp16 at pixel stride ldx >= 3 (3 channels written, the others untouched): per sample
+ *   x = fp16(fp16(fp32(v) / fp32(max_val)) - 0.5), a correctly rounded division (dcvc_yuv420_to_x / dcvc_yuv420p16_to_x);
+ *   chroma is nearest-neighbour, sample (h >> sub_h, w >> sub_w); P010 reads v >> (16 - b) and ignores the low bits.
+ *   planar (optional): the picture as LSB-aligned planar samples, Y [H][W] then [2][Hc][Wc], u8 or u16 - the source as the
+ *   metrics want it; a plain copy for the planar formats. x or planar may be NULL, not both. Samples above max_val are not
+ *   checked. */
+int dcvc_pix_to_x(const void* src, int fmt, int bit_depth, int H, int W, void* x, int ldx, void* planar, void* stream);
+/*   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture. t = fp16(x_hat + 0.5) for Y; chroma t: the same (4:4:4),
+ *   fp16((fp32(t_left) + fp32(t_right)) * 0.5f) (4:2:2), or fp16(sum * 0.25f) of the 2 x 2 block summed in fp32 in the order
+ *   (0, 0), (0, 1), (1, 0), (1, 1) (4:2:0, as dcvc_x_to_yuv420). dist32: planar fp32 [H][W] then [2][Hc][Wc] - at 8 bits
+ *   fp32 of dcvc_x_to_yuv420's fp16 planes (clamp(fp16(t * 255), 0, 255)), at 9..16 bits clamp(fp32(t) * max_val, 0, max_val).
+ *   out: the samples in file layout, rint(dist32) (half to even) on every plane - except that DCVC_PIX_YUV420P and
+ *   DCVC_PIX_NV12 at 8 bits truncate Cb / Cr as dcvc_x_to_yuv420 does (the reference writer's quirk, kept so that one stream
+ *   decodes to the same samples in both 4:2:0 layouts; 4:2:2 and 4:4:4 have no reference writer and round). P010 stores
+ *   s << (16 - b). Either output may be NULL; with both NULL the call returns 0 without a launch.
+ * DCVC_PIX_YUV420P and DCVC_PIX_NV12 give the bits of dcvc_yuv420_to_x, dcvc_x_to_yuv420, dcvc_yuv420p16_to_x and
+ * dcvc_x_to_yuv420p16, up to the layout. */
+int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H, int W, int fmt, int bit_depth, void* dist32, void* out, void* stream);
+
 /* sample types of dcvc_msssim (U8, F16) and of dcvc_sse / dcvc_sse_ws / dcvc_msssim_range (all four; 2 is unassigned) */
 #define DCVC_SAMPLE_U8  0
 #define DCVC_SAMPLE_F16 1

@@ -789,6 +789,22 @@ int dcvc_luma_sad(const void* x, int ldx, int H_, int W_, const void* prev_luma8
     });
 }
 
+int dcvc_crc32_segments(const void* base, const long long* offsets, const long long* lengths, int n, void* crc_out, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::Crc32Desc d;
+        d.base = base; d.offsets = offsets; d.lengths = lengths; d.n = n; d.out = crc_out;
+        dcvc::crc32_segments(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+uint32_t dcvc_crc32_combine(uint32_t crc_a, uint32_t crc_b, long long len_b)
+{
+    uint32_t crc = 0;
+    dcvc::guarded([&] { crc = dcvc::crc32_combine(crc_a, crc_b, len_b); });
+    return crc;
+}
+
 int dcvc_resample_ntaps(int n_in, int n_out) { return dcvc::resample_ntaps(n_in, n_out); }
 
 int dcvc_resample_taps(int n_in, int n_out, int16_t* coef, int32_t* first)

@@ -12,10 +12,10 @@
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
-//               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH]
+//               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
-//               [--fps N:D]
+//               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
 //               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
@@ -97,6 +97,24 @@
 //               samples against the reference's) and --calc-ssim (dcvc_msssim_range_ws on the same planes) work
 //               at that size, frame_pixel_num and the bpp figures count its pixels, and the log gains coded_width and
 //               coded_height.
+//               --hash-log FILE (decode; encode: all-intra runs) / --verify-hash FILE (decode): picture hashes.
+//               Every output picture - the frame_bytes() bytes -o writes or would write, in raw file layout: no Y4M FRAME
+//               lines, for png the packed RGB the PNG encodes, with --out-size the resampled picture - is hashed on the
+//               device (dcvc_crc32_segments: zlib's CRC-32, one segment per plane - Y, U, V; Y and the interleaved chroma
+//               for nv12 / p010; the packed pixels for rgb24 / png), and only the CRC words come to the host: -o and --ref
+//               are not needed. A picture's CRC is the combination of its planes' (dcvc_crc32_combine), the sequence CRC
+//               that of the pictures': for the raw YUV types and rgb24 it is the crc32 of the whole -o file. Padding pictures
+//               of a ragged last chunk and pictures beyond -n are not hashed, as they are not written. The manifest is text:
+//                   # dcvc-hash 1 crc32 <src_type> <bit_depth> <width> <height>
+//                   <idx> <crc: 8 lowercase hex digits> <plane crc> ...          one line per picture
+//                   sequence <crc> <total bytes>
+//               --verify-hash compares every picture as it is decoded: the first mismatch prints the picture, the plane,
+//               expected and got and ends the run with status 3, as does a manifest with more or fewer pictures than were
+//               decoded; a manifest that cannot be read, or whose algorithm, source type, bit depth or size are not the
+//               run's, is refused with status 2 before a picture is decoded. encode --hash-log converts the intra encoder's
+//               reconstruction with the source's type and depth (at the coded size with --scale) and writes the manifest
+//               decode --hash-log writes for that stream with the same type and depth, byte for byte; any --batch. With
+//               P pictures the flag is refused: the inter encoders reconstruct no pictures.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -863,6 +881,250 @@ struct ScaledOut {
     }
 };
 
+// ------------------------------------------------------------------------------------ picture hashes
+// --hash-log / --verify-hash: CRC-32 of every output picture's bytes in raw file layout, hashed on the device
+// (dcvc_crc32_segments, one segment per plane); only the CRC words travel to the host.
+struct HashPicture {
+    uint32_t crc = 0;
+    std::vector<uint32_t> planes;
+};
+
+struct HashManifest {
+    std::string src_type;
+    int depth = 0, W = 0, H = 0;
+    std::vector<HashPicture> pictures;
+    uint32_t sequence = 0;
+    long long total_bytes = 0;
+};
+
+std::string hex8(uint32_t v)
+{
+    char buf[16];
+    snprintf(buf, sizeof(buf), "%08x", v);
+    return buf;
+}
+
+// # dcvc-hash 1 crc32 <src_type> <bit_depth> <width> <height> / <idx> <crc> <plane crc> ... / sequence <crc> <total bytes>
+std::string manifest_text(const HashManifest& m)
+{
+    std::string s = "# dcvc-hash 1 crc32 " + m.src_type + " " + std::to_string(m.depth) + " " + std::to_string(m.W) + " " +
+                    std::to_string(m.H) + "\n";
+    for (size_t i = 0; i < m.pictures.size(); ++i) {
+        s += std::to_string(i) + " " + hex8(m.pictures[i].crc);
+        for (uint32_t p : m.pictures[i].planes) s += " " + hex8(p);
+        s += "\n";
+    }
+    return s + "sequence " + hex8(m.sequence) + " " + std::to_string(m.total_bytes) + "\n";
+}
+
+// the structure of a manifest, strictly; whether its CRCs are the run's is --verify-hash's business
+HashManifest read_manifest(const std::string& path)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) die("--verify-hash: cannot open " + path);
+    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    auto bad = [&](const std::string& why) { die("--verify-hash: " + path + " is no hash manifest: " + why); };
+    if (text.empty() || text.back() != '\n') bad("the last line is not terminated");
+    std::vector<std::vector<std::string>> lines;
+    for (size_t at = 0; at < text.size();) {
+        const size_t nl = text.find('\n', at);
+        std::vector<std::string> tok;
+        for (size_t t = at; t <= nl;) {
+            const size_t sp = std::min(text.find(' ', t), nl);
+            tok.push_back(text.substr(t, sp - t));
+            t = sp + 1;
+        }
+        lines.push_back(tok);
+        at = nl + 1;
+    }
+    auto dec = [&](const std::string& s, long long& v) {
+        if (s.empty() || s.size() > 18 || s.find_first_not_of("0123456789") != std::string::npos || (s.size() > 1 && s[0] == '0')) return false;
+        v = atoll(s.c_str());
+        return true;
+    };
+    auto hex = [&](const std::string& s, uint32_t& v) {
+        if (s.size() != 8 || s.find_first_not_of("0123456789abcdef") != std::string::npos) return false;
+        v = static_cast<uint32_t>(strtoul(s.c_str(), nullptr, 16));
+        return true;
+    };
+    HashManifest m;
+    const std::vector<std::string>& h = lines[0];
+    if (h.size() != 8 || h[0] != "#" || h[1] != "dcvc-hash") bad("no '# dcvc-hash 1 crc32 <src_type> <bit_depth> <width> <height>' header");
+    if (h[2] != "1") bad("version " + h[2] + " (this tool reads version 1)");
+    if (h[3] != "crc32") bad("algorithm " + h[3] + " (this tool hashes with crc32)");
+    long long v[3];
+    for (int i = 0; i < 3; ++i) {
+        if (!dec(h[5 + static_cast<size_t>(i)], v[i]) || v[i] < 1 || v[i] > (1 << 20)) bad("bad numbers in the header");
+    }
+    m.src_type = h[4];
+    m.depth = static_cast<int>(v[0]); m.W = static_cast<int>(v[1]); m.H = static_cast<int>(v[2]);
+    const bool packed = m.src_type == "rgb24" || m.src_type == "png";
+    const size_t planes = packed ? 1 : m.src_type == "nv12" ? 2 : 3;
+    if (!packed && m.src_type != "nv12" && m.src_type != "yuv420" && m.src_type != "yuv422" && m.src_type != "yuv444") {
+        bad("unknown source type " + m.src_type);
+    }
+    if (lines.size() < 2 || lines.back()[0] != "sequence") bad("no sequence line at the end");
+    for (size_t i = 1; i + 1 < lines.size(); ++i) {
+        const std::vector<std::string>& t = lines[i];
+        const std::string what = "line " + std::to_string(i + 1);
+        HashPicture p;
+        p.planes.resize(planes);
+        if (t.size() != 2 + planes || t[0] != std::to_string(i - 1) || !hex(t[1], p.crc)) bad(what + ": no '<idx> <crc> <plane crc> ...' of picture " + std::to_string(i - 1));
+        for (size_t k = 0; k < planes; ++k) {
+            if (!hex(t[2 + k], p.planes[k])) bad(what + ": a CRC is 8 lowercase hex digits");
+        }
+        m.pictures.push_back(p);
+    }
+    const std::vector<std::string>& s = lines.back();
+    if (s.size() != 3 || !hex(s[1], m.sequence) || !dec(s[2], m.total_bytes)) bad("no 'sequence <crc> <total bytes>' line at the end");
+    return m;
+}
+
+// the hashed segments of one picture in file layout: its planes
+int hash_segments(const Geometry& g, long long* off, long long* len)
+{
+    if (g.rgb) {
+        off[0] = 0; len[0] = static_cast<long long>(g.frame_bytes());
+        return 1;
+    }
+    const long long es = g.hbd() ? 2 : 1, y = static_cast<long long>(g.y_bytes()) * es, uv = static_cast<long long>(g.uv_bytes()) * es;
+    off[0] = 0; len[0] = y;
+    if (g.pix_fmt == DCVC_PIX_NV12) {
+        off[1] = y; len[1] = uv;
+        return 2;
+    }
+    off[1] = y; len[1] = uv / 2;
+    off[2] = y + uv / 2; len[2] = uv / 2;
+    return 3;
+}
+
+// what the flags alone decide is refused before a model is loaded; --verify-hash's file is read there too
+struct HashRun {
+    std::string log, verify;
+    HashManifest expect, got;
+    uint32_t* d_crc = nullptr;
+    uint32_t* h_crc = nullptr;     // pinned
+    bool on() const { return !log.empty() || !verify.empty(); }
+    void parse(const Args& a, bool encoding)
+    {
+        if (a.has("verify-hash") && encoding) die("--verify-hash is a decoder flag: encode writes a manifest with --hash-log, decode checks it");
+        if (a.has("hash-log") && encoding && a.has("inter") && a.num("intra-period", -1) != 1) {
+            die("--hash-log on encode is for all-intra runs (no --inter, or --intra-period 1): the inter encoders reconstruct no "
+                "pictures; hash the decoder's output instead");
+        }
+        log = a.str("hash-log");
+        verify = a.str("verify-hash");
+        if (a.has("hash-log") && log.empty()) die("--hash-log needs a file name");
+        if (a.has("verify-hash") && verify.empty()) die("--verify-hash needs a file name");
+        if (!verify.empty()) expect = read_manifest(verify);
+    }
+    // the run's source type and bit depth, known before the first picture
+    void begin(const char* type, int depth)
+    {
+        if (!on()) return;
+        got.src_type = type; got.depth = depth;
+        if (!verify.empty() && (expect.src_type != got.src_type || expect.depth != depth)) {
+            die("--verify-hash: " + verify + " holds " + expect.src_type + " pictures of " + std::to_string(expect.depth) + " bits, this run's are " +
+                got.src_type + " of " + std::to_string(depth) + " bits");
+        }
+        hip_ok(hipMalloc(&d_crc, 16 * sizeof(uint32_t)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_crc), 16 * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+    }
+    // the output pictures' size, known before the first of them is decoded
+    void size(int W, int H)
+    {
+        if (!on()) return;
+        if (got.W != 0 && (got.W != W || got.H != H)) {
+            die("picture hashes: the stream switches from " + std::to_string(got.W) + "x" + std::to_string(got.H) + " to " + std::to_string(W) +
+                "x" + std::to_string(H) + ", a manifest holds pictures of one size");
+        }
+        got.W = W; got.H = H;
+        if (!verify.empty() && (expect.W != W || expect.H != H)) {
+            die("--verify-hash: " + verify + " holds " + std::to_string(expect.W) + "x" + std::to_string(expect.H) + " pictures, this run's are " +
+                std::to_string(W) + "x" + std::to_string(H));
+        }
+    }
+    [[noreturn]] void mismatch(const std::string& what) const
+    {
+        fprintf(stderr, "dcvc: --verify-hash: %s\n", what.c_str());
+        exit(3);
+    }
+    // one output picture on the device (g.frame_bytes() bytes in file layout); waits for the stream
+    void picture(const uint8_t* dev, const Geometry& g, hipStream_t st)
+    {
+        long long off[3], len[3];
+        const int n = hash_segments(g, off, len);
+        abi_ok(dcvc_crc32_segments(dev, off, len, n, d_crc, st), "crc32");
+        hip_ok(hipMemcpyAsync(h_crc, d_crc, static_cast<size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        HashPicture p;
+        for (int k = 0; k < n; ++k) {
+            p.planes.push_back(h_crc[k]);
+            p.crc = dcvc_crc32_combine(p.crc, h_crc[k], len[k]);
+        }
+        const size_t idx = got.pictures.size();
+        if (!verify.empty()) {
+            if (idx >= expect.pictures.size()) {
+                mismatch("picture " + std::to_string(idx) + " was decoded, " + verify + " holds " + std::to_string(expect.pictures.size()) + " pictures");
+            }
+            const HashPicture& e = expect.pictures[idx];
+            const char* names = g.rgb ? "P" : "YUV";      // P: the packed pixels; nv12: Y and the interleaved chroma
+            for (int k = 0; k < n; ++k) {
+                if (e.planes[static_cast<size_t>(k)] != p.planes[static_cast<size_t>(k)]) {
+                    mismatch("picture " + std::to_string(idx) + ", plane " + std::to_string(k) + " (" + (n == 2 && k == 1 ? "UV" : std::string(1, names[k])) +
+                             "): expected " + hex8(e.planes[static_cast<size_t>(k)]) + ", got " + hex8(p.planes[static_cast<size_t>(k)]));
+                }
+            }
+            if (e.crc != p.crc) mismatch("picture " + std::to_string(idx) + ", whole picture: expected " + hex8(e.crc) + ", got " + hex8(p.crc));
+        }
+        got.sequence = dcvc_crc32_combine(got.sequence, p.crc, static_cast<long long>(g.frame_bytes()));
+        got.total_bytes += static_cast<long long>(g.frame_bytes());
+        got.pictures.push_back(p);
+    }
+    void finish()
+    {
+        if (!on()) return;
+        if (d_crc) hip_ok(hipFree(d_crc), "hipFree");
+        if (h_crc) hip_ok(hipHostFree(h_crc), "hipHostFree");
+        d_crc = h_crc = nullptr;
+        if (!log.empty()) {
+            const std::string text = manifest_text(got);
+            FILE* lf = fopen(log.c_str(), "wb");
+            if (!lf || fwrite(text.data(), 1, text.size(), lf) != text.size()) die("cannot write " + log);
+            fclose(lf);
+        }
+        if (!verify.empty()) {
+            if (expect.pictures.size() != got.pictures.size()) {
+                mismatch(std::to_string(got.pictures.size()) + " pictures were decoded, " + verify + " holds " + std::to_string(expect.pictures.size()));
+            }
+            if (expect.sequence != got.sequence || expect.total_bytes != got.total_bytes) {
+                mismatch("sequence: expected " + hex8(expect.sequence) + " over " + std::to_string(expect.total_bytes) + " bytes, got " +
+                         hex8(got.sequence) + " over " + std::to_string(got.total_bytes));
+            }
+            printf("verified %zu pictures against %s: sequence %s\n", got.pictures.size(), verify.c_str(), hex8(got.sequence).c_str());
+        }
+    }
+};
+
+// x_hat (fp16 [rows][g.Wp][3], top-left H x W) -> the distortion planes in b.y16 and the output samples in file layout in
+// b.out8 (RGB, the other chroma formats and high bit depths: only when `samples`; 8-bit YUV420 always writes them)
+void x_hat_to_picture(const Geometry& g, const DeviceBuffers& b, const char* xh, bool samples)
+{
+    char* y16 = static_cast<char*>(b.y16);
+    if (g.rgb) {
+        // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
+        abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, b.st), "x_to_rgb");
+    } else if (g.pix()) {
+        // fp32 distortion planes [H][W] + [2][Hc][Wc] in y16, the output samples in file layout in out8
+        abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_pix");
+    } else if (g.hbd()) {
+        // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
+        abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_yuv420p16");
+    } else {
+        abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
+    }
+}
+
 // one source picture in --scene-log
 struct ScenePicture {
     long long sad = 0;
@@ -884,6 +1146,8 @@ int encode(const Args& a)
     const int batch = batch_arg(a);
     const SceneArgs scene = scene_args(a, batch);
     const RateArgs rate = rate_args(a, batch);
+    HashRun hash;
+    hash.parse(a, true);
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
     }
@@ -942,6 +1206,14 @@ int encode(const Args& a)
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
     DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
+    // --hash-log: the intra encoder's reconstruction as the decoder would write it, with the source's type and depth at the
+    // coded size
+    hash.begin(src_type_name(type), depth);
+    hash.size(g.W, g.H);
+    auto hash_x_hat = [&](const char* xh) {
+        x_hat_to_picture(g, b, xh, true);
+        hash.picture(b.out8, g, b.st);
+    };
     // --scale: the source picture's own staging, pinned and on the device, in front of b.yuv8
     Resampler rs;
     uint8_t* h_full = nullptr;
@@ -1087,6 +1359,7 @@ int encode(const Args& a)
                 const char* xh = static_cast<const char*>(b.x_hat) + slot_hat * j;
                 if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
                 if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (hash.on()) hash_x_hat(xh);
                 put_unit(true, qp_i, ecs[j], 0, payload);
             }
             idx += nb;
@@ -1132,6 +1405,7 @@ int encode(const Args& a)
             abi_ok(dcvc_dmci_get_stream(c.intra, payload.data(), payload.size()), "get_stream");
             if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
             if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
+            if (hash.on()) hash_x_hat(static_cast<const char*>(b.x_hat));
         } else {
             if (!ctl && !rate_probe) qp = qp_p;
             reset = (reset_interval > 0 && (idx + delay) % reset_interval == 1) ? 1 : 0;
@@ -1168,6 +1442,7 @@ int encode(const Args& a)
         hip_ok(hipFree(d_full), "hipFree");
     }
     if (ctl) dcvc_rc_destroy(ctl);
+    hash.finish();
     if (scd) {
         dcvc_scd_destroy(scd);
         int cuts = 0;
@@ -1236,6 +1511,8 @@ int decode(const Args& a)
     int fps_num = 25, fps_den = 1;
     const bool has_fps = fps_arg(a, fps_num, fps_den);
     if (has_fps && !rec_y4m) die("--fps is the rate in the header of -o *.y4m");
+    HashRun hash;
+    hash.parse(a, false);
     if (rec_y4m) {
         const std::string t = a.str("src-type");
         if (t == "nv12" || t == "p010") die("-o " + a.str("o") + ": Y4M has no tag for interleaved chroma (--src-type " + t + "); write a raw file");
@@ -1270,6 +1547,7 @@ int decode(const Args& a)
     if (out_size.on && pix_fmt >= 0) {
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
     }
+    hash.begin(src_type_name(type), depth);
     FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
     // -o *.y4m: the header once the first picture's size is known, then a FRAME line in front of every picture
@@ -1364,6 +1642,7 @@ int decode(const Args& a)
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             if (out_size.on) check_ratio("--out-size", s->width, s->height, go.W, go.H);
+            hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth, pix_fmt);
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
@@ -1431,19 +1710,8 @@ int decode(const Args& a)
         for (int j = 0; j < frames && decoded < limit; ++j) {
             const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
             char* y16 = static_cast<char*>(b.y16);
-            if (rgb) {
-                // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
-                abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_rgb");
-            } else if (g.pix()) {
-                // fp32 distortion planes [H][W] + [2][Hc][Wc] in y16, the output samples in file layout in out8
-                abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, y16, has_rec ? b.out8 : nullptr, b.st), "x_to_pix");
-            } else if (g.hbd()) {
-                // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
-                abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, has_rec || out_size.on ? b.out8 : nullptr, b.st),
-                       "x_to_yuv420p16");
-            } else {
-                abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
-            }
+            // --hash-log / --verify-hash without -o: the samples are wanted on the device although nothing is written
+            x_hat_to_picture(g, b, xh, g.hbd() && !g.pix() ? has_rec || out_size.on || hash.on() : has_rec || hash.on());
             if (out_size.on) {
                 // b.out8 holds the integer samples -o would write at the coded size: resample them, then the output picture is
                 // written and measured at its own size, sample against sample (the source first, as below)
@@ -1453,6 +1721,7 @@ int decode(const Args& a)
                     die("reference file is shorter than the stream");
                 }
                 so.rs.run(b.out8, so.out, b.st);
+                if (hash.on()) hash.picture(so.out, go, b.st);
                 if (has_rec) hip_ok(hipMemcpyAsync(so.h_out, so.out, go.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 if (has_ref) {
                     const int dt = go.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
@@ -1502,6 +1771,7 @@ int decode(const Args& a)
                     die("reference file is shorter than the stream");
                 }
             }
+            if (hash.on()) hash.picture(b.out8, g, b.st);
             if (has_rec) {
                 hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
@@ -1622,6 +1892,7 @@ int decode(const Args& a)
     so.destroy();
     if (rec) fclose(rec);
     ref_file.close();
+    hash.finish();
     const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (out_size.on) {

@@ -353,6 +353,22 @@ struct LumaSadDesc {
 void luma_sad_validate(const LumaSadDesc& d);    // throws std::invalid_argument for what luma_sad() refuses
 void luma_sad(const LumaSadDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- picture hashes (crc32.hip)
+// out[k] (device uint32 [n]) = zlib's crc32 of the bytes base[offsets[k] .. offsets[k] + lengths[k]), 0 for an empty segment;
+// out[n..] is not touched. offsets and lengths are host arrays, read during the call. An exact integer result, the same for
+// every launch geometry and arrival order. At most two launches, no allocation, no host synchronisation.
+constexpr int kCrc32MaxSegments = 16;
+struct Crc32Desc {
+    const void* base = nullptr;
+    const long long* offsets = nullptr;
+    const long long* lengths = nullptr;
+    int n = 0;
+    void* out = nullptr;
+};
+void crc32_validate(const Crc32Desc& d);         // throws std::invalid_argument for what crc32_segments() refuses
+void crc32_segments(const Crc32Desc& d, hipStream_t stream);
+uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, long long len_b);      // host: crc32(A || B); throws for len_b < 0
+
 // ---------------------------------------------------------------- resampling (resample.hip)
 // Planes of u8 / u16 samples at another size: separable integer Lanczos-3, horizontal pass then vertical pass through an
 // intermediate plane of clamped samples (the filter is stated at the head of resample.hip).

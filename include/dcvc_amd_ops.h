@@ -300,6 +300,20 @@ int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, 
  * sad_out; H, W or ldx below 1; a side above 16384; luma8_out == prev_luma8. */
 int dcvc_luma_sad(const void* x, int ldx, int H, int W, const void* prev_luma8, void* luma8_out, void* sad_out, void* stream);
 
+/* Picture hashes (no reference counterpart): CRC-32 as zlib's crc32() - reflected polynomial 0xEDB88320, init
+ * and final XOR 0xFFFFFFFF - of n byte segments of one device buffer, the planes of a picture in one call.
+ *   dcvc_crc32_segments: crc_out[k] (device uint32_t [n], 4-byte aligned) = crc32 of base[offsets[k] .. offsets[k] +
+ *   lengths[k]), 0 for a length of 0; crc_out[n..] is not touched. offsets and lengths are host arrays, in bytes, read during
+ *   the call; segments may start anywhere, overlap and come in any order. Integer arithmetic: the same value for every launch
+ *   geometry and on every run. At most two launches on `stream`, no allocation, no host synchronisation. Refused before
+ *   anything is enqueued: NULL base, offsets, lengths or crc_out; n outside 1..16; a negative offset or length; a segment
+ *   that ends above 2^44 bytes; crc_out not 4-byte aligned.
+ *   dcvc_crc32_combine: host only; crc32(A || B) from crc_a = crc32(A), crc_b = crc32(B) and len_b = the bytes of B. len_b = 0
+ *   returns crc_a; a negative len_b returns 0 and sets dcvc_last_error. */
+int dcvc_crc32_segments(const void* base, const long long* offsets, const long long* lengths, int n,
+                        void* crc_out /* device uint32_t[n] */, void* stream);
+uint32_t dcvc_crc32_combine(uint32_t crc_a, uint32_t crc_b, long long len_b);
+
 /* Planes of integer samples at another size (no reference counterpart): a separable Lanczos-3 filter with
  * 12-bit integer coefficients, every output sample defined exactly. One 1-D pass n_in -> n_out, the tables in IEEE double:
  *   scale = n_in / n_out, fs = max(1, scale), support = 3 fs, T = 2 ceil(support) taps for every output of the pass;

@@ -744,6 +744,27 @@ int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H_, int W_, void* rgb16
     });
 }
 
+int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H_, int W_,
+                     void* x, int ldx, void* planar, int matrix, int range, int yuv_bit_depth, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::RgbToXDesc d;
+        d.src = static_cast<const uint8_t*>(src);
+        d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
+        d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint8_t*>(planar);
+        dcvc::rgb_to_x_cs(d, dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
+    });
+}
+
+int dcvc_x_to_rgb_cs(const void* x_hat, int row_pixels, int H_, int W_, void* rgb16, void* rgb8, int matrix, int range,
+                     int yuv_bit_depth, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::x_to_rgb_cs(H(x_hat), row_pixels, H_, W_, H(rgb16), static_cast<uint8_t*>(rgb8),
+                          dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
+    });
+}
+
 int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
              long long plane_stride, double* out, void* stream)
 {

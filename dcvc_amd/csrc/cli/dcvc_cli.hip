@@ -13,9 +13,11 @@
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
+//               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
+//               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
 //               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
@@ -115,6 +117,19 @@
 //               reconstruction with the source's type and depth (at the coded size with --scale) and writes the manifest
 //               decode --hash-log writes for that stream with the same type and depth, byte for byte; any --batch. With
 //               P pictures the flag is refused: the inter encoders reconstruct no pictures.
+//               --matrix bt601|bt709|bt2020, --range full|limited, --yuv-depth B (--src-type rgb24 | png): the
+//               colour matrix and the range of the YCbCr picture behind the RGB samples, at every crossing between the two:
+//               encode -i, decode -o and --ref (PSNR and --calc-ssim stay between the source's RGB samples and the converted
+//               reconstruction), and the pictures --hash-log / --verify-hash hash (encode --hash-log included). limited is
+//               Y 16..235, C 16..240 times 2^(B-8) on the scale of B-bit samples, v / (2^B - 1): --yuv-depth (8..16,
+//               default 8, only with --range limited) is the depth of the YUV pictures the stream stands for, e.g. 10 to
+//               look at a stream coded from yuv420 --bit-depth 10. The defaults, bt709 and full, are the reference's
+//               conversion: a run without the flags issues dcvc_rgb_to_x / dcvc_x_to_rgb as before, a run with any of them
+//               dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs, which give the same bytes at bt709 / full. The stream carries none of
+//               this: decode with the flags of the encode, and verify a manifest with the flags it was hashed with. With
+//               any of the flags the JSON log gains color_matrix, color_range and color_yuv_depth. Refused: an unknown
+//               name, a depth outside 8..16 or without --range limited, and any of the flags with a YUV source type, where
+//               nothing is converted. Colour tags in a Y4M header stay ignored.
 //
 // Picture-type decisions, reset rule, chunk padding, container, PSNR ((6 Y + U + V) / 8 on the
 // 0..255 planes) and the JSON log (what compare_bd_rate.py / dcvc_amd/bd_rate.py read) follow
@@ -286,6 +301,10 @@ struct Geometry {
     // --src-type yuv422 / yuv444 / nv12 / p010: a DCVC_PIX_* layout at any depth, on the picture path of dcvc_pix_to_x /
     // dcvc_x_to_pix; -1: YUV420 planes or RGB on the paths that were here before
     int pix_fmt = -1;
+    // RGB with --matrix / --range / --yuv-depth: dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs with these; without: the BT.709 / full
+    // range entry points that were here before
+    bool cs = false;
+    int matrix = DCVC_MATRIX_BT709, range = DCVC_RANGE_FULL, yuv_depth = 8;
     bool pix() const { return pix_fmt >= 0; }
     bool hbd() const { return bit_depth > 8; }
     int Hc() const { return pix_fmt == DCVC_PIX_YUV422P || pix_fmt == DCVC_PIX_YUV444P ? H : H / 2; }      // a chroma plane's sides
@@ -687,6 +706,40 @@ int int_arg(const Args& a, const std::string& key, int def, int lo, int hi)
         die("--" + key + " must be in " + std::to_string(lo) + ".." + std::to_string(hi) + ", got " + s);
     }
     return static_cast<int>(v);
+}
+
+// --matrix, --range, --yuv-depth: the colour conversion of RGB sources, refused before anything touches the device
+struct ColourArgs {
+    bool on = false;       // any of the three flags given
+    int matrix = DCVC_MATRIX_BT709, range = DCVC_RANGE_FULL, yuv_depth = 8;
+    std::string matrix_name = "bt709", range_name = "full";
+    void apply(Geometry& g) const { g.cs = on; g.matrix = matrix; g.range = range; g.yuv_depth = yuv_depth; }
+};
+
+ColourArgs colour_args(const Args& a)
+{
+    ColourArgs c;
+    c.on = a.has("matrix") || a.has("range") || a.has("yuv-depth");
+    if (!c.on) return c;
+    c.matrix_name = a.str("matrix", "bt709");
+    c.range_name = a.str("range", "full");
+    if (c.matrix_name == "bt601") c.matrix = DCVC_MATRIX_BT601;
+    else if (c.matrix_name == "bt709") c.matrix = DCVC_MATRIX_BT709;
+    else if (c.matrix_name == "bt2020") c.matrix = DCVC_MATRIX_BT2020;
+    else die("unknown --matrix " + c.matrix_name + " (bt601, bt709 or bt2020)");
+    if (c.range_name == "full") c.range = DCVC_RANGE_FULL;
+    else if (c.range_name == "limited") c.range = DCVC_RANGE_LIMITED;
+    else die("unknown --range " + c.range_name + " (full or limited)");
+    c.yuv_depth = int_arg(a, "yuv-depth", 8, 8, 16);
+    if (a.has("yuv-depth") && c.range != DCVC_RANGE_LIMITED) {
+        die("--yuv-depth needs --range limited: the depth places the limited-range levels, full range does not depend on it");
+    }
+    // a Y4M -i or --ref cannot make the type RGB: a header that disagrees with --src-type is refused
+    const std::string t = a.str("src-type", "yuv420");
+    if (t != "rgb24" && t != "png") {
+        die("--matrix, --range and --yuv-depth are for --src-type rgb24 and png: " + t + " pictures are not converted");
+    }
+    return c;
 }
 
 RateArgs rate_args(const Args& a, int batch)
@@ -1113,7 +1166,11 @@ void x_hat_to_picture(const Geometry& g, const DeviceBuffers& b, const char* xh,
     char* y16 = static_cast<char*>(b.y16);
     if (g.rgb) {
         // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
-        abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, b.st), "x_to_rgb");
+        if (g.cs) {
+            abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, g.matrix, g.range, g.yuv_depth, b.st), "x_to_rgb_cs");
+        } else {
+            abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, b.st), "x_to_rgb");
+        }
     } else if (g.pix()) {
         // fp32 distortion planes [H][W] + [2][Hc][Wc] in y16, the output samples in file layout in out8
         abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_pix");
@@ -1146,6 +1203,7 @@ int encode(const Args& a)
     const int batch = batch_arg(a);
     const SceneArgs scene = scene_args(a, batch);
     const RateArgs rate = rate_args(a, batch);
+    const ColourArgs colour = colour_args(a);
     HashRun hash;
     hash.parse(a, true);
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
@@ -1179,7 +1237,8 @@ int encode(const Args& a)
         die("--src-type rgb24 needs -W and -H");
     }
     // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
-    const Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type));
+    Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type));
+    if (rgb) colour.apply(gs);
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
     if (scene.on) {
@@ -1245,7 +1304,9 @@ int encode(const Args& a)
     // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
     int luma_turn = 0;
     auto convert = [&](char* dst, int ldx, bool measure = false, bool has_prev = false) {
-        if (rgb) {
+        if (rgb && g.cs) {
+            abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, g.matrix, g.range, g.yuv_depth, b.st), "rgb_to_x_cs");
+        } else if (rgb) {
             abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, b.st), "rgb_to_x");
         } else if (g.pix()) {
             abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, dst, ldx, nullptr, b.st), "pix_to_x");
@@ -1511,6 +1572,7 @@ int decode(const Args& a)
     int fps_num = 25, fps_den = 1;
     const bool has_fps = fps_arg(a, fps_num, fps_den);
     if (has_fps && !rec_y4m) die("--fps is the rate in the header of -o *.y4m");
+    const ColourArgs colour = colour_args(a);
     HashRun hash;
     hash.parse(a, false);
     if (rec_y4m) {
@@ -1645,6 +1707,7 @@ int decode(const Args& a)
             hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth, pix_fmt);
+            if (rgb) colour.apply(g);
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
             if (out_size.on) so.create(g, go, has_ref, calc_ssim);
             src.resize(g.frame_bytes());
@@ -1918,6 +1981,10 @@ int decode(const Args& a)
         const char* sfx[4] = {"", "_y", "_u", "_v"};
         fprintf(jf, "{\n  \"arith_policy\": %d,\n  \"frame_pixel_num\": %.0f,\n  \"i_frame_num\": %d,\n  \"p_frame_num\": %d,\n", dcvc_arith_policy_version(), px, ni, np);
         if (out_size.on) fprintf(jf, "  \"coded_width\": %d,\n  \"coded_height\": %d,\n", g.W, g.H);
+        if (colour.on) {
+            fprintf(jf, "  \"color_matrix\": \"%s\",\n  \"color_range\": \"%s\",\n  \"color_yuv_depth\": %d,\n", colour.matrix_name.c_str(),
+                    colour.range_name.c_str(), colour.yuv_depth);
+        }
         fprintf(jf, "  \"ave_i_frame_bpp\": %.9g,\n  \"ave_p_frame_bpp\": %.9g,\n", ni ? ib / ni / px : 0.0, np ? pb / np / px : 0.0);
         if (rgb) {
             // 17 digits, as Python's json writes a float (the YUV log keeps its 9)

@@ -324,6 +324,18 @@ void rgb_to_x(const RgbToXDesc& d, hipStream_t stream);
 // H x W picture as planar fp16 [3][H][W] in 0..255 (the distortion planes) and / or packed u8 HWC (rint of those, the
 // writer's pixels). Null outputs are skipped.
 void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, hipStream_t stream);
+void rgb_validate(int H, int W, const char* what);      // throws std::invalid_argument: sides not positive and even, or too large
+// ---------------------------------------------------------------- RGB pictures, other matrices and ranges (rgb_cs.hip)
+// rgb_to_x / x_to_rgb with the colour matrix (DCVC_MATRIX_*) and range (DCVC_RANGE_*) chosen; yuv_bit_depth (8..16) is the
+// depth b of the YUV samples x stands for (x = v / (2^b - 1) - 0.5), which places the limited-range levels. Layouts, null
+// rules and refusals are those of the two functions above; BT.709 / full range gives their bits.
+constexpr int kMatrixBt601 = 0, kMatrixBt709 = 1, kMatrixBt2020 = 2;
+constexpr int kRangeFull = 0, kRangeLimited = 1;
+struct ColourSpace {
+    int matrix = kMatrixBt709, range = kRangeFull, yuv_bit_depth = 8;
+};
+void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream);
+void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream);
 // metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8, fp16, u16 or fp32 samples; src and rec share
 // row_stride and plane_stride, in samples) -> out[plane] (device). Per-workgroup partials in the workspace
 // (sse_workspace_bytes), reduced by a second launch in a fixed order.

@@ -1,0 +1,319 @@
+// rgb_cs.hip - 8-bit RGB pictures <-> the codec's fp16 NHWC picture tensor with a chosen colour matrix (BT.601, BT.709,
+// BT.2020 non-constant luminance) and range (full, or limited: Y 16..235, C 16..240 scaled to the YUV bit depth).
+//
+// No reference counterpart beyond BT.709 / full range, which is rgb_io.hip's conversion (transforms.py:17-27, 53-66) and
+// which these kernels reproduce bit for bit: the op sequences are rgb_io.hip's with the matrix constants as arguments and,
+// in limited range, one multiply and one add (to x) or one subtract and one multiply (to RGB) per channel between the
+// matrix and the fp16 rounding. DESIGN.md 20 has the definition; tests/colour_np.py restates it in numpy.
+//
+// Every step is one fp32 operation (the library builds with -ffp-contract=off: no v_fma) and every constant is the fp32
+// value of a double expression, computed on the host (colour_consts) and passed by value in the kernel argument: the
+// constants are wave-uniform and sit in SGPRs. The range is a template switch, so the full-range kernels hold no extra
+// operation. Layout and access modes are rgb_io.hip's: one thread per 8 pixels of a row, 8- / 16-byte accesses where the
+// layout allows them, element accesses elsewhere.
+#include "arith.h"
+#include "ops.h"
+
+namespace dcvc {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr float kInv255 = 1.0f / 255.0f;                              // x.float() / 255.0
+
+// what the two kernels read: the matrix (8 values) and the limited-range levels (6 values; unused in full range)
+struct ColourConsts {
+    float kr, kg, kb;               // fp32(Kr), fp32(Kg), fp32(Kb)
+    float inv_1mkb, inv_1mkr;       // 1.0f / fp32(1 - Kb), 1.0f / fp32(1 - Kr)
+    float inv_kg;                   // 1.0f / fp32(Kg)
+    float c2m2kr, c2m2kb;           // fp32(2 - 2 Kr), fp32(2 - 2 Kb)
+    float lo, ry, mid, rc;          // fp32(16 s / m), fp32(219 s / m), fp32(128 s / m), fp32(224 s / m)
+    float iy, ic;                   // fp32(m / (219 s)), fp32(m / (224 s))
+};
+
+ColourConsts colour_consts(const ColourSpace& cs)
+{
+    static const double kK[3][3] = {{0.299, 0.587, 0.114}, {0.2126, 0.7152, 0.0722}, {0.2627, 0.6780, 0.0593}};
+    const double Kr = kK[cs.matrix][0], Kg = kK[cs.matrix][1], Kb = kK[cs.matrix][2];
+    ColourConsts c;
+    c.kr = static_cast<float>(Kr); c.kg = static_cast<float>(Kg); c.kb = static_cast<float>(Kb);
+    c.inv_1mkb = 1.0f / static_cast<float>(1.0 - Kb);
+    c.inv_1mkr = 1.0f / static_cast<float>(1.0 - Kr);
+    c.inv_kg = 1.0f / c.kg;
+    c.c2m2kr = static_cast<float>(2 - 2 * Kr); c.c2m2kb = static_cast<float>(2 - 2 * Kb);
+    // the levels of b-bit samples on x's scale v / (2^b - 1): one division in double each, then fp32
+    const double s = static_cast<double>(1 << (cs.yuv_bit_depth - 8)), m = static_cast<double>((1 << cs.yuv_bit_depth) - 1);
+    c.lo = static_cast<float>(16 * s / m); c.ry = static_cast<float>(219 * s / m);
+    c.mid = static_cast<float>(128 * s / m); c.rc = static_cast<float>(224 * s / m);
+    c.iy = static_cast<float>(m / (219 * s)); c.ic = static_cast<float>(m / (224 * s));
+    return c;
+}
+
+// torch.clamp: NaN passes through
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// one RGB pixel -> the three fp16 channels of x
+template <bool LIMITED>
+__device__ __forceinline__ void pixel_to_x(const ColourConsts& k, unsigned r8, unsigned g8, unsigned b8, half_t* o)
+{
+    const float r = static_cast<float>(r8) * kInv255, g = static_cast<float>(g8) * kInv255, b = static_cast<float>(b8) * kInv255;
+    float y = (k.kr * r + k.kg * g) + k.kb * b;
+    const float pb = (0.5f * (b - y)) * k.inv_1mkb;
+    const float pr = (0.5f * (r - y)) * k.inv_1mkr;
+    float cb, cr;
+    if constexpr (LIMITED) {
+        y = y * k.ry + k.lo;
+        cb = pb * k.rc + k.mid;
+        cr = pr * k.rc + k.mid;
+    } else {
+        cb = pb + 0.5f;
+        cr = pr + 0.5f;
+    }
+    o[0] = to_half(static_cast<float>(to_half(clampf(y, 0.f, 1.f))) - 0.5f);
+    o[1] = to_half(static_cast<float>(to_half(clampf(cb, 0.f, 1.f))) - 0.5f);
+    o[2] = to_half(static_cast<float>(to_half(clampf(cr, 0.f, 1.f))) - 0.5f);
+}
+
+// load modes of rgb_to_x_cs
+constexpr int kLoadScalar = 0, kLoadPacked = 1, kLoadPlanar = 2;
+
+// one thread = 8 consecutive pixels of a row. LOAD: kLoadPacked (pixel stride 3, channel stride 1: 3 x 8-B loads),
+// kLoadPlanar (pixel stride 1: one 8-B load per channel) or kLoadScalar (any strides). VEC_X: x at ldx == 3, 3 x 16-B
+// stores. Vector modes need W % 8 == 0 and aligned rows (checked by the host).
+template <int LOAD, bool VEC_X, bool LIMITED>
+__global__ void __launch_bounds__(kThreads) rgb_to_x_cs_kernel(const uint8_t* __restrict__ src, long long rs, long long ps,
+                                                               long long cs, int H, int W, half_t* __restrict__ x, int ldx,
+                                                               uint8_t* __restrict__ planar, const ColourConsts k)
+{
+    const unsigned wv = (W + 7) >> 3;
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (rgb_validate)
+    if (i >= static_cast<unsigned>(H) * wv) return;
+    const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
+    const int n = min(8, W - w0);
+    const uint8_t* row = src + h * rs + w0 * ps;
+    uint8_t c[3][8];
+    if constexpr (LOAD == kLoadPacked) {
+        uint2 v[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) v[q] = reinterpret_cast<const uint2*>(row)[q];
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) c[q][e] = bytes[3 * e + q];
+    } else if constexpr (LOAD == kLoadPlanar) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint2 v = *reinterpret_cast<const uint2*>(row + q * cs);
+            const uint8_t* bytes = reinterpret_cast<const uint8_t*>(&v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) c[q][e] = bytes[e];
+        }
+    } else {
+        for (int e = 0; e < 8; ++e)
+            for (int q = 0; q < 3; ++q) c[q][e] = e < n ? row[e * ps + q * cs] : 0;
+    }
+    if (planar) {
+        const size_t plane = static_cast<size_t>(H) * W, o = static_cast<size_t>(h) * W + w0;
+        if constexpr (LOAD != kLoadScalar) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint2*>(planar + q * plane + o) = *reinterpret_cast<const uint2*>(c[q]);
+        } else {
+            for (int e = 0; e < n; ++e)
+                for (int q = 0; q < 3; ++q) planar[q * plane + o + e] = c[q][e];
+        }
+    }
+    if (x) {
+        half_t* o = x + (static_cast<size_t>(h) * W + w0) * ldx;
+        if constexpr (VEC_X) {
+            half8 v[3];
+            half_t* hv = reinterpret_cast<half_t*>(v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) pixel_to_x<LIMITED>(k, c[0][e], c[1][e], c[2][e], hv + 3 * e);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) reinterpret_cast<half8*>(o)[q] = v[q];
+        } else {
+            for (int e = 0; e < n; ++e) pixel_to_x<LIMITED>(k, c[0][e], c[1][e], c[2][e], o + e * ldx);
+        }
+    }
+}
+
+// one pixel of x_hat -> the three fp16 distortion samples (0..255)
+template <bool LIMITED>
+__device__ __forceinline__ void x_to_pixel(const ColourConsts& k, const half_t* p, half_t* o)
+{
+    float y = static_cast<float>(to_half(static_cast<float>(p[0]) + 0.5f));              // x_hat + 0.5 (fp16)
+    const float cb = static_cast<float>(to_half(static_cast<float>(p[1]) + 0.5f));
+    const float cr = static_cast<float>(to_half(static_cast<float>(p[2]) + 0.5f));
+    float pb, pr;
+    if constexpr (LIMITED) {
+        y = (y - k.lo) * k.iy;
+        pb = (cb - k.mid) * k.ic;
+        pr = (cr - k.mid) * k.ic;
+    } else {
+        pb = cb - 0.5f;
+        pr = cr - 0.5f;
+    }
+    const float r = y + k.c2m2kr * pr;
+    const float b = y + k.c2m2kb * pb;
+    const float g = ((y - k.kr * r) - k.kb * b) * k.inv_kg;
+    const float rgb[3] = {r, g, b};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const half_t t = to_half(clampf(rgb[q], 0.f, 1.f));                                  // .to(fp16)
+        const float s = static_cast<float>(to_half(static_cast<float>(t) * 255.0f));           // * 255 (fp16)
+        o[q] = to_half(clampf(s, 0.f, 255.f));                                                  // clamp(0, 255), exact
+    }
+}
+
+// .round().byte(): half to even (the samples are in 0..255; NaN, which no clamp removes, is written as 0)
+__device__ __forceinline__ uint8_t to_u8(half_t v)
+{
+    const float f = static_cast<float>(v);
+    return f == f ? static_cast<uint8_t>(rintf(f)) : 0;
+}
+
+// one thread = 8 consecutive pixels of a row. VEC: row_pixels % 8 == 0, W % 8 == 0, aligned bases: 3 x 16-B loads,
+// one 16-B store per fp16 plane, 3 x 8-B stores of packed u8.
+template <bool VEC, bool LIMITED>
+__global__ void __launch_bounds__(kThreads) x_to_rgb_cs_kernel(const half_t* __restrict__ x, int row_pixels, int H, int W,
+                                                               half_t* __restrict__ rgb16, uint8_t* __restrict__ rgb8,
+                                                               const ColourConsts k)
+{
+    const unsigned wv = (W + 7) >> 3;
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (rgb_validate)
+    if (i >= static_cast<unsigned>(H) * wv) return;
+    const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
+    const int n = min(8, W - w0);
+    const half_t* p = x + (static_cast<size_t>(h) * row_pixels + w0) * 3;
+    const size_t plane = static_cast<size_t>(H) * W, o = static_cast<size_t>(h) * W + w0;
+    if constexpr (VEC) {
+        half8 in[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) in[q] = reinterpret_cast<const half8*>(p)[q];
+        const half_t* hin = reinterpret_cast<const half_t*>(in);
+        half8 out[3];
+        half_t* ho = reinterpret_cast<half_t*>(out);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            half_t t[3];
+            x_to_pixel<LIMITED>(k, hin + 3 * e, t);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) ho[q * 8 + e] = t[q];
+        }
+        if (rgb16) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<half8*>(rgb16 + q * plane + o) = out[q];
+        }
+        if (rgb8) {
+            uint8_t b[24];
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) b[3 * e + q] = to_u8(ho[q * 8 + e]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) reinterpret_cast<uint2*>(rgb8 + o * 3)[q] = reinterpret_cast<const uint2*>(b)[q];
+        }
+    } else {
+        for (int e = 0; e < n; ++e) {
+            half_t t[3];
+            x_to_pixel<LIMITED>(k, p + 3 * e, t);
+            for (int q = 0; q < 3; ++q) {
+                if (rgb16) rgb16[q * plane + o + e] = t[q];
+                if (rgb8) rgb8[(o + e) * 3 + q] = to_u8(t[q]);
+            }
+        }
+    }
+}
+
+bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+unsigned grid_of(int H, int W)
+{
+    const long long n = static_cast<long long>(H) * ((W + 7) / 8);
+    return static_cast<unsigned>((n + kThreads - 1) / kThreads);
+}
+
+void colour_validate(const ColourSpace& cs, const char* what)
+{
+    if (cs.matrix != kMatrixBt601 && cs.matrix != kMatrixBt709 && cs.matrix != kMatrixBt2020) {
+        throw std::invalid_argument(std::string(what) + ": unknown colour matrix " + std::to_string(cs.matrix));
+    }
+    if (cs.range != kRangeFull && cs.range != kRangeLimited) {
+        throw std::invalid_argument(std::string(what) + ": unknown colour range " + std::to_string(cs.range));
+    }
+    if (cs.yuv_bit_depth < 8 || cs.yuv_bit_depth > 16) {
+        throw std::invalid_argument(std::string(what) + ": the YUV bit depth must be in 8..16, got " + std::to_string(cs.yuv_bit_depth));
+    }
+}
+
+template <int LOAD, bool VEC_X>
+void launch_to_x(const RgbToXDesc& d, bool limited, const ColourConsts& k, hipStream_t stream)
+{
+    const dim3 grid(grid_of(d.H, d.W)), block(kThreads);
+    if (limited) {
+        hipLaunchKernelGGL((rgb_to_x_cs_kernel<LOAD, VEC_X, true>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+                           d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k);
+    } else {
+        hipLaunchKernelGGL((rgb_to_x_cs_kernel<LOAD, VEC_X, false>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+                           d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k);
+    }
+}
+
+}  // namespace
+
+void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream)
+{
+    rgb_validate(d.H, d.W, "rgb_to_x_cs");
+    colour_validate(cs, "rgb_to_x_cs");
+    if (d.src == nullptr) throw std::invalid_argument("rgb_to_x_cs: no source picture");
+    if (d.x == nullptr && d.planar == nullptr) throw std::invalid_argument("rgb_to_x_cs: neither x nor the planar copy requested");
+    if (d.x != nullptr && d.ldx < 3) throw std::invalid_argument("rgb_to_x_cs: the pixel stride of x must be >= 3");
+    // the three (stride, extent) pairs must not overlap: sorted by stride, each stride covers the previous dimension
+    long long st[3] = {d.channel_stride, d.pixel_stride, d.row_stride}, ex[3] = {3, d.W, d.H};
+    for (int q = 0; q < 3; ++q) {
+        if (st[q] <= 0) throw std::invalid_argument("rgb_to_x_cs: the source strides must be positive");
+    }
+    for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b)
+            if (st[b] < st[a]) { std::swap(st[a], st[b]); std::swap(ex[a], ex[b]); }
+    if (st[1] < st[0] * ex[0] || st[2] < st[1] * ex[1]) {
+        throw std::invalid_argument("rgb_to_x_cs: source strides too small (row " + std::to_string(d.row_stride) + ", pixel " +
+                                    std::to_string(d.pixel_stride) + ", channel " + std::to_string(d.channel_stride) +
+                                    " for " + std::to_string(d.W) + "x" + std::to_string(d.H) + ")");
+    }
+    const bool rows8 = d.W % 8 == 0 && d.row_stride % 8 == 0 && aligned(d.src, 8) && (d.planar == nullptr || aligned(d.planar, 8));
+    int load = kLoadScalar;
+    if (rows8 && d.pixel_stride == 3 && d.channel_stride == 1) load = kLoadPacked;
+    else if (rows8 && d.pixel_stride == 1 && d.channel_stride % 8 == 0) load = kLoadPlanar;
+    const bool vec_x = d.x != nullptr && load != kLoadScalar && d.ldx == 3 && aligned(d.x, 16);
+    const bool limited = cs.range == kRangeLimited;
+    const ColourConsts k = colour_consts(cs);
+    if (load == kLoadPacked && vec_x) launch_to_x<kLoadPacked, true>(d, limited, k, stream);
+    else if (load == kLoadPacked) launch_to_x<kLoadPacked, false>(d, limited, k, stream);
+    else if (load == kLoadPlanar && vec_x) launch_to_x<kLoadPlanar, true>(d, limited, k, stream);
+    else if (load == kLoadPlanar) launch_to_x<kLoadPlanar, false>(d, limited, k, stream);
+    else launch_to_x<kLoadScalar, false>(d, limited, k, stream);
+    hip_check(hipGetLastError(), "rgb_to_x_cs launch");
+}
+
+void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream)
+{
+    rgb_validate(H, W, "x_to_rgb_cs");
+    colour_validate(cs, "x_to_rgb_cs");
+    if (x == nullptr) throw std::invalid_argument("x_to_rgb_cs: no x_hat");
+    if (row_pixels < W) throw std::invalid_argument("x_to_rgb_cs: the rows of x_hat are shorter than the picture");
+    const bool vec = row_pixels % 8 == 0 && W % 8 == 0 && aligned(x, 16) && (rgb16 == nullptr || aligned(rgb16, 16)) &&
+                     (rgb8 == nullptr || aligned(rgb8, 8));
+    if (rgb16 == nullptr && rgb8 == nullptr) return;
+    const bool limited = cs.range == kRangeLimited;
+    const ColourConsts k = colour_consts(cs);
+    const dim3 grid(grid_of(H, W)), block(kThreads);
+    if (vec && limited) hipLaunchKernelGGL((x_to_rgb_cs_kernel<true, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else if (vec) hipLaunchKernelGGL((x_to_rgb_cs_kernel<true, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else if (limited) hipLaunchKernelGGL((x_to_rgb_cs_kernel<false, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else hipLaunchKernelGGL((x_to_rgb_cs_kernel<false, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    hip_check(hipGetLastError(), "x_to_rgb_cs launch");
+}
+
+}  // namespace dcvc

@@ -4,6 +4,7 @@
 Thin wrappers over the C-ABI entry points ``dcvc_rgb_to_x``, ``dcvc_x_to_rgb``, ``dcvc_sse`` (include/dcvc_amd_ops.h) and
 ``dcvc_png_*`` (include/dcvc_amd_image.h). Device operands are CUDA tensors; the kernels run on ``torch.cuda.current_stream()``.
 The arithmetic is that of the reference's torch ops on a GPU, where a tensor divided by a scalar is a * fp32(1 / b).
+``rgb_to_x`` / ``x_to_rgb`` with another colour matrix or range go through ``dcvc_rgb_to_x_cs`` / ``dcvc_x_to_rgb_cs``.
 """
 import ctypes
 import os
@@ -15,12 +16,16 @@ from . import _lib
 
 DCVC_SAMPLE_U8 = 0
 DCVC_SAMPLE_F16 = 1
+MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}      # DCVC_MATRIX_*
+RANGES = {"full": 0, "limited": 1}                    # DCVC_RANGE_*
 
 _vp, _ci, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 _fns = {}
 _SIGS = {
     "dcvc_rgb_to_x": [_vp, _ll, _ll, _ll, _ci, _ci, _vp, _ci, _vp, _vp],
     "dcvc_x_to_rgb": [_vp, _ci, _ci, _ci, _vp, _vp, _vp],
+    "dcvc_rgb_to_x_cs": [_vp, _ll, _ll, _ll, _ci, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _vp],
+    "dcvc_x_to_rgb_cs": [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _vp],
     "dcvc_sse": [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ll, _vp, _vp],
     "dcvc_png_info": [ctypes.c_char_p, ctypes.POINTER(_ci), ctypes.POINTER(_ci)],
     "dcvc_png_read_rgb": [ctypes.c_char_p, _vp, ctypes.c_size_t, ctypes.POINTER(_ci), ctypes.POINTER(_ci)],
@@ -54,12 +59,26 @@ def _u8_picture(rgb):
     raise ValueError("rgb: a uint8 CUDA tensor [3, H, W] or [H, W, 3] expected, got %s" % (tuple(rgb.shape),))
 
 
-def rgb_to_x(rgb, ldx=3, x=None, planar=False):
+def _colour(matrix, range, yuv_depth):
+    """None for the reference's conversion (bt709, full, 8: the entry points without _cs), else the three codes"""
+    if matrix not in MATRICES:
+        raise ValueError("unknown matrix %r (bt601, bt709 or bt2020)" % (matrix,))
+    if range not in RANGES:
+        raise ValueError("unknown range %r (full or limited)" % (range,))
+    if (matrix, range, yuv_depth) == ("bt709", "full", 8):
+        return None
+    return MATRICES[matrix], RANGES[range], int(yuv_depth)
+
+
+def rgb_to_x(rgb, ldx=3, x=None, planar=False, matrix="bt709", range="full", yuv_depth=8):
     """get_src_frame's model input of one RGB picture: [H, W, 3] fp16 (NHWC, x = rgb2ycbcr(rgb / 255).half() - 0.5).
     rgb: uint8 CUDA tensor [3, H, W] or [H, W, 3] (any strides). With ``x`` given, writes into it at pixel stride ``ldx``
     (a flat fp16 tensor view starting at the picture's first channel, e.g. a chunk slot) instead. planar=True also returns a
-    [3, H, W] uint8 copy of the source: (x, planar)."""
+    [3, H, W] uint8 copy of the source: (x, planar). matrix ("bt601", "bt709", "bt2020"), range ("full", "limited") and
+    yuv_depth (8..16, the depth of the YUV samples x stands for, which places the limited-range levels) choose the
+    conversion (dcvc_rgb_to_x_cs); the defaults are the reference's and call dcvc_rgb_to_x."""
     import torch
+    colour = _colour(matrix, range, yuv_depth)
     H, W, rs, ps, cs = _u8_picture(rgb)
     if x is None:
         if ldx != 3:
@@ -68,15 +87,20 @@ def rgb_to_x(rgb, ldx=3, x=None, planar=False):
     elif x.dtype != torch.float16 or not x.is_cuda or x.numel() < (H * W - 1) * ldx + 3:
         raise ValueError("rgb_to_x: x must be a CUDA float16 tensor of at least (H W - 1) ldx + 3 elements")
     pl = torch.empty((3, H, W), dtype=torch.uint8, device=rgb.device) if planar else None
-    _lib.check(_fn("dcvc_rgb_to_x")(_vp(rgb.data_ptr()), rs, ps, cs, H, W, _vp(x.data_ptr()), ldx,
-                                    _vp(pl.data_ptr()) if pl is not None else None, _stream(rgb)))
+    args = (_vp(rgb.data_ptr()), rs, ps, cs, H, W, _vp(x.data_ptr()), ldx, _vp(pl.data_ptr()) if pl is not None else None)
+    if colour is None:
+        _lib.check(_fn("dcvc_rgb_to_x")(*args, _stream(rgb)))
+    else:
+        _lib.check(_fn("dcvc_rgb_to_x_cs")(*args, *colour, _stream(rgb)))
     return (x, pl) if planar else x
 
 
-def x_to_rgb(x_hat, H, W):
+def x_to_rgb(x_hat, H, W, matrix="bt709", range="full", yuv_depth=8):
     """get_distortion's RGB planes and the writer's pixels of a decoded picture. x_hat: fp16 CUDA tensor [1, 3, Hp, Wp]
-    (channels_last) or [Hp, Wp, 3], Hp >= H, Wp >= W. Returns (rgb16 [3, H, W] fp16 in 0..255, rgb8 [H, W, 3] uint8)."""
+    (channels_last) or [Hp, Wp, 3], Hp >= H, Wp >= W. Returns (rgb16 [3, H, W] fp16 in 0..255, rgb8 [H, W, 3] uint8).
+    matrix, range and yuv_depth as for rgb_to_x (dcvc_x_to_rgb_cs; the defaults call dcvc_x_to_rgb)."""
     import torch
+    colour = _colour(matrix, range, yuv_depth)
     if x_hat.dim() == 4:
         x_hat = x_hat[0].permute(1, 2, 0)
     if x_hat.dtype != torch.float16 or not x_hat.is_cuda or x_hat.dim() != 3 or x_hat.shape[2] != 3:
@@ -86,8 +110,11 @@ def x_to_rgb(x_hat, H, W):
         raise ValueError("x_to_rgb: x_hat (%d x %d) is smaller than the picture (%d x %d)" % (x_hat.shape[1], x_hat.shape[0], W, H))
     rgb16 = torch.empty((3, H, W), dtype=torch.float16, device=x_hat.device)
     rgb8 = torch.empty((H, W, 3), dtype=torch.uint8, device=x_hat.device)
-    _lib.check(_fn("dcvc_x_to_rgb")(_vp(x_hat.data_ptr()), x_hat.shape[1], H, W, _vp(rgb16.data_ptr()), _vp(rgb8.data_ptr()),
-                                    _stream(x_hat)))
+    args = (_vp(x_hat.data_ptr()), x_hat.shape[1], H, W, _vp(rgb16.data_ptr()), _vp(rgb8.data_ptr()))
+    if colour is None:
+        _lib.check(_fn("dcvc_x_to_rgb")(*args, _stream(x_hat)))
+    else:
+        _lib.check(_fn("dcvc_x_to_rgb_cs")(*args, *colour, _stream(x_hat)))
     return rgb16, rgb8
 
 
@@ -187,4 +214,4 @@ def png_sequence(directory, start=1):
 
 
 __all__ = ["rgb_to_x", "x_to_rgb", "sse", "psnr_rgb", "psnr_from_sse", "png_info", "read_png", "write_png", "png_naming",
-           "png_sequence", "DCVC_SAMPLE_U8", "DCVC_SAMPLE_F16"]
+           "png_sequence", "DCVC_SAMPLE_U8", "DCVC_SAMPLE_F16", "MATRICES", "RANGES"]

@@ -277,6 +277,35 @@ int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride,
  *   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture; rgb16: fp16 [3][H][W] = clamp(fp16(clamp(rgb, 0, 1)) * 255,
  *   0, 255), the distortion planes; rgb8: packed u8 [H][W][3] = rint(rgb16) (half to even). NULL = skip. */
 int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8, void* stream);
+/* dcvc_rgb_to_x / dcvc_x_to_rgb with the colour matrix and the range chosen (no reference counterpart beyond BT.709 / full
+ * range). Layouts, NULL rules, the stride rules and stream order are those of the two entry points above. */
+#define DCVC_MATRIX_BT601  0   /* Kr, Kg, Kb = 0.299,  0.587,  0.114  */
+#define DCVC_MATRIX_BT709  1   /*              0.2126, 0.7152, 0.0722 */
+#define DCVC_MATRIX_BT2020 2   /*              0.2627, 0.6780, 0.0593 (non-constant luminance) */
+#define DCVC_RANGE_FULL    0
+#define DCVC_RANGE_LIMITED 1
+/* yuv_bit_depth (8..16) is the depth b of the YUV samples that x stands for: x = v / (2^b - 1) - 0.5, so the limited-range
+ * levels (Y 16..235, C 16..240 at 8 bits, times s = 2^(b-8)) sit on x's scale at, with m = 2^b - 1,
+ *   lo = 16 s / m, ry = 219 s / m, mid = 128 s / m, rc = 224 s / m, iy = m / (219 s), ic = m / (224 s),
+ * each one division in double, then fp32. Full range ignores the depth (it is checked all the same). Every step below is
+ * one fp32 operation and every constant the fp32 value of the double expression written:
+ *   r, g, b = u8 * (1.0f / 255.0f);  y = (Kr r + Kg g) + Kb b
+ *   pb = (0.5 (b - y)) * (1.0f / fp32(1 - Kb));  pr = (0.5 (r - y)) * (1.0f / fp32(1 - Kr))
+ *   full: Y = y, Cb = pb + 0.5, Cr = pr + 0.5;  limited: Y = y * ry + lo, Cb = pb * rc + mid, Cr = pr * rc + mid
+ *   x_k = fp16(fp32(fp16(clamp(., 0, 1))) - 0.5)
+ * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_rgb_to_x's sequence and gives its bits. Refused before any launch:
+ * an unknown matrix or range, a depth outside 8..16, and everything dcvc_rgb_to_x refuses. */
+int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H, int W,
+                     void* x, int ldx, void* planar, int matrix, int range, int yuv_bit_depth, void* stream);
+/* The inverse, with the same constants:
+ *   Y, Cb, Cr = fp32(fp16(fp32(x_k) + 0.5))
+ *   full: y = Y, pb = Cb - 0.5, pr = Cr - 0.5;  limited: y = (Y - lo) * iy, pb = (Cb - mid) * ic, pr = (Cr - mid) * ic
+ *   r = y + fp32(2 - 2 Kr) * pr;  b = y + fp32(2 - 2 Kb) * pb;  g = ((y - Kr r) - Kb b) * (1.0f / fp32(Kg))
+ *   rgb16_k = clamp(fp16(fp32(fp16(clamp(., 0, 1))) * 255), 0, 255);  rgb8 = rint(rgb16) (half to even), NaN -> 0
+ * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_x_to_rgb's sequence and gives its bits. Over all 2^24 colours
+ * dcvc_x_to_rgb_cs(dcvc_rgb_to_x_cs(c)) = c for every matrix, in full range and in limited range at every depth. */
+int dcvc_x_to_rgb_cs(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8,
+                     int matrix, int range, int yuv_bit_depth, void* stream);
 /* metrics.py:10-24 calc_psnr's fp64 sum of squared differences, one value per plane: n_planes planes of H x W samples (u8,
  * fp16, u16 or fp32; DCVC_SAMPLE_*), src and rec sharing the geometry (row_stride, plane_stride in samples). out: device memory, n_planes
  * doubles, written asynchronously on `stream`. Per-workgroup partials reduced in a fixed order: the same bits on every run and

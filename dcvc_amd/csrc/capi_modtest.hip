@@ -271,16 +271,18 @@ int dcvc_modtest_block_forward(dcvc_modtest* h, int module, int index, void* x, 
         if (b == nullptr) throw std::invalid_argument("modtest: block_forward needs a block");
         FinCall fin;
         const bool has_fin = make_fin(h, fin_module, fin_q, fin_y, fin_ldy, keep_block_output, &fin);
-        b->forward(V(x, ldx, cx), V(y, ldy, cy), Hh, W, h->s, S(stream), shortcut != 0, H(q_fused), H(q_after),
-                   V(alt, ldalt, calt), h->block(next_module, next_index), dc0_done != 0, has_fin ? &fin : nullptr);
+        dcvc::DcbCall c;
+        c.shortcut = shortcut != 0; c.q_fused = H(q_fused); c.q_after = H(q_after); c.alt = V(alt, ldalt, calt);
+        c.next = h->block(next_module, next_index); c.dc0_done = dc0_done != 0; c.fin = has_fin ? &fin : nullptr;
+        b->forward(V(x, ldx, cx), V(y, ldy, cy), Hh, W, h->s, S(stream), c);
     });
 }
 
-int dcvc_modtest_chain_forward(dcvc_modtest* h, int module, int first, int n, void* x, int ldx, int cx,
-                               void* tmp, int ldtmp, int ctmp, void* y, int ldy, int cy, int Hh, int W,
-                               const void* q_fused_last, void* tmp2, int ldtmp2, int ctmp2,
-                               int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output,
-                               int after_module, int after_index, int first_dc0_done, void* stream)
+int dcvc_modtest_chain_forward_qa(dcvc_modtest* h, int module, int first, int n, void* x, int ldx, int cx,
+                                  void* tmp, int ldtmp, int ctmp, void* y, int ldy, int cy, int Hh, int W,
+                                  const void* q_fused_last, const void* q_after_last, void* tmp2, int ldtmp2, int ctmp2,
+                                  int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output,
+                                  int after_module, int after_index, int first_dc0_done, void* stream)
 {
     return dcvc::guarded([&] {
         dcvc_modtest::Module& m = h->module(module);
@@ -291,15 +293,26 @@ int dcvc_modtest_chain_forward(dcvc_modtest* h, int module, int first, int n, vo
         if (first < 0 || count < 1 || first + count > total) throw std::invalid_argument("modtest: no such range of blocks");
         FinCall fin;
         const bool has_fin = make_fin(h, fin_module, fin_q, fin_y, fin_ldy, keep_block_output, &fin);
-        const DcbW* after = h->block(after_module, after_index);
-        if (m.kind == dcvc_modtest::kChain && first == 0 && count == total && after == nullptr && first_dc0_done == 0) {
-            m.chain.forward(V(x, ldx, cx), V(tmp, ldtmp, ctmp), V(y, ldy, cy), Hh, W, h->s, S(stream), H(q_fused_last),
-                            V(tmp2, ldtmp2, ctmp2), has_fin ? &fin : nullptr);
+        dcvc::ChainCall c;
+        c.q_fused_last = H(q_fused_last); c.q_after_last = H(q_after_last); c.tmp2 = V(tmp2, ldtmp2, ctmp2);
+        c.fin = has_fin ? &fin : nullptr; c.after = h->block(after_module, after_index); c.first_dc0_done = first_dc0_done != 0;
+        if (m.kind == dcvc_modtest::kChain && first == 0 && count == total) {
+            m.chain.forward(V(x, ldx, cx), V(tmp, ldtmp, ctmp), V(y, ldy, cy), Hh, W, h->s, S(stream), c);
             return;
         }
-        dcvc::run_dcb_chain(a->data() + first, count, V(x, ldx, cx), V(tmp, ldtmp, ctmp), V(y, ldy, cy), Hh, W, h->s, S(stream),
-                            H(q_fused_last), V(tmp2, ldtmp2, ctmp2), has_fin ? &fin : nullptr, after, first_dc0_done != 0);
+        dcvc::run_dcb_chain(a->data() + first, count, V(x, ldx, cx), V(tmp, ldtmp, ctmp), V(y, ldy, cy), Hh, W, h->s, S(stream), c);
     });
+}
+
+int dcvc_modtest_chain_forward(dcvc_modtest* h, int module, int first, int n, void* x, int ldx, int cx,
+                               void* tmp, int ldtmp, int ctmp, void* y, int ldy, int cy, int Hh, int W,
+                               const void* q_fused_last, void* tmp2, int ldtmp2, int ctmp2,
+                               int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output,
+                               int after_module, int after_index, int first_dc0_done, void* stream)
+{
+    return dcvc_modtest_chain_forward_qa(h, module, first, n, x, ldx, cx, tmp, ldtmp, ctmp, y, ldy, cy, Hh, W, q_fused_last, nullptr,
+                                         tmp2, ldtmp2, ctmp2, fin_module, fin_q, fin_y, fin_ldy, keep_block_output, after_module,
+                                         after_index, first_dc0_done, stream);
 }
 
 int dcvc_modtest_stride2_forward(dcvc_modtest* h, int module, void* x, int ldx, int cx, void* tmp, int ldtmp, int ctmp,

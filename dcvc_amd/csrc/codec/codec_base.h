@@ -106,15 +106,15 @@ protected:
     };
     static void copy_qp_rows(std::initializer_list<QpRow> rows, int qp, hipStream_t st);
 
-    // Size probe of the inter codecs. set_param: what the coder spends on every symbol under this model's
-    // CDFs (rans/code_length.h), on the device. probe_code_length: behind the encoder's first stage, the code length of
-    // the compacted y symbols (`count` at most, the `n_totals` device totals say how many) and of the z rows of `qp`,
-    // summed on the device; ONE small copy to the host, and the call blocks for it. units = {y, z} in 2^-16 bit.
-    // DmciCodec (dmci.hip, set_param / estimate_bits) keeps a private copy of this table setup and sums buffer, which its
-    // batched probe indexes per picture: a change to the tables or the sums layout goes into both until DMCI moves here.
-    void upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z);
-    void probe_code_length(const int16_t* comp, int count, const int32_t* totals, int n_totals, const int8_t* z, int nz,
-                           int qp, int64_t units[2], int64_t* kept, hipStream_t st);
+    // Size probe. set_param: what the coder spends on every symbol under this model's CDFs
+    // (rans/code_length.h), on the device, and the sums of a probe of at most max_n pictures, [max_n][3] = {y units, y symbols,
+    // z units}. probe_code_length: behind the encoder's first stage, for each of n pictures the code length of its compacted
+    // y symbols (picture b's at comp + b * comp_stride, `count` at most, its `n_totals` device totals say how many) and of
+    // its nz z values under the rows of `qp`, summed on the device; ONE small copy to the host, and the call blocks for it.
+    // Picture b: units[2 b] = y, units[2 b + 1] = z, in 2^-16 bit; kept[b] = y symbols counted (kept may be null).
+    void upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z, int max_n);
+    void probe_code_length(int n, const int16_t* comp, long long comp_stride, int count, const int32_t* totals, int n_totals,
+                           const int8_t* z, int nz, int qp, int64_t* units, int64_t* kept, hipStream_t st);
 
     RansEncoder m_enc;
     RansDecoder m_dec;
@@ -125,8 +125,8 @@ protected:
 
 private:
     const uint32_t *m_cl_y = nullptr, *m_cl_z = nullptr;
-    int m_cl_y_num = 0, m_cl_z_num = 0, m_cl_ch_z = 0;
-    unsigned long long* m_cl_sums = nullptr;      // y units, y symbols, z units
+    int m_cl_y_num = 0, m_cl_z_num = 0, m_cl_ch_z = 0, m_cl_max_n = 0;
+    unsigned long long* m_cl_sums = nullptr;      // [m_cl_max_n][3]
     Pinned<unsigned long long> m_h_cl;
 
     void worker_loop();

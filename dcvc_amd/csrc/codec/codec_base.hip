@@ -190,7 +190,7 @@ void CodecBase::load_cdf_tables(const ParamStore& ps)
     cdf("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", 1);
 }
 
-void CodecBase::upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z)
+void CodecBase::upload_code_length_tables(const ParamStore& ps, DeviceArena& mem, int ch_z, int max_n)
 {
     auto upload = [&](const char* name_cdf, const char* name_len, int cols, int& num) {
         const HostTensor& c = ps.at(name_cdf);
@@ -206,33 +206,37 @@ void CodecBase::upload_code_length_tables(const ParamStore& ps, DeviceArena& mem
     m_cl_y = upload("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", kCodeLengthYCols, m_cl_y_num);
     if (m_cl_y_num > 256) throw std::invalid_argument("more than 256 Gaussian CDFs");
     m_cl_ch_z = ch_z;
-    m_cl_sums = static_cast<unsigned long long*>(mem.alloc(sizeof(unsigned long long) * 3));
-    m_h_cl.reserve(3);
+    m_cl_max_n = max_n;
+    m_cl_sums = static_cast<unsigned long long*>(mem.alloc(sizeof(unsigned long long) * 3 * max_n));
+    m_h_cl.reserve(3 * static_cast<size_t>(max_n));
 }
 
-void CodecBase::probe_code_length(const int16_t* comp, int count, const int32_t* totals, int n_totals, const int8_t* z, int nz,
-                                  int qp, int64_t units[2], int64_t* kept, hipStream_t st)
+void CodecBase::probe_code_length(int n, const int16_t* comp, long long comp_stride, int count, const int32_t* totals, int n_totals,
+                                  const int8_t* z, int nz, int qp, int64_t* units, int64_t* kept, hipStream_t st)
 {
     if (m_cl_sums == nullptr) throw std::runtime_error("estimate_bits: set_param() has not been called");
+    if (n < 1 || n > m_cl_max_n) throw std::invalid_argument("estimate_bits: more pictures than the sums buffer holds");
     if (qp < 0 || (qp + 1) * m_cl_ch_z > m_cl_z_num) throw std::invalid_argument("estimate_bits: no z CDFs for this qp");
-    hip_check(hipMemsetAsync(m_cl_sums, 0, sizeof(unsigned long long) * 3, st), "hipMemsetAsync(code length)");
+    hip_check(hipMemsetAsync(m_cl_sums, 0, sizeof(unsigned long long) * 3 * n, st), "hipMemsetAsync(code length)");
     CodeLengthY dy;
-    dy.sym = comp;
+    dy.sym = comp; dy.sym_stride = comp_stride;
     dy.totals = totals; dy.totals_stride = 4; dy.n_totals = n_totals;
     dy.count = count;
     dy.table = m_cl_y; dy.num_cdf = m_cl_y_num;
-    dy.out = m_cl_sums; dy.out_stride = 3; dy.kept_slot = 1;
+    dy.out = m_cl_sums; dy.out_stride = 3; dy.kept_slot = 1; dy.n = n;
     code_length_y(dy, st);
     CodeLengthZ dz;
     dz.z = z; dz.count = nz; dz.ch = m_cl_ch_z;
     dz.table = m_cl_z + static_cast<size_t>(qp) * m_cl_ch_z * kCodeLengthZCols;
-    dz.out = m_cl_sums + 2; dz.out_stride = 3;
+    dz.out = m_cl_sums + 2; dz.out_stride = 3; dz.n = n;
     code_length_z(dz, st);
-    hip_check(hipMemcpyAsync(m_h_cl.get(), m_cl_sums, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost, st), "D2H code length");
+    hip_check(hipMemcpyAsync(m_h_cl.get(), m_cl_sums, sizeof(unsigned long long) * 3 * n, hipMemcpyDeviceToHost, st), "D2H code length");
     hip_check(hipStreamSynchronize(st), "sync");
-    units[0] = static_cast<int64_t>(m_h_cl[0]);
-    units[1] = static_cast<int64_t>(m_h_cl[2]);
-    if (kept) *kept = static_cast<int64_t>(m_h_cl[1]);
+    for (int b = 0; b < n; ++b) {
+        units[2 * b] = static_cast<int64_t>(m_h_cl[3 * b]);
+        units[2 * b + 1] = static_cast<int64_t>(m_h_cl[3 * b + 2]);
+        if (kept) kept[b] = static_cast<int64_t>(m_h_cl[3 * b + 1]);
+    }
 }
 
 const half_t* CodecBase::upload_qp_table(const ParamStore& ps, DeviceArena& mem, const char* name, int ch)

@@ -81,7 +81,7 @@ void DmcHtCodec::set_param(const ParamStore& ps, float skip_thres)
     }
     if (m_sp3.conv.cout != (m_hts ? kChY : 2 * kChY)) throw std::invalid_argument("unexpected y_spatial_prior.conv.3 width");
     load_cdf_tables(ps);
-    upload_code_length_tables(ps, m_wmem, kChZ);      // for estimate_bits
+    upload_code_length_tables(ps, m_wmem, kChZ, 1);      // for estimate_bits
     m_has_params = true;
     m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
 }
@@ -186,7 +186,8 @@ void DmcHtCodec::run_encoder(hipStream_t st)
 {
     const Geometry& g = m_g;
     const View t(m_T, kChD, kChD);
-    m_enc1.forward(View(m_CATE, kChSrc + kChD, kChSrc + kChD), t, t, g.H8, g.W8, m_s, st, m_cur_q_encoder);
+    ChainCall c; c.q_fused_last = m_cur_q_encoder;
+    m_enc1.forward(View(m_CATE, kChSrc + kChD, kChSrc + kChD), t, t, g.H8, g.W8, m_s, st, c);
     ConvKxKDesc d;
     d.x = m_T; d.ldx = kChD; d.w = m_enc_down.w; d.bias = m_enc_down.b; d.zeros = m_zeros;
     d.y = m_Y; d.ldy = kChY; d.in_h = g.H8; d.in_w = g.W8; d.cin = kChD; d.cout = kChY;
@@ -220,7 +221,8 @@ void DmcHtCodec::run_common(hipStream_t st)
     crop(m_HP, kChY, g.W16p, m_CATPF, 3 * kChY, g.H16, g.W16, kChY, st);       // crop_hyper_params
     const View pf(m_CATPF, 3 * kChY, 3 * kChY);
     const FinCall fin(m_fus3, m_COMMON, 3 * kChY);          // y_prior_fusion.conv.3 closes the chain
-    m_fus.forward(pf, pf, pf, g.H16, g.W16, m_s, st, nullptr, View(), &fin);
+    ChainCall c; c.fin = &fin;
+    m_fus.forward(pf, pf, pf, g.H16, g.W16, m_s, st, c);
 }
 
 void DmcHtCodec::run_reduction(hipStream_t st)
@@ -237,7 +239,8 @@ void DmcHtCodec::run_spatial_prior(int k, hipStream_t st)
     const View ad(m_AD, 2 * kChY, 2 * kChY);
     m_sp_adaptor[k].forward(View(m_CATSP, 2 * kChY, 2 * kChY), ad, g.H16, g.W16, m_s, st);
     const FinCall fin(m_sp3, m_SP, m_sp3.conv.cout);       // y_spatial_prior.conv.3 closes the chain
-    m_sp.forward(ad, ad, ad, g.H16, g.W16, m_s, st, nullptr, View(), &fin);
+    ChainCall c; c.fin = &fin;
+    m_sp.forward(ad, ad, ad, g.H16, g.W16, m_s, st, c);
 }
 
 void DmcHtCodec::run_decoder(hipStream_t st)
@@ -247,8 +250,8 @@ void DmcHtCodec::run_decoder(hipStream_t st)
     half_t* cat = m_CATE + (kChSrc - kChD);                 // [up out | ctx], dmc_hts_proxy.cpp:936-941
     m_dec_up.forward(View(m_CATSP, 2 * kChY, kChY), View(cat, ld, kChD), g.H16, g.W16, st, m_UPT, m_zeros);
     const View t(m_T, kChD, kChD);
-    m_dec1.forward(View(cat, ld, 2 * kChD), t, View(m_CATM + kChM, kChM + kChD, kChD), g.H8, g.W8, m_s, st,
-                   m_cur_q_decoder);
+    ChainCall c; c.q_fused_last = m_cur_q_decoder;
+    m_dec1.forward(View(cat, ld, 2 * kChD), t, View(m_CATM + kChM, kChM + kChD, kChD), g.H8, g.W8, m_s, st, c);
 }
 
 void DmcHtCodec::run_recon_head(half_t* x_hat, hipStream_t st)
@@ -269,7 +272,8 @@ void DmcHtCodec::run_recon_head(half_t* x_hat, hipStream_t st)
         }
         half_t* head = (i == kFrames - 1) ? m_FI : m_RH;    // the last head output doubles as the reset feature
         const FinCall fin(m_rh_head[i], head, kChSrcI);     // the head conv closes the chain
-        m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, nullptr, View(), &fin);
+        ChainCall c; c.fin = &fin;
+        m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, c);
         shuffle8(head, kChSrcI, g.H8, g.W8, 3, true, x_hat + i * picture, st);
     }
 }
@@ -287,7 +291,8 @@ void DmcHtCodec::run_recon_reset(hipStream_t st)
         trunk = rc;
     }
     const FinCall fin(m_rh_head[i], m_FI, kChSrcI);
-    m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, nullptr, View(), &fin);
+    ChainCall c; c.fin = &fin;
+    m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, c);
 }
 
 // ------------------------------------------------------------------------------------ reference frame
@@ -411,7 +416,7 @@ void DmcHtCodec::estimate_bits(const half_t* x, int height, int width, int qp, i
     // run_tpe derives its input and the temporal parameters into buffers of their own.
     run_stage(kEnc0, st, [&] { enc_stage0(st); });
     // HT-S: all symbols behind one total; HT-L: the four groups back to back, four totals
-    probe_code_length(m_COMP, g.P16() * kChY, m_TOTALS, m_hts ? 1 : 4, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
+    probe_code_length(1, m_COMP, g.P16() * kChY, g.P16() * kChY, m_TOTALS, m_hts ? 1 : 4, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
     leave(user);
 }
 

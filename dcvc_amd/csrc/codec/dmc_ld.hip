@@ -74,7 +74,7 @@ void DmcLdCodec::set_param(const ParamStore& ps, float skip_thres)
     chain(m_rh, 3, "recon_head.conv.");
     m_rh_head.load(ps, m_wmem, "recon_head.head.");
     load_cdf_tables(ps);
-    upload_code_length_tables(ps, m_wmem, kChZ);      // for estimate_bits
+    upload_code_length_tables(ps, m_wmem, kChZ, 1);      // for estimate_bits
     m_has_params = true;
     m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
 }
@@ -141,24 +141,24 @@ void DmcLdCodec::select_qp(int qp, hipStream_t st)
 void DmcLdCodec::run_fa_i(hipStream_t st, bool feed_fe)
 {
     const View t(m_T, kChM, kChM);
-    const bool feed = feed_fe && m_fa_i[3].feeds(m_fe[0]);
-    run_dcb_chain(m_fa_i, 4, View(m_FI, kChSrc, kChSrc), t, View(m_CATM, kChM + kChD, kChM), m_g.H8, m_g.W8, m_s, st,
-                  nullptr, View(m_T2, kChM, kChM), nullptr, feed ? &m_fe[0] : nullptr);
+    ChainCall c; c.tmp2 = View(m_T2, kChM, kChM); c.after = feed_fe && m_fa_i[3].feeds(m_fe[0]) ? &m_fe[0] : nullptr;
+    run_dcb_chain(m_fa_i, 4, View(m_FI, kChSrc, kChSrc), t, View(m_CATM, kChM + kChD, kChM), m_g.H8, m_g.W8, m_s, st, c);
 }
 
 void DmcLdCodec::run_fa_m(hipStream_t st, bool feed_fe)
 {
     const View t(m_T, kChM, kChM);
-    const bool feed = feed_fe && m_fa_m[3].feeds(m_fe[0]);
+    ChainCall c; c.tmp2 = View(m_T2, kChM, kChM); c.after = feed_fe && m_fa_m[3].feeds(m_fe[0]) ? &m_fe[0] : nullptr;
     run_dcb_chain(m_fa_m, 4, View(m_CATM, kChM + kChD, kChM + kChD), t, View(m_CATM, kChM + kChD, kChM),
-                  m_g.H8, m_g.W8, m_s, st, nullptr, View(m_T2, kChM, kChM), nullptr, feed ? &m_fe[0] : nullptr);
+                  m_g.H8, m_g.W8, m_s, st, c);
 }
 
 void DmcLdCodec::run_fe(hipStream_t st, bool dc0_done)
 {
     const View t(m_T, kChM, kChM);
+    ChainCall c; c.tmp2 = View(m_T2, kChM, kChM); c.first_dc0_done = dc0_done;
     run_dcb_chain(m_fe, 5, View(m_CATM, kChM + kChD, kChM), t, View(m_CATD + kChD, kChD + kChM, kChM),
-                  m_g.H8, m_g.W8, m_s, st, nullptr, View(m_T2, kChM, kChM), nullptr, nullptr, dc0_done);
+                  m_g.H8, m_g.W8, m_s, st, c);
 }
 
 void DmcLdCodec::run_tpe(hipStream_t st)
@@ -174,8 +174,8 @@ void DmcLdCodec::run_encoder(hipStream_t st)
     // [x unshuffled | ctx] = channels 64..511 of CATD (dmc_ld_proxy.cpp:755-757)
     // encoder.conv1 (two blocks) and encoder.conv2 (its output scaled by q_encoder inside its last conv) as ONE chain: every
     // launch also computes dc.0 of the block behind it
-    run_dcb_chain(m_encb, 3, View(m_CATD + 64, kChD + kChM, kChSrc + kChM), t, t, g.H8, g.W8, m_s, st, m_cur_q_encoder,
-                  View(m_T2, kChD, kChD));
+    ChainCall c; c.q_fused_last = m_cur_q_encoder; c.tmp2 = View(m_T2, kChD, kChD);
+    run_dcb_chain(m_encb, 3, View(m_CATD + 64, kChD + kChM, kChSrc + kChM), t, t, g.H8, g.W8, m_s, st, c);
     ConvKxKDesc d;
     d.x = m_T; d.ldx = kChD; d.w = m_enc_down.w; d.bias = m_enc_down.b; d.zeros = m_zeros;
     d.y = m_Y; d.ldy = kChY; d.in_h = g.H8; d.in_w = g.W8; d.cin = kChD; d.cout = kChY;
@@ -212,7 +212,8 @@ void DmcLdCodec::run_priors(hipStream_t st)
     // y_prior_fusion: three (384, 192) blocks in place, each launch with dc.0 of the next inside, the last one with
     // y_prior_fusion.conv.3 -> (q_dec | scales | means) behind y_hat in the spatial-prior input
     const FinCall fin(m_fus3, m_CATSP + kChY, 4 * kChY);
-    run_dcb_chain(m_fus, 3, pf, pf, pf, g.H16, g.W16, m_s, st, nullptr, View(), &fin);
+    ChainCall c; c.fin = &fin;
+    run_dcb_chain(m_fus, 3, pf, pf, pf, g.H16, g.W16, m_s, st, c);
 }
 
 void DmcLdCodec::run_spatial_prior(hipStream_t st)
@@ -220,7 +221,8 @@ void DmcLdCodec::run_spatial_prior(hipStream_t st)
     const Geometry& g = m_g;
     const View t(m_SPT, 2 * kChY, 2 * kChY);
     const FinCall fin(m_sp2, m_MEANS1, kChY);              // y_spatial_prior.conv.2 closes the chain
-    run_dcb_chain(m_sp, 2, View(m_CATSP, 4 * kChY, 4 * kChY), t, t, g.H16, g.W16, m_s, st, nullptr, View(), &fin);
+    ChainCall c; c.fin = &fin;
+    run_dcb_chain(m_sp, 2, View(m_CATSP, 4 * kChY, 4 * kChY), t, t, g.H16, g.W16, m_s, st, c);
 }
 
 void DmcLdCodec::run_decoder(hipStream_t st)
@@ -230,8 +232,8 @@ void DmcLdCodec::run_decoder(hipStream_t st)
     const View t(m_T, kChD, kChD);
     // decoder.conv2 (conv1x1_bias_with_quant) closes the chain -> feature_p, second half of the adaptor_m input
     const FinCall fin(m_dec2, m_CATM + kChM, kChM + kChD, m_cur_q_decoder);
-    run_dcb_chain(m_dec1, 3, View(m_CATD, kChD + kChM, kChD + kChM), t, t, g.H8, g.W8, m_s, st, nullptr,
-                  View(m_T2, kChD, kChD), &fin);
+    ChainCall c; c.tmp2 = View(m_T2, kChD, kChD); c.fin = &fin;
+    run_dcb_chain(m_dec1, 3, View(m_CATD, kChD + kChM, kChD + kChM), t, t, g.H8, g.W8, m_s, st, c);
 }
 
 void DmcLdCodec::run_recon_head(half_t* x_hat, hipStream_t st)
@@ -239,8 +241,8 @@ void DmcLdCodec::run_recon_head(half_t* x_hat, hipStream_t st)
     const Geometry& g = m_g;
     const View t(m_T, kChD, kChD);
     const FinCall fin(m_rh_head, m_FI, kChSrc);            // the head output doubles as the reference feature after a reset
-    run_dcb_chain(m_rh, 3, View(m_CATM + kChM, kChM + kChD, kChD), t, t, g.H8, g.W8, m_s, st, nullptr,
-                  View(m_T2, kChD, kChD), &fin);
+    ChainCall c; c.tmp2 = View(m_T2, kChD, kChD); c.fin = &fin;
+    run_dcb_chain(m_rh, 3, View(m_CATM + kChM, kChM + kChD, kChD), t, t, g.H8, g.W8, m_s, st, c);
     if (x_hat != nullptr) shuffle8(m_FI, kChSrc, g.H8, g.W8, 3, true, x_hat, st);
 }
 
@@ -338,7 +340,7 @@ void DmcLdCodec::estimate_bits(const half_t* x, int height, int width, int qp, i
     // the stage compress() runs (and, with graphs, the graph it replays). It reads the temporal state - ctx, the temporal
     // prior - and writes none of it; what it leaves in the scratch buffers the next call's first stage overwrites.
     run_stage(kEnc0, st, [&] { enc_stage0(st); });
-    probe_code_length(m_COMP, g.P16() * kChY, m_TOTALS, 1, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
+    probe_code_length(1, m_COMP, g.P16() * kChY, g.P16() * kChY, m_TOTALS, 1, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
     leave(user);
 }
 

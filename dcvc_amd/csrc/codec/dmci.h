@@ -97,12 +97,6 @@ private:
     DcbW m_dec1[12], m_dec2;
     float m_skip_thres = 0.f;
     bool m_has_params = false;
-    // code-length tables (estimate_bits): y [m_cl_y_num][256], z [m_cl_z_num][128], and the sums of a call
-    // [kMaxBatch][3] = {y units, y symbols, z units}
-    const uint32_t *m_cl_y = nullptr, *m_cl_z = nullptr;
-    int m_cl_y_num = 0, m_cl_z_num = 0;
-    unsigned long long* m_cl_sums = nullptr;
-    Pinned<unsigned long long> m_h_cl;
 
     // ---- per-resolution buffers
     Geometry m_g;

@@ -4,8 +4,6 @@
 // device->host transfer of the compacted symbols of all four steps.
 #include "codec/dmci.h"
 
-#include "rans/code_length.h"
-
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -68,23 +66,7 @@ void DmciCodec::set_param(const ParamStore& ps, float skip_thres)
     m_dec2.load(ps, m_wmem, "dec.dec_2.");
 
     load_cdf_tables(ps);
-    {   // what the coder will spend on every symbol under these CDFs, for estimate_bits (rans/code_length.h)
-        auto upload = [&](const char* name_cdf, const char* name_len, int cols, int& num) {
-            const HostTensor& c = ps.at(name_cdf);
-            const HostTensor& l = ps.at(name_len);
-            num = static_cast<int>(l.numel());
-            std::vector<uint32_t> host(static_cast<size_t>(num) * cols);
-            code_length_table(c.i.data(), num, static_cast<int>(c.numel() / num), l.i.data(), cols, host.data());
-            void* dev = m_wmem.alloc(host.size() * sizeof(uint32_t));
-            hip_check(hipMemcpy(dev, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D code-length table");
-            return static_cast<const uint32_t*>(dev);
-        };
-        m_cl_z = upload("bit_estimator_z.quantized_cdf", "bit_estimator_z.cdf_length", kCodeLengthZCols, m_cl_z_num);
-        m_cl_y = upload("gaussian_encoder.quantized_cdf", "gaussian_encoder.cdf_length", kCodeLengthYCols, m_cl_y_num);
-        if (m_cl_y_num > 256) throw std::invalid_argument("DMCI: more than 256 Gaussian CDFs");
-        m_cl_sums = static_cast<unsigned long long*>(m_wmem.alloc(sizeof(unsigned long long) * 3 * kMaxBatch));
-        m_h_cl.reserve(3 * kMaxBatch);
-    }
+    upload_code_length_tables(ps, m_wmem, kChZ, kMaxBatch);      // for estimate_bits
     m_has_params = true;
 }
 
@@ -160,16 +142,14 @@ void DmciCodec::run_encoder(hipStream_t st)
     const Geometry& g = m_g;
     // dmci_proxy.cpp:92-105 (the per-channel q_scale_enc multiply is applied to the rounded
     // output of enc_1 inside its last conv's epilogue)
-    // consecutive full-width blocks hand dc.0 over: block i's launch also computes dc.0 of block i+1
-    bool handed = m_enc1.feeds(m_enc2[0]);
-    m_enc1.forward(View(m_U, kChSrc, kChSrc), View(m_F, kChEncDec, kChEncDec), g.H8, g.W8, m_s, st,
-                   false, nullptr, m_cur_q_enc, View(), handed ? &m_enc2[0] : nullptr);
+    // consecutive full-width blocks hand dc.0 over: block i's launch also computes dc.0 of block i+1, across the seam too
     const View f(m_F, kChEncDec, kChEncDec);
-    for (int i = 0; i < 6; ++i) {
-        const DcbW* next = (i < 5 && m_enc2[i].feeds(m_enc2[i + 1])) ? &m_enc2[i + 1] : nullptr;
-        m_enc2[i].forward(f, f, g.H8, g.W8, m_s, st, false, nullptr, nullptr, View(), next, handed);
-        handed = next != nullptr;
-    }
+    ChainCall enc1, enc2;
+    enc1.q_after_last = m_cur_q_enc;
+    enc1.after = m_enc1.feeds(m_enc2[0]) ? &m_enc2[0] : nullptr;
+    enc2.first_dc0_done = enc1.after != nullptr;
+    run_dcb_chain(&m_enc1, 1, View(m_U, kChSrc, kChSrc), f, f, g.H8, g.W8, m_s, st, enc1);
+    run_dcb_chain(m_enc2, 6, f, f, f, g.H8, g.W8, m_s, st, enc2);
     ConvKxKDesc d;
     d.x = m_F; d.ldx = kChEncDec; d.w = m_enc_down.w; d.bias = m_enc_down.b; d.zeros = m_zeros;
     d.y = m_Y; d.ldy = kChY; d.in_h = g.H8; d.in_w = g.W8; d.cin = kChEncDec; d.cout = kChY;
@@ -199,14 +179,12 @@ void DmciCodec::run_priors_from_zhat(hipStream_t st)
     m_hdec1.forward(View(m_H1, kChZ, kChZ), View(m_H2a, kChZ, kChZ), View(m_H2, kChZ, kChZ), g.H32, g.W32, m_s, st);
     m_hdec2.forward(View(m_H2, kChZ, kChZ), View(m_HP, kChY, kChY), g.H16p, g.W16p, m_s, st);
     const View pf(m_PF, 2 * kChY, 2 * kChY);
-    {   // a chain of full-width blocks: each launch also computes dc.0 of the block behind it (DcbW::feeds)
-        const DcbW* n1 = m_fus[0].feeds(m_fus[1]) ? &m_fus[1] : nullptr;
-        const DcbW* n2 = m_fus[1].feeds(m_fus[2]) ? &m_fus[2] : nullptr;
-        m_fus[0].forward(View(m_HP, kChY, kChY), pf, g.H16p, g.W16p, m_s, st, false, nullptr, nullptr, View(), n1, false);
-        m_fus[1].forward(pf, pf, g.H16p, g.W16p, m_s, st, false, nullptr, nullptr, View(), n2, n1 != nullptr);
-        // ... and the last one the conv that closes the chain (y_prior_fusion.conv.3 -> params)
+    {   // a chain of full-width blocks: each launch also computes dc.0 of the block behind it (DcbW::feeds), and the last
+        // one the conv that closes the chain (y_prior_fusion.conv.3 -> params)
         const FinCall fin(m_fus3, m_PARAMSp, 2 * kChY);
-        m_fus[2].forward(pf, pf, g.H16p, g.W16p, m_s, st, false, nullptr, nullptr, View(), nullptr, n2 != nullptr, &fin);
+        ChainCall fus;
+        fus.fin = &fin;
+        run_dcb_chain(m_fus, 3, View(m_HP, kChY, kChY), pf, pf, g.H16p, g.W16p, m_s, st, fus);
     }
     if (g.padded()) {
         crop_b(m_PARAMSp, 2 * kChY, g.H16p, g.W16p, m_PARAMS, 2 * kChY, g.H16, g.W16, 2 * kChY, g.N, st);
@@ -223,30 +201,27 @@ void DmciCodec::run_spatial_prior(int k, hipStream_t st)
 {
     const Geometry& g = m_g;
     const View ad(m_AD, 2 * kChY, 2 * kChY);
-    const DcbW* next = m_sp_adaptor[k].feeds(m_sp[0]) ? &m_sp[0] : nullptr;
-    m_sp_adaptor[k].forward(View(m_CAT, 2 * kChY, 2 * kChY), ad, g.H16, g.W16, m_s, st, false, nullptr, nullptr, View(), next, false);
-    for (int i = 0; i < 3; ++i) {
-        const bool handed = next != nullptr;
-        next = (i < 2 && m_sp[i].feeds(m_sp[i + 1])) ? &m_sp[i + 1] : nullptr;
-        const FinCall fin(m_sp3, m_SP, 2 * kChY);          // y_spatial_prior.conv.3 closes the chain
-        m_sp[i].forward(ad, ad, g.H16, g.W16, m_s, st, false, nullptr, nullptr, View(), next, handed, i == 2 ? &fin : nullptr);
-    }
+    const FinCall fin(m_sp3, m_SP, 2 * kChY);              // y_spatial_prior.conv.3 closes the chain
+    ChainCall adaptor, sp;
+    adaptor.after = m_sp_adaptor[k].feeds(m_sp[0]) ? &m_sp[0] : nullptr;
+    sp.first_dc0_done = adaptor.after != nullptr;
+    sp.fin = &fin;
+    run_dcb_chain(&m_sp_adaptor[k], 1, View(m_CAT, 2 * kChY, 2 * kChY), ad, ad, g.H16, g.W16, m_s, st, adaptor);
+    run_dcb_chain(m_sp, 3, ad, ad, ad, g.H16, g.W16, m_s, st, sp);
 }
 
 void DmciCodec::run_decoder(half_t* x_hat, hipStream_t st)
 {
     const Geometry& g = m_g;
     // dmci_proxy.cpp:14-33
-    bool handed = m_dec_up.block.feeds(m_dec1[0]);
-    m_dec_up.forward(View(m_YHAT, kChY, kChY), View(m_D0, kChEncDec, kChEncDec), View(m_D1, kChEncDec, kChEncDec),
-                     g.H16, g.W16, m_s, st, nullptr, nullptr, handed ? &m_dec1[0] : nullptr);
     const View d1(m_D1, kChEncDec, kChEncDec);
-    for (int i = 0; i < 12; ++i) {
-        const DcbW* next = (i < 11 && m_dec1[i].feeds(m_dec1[i + 1])) ? &m_dec1[i + 1] : nullptr;
-        m_dec1[i].forward(d1, d1, g.H8, g.W8, m_s, st, false, nullptr, i == 11 ? m_cur_q_dec : nullptr, View(),
-                          next, handed);
-        handed = next != nullptr;
-    }
+    const DcbW* after_up = m_dec_up.block.feeds(m_dec1[0]) ? &m_dec1[0] : nullptr;
+    m_dec_up.forward(View(m_YHAT, kChY, kChY), View(m_D0, kChEncDec, kChEncDec), d1, g.H16, g.W16, m_s, st, nullptr, nullptr,
+                     after_up);
+    ChainCall dec1;
+    dec1.q_after_last = m_cur_q_dec;
+    dec1.first_dc0_done = after_up != nullptr;
+    run_dcb_chain(m_dec1, 12, d1, d1, d1, g.H8, g.W8, m_s, st, dec1);
     m_dec2.forward(d1, View(m_R, kChSrc, kChSrc), g.H8, g.W8, m_s, st);
     shuffle8_b(m_R, kChSrc, g.H8, g.W8, 3, true, x_hat, g.N, st);
 }
@@ -319,34 +294,15 @@ void DmciCodec::estimate_bits(int n, const half_t* x, int height, int width, int
 {
     if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMCI estimate_bits: qp must be in [0, 63]");
     prepare(height, width, n);
-    if ((qp + 1) * kChZ > m_cl_z_num) throw std::invalid_argument("DMCI estimate_bits: no z CDFs for this qp");
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8_b(x, height, width, 3, m_U, g.H8, g.W8, n, st);
     run_stage(kEnc0, st, [&] { enc_stage0(st); });          // the graph compress() replays; nothing below is part of it
     const long long nq = static_cast<long long>(g.P16()) * (kChY / 4);
-    hip_check(hipMemsetAsync(m_cl_sums, 0, sizeof(unsigned long long) * 3 * n, st), "hipMemsetAsync(code length)");
-    CodeLengthY dy;
-    dy.sym = m_COMP; dy.sym_stride = 4 * nq;
-    dy.totals = m_TOTALS; dy.totals_stride = 4; dy.n_totals = 4;
-    dy.count = static_cast<int>(4 * nq);
-    dy.table = m_cl_y; dy.num_cdf = m_cl_y_num;
-    dy.out = m_cl_sums; dy.out_stride = 3; dy.kept_slot = 1; dy.n = n;
-    code_length_y(dy, st);
-    CodeLengthZ dz;
-    dz.z = m_ZI8; dz.count = g.P64() * kChZ; dz.ch = kChZ;
-    dz.table = m_cl_z + static_cast<size_t>(qp) * kChZ * kCodeLengthZCols;
-    dz.out = m_cl_sums + 2; dz.out_stride = 3; dz.n = n;
-    code_length_z(dz, st);
-    hip_check(hipMemcpyAsync(m_h_cl.get(), m_cl_sums, sizeof(unsigned long long) * 3 * n, hipMemcpyDeviceToHost, st), "D2H code length");
-    hip_check(hipStreamSynchronize(st), "sync");
+    // picture b: its four compacted steps at m_COMP + b * 4 nq, its four totals at m_TOTALS + 4 b
+    probe_code_length(n, m_COMP, 4 * nq, static_cast<int>(4 * nq), m_TOTALS, 4, m_ZI8, g.P64() * kChZ, qp, units, kept, st);
     leave(user);
-    for (int b = 0; b < n; ++b) {
-        units[2 * b] = static_cast<int64_t>(m_h_cl[3 * b]);
-        units[2 * b + 1] = static_cast<int64_t>(m_h_cl[3 * b + 2]);
-        if (kept) kept[b] = static_cast<int64_t>(m_h_cl[3 * b + 1]);
-    }
 }
 
 void DmciCodec::entropy_encode(int qp)

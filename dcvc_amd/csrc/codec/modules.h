@@ -105,6 +105,28 @@ struct FinCall {
     FinCall(const FinW& w_, half_t* y_, int ldy_, const half_t* q_ = nullptr) : w(&w_), q(q_), y(y_), ldy(ldy_) {}
 };
 
+struct DcbW;
+
+// What a DcbW::forward call may ask for beyond the plain block.
+struct DcbCall {
+    bool shortcut = false;              // block-level skip connection: y += x. y may alias x only without it and without an adaptor
+    const half_t* q_fused = nullptr;    // scale fused into the block (DepthConvBlockProxy::forward(x, quant), layers_proxy.cpp:92-95)
+    const half_t* q_after = nullptr;    // a second scale applied behind it
+    // a spare [pixels][c] buffer for the adaptor output; with it (or without an adaptor) and y != x the half-width blocks of
+    // the inter models run as ONE launch (kernels/dcb_tail.hip reads the block input of neighbouring patches, so it cannot
+    // run in place)
+    View alt;
+    // Blocks whose shape the N-split kernel has (kernels/dcb_nsplit.hip) run everything behind the depthwise conv in one
+    // launch, which can also compute dc.0 of the block that FOLLOWS in a chain: `next` = that block (must satisfy
+    // feeds(next)), its dc.0 output then waits in the plane Scratch::hand names and the caller sets dc0_done in the call of
+    // next->forward() - the next launch that uses s.
+    const DcbW* next = nullptr;
+    bool dc0_done = false;
+    // the conv that closes the chain this block is the last of: yfin = conv(y) - inside the block launch where the kernel has
+    // the variant, as a launch of its own behind it otherwise (the caller never launches it)
+    const FinCall* fin = nullptr;
+};
+
 // layers.py:128-159 DepthConvBlock; layers_proxy.cpp:160-206 for the folding
 struct DcbW {
     bool has_adaptor = false;
@@ -117,24 +139,14 @@ struct DcbW {
     int cdc = 0;            // depthwise width (c or c/2)
     int cffn = 0;           // ffn inner width after chunk-add (c or c/2)
     void load(const ParamStore& ps, DeviceArena& mem, const std::string& prefix);
-    // y may alias x only when the block has no adaptor and `shortcut` is false. `alt`: a spare
-    // [pixels][c] buffer for the adaptor output; with it (or without an adaptor) and y != x the
-    // half-width blocks of the inter models run as ONE launch (kernels/dcb_tail.hip reads the block
-    // input of neighbouring patches, so it cannot run in place)
-    // Blocks whose shape the N-split kernel has (kernels/dcb_nsplit.hip) run everything behind the depthwise conv in one
-    // launch, which can also compute dc.0 of the block that FOLLOWS in a chain:
-    // `next` = that block (must satisfy feeds(next)), its dc.0 output then waits in s.t1 and the
-    // caller passes dc0_done = true to next->forward().
-    // `fin`: the conv that closes the chain this block is the last of: yfin = conv(y) - inside the block launch where the
-    // kernel has the variant, as a launch of its own behind it otherwise (the caller never launches it)
-    void forward(View x, View y, int H, int W, const Scratch& s, hipStream_t st, bool shortcut = false,
-                 const half_t* q_fused = nullptr, const half_t* q_after = nullptr, View alt = View(),
-                 const DcbW* next = nullptr, bool dc0_done = false, const FinCall* fin = nullptr) const;
-    bool core_fused() const;                     // this block runs through dcb_nsplit
+    void forward(View x, View y, int H, int W, const Scratch& s, hipStream_t st, const DcbCall& call = {}) const;
     // this block on an H x W grid can run as ONE launch (dcb_tail with dc.0 inside) when its input is not its output
     bool one_launch(int H, int W) const;
-    bool nsplit() const { return packed_main != nullptr; }
+    bool nsplit() const { return packed_main != nullptr; }      // this block runs through dcb_nsplit
     bool feeds(const DcbW& next) const;          // ... and can compute next's dc.0 on the way out
+
+private:
+    bool tail_takes(int H, int W) const;         // dcb_tail can take this block on this grid
 };
 
 // layers.py:176-188: pixel_unshuffle(2) + 1x1 == 2x2 stride-2 conv (layers_proxy.cpp:263-264)
@@ -176,25 +188,30 @@ struct UpsampleW {
                  half_t* up_tmp = nullptr, const half_t* zeros = nullptr, const DcbW* next = nullptr) const;
 };
 
+// What a chain call may ask for beyond x -> (first block) -> tmp -> ... in place ... -> (last block) -> y.
+struct ChainCall {
+    const half_t* q_fused_last = nullptr;   // DcbCall::q_fused of the last block
+    const half_t* q_after_last = nullptr;   // DcbCall::q_after of the last block
+    View tmp2;                              // a second temporary: the blocks ping-pong between the two instead of running in place
+    const FinCall* fin = nullptr;           // DcbCall::fin of the last block
+    // the first block of the chain that runs NEXT on this chain's output (it must satisfy blocks[n-1].feeds(*after)): the
+    // last launch also computes its dc.0 (DcbCall::next), and that chain is then run with first_dc0_done - nothing else may
+    // use s in between.
+    const DcbW* after = nullptr;
+    bool first_dc0_done = false;
+};
+
+// the launch sequence of a chain over a plain array of blocks (codecs that keep DcbW[n] members)
+void run_dcb_chain(const DcbW* blocks, int n, View x, View tmp, View y, int H, int W, const Scratch& s,
+                   hipStream_t st, const ChainCall& call = {});
+
 // nn.Sequential of DepthConvBlocks prefix + "0.", "1.", ... (as many as the checkpoint has)
 struct DcbChain {
     std::vector<DcbW> blocks;
     void load(const ParamStore& ps, DeviceArena& mem, const std::string& prefix);
-    // x -> (first block) -> tmp -> ... in place ... -> (last block) -> y; q_fused_last: scale fused
-    // into the last block (DepthConvBlockProxy::forward(x, quant), layers_proxy.cpp:92-95).
-    // With a second temporary the blocks ping-pong between the two instead of running in place.
-    void forward(View x, View tmp, View y, int H, int W, const Scratch& s, hipStream_t st,
-                 const half_t* q_fused_last = nullptr, View tmp2 = View(), const FinCall* fin = nullptr) const;
+    void forward(View x, View tmp, View y, int H, int W, const Scratch& s, hipStream_t st, const ChainCall& call = {}) const;
     size_t size() const { return blocks.size(); }
 };
-
-// the same launch sequence over a plain array of blocks (codecs that keep DcbW[n] members)
-// `after`: the first block of the chain that runs NEXT on this chain's output (it must satisfy blocks[n-1].feeds(*after)):
-// the last launch also computes its dc.0 into s.t1, and that chain is then run with first_dc0_done = true - nothing else
-// may touch s.t1 in between.
-void run_dcb_chain(const DcbW* blocks, int n, View x, View tmp, View y, int H, int W, const Scratch& s,
-                   hipStream_t st, const half_t* q_fused_last = nullptr, View tmp2 = View(), const FinCall* fin = nullptr,
-                   const DcbW* after = nullptr, bool first_dc0_done = false);
 
 // dense k x k conv weight in tap-major layout
 struct ConvKW {

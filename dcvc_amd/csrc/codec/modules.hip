@@ -196,31 +196,35 @@ void DcbW::load(const ParamStore& ps, DeviceArena& mem, const std::string& p)
     }
 }
 
-bool DcbW::core_fused() const
+bool DcbW::tail_takes(int H, int W) const
 {
-    return nsplit();
+    return !nsplit() && dcb_tail_supported(H, W, c, cdc, cffn) && ffn0.b != nullptr && ffn2.b != nullptr && dc3.b != nullptr &&
+           dc0.b != nullptr;
 }
 
 bool DcbW::one_launch(int H, int W) const
 {
-    return !nsplit() && !has_adaptor && dcb_tail_supported(H, W, c, cdc, cffn) && dcb_tail_takes_dc0() && ffn0.b != nullptr &&
-           ffn2.b != nullptr && dc3.b != nullptr && dc0.b != nullptr;
+    return !has_adaptor && tail_takes(H, W) && dcb_tail_takes_dc0();
 }
 
 bool DcbW::feeds(const DcbW& next) const
 {
-    return core_fused() && next.core_fused() && !next.has_adaptor && next.c == c && next.cdc == cdc && nsplit() == next.nsplit();
+    return nsplit() && next.nsplit() && !next.has_adaptor && next.c == c && next.cdc == cdc;
 }
 
-void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t st, bool shortcut,
-                   const half_t* q_fused, const half_t* q_after, View alt, const DcbW* next, bool dc0_done, const FinCall* fin) const
+void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t st, const DcbCall& call) const
 {
+    const bool shortcut = call.shortcut;
+    const DcbW* const next = call.next;
+    const FinCall* const fin = call.fin;
+    View alt = call.alt;
+    bool dc0_done = call.dc0_done;
     const int P = H * W;                 // one picture: what the launch choices below follow
     const int NP = P * s.batch;          // the pixels of the launches
     if (fin != nullptr && (next != nullptr || fin->w == nullptr || fin->w->conv.cin != c)) {
         throw std::invalid_argument("DepthConvBlock: a closing conv sits behind the LAST block of a chain and reads its output");
     }
-    if ((next != nullptr && !feeds(*next)) || (dc0_done && (!core_fused() || has_adaptor))) {
+    if ((next != nullptr && !feeds(*next)) || (dc0_done && (!nsplit() || has_adaptor))) {
         throw std::invalid_argument("DepthConvBlock: dc.0 hand-over between blocks that do not support it");
     }
     if (static_cast<size_t>(NP) * cdc > s.elems || static_cast<size_t>(NP) * cffn > s.elems) {
@@ -236,8 +240,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         // the adaptor output would have to survive the in-place dc.3 / ffn.2 updates
         throw std::invalid_argument("DepthConvBlock with adaptor and shortcut is not a DCVC-UF block");
     }
-    const bool tail = !nsplit() && dcb_tail_supported(H, W, c, cdc, cffn) && ffn0.b != nullptr && ffn2.b != nullptr &&
-                      dc3.b != nullptr && dc0.b != nullptr;
+    const bool tail = tail_takes(H, W);
     if (has_adaptor) {
         // the one-launch block (dcb_tail with dc.0 inside) reads its input's neighbours, so the adaptor output must not be
         // the block output: without a spare buffer from the caller it goes to the third scratch plane, which that launch leaves alone
@@ -273,7 +276,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         if (tail_dc0) { d.w1 = dc0.w; d.b1 = dc0.b; }
         d.t = p1; d.ldt = cdc; d.dw = dw; d.x = in.p; d.ldx = in.ld;
         d.w3 = dc3.w; d.b3 = dc3.b; d.w0 = ffn0.w; d.b0 = ffn0.b; d.w2 = ffn2.w; d.b2 = ffn2.b;
-        d.q = q_fused; d.q2 = q_after; d.y = y.p; d.ldy = y.ld;
+        d.q = call.q_fused; d.q2 = call.q_after; d.y = y.p; d.ldy = y.ld;
         d.H = H; d.W = W; d.c = c; d.cdc = cdc; d.cffn = cffn; d.shortcut = shortcut; d.n = s.batch;
         dcb_tail(d, st);
         if (fin != nullptr) run_fin(*fin, y, NP, st);
@@ -293,7 +296,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         if (dw_inside) { d.t1 = p1; d.wdw = dw; d.width = W; }
         else d.t2 = p2;
         d.wmain = packed_main; d.b3 = dc3.b; d.b0 = ffn0.b; d.b2 = ffn2.b;
-        d.q = q_fused; d.q2 = q_after; d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.c = c; d.ci = cdc; d.shortcut = shortcut;
+        d.q = call.q_fused; d.q2 = call.q_after; d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.c = c; d.ci = cdc; d.shortcut = shortcut;
         if (next != nullptr) {
             d.wnext = next->packed_dc0; d.b1n = next->dc0.b; d.t1n = dw_inside ? p2 : p1; d.ldt1 = next->cdc;
             if (dw_inside) s.hand ^= 1;
@@ -319,7 +322,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         FfnFusedDesc d;
         d.x = y.p; d.ldx = y.ld; d.w0 = ffn0.w; d.b0 = ffn0.b; d.w2 = ffn2.w; d.b2 = ffn2.b;
         if (shortcut) { d.r2 = in.p; d.ldr2 = in.ld; }
-        d.q = q_fused; d.q2 = q_after;
+        d.q = call.q_fused; d.q2 = call.q_after;
         d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.c = c; d.cffn = cffn;
         ffn_fused(d, st);
         if (fin != nullptr) run_fin(*fin, y, NP, st);
@@ -335,7 +338,7 @@ void DcbW::forward(View x, View y, int H, int W, const Scratch& s, hipStream_t s
         Conv1x1Desc d;
         d.x = s.t3; d.ldx = cffn; d.w = ffn2.w; d.bias = ffn2.b; d.r1 = y.p; d.ldr1 = y.ld;
         if (shortcut) { d.r2 = in.p; d.ldr2 = in.ld; }
-        d.q = q_fused; d.q2 = q_after;
+        d.q = call.q_fused; d.q2 = call.q_after;
         d.y = y.p; d.ldy = y.ld; d.pixels = NP; d.cin = cffn; d.cout = c;
         conv1x1(d, st);
     }
@@ -373,7 +376,8 @@ void Stride2W::forward(View x, View tmp, View y, int H, int W, const half_t* zer
         d.y = tmp.p; d.ldy = tmp.ld;
     }
     conv_kxk(d, st);
-    block.forward(tmp, y, H / 2, W / 2, s, st, shortcut);
+    DcbCall c; c.shortcut = shortcut;
+    block.forward(tmp, y, H / 2, W / 2, s, st, c);
 }
 
 void SubpelW::load(const ParamStore& ps, DeviceArena& mem, const std::string& p)
@@ -442,7 +446,8 @@ void UpsampleW::forward(View x, View tmp, View y, int H, int W, const Scratch& s
         tmp = View(s.t3, up.cout, up.cout);      // (as Stride2W::forward: the one-launch block cannot run in place)
     }
     up.forward(x, tmp, H, W, st, up_tmp, zeros, s.batch);
-    block.forward(tmp, y, 2 * H, 2 * W, s, st, shortcut, nullptr, nullptr, View(), next);
+    DcbCall c; c.shortcut = shortcut; c.next = next;
+    block.forward(tmp, y, 2 * H, 2 * W, s, st, c);
 }
 
 void DcbChain::load(const ParamStore& ps, DeviceArena& mem, const std::string& prefix)
@@ -456,53 +461,45 @@ void DcbChain::load(const ParamStore& ps, DeviceArena& mem, const std::string& p
 }
 
 void run_dcb_chain(const DcbW* blocks, int n, View x, View tmp, View y, int H, int W, const Scratch& s,
-                   hipStream_t st, const half_t* q_fused_last, View tmp2, const FinCall* fin, const DcbW* after, bool first_dc0_done)
+                   hipStream_t st, const ChainCall& call)
 {
-    if (after != nullptr && (fin != nullptr || !blocks[n - 1].feeds(*after))) {
+    if (call.after != nullptr && (call.fin != nullptr || !blocks[n - 1].feeds(*call.after))) {
         throw std::invalid_argument("run_dcb_chain: the chain behind this one cannot take its dc.0 from the last launch");
     }
-    auto next_of = [&](int i) -> const DcbW* {
-        if (i + 1 < n) return blocks[i].feeds(blocks[i + 1]) ? &blocks[i + 1] : nullptr;
-        return after;
-    };
-    if (tmp2.p == nullptr) {
-        View cur = x;
-        bool handed = first_dc0_done;   // the previous block left this block's dc.0 output in s.t1
-        for (int i = 0; i < n; ++i) {
-            const View out = (i == n - 1) ? y : tmp;
-            const DcbW* next = next_of(i);
-            blocks[i].forward(cur, out, H, W, s, st, false, i == n - 1 ? q_fused_last : nullptr, nullptr, View(),
-                              next, handed, i == n - 1 ? fin : nullptr);
-            handed = next != nullptr;
-            cur = out;
-        }
-        return;
-    }
-    // ping-pong: out[n-1] = y, the outputs before it alternate between the two temporaries so that no
-    // block runs in place (the one-launch block kernel needs input != output)
-    const View a = tmp, b = tmp2;
+    const View a = tmp, b = call.tmp2;
+    const bool ping_pong = b.p != nullptr;
     View cur = x;
-    bool handed = first_dc0_done;
+    DcbCall c;
+    c.dc0_done = call.first_dc0_done;   // the previous block left this block's dc.0 output in s.t1
     for (int i = 0; i < n; ++i) {
-        View out = y;
-        if (i != n - 1) {
-            const bool y_is_a = y.p == a.p;
-            const int back = n - 1 - i;                         // distance from the last block
-            out = (back % 2 == 1) ? (y_is_a ? b : a) : (y_is_a ? a : b);
+        const bool last = i == n - 1;
+        View out = last ? y : a;
+        if (ping_pong) {
+            // out[n-1] = y, the outputs before it alternate between the two temporaries so that no block runs in place (the
+            // one-launch block kernel needs input != output)
+            if (!last) {
+                const bool y_is_a = y.p == a.p;
+                const int back = n - 1 - i;                         // distance from the last block
+                out = (back % 2 == 1) ? (y_is_a ? b : a) : (y_is_a ? a : b);
+            }
+            const View spare = (out.p == a.p) ? b : a;              // for an adaptor: neither input nor output
+            c.alt = cur.p == spare.p ? View() : spare;
         }
-        const View spare = (out.p == a.p) ? b : a;              // for an adaptor: neither input nor output
-        const DcbW* next = next_of(i);
-        blocks[i].forward(cur, out, H, W, s, st, false, i == n - 1 ? q_fused_last : nullptr, nullptr,
-                          cur.p == spare.p ? View() : spare, next, handed, i == n - 1 ? fin : nullptr);
-        handed = next != nullptr;
+        if (last) {
+            c.q_fused = call.q_fused_last; c.q_after = call.q_after_last; c.fin = call.fin;
+            c.next = call.after;
+        } else {
+            c.next = blocks[i].feeds(blocks[i + 1]) ? &blocks[i + 1] : nullptr;
+        }
+        blocks[i].forward(cur, out, H, W, s, st, c);
+        c.dc0_done = c.next != nullptr;
         cur = out;
     }
 }
 
-void DcbChain::forward(View x, View tmp, View y, int H, int W, const Scratch& s, hipStream_t st,
-                       const half_t* q_fused_last, View tmp2, const FinCall* fin) const
+void DcbChain::forward(View x, View tmp, View y, int H, int W, const Scratch& s, hipStream_t st, const ChainCall& call) const
 {
-    run_dcb_chain(blocks.data(), static_cast<int>(blocks.size()), x, tmp, y, H, W, s, st, q_fused_last, tmp2, fin);
+    run_dcb_chain(blocks.data(), static_cast<int>(blocks.size()), x, tmp, y, H, W, s, st, call);
 }
 
 }  // namespace dcvc

@@ -54,18 +54,25 @@ long long dcvc_modtest_read(dcvc_modtest* h, int module, int index, int what, vo
 /* the scratch planes and Scratch::hand (state tests) */
 int dcvc_modtest_scratch(dcvc_modtest* h, void** t1, void** t2, void** t3, int* hand);
 
-/* DcbW::forward, every argument passed through. fin_module < 0: no closing conv */
+/* DcbW::forward, the flat arguments gathered into its DcbCall. fin_module < 0: no closing conv */
 int dcvc_modtest_block_forward(dcvc_modtest* h, int module, int index, void* x, int ldx, int cx, void* y, int ldy, int cy,
                                int H, int W, int shortcut, const void* q_fused, const void* q_after,
                                void* alt, int ldalt, int calt, int next_module, int next_index, int dc0_done,
                                int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output, void* stream);
-/* run_dcb_chain over blocks [first, first + n) of a module (n = 0: all of them; a DcbChain runs through DcbChain::forward
- * when nothing it lacks - after, first_dc0_done, a sub-range - is asked for) */
+/* run_dcb_chain over blocks [first, first + n) of a module, the flat arguments gathered into its ChainCall (n = 0: all of
+ * them; a DcbChain that is run whole runs through DcbChain::forward) */
 int dcvc_modtest_chain_forward(dcvc_modtest* h, int module, int first, int n, void* x, int ldx, int cx,
                                void* tmp, int ldtmp, int ctmp, void* y, int ldy, int cy, int H, int W,
                                const void* q_fused_last, void* tmp2, int ldtmp2, int ctmp2,
                                int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output,
                                int after_module, int after_index, int first_dc0_done, void* stream);
+/* the same with ChainCall::q_after_last (chain_forward passes null); an entry of its own so that callers bound to
+ * chain_forward's argument list keep working */
+int dcvc_modtest_chain_forward_qa(dcvc_modtest* h, int module, int first, int n, void* x, int ldx, int cx,
+                                  void* tmp, int ldtmp, int ctmp, void* y, int ldy, int cy, int H, int W,
+                                  const void* q_fused_last, const void* q_after_last, void* tmp2, int ldtmp2, int ctmp2,
+                                  int fin_module, const void* fin_q, void* fin_y, int fin_ldy, int keep_block_output,
+                                  int after_module, int after_index, int first_dc0_done, void* stream);
 int dcvc_modtest_stride2_forward(dcvc_modtest* h, int module, void* x, int ldx, int cx, void* tmp, int ldtmp, int ctmp,
                                  void* y, int ldy, int cy, int H, int W, void* stream);
 int dcvc_modtest_upsample_forward(dcvc_modtest* h, int module, void* x, int ldx, int cx, void* tmp, int ldtmp, int ctmp,

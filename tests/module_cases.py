@@ -286,8 +286,9 @@ def blk(mod, x, y, i=0, sc=False, qf=None, qa=None, alt=None, nxt=None, done=Fal
     return dict(op="block", mod=mod, i=i, x=x, y=y, sc=sc, qf=qf, qa=qa, alt=alt, next=nxt, done=done, fin=fin)
 
 
-def chn(mod, x, tmp, y, first=0, n=0, qf=None, tmp2=None, fin=None, after=None, done=False):
-    return dict(op="chain", mod=mod, first=first, n=n, x=x, tmp=tmp, y=y, qf=qf, tmp2=tmp2, fin=fin, after=after, done=done)
+def chn(mod, x, tmp, y, first=0, n=0, qf=None, qa=None, tmp2=None, fin=None, after=None, done=False):
+    """qf / qa: ChainCall::q_fused_last / q_after_last, the scales of the LAST block"""
+    return dict(op="chain", mod=mod, first=first, n=n, x=x, tmp=tmp, y=y, qf=qf, qa=qa, tmp2=tmp2, fin=fin, after=after, done=done)
 
 
 def s2(mod, x, tmp, y):
@@ -340,13 +341,13 @@ def scratch_elems(case):
 
 # ---- dmci.hip ----------------------------------------------------------------------------------------------------------
 def dmci_encoder(H, W, batch=1):
-    # dmci.hip run_encoder: enc_1 (adaptor block, q_after, next) into the in-place loop of enc_2 with hand-over
+    # dmci.hip run_encoder: enc_1 as a one-block chain (adaptor block, q_after_last, after) into the in-place chain of enc_2
+    # with first_dc0_done
     return case("dmci-encoder", "dmci.hip run_encoder", H, W,
                 {"E1": ("block", "i_enc1"), "E2": ("blocks", ["i_384", "i_384"])},
                 {"U": (192, "g"), "F": (384, "g")}, [V("U", 192)],
-                [blk("E1", V("U", 192), V("F", 384), qa="q", nxt=("E2", 0)),
-                 blk("E2", V("F", 384), V("F", 384), i=0, nxt=("E2", 1), done=True),
-                 blk("E2", V("F", 384), V("F", 384), i=1, done=True)], qs={"q": 384}, batch=batch)
+                [chn("E1", V("U", 192), V("F", 384), V("F", 384), qa="q", after=("E2", 0)),
+                 chn("E2", V("F", 384), V("F", 384), V("F", 384), done=True)], qs={"q": 384}, batch=batch)
 
 
 def dmci_hyper_enc(H, W, batch=1, f64=False):
@@ -369,37 +370,34 @@ def dmci_hyper_dec(H, W, batch=1):
 
 
 def dmci_fusion(H, W, batch=1, keep=False):
-    # dmci.hip run_priors_from_zhat: y_prior_fusion as three block calls - adaptor block with next, an in-place block handed
-    # its dc.0, and the last one with the closing conv (the block's own output is not stored unless keep_block_output)
+    # dmci.hip run_priors_from_zhat: y_prior_fusion as ONE chain - adaptor block into a distinct buffer, two blocks in place,
+    # the closing conv behind the last one (the block's own output is not stored unless keep_block_output)
     return case("dmci-fusion" + ("-keep" if keep else ""), "dmci.hip run_priors_from_zhat (y_prior_fusion)", H, W,
                 {"F": ("blocks", ["i_fus0", "i_512", "i_512"]), "F3": ("fin", "i_fus3")},
                 {"HP": (256, "g"), "PF": (512, "g"), "PAR": (512, "g")}, [V("HP", 256)],
-                [blk("F", V("HP", 256), V("PF", 512), i=0, nxt=("F", 1)),
-                 blk("F", V("PF", 512), V("PF", 512), i=1, nxt=("F", 2), done=True),
-                 blk("F", V("PF", 512), V("PF", 512), i=2, done=True, fin=fin("F3", V("PAR", 512), keep=keep))],
+                [chn("F", V("HP", 256), V("PF", 512), V("PF", 512), fin=fin("F3", V("PAR", 512), keep=keep))],
                 temps=() if keep else ("PF",), batch=batch)
 
 
 def dmci_spatial_prior(H, W, batch=1):
-    # dmci.hip run_spatial_prior: y_spatial_prior_adaptor_k (adaptor of its own width, next) and the in-place loop that ends
-    # in y_spatial_prior.conv.3
+    # dmci.hip run_spatial_prior: y_spatial_prior_adaptor_k as a one-block chain (adaptor of its own width, after) and the
+    # in-place chain with first_dc0_done that ends in y_spatial_prior.conv.3
     return case("dmci-spatial-prior", "dmci.hip run_spatial_prior", H, W,
                 {"A": ("block", "i_spad"), "S": ("blocks", ["i_512", "i_512"]), "S3": ("fin", "i_fus3")},
                 {"CAT": (512, "g"), "AD": (512, "g"), "SP": (512, "g")}, [V("CAT", 512)],
-                [blk("A", V("CAT", 512), V("AD", 512), nxt=("S", 0)),
-                 blk("S", V("AD", 512), V("AD", 512), i=0, nxt=("S", 1), done=True),
-                 blk("S", V("AD", 512), V("AD", 512), i=1, done=True, fin=fin("S3", V("SP", 512)))],
+                [chn("A", V("CAT", 512), V("AD", 512), V("AD", 512), after=("S", 0)),
+                 chn("S", V("AD", 512), V("AD", 512), V("AD", 512), done=True, fin=fin("S3", V("SP", 512)))],
                 temps=("AD",), batch=batch)
 
 
 def dmci_decoder(H, W, batch=1):
-    # dmci.hip run_decoder: UpsampleW with next, the in-place loop with q_after on its last block, dec_2 (192-wide adaptor block)
+    # dmci.hip run_decoder: UpsampleW with next, the in-place chain with first_dc0_done and q_after_last, dec_2 (192-wide
+    # adaptor block)
     return case("dmci-decoder", "dmci.hip run_decoder", H, W,
                 {"U": ("upsample", 256, "i_384", True, 1, False), "D": ("blocks", ["i_384", "i_384"]), "D2": ("block", "i_dec2")},
                 {"YH": (256, "g"), "D0": (384, "d"), "D1": (384, "d"), "R": (192, "d")}, [V("YH", 256)],
                 [ups("U", V("YH", 256), V("D0", 384), V("D1", 384), nxt=("D", 0)),
-                 dict(blk("D", V("D1", 384), V("D1", 384), i=0, nxt=("D", 1), done=True), grid="d"),
-                 dict(blk("D", V("D1", 384), V("D1", 384), i=1, qa="q", done=True), grid="d"),
+                 dict(chn("D", V("D1", 384), V("D1", 384), V("D1", 384), qa="q", done=True), grid="d"),
                  dict(blk("D2", V("D1", 384), V("R", 192)), grid="d")],
                 temps=("D0",), qs={"q": 384}, batch=batch)
 
@@ -627,6 +625,53 @@ def x_ffn(H, W):
                  blk("A", V("X", 192), V("Y2", 256))], temps=("ALT",), qs={"q": 256})
 
 
+def x_blk_encoder(H, W, batch=1):
+    # no call site: the encoder's sequence as DcbW::forward calls - an adaptor block with q_after and next, then blocks in
+    # place that are handed their dc.0 (dc0_done) and hand the next one over
+    return case("x-blk-encoder", "none: DcbW::forward, q_after with next and the block-level hand-over", H, W,
+                {"E1": ("block", "i_enc1"), "E2": ("blocks", ["i_384", "i_384"])},
+                {"U": (192, "g"), "F": (384, "g")}, [V("U", 192)],
+                [blk("E1", V("U", 192), V("F", 384), qa="q", nxt=("E2", 0)),
+                 blk("E2", V("F", 384), V("F", 384), i=0, nxt=("E2", 1), done=True),
+                 blk("E2", V("F", 384), V("F", 384), i=1, done=True)], qs={"q": 384}, batch=batch)
+
+
+def x_blk_fusion(H, W, batch=1, keep=False):
+    # no call site: the fusion sequence as DcbW::forward calls - the last block with fin, with and without keep_block_output
+    return case("x-blk-fusion" + ("-keep" if keep else ""), "none: DcbW::forward, fin with keep_block_output", H, W,
+                {"F": ("blocks", ["i_fus0", "i_512", "i_512"]), "F3": ("fin", "i_fus3")},
+                {"HP": (256, "g"), "PF": (512, "g"), "PAR": (512, "g")}, [V("HP", 256)],
+                [blk("F", V("HP", 256), V("PF", 512), i=0, nxt=("F", 1)),
+                 blk("F", V("PF", 512), V("PF", 512), i=1, nxt=("F", 2), done=True),
+                 blk("F", V("PF", 512), V("PF", 512), i=2, done=True, fin=fin("F3", V("PAR", 512), keep=keep))],
+                temps=() if keep else ("PF",), batch=batch)
+
+
+def x_blk_spatial_prior(H, W, batch=1):
+    # no call site: the spatial prior's sequence as DcbW::forward calls - an adaptor of the block's own width with next, blocks
+    # in place, fin behind a block that was handed its dc.0
+    return case("x-blk-spatial-prior", "none: DcbW::forward, hand-over into a block with fin", H, W,
+                {"A": ("block", "i_spad"), "S": ("blocks", ["i_512", "i_512"]), "S3": ("fin", "i_fus3")},
+                {"CAT": (512, "g"), "AD": (512, "g"), "SP": (512, "g")}, [V("CAT", 512)],
+                [blk("A", V("CAT", 512), V("AD", 512), nxt=("S", 0)),
+                 blk("S", V("AD", 512), V("AD", 512), i=0, nxt=("S", 1), done=True),
+                 blk("S", V("AD", 512), V("AD", 512), i=1, done=True, fin=fin("S3", V("SP", 512)))],
+                temps=("AD",), batch=batch)
+
+
+def x_blk_decoder(H, W, batch=1):
+    # no call site: the decoder's sequence as DcbW::forward calls - UpsampleW with next, blocks in place with the hand-over,
+    # q_after on a block that was handed its dc.0
+    return case("x-blk-decoder", "none: UpsampleW::forward with next, DcbW::forward with q_after and dc0_done", H, W,
+                {"U": ("upsample", 256, "i_384", True, 1, False), "D": ("blocks", ["i_384", "i_384"]), "D2": ("block", "i_dec2")},
+                {"YH": (256, "g"), "D0": (384, "d"), "D1": (384, "d"), "R": (192, "d")}, [V("YH", 256)],
+                [ups("U", V("YH", 256), V("D0", 384), V("D1", 384), nxt=("D", 0)),
+                 dict(blk("D", V("D1", 384), V("D1", 384), i=0, nxt=("D", 1), done=True), grid="d"),
+                 dict(blk("D", V("D1", 384), V("D1", 384), i=1, qa="q", done=True), grid="d"),
+                 dict(blk("D2", V("D1", 384), V("R", 192)), grid="d")],
+                temps=("D0",), qs={"q": 384}, batch=batch)
+
+
 def x_single(shape, H, W, sc=False, batch=1):
     # no single call site: one block of a model shape on its own, input != output - the float64 cases
     c, _, _, cin = SHAPES[shape]
@@ -700,6 +745,10 @@ def _cases():
            x_stride2("i_128", 128, 10, 6, True), x_stride2("l_128", 128, 18, 34, False), x_stride2("l_256", 256, 10, 6, False),
            x_stride2("i_512", 512, 10, 6, True),
            x_upsample("i_128", 128, 5, 3, True), x_upsample("l_128", 128, 9, 17, False), x_upsample("i_384", 256, 5, 3, True)]
+    # --- the block form of the intra sequences (DMCI itself runs them as chains): DcbW::forward's next / dc0_done / q_after / fin
+    for hw in ((9, 17), (5, 3)):
+        cs += [x_blk_encoder(*hw), x_blk_fusion(*hw), x_blk_fusion(*hw, keep=True), x_blk_spatial_prior(*hw), x_blk_decoder(*hw)]
+    cs += [x_blk_encoder(5, 3, 2), x_blk_fusion(5, 3, 2), x_blk_spatial_prior(5, 3, 2), x_blk_decoder(5, 3, 2)]
     names = [c["name"] for c in cs]
     assert len(set(names)) == len(names), sorted(n for n in names if names.count(n) > 1)
     return cs
@@ -775,7 +824,8 @@ def predict_block(shape, H, W, batch, xp, yp, altp=None, with_fin=None, fin_pack
 
 def predict_call(case, call):
     """the branches of one call of the table: run_dcb_chain's choice of outputs and spare buffers, Stride2W's and UpsampleW's
-    redirect of tmp == y to the third scratch plane, then predict_block per block"""
+    redirect of tmp == y to the third scratch plane, then predict_block per block (a chain's qf / qa go to its last block;
+    no launch choice depends on a scale)"""
     op = call["op"]
     if op == "subpel":
         return set()
@@ -916,7 +966,8 @@ def run_reference(ops, U, case, sd, bufs, qs):
                 else:
                     c = P(p)["c"]
                     y, ldy = U.ptr(dev.empty(case["batch"] * H * W, c)), c
-                block(p, x, ldx, y, ldy, H, W, False, call["qf"] if last else None, None, call["fin"] if last else None)
+                block(p, x, ldx, y, ldy, H, W, False, call["qf"] if last else None, call["qa"] if last else None,
+                      call["fin"] if last else None)
                 x, ldx = y, ldy
         elif op == "stride2":
             m = case["mods"][call["mod"]]
@@ -1010,7 +1061,8 @@ def f64_call(R, case, sd, x, qs):
         pre = block_prefixes(case, call["mod"])
         cur = x2
         for i, p in enumerate(pre):
-            ap = f64_block(R, sd, p, cur, geom, q=qs.get(call["qf"]) if i == len(pre) - 1 else None)
+            last = i == len(pre) - 1
+            ap = f64_block(R, sd, p, cur, geom, q=qs.get(call["qf"]) if last else None, q2=qs.get(call["qa"]) if last else None)
             cur = R.Mid.of(ap)
         return ap
     m = case["mods"][call["mod"]]

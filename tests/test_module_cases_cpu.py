@@ -308,6 +308,6 @@ def test_library_exports_the_test_surface():
     import ctypes
     from dcvc_amd import _lib
     for name in ("create", "destroy", "set_param", "load_blocks", "load_stride2", "load_upsample", "load_subpel", "load_fin",
-                 "block_info", "read", "scratch", "block_forward", "chain_forward", "stride2_forward", "upsample_forward",
+                 "block_info", "read", "scratch", "block_forward", "chain_forward", "chain_forward_qa", "stride2_forward", "upsample_forward",
                  "subpel_forward"):
         _lib.fn("dcvc_modtest_" + name, ctypes.c_int, [])

@@ -59,6 +59,8 @@ class Surface:
                                [ci, ci, ci, ci, vp, vp, ci, ci, vp])
         self.chain_forward = f("dcvc_modtest_chain_forward", ci, [vp, ci, ci, ci] + view + view + view + [ci, ci, vp] + view +
                                [ci, vp, vp, ci, ci, ci, ci, ci, vp])
+        self.chain_forward_qa = f("dcvc_modtest_chain_forward_qa", ci, [vp, ci, ci, ci] + view + view + view + [ci, ci, vp, vp] +
+                                  view + [ci, vp, vp, ci, ci, ci, ci, ci, vp])
         self.stride2_forward = f("dcvc_modtest_stride2_forward", ci, [vp, ci] + view + view + view + [ci, ci, vp])
         self.upsample_forward = f("dcvc_modtest_upsample_forward", ci, [vp, ci] + view + view + view + [ci, ci, vp, ci, ci, ci, vp])
         self.subpel_forward = f("dcvc_modtest_subpel_forward", ci, [vp, ci] + view + view + [ci, ci, vp, ci, ci, vp])
@@ -202,9 +204,10 @@ def run_module(mt, hd, case, bufs, qs, record=None, calls=None, sync=True):
                        U.ptr(qs.get(call["qf"])), U.ptr(qs.get(call["qa"])), *vw(call["alt"]), *blk_of(call["next"]),
                        int(call["done"]), *fin_of(call["fin"]), st)
             elif op == "chain":
-                U.call(mt.chain_forward, hd.h, m, call["first"], call["n"], *vw(call["x"]), *vw(call["tmp"]), *vw(call["y"]),
-                       H, W, U.ptr(qs.get(call["qf"])), *vw(call["tmp2"]), *fin_of(call["fin"]), *blk_of(call["after"]),
-                       int(call["done"]), st)
+                qa = () if call["qa"] is None else (U.ptr(qs[call["qa"]]),)
+                U.call(mt.chain_forward_qa if qa else mt.chain_forward, hd.h, m, call["first"], call["n"], *vw(call["x"]),
+                       *vw(call["tmp"]), *vw(call["y"]), H, W, U.ptr(qs.get(call["qf"])), *qa, *vw(call["tmp2"]),
+                       *fin_of(call["fin"]), *blk_of(call["after"]), int(call["done"]), st)
             elif op == "stride2":
                 U.call(mt.stride2_forward, hd.h, m, *vw(call["x"]), *vw(call["tmp"]), *vw(call["y"]), H, W, st)
             elif op == "upsample":
@@ -471,7 +474,7 @@ def test_handed_dc0_waits_in_the_plane_the_header_names(env, kind):
     """modules.h: with `next`, the following block's dc.0 output waits in s.t1 - or, behind a launch with its depthwise conv
     inside, in the plane Scratch::hand names (hand set: s.t2)"""
     mt, ops = env
-    case = M.dmci_encoder(9, 17) if kind == "dw_outside" else M.ld_fusion(9, 17)
+    case = M.x_blk_encoder(9, 17) if kind == "dw_outside" else M.ld_fusion(9, 17)
     if kind == "dw_inside":
         case = dict(case, calls=[M.blk("F", M.V("PF", 384), M.V("PF", 384), i=0, nxt=("F", 1))])
     else:

@@ -29,6 +29,29 @@ inline int ec_parallel_for(int symbols)
     return p < 1 ? 1 : (p > kMaxEcParallel ? kMaxEcParallel : p);
 }
 
+// Extents of one picture's planes at the strides the models work at: 1/8 (features), 1/16 (y), 1/16 padded to a multiple of
+// 4 (the hyper networks' input), 1/32 and 1/64 (z).
+struct Geometry {
+    int H8 = 0, W8 = 0, H16 = 0, W16 = 0, H16p = 0, W16p = 0, H32 = 0, W32 = 0, H64 = 0, W64 = 0;
+    int P8() const { return H8 * W8; }
+    int P16() const { return H16 * W16; }
+    int P16p() const { return H16p * W16p; }
+    int P32() const { return H32 * W32; }
+    int P64() const { return H64 * W64; }
+    bool padded() const { return H16p != H16 || W16p != W16; }
+
+    static Geometry of(int height, int width)
+    {
+        Geometry g;
+        g.H8 = ceil_div(height, 16) * 2; g.W8 = ceil_div(width, 16) * 2;
+        g.H16 = g.H8 / 2; g.W16 = g.W8 / 2;
+        g.H16p = ceil_div(g.H16, 4) * 4; g.W16p = ceil_div(g.W16, 4) * 4;      // dmc_common.cpp:73-83
+        g.H32 = g.H16p / 2; g.W32 = g.W16p / 2;
+        g.H64 = g.H16p / 4; g.W64 = g.W16p / 4;
+        return g;
+    }
+};
+
 // Pinned host buffer that only ever grows.
 template <typename T>
 class Pinned {

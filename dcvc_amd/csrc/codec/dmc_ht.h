@@ -7,19 +7,18 @@
 //   HT-L  the intra model's scheme: four symbol groups with their own scales (y_step_*)
 #pragma once
 
-#include "codec/codec_base.h"
+#include "codec/inter_codec.h"
 
 namespace dcvc {
 
-class DmcHtCodec : public CodecBase {
+class DmcHtCodec : public InterCodec {
 public:
     // video_model_ht.py:16-23
     static constexpr int kFrames = 8;
     static constexpr int kChSrcI = 192, kChSrc = kChSrcI * kFrames;
-    static constexpr int kChY = 256, kChZ = 128, kChD = 512, kChM = 512, kChRecon = 256;
+    static constexpr int kChY = 256, kChD = 512, kChM = 512, kChRecon = 256;
 
     explicit DmcHtCodec(bool is_hts);
-    ~DmcHtCodec();
     bool is_hts() const { return m_hts; }
 
     // dmc_hts_proxy.cpp:712-760
@@ -63,18 +62,9 @@ public:
     void run_recon_heads(unsigned mask, half_t* x_hat, hipStream_t stream);
 
 private:
-    struct Geometry {
-        int H8 = 0, W8 = 0, H16 = 0, W16 = 0, H16p = 0, W16p = 0, H32 = 0, W32 = 0, H64 = 0, W64 = 0;
-        int P8() const { return H8 * W8; }
-        int P16() const { return H16 * W16; }
-        int P16p() const { return H16p * W16p; }
-        int P32() const { return H32 * W32; }
-        int P64() const { return H64 * W64; }
-        bool padded() const { return H16p != H16 || W16p != W16; }
-    };
-
     void prepare(int height, int width);
-    void select_qp(int qp, hipStream_t st);
+    std::vector<StatePart> state_parts() const;
+    uint32_t state_magic() const { return 0x44434854u ^ (m_hts ? 1u : 0u); }     // "DCHT" / "DCHU"
     void run_fa_i(hipStream_t st);                    // FI -> memory
     void run_fa_m(hipStream_t st);                    // [memory | feature_p] -> memory
     void run_fe(hipStream_t st);                      // memory -> ctx
@@ -85,18 +75,13 @@ private:
     void run_reduction(hipStream_t st);               // common -> second half of the adaptor input
     void run_spatial_prior(int k, hipStream_t st);    // [y_hat so far | reduced] -> SP
     void run_decoder(hipStream_t st);                 // y_hat, ctx -> feature_p
+    void run_head(int i, bool need_trunk, half_t* head_out, hipStream_t st);   // feature_p -> head output of picture i
     void run_recon_head(half_t* x_hat, hipStream_t st);   // feature_p -> 8 pictures + FI
-    void run_recon_reset(hipStream_t st);             // feature_p -> FI (picture 7's head only)
     void enc_entropy_stage(hipStream_t st);
     void enc_stage0(hipStream_t st);                  // x, ctx, memory -> symbols, totals, z: all compress() codes
-    void entropy_encode(int qp);                      // worker thread
 
     const bool m_hts;
     // ---- parameters
-    DeviceArena m_wmem;
-    const half_t *m_q_encoder = nullptr, *m_q_decoder = nullptr, *m_q_feature = nullptr;
-    half_t *m_cur_q_encoder = nullptr, *m_cur_q_decoder = nullptr, *m_cur_q_feature = nullptr;
-    half_t* m_zeros = nullptr;
     DcbChain m_fa_i, m_fa_m, m_fe, m_enc1, m_dec1, m_fus, m_sp;
     ConvKW m_enc_down;
     DcbW m_henc0, m_hdec2;
@@ -109,13 +94,8 @@ private:
     DcbW m_rh_common[kFrames / 2];          // HT-S: recon_head.conv1.i.0
     DcbChain m_rh[kFrames];                 // HT-S: recon_head.conv2.i.{0,1,2}; HT-L: recon_head.conv.i.{0..4}
     FinW m_rh_head[kFrames];
-    float m_skip_thres = 0.f;
-    bool m_has_params = false;
 
-    // ---- resident buffers (per resolution)
-    Geometry m_g;
-    DeviceArena m_bmem;
-    Scratch m_s;
+    // ---- resident buffers (per resolution, views into m_bmem)
     half_t* m_FI = nullptr;      // [P8][192]   reference feature
     half_t* m_CATM = nullptr;    // [P8][1024]  memory | feature_p
     half_t* m_CATE = nullptr;    // [P8][2048]  x unshuffled (1536) | ctx (512); decoder.up out at 1024:1536
@@ -127,32 +107,14 @@ private:
     half_t* m_UPT = nullptr;     // biased upsampler temporary (HT-L)
     half_t *m_Y = nullptr, *m_Ypad = nullptr;
     half_t *m_Z1 = nullptr, *m_Z2 = nullptr, *m_Z3 = nullptr, *m_ZH = nullptr;
-    int8_t* m_ZI8 = nullptr;
     half_t *m_H1 = nullptr, *m_H2 = nullptr, *m_HP = nullptr;
     half_t* m_CATPF = nullptr;   // [P16][768]  hyper params | temporal params
     half_t* m_COMMON = nullptr;  // [P16][768]  q_dec | scales | means
     half_t* m_CATSP = nullptr;   // [P16][512]  y_hat so far | reduced params
     half_t* m_AD = nullptr;      // [P16][512]
     half_t* m_SP = nullptr;      // [P16][256] means (HT-S) / [P16][512] scales | means (HT-L)
-    int16_t *m_SYM = nullptr, *m_COMP = nullptr;
-    uint8_t *m_COND = nullptr, *m_IDX = nullptr, *m_CIDX = nullptr;
     size_t m_idx_region = 0;          // bytes per decode round trip in m_CIDX / m_h_idx: 16 (count) + its symbols
     static constexpr size_t kFirstIdxCopy = 192 * 1024;      // index bytes the first copy of a round trip takes along
-    int8_t *m_DECODED = nullptr, *m_YQ = nullptr;
-    int32_t *m_CNT = nullptr, *m_TOTALS = nullptr;
-    Pinned<int32_t> m_h_totals;
-    Pinned<int16_t> m_h_sym;
-    Pinned<int8_t> m_h_z;
-    Pinned<uint8_t> m_h_idx;
-    Pinned<int8_t> m_h_dec;
-    hipEvent_t m_ev_idx = nullptr;
-    int m_ec_parallel = 1;
-
-    // ---- temporal state flags
-    bool m_has_ref = false;
-    bool m_enc_ready = false;          // memory and ctx are those of the next chunk to encode
-    bool m_memory_has_value = false;
-    bool m_has_feature_p = false;
     unsigned m_recon_mask = 0xffu;     // pictures whose heads decompress() runs
 };
 

@@ -14,37 +14,18 @@ enum StageKey : int { kRef = 0, kEnc0 = 1, kEnc1 = 2 /* +reset */, kDec0 = 10 /*
 
 }  // namespace
 
-DmcHtCodec::DmcHtCodec(bool is_hts) : m_hts(is_hts)
-{
-    hip_check(hipEventCreateWithFlags(&m_ev_idx, hipEventDisableTiming), "hipEventCreate");
-}
-
-DmcHtCodec::~DmcHtCodec()
-{
-    quiesce();
-    if (m_ev_idx) (void)hipEventDestroy(m_ev_idx);
-}
+DmcHtCodec::DmcHtCodec(bool is_hts) : InterCodec("DMC-HT"), m_hts(is_hts) {}
 
 // ------------------------------------------------------------------------------------ set_param
 void DmcHtCodec::set_param(const ParamStore& ps, float skip_thres)
 {
-    quiesce();
-    clear_graphs();
-    m_wmem.release();
-    kernels_init();
-    m_skip_thres = skip_thres;
+    // refused before anything is touched: the parameters of an earlier call stay usable
     const bool want_hts = ps.has("recon_head.conv1.0.0.dc.0.weight");
     if (want_hts != m_hts) {
         throw std::invalid_argument(m_hts ? "DMCHTSProxy was given an HT-L state_dict"
                                           : "DMCHTLProxy was given an HT-S state_dict");
     }
-    m_q_encoder = upload_qp_table(ps, m_wmem, "q_encoder", kChD);
-    m_q_decoder = upload_qp_table(ps, m_wmem, "q_decoder", kChD);
-    m_q_feature = upload_qp_table(ps, m_wmem, "q_feature", kChD);
-    m_cur_q_encoder = m_wmem.alloc_half(kChD);
-    m_cur_q_decoder = m_wmem.alloc_half(kChD);
-    m_cur_q_feature = m_wmem.alloc_half(kChD);
-    m_zeros = m_wmem.alloc_half(2048);
+    begin_set_param(ps, skip_thres, kChD, kChD);
     const bool sc = !m_hts;          // block-level shortcuts of the hyper / temporal nets (HT-L only)
     m_fa_i.load(ps, m_wmem, "feature_adaptor_i.conv.");
     m_fa_m.load(ps, m_wmem, "feature_adaptor_m.conv.");
@@ -80,30 +61,14 @@ void DmcHtCodec::set_param(const ParamStore& ps, float skip_thres)
         }
     }
     if (m_sp3.conv.cout != (m_hts ? kChY : 2 * kChY)) throw std::invalid_argument("unexpected y_spatial_prior.conv.3 width");
-    load_cdf_tables(ps);
-    upload_code_length_tables(ps, m_wmem, kChZ, 1);      // for estimate_bits
-    m_has_params = true;
-    m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
+    finish_set_param(ps);
 }
 
 // ------------------------------------------------------------------------------------ buffers
 void DmcHtCodec::prepare(int height, int width)
 {
-    if (!m_has_params) throw std::runtime_error("DMC-HT: set_param() has not been called");
-    if (height <= 0 || width <= 0) throw std::invalid_argument("DMC-HT: empty picture");
-    const int H8 = ceil_div(height, 16) * 2, W8 = ceil_div(width, 16) * 2;
-    if (m_g.H8 == H8 && m_g.W8 == W8) return;
-    quiesce();
-    clear_graphs();
-    m_bmem.release();
-    m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
-    Geometry g;
-    g.H8 = H8; g.W8 = W8;
-    g.H16 = H8 / 2; g.W16 = W8 / 2;
-    g.H16p = ceil_div(g.H16, 4) * 4; g.W16p = ceil_div(g.W16, 4) * 4;      // dmc_common.cpp:73-83
-    g.H32 = g.H16p / 2; g.W32 = g.W16p / 2;
-    g.H64 = g.H16p / 4; g.W64 = g.W16p / 4;
-    m_g = g;
+    if (!begin_prepare(height, width)) return;
+    const Geometry& g = m_g;
     auto H = [&](size_t n) { return m_bmem.alloc_half(n); };
     const size_t P8 = g.P8(), P16 = g.P16(), P16p = g.P16p(), P32 = g.P32(), P64 = g.P64();
     m_s.elems = std::max<size_t>(P8 * kChD, P16p * 3 * kChY);
@@ -126,29 +91,10 @@ void DmcHtCodec::prepare(int height, int width)
     m_AD = H(P16 * 2 * kChY);
     m_SP = H(P16 * 2 * kChY);
     const size_t n = P16 * kChY;                 // all symbols of a chunk
-    m_SYM = static_cast<int16_t*>(m_bmem.alloc(n * 2));
-    m_COMP = static_cast<int16_t*>(m_bmem.alloc(n * 2));
-    m_COND = static_cast<uint8_t*>(m_bmem.alloc(n / 8 + 8));
-    m_IDX = static_cast<uint8_t*>(m_bmem.alloc(n));
     // decode side: [count, int32 | 12 B pad | compacted indexes] per round trip (HT-S: one of n symbols, HT-L: four
     // of n / 4), so that ONE device->host copy brings the count and (nearly always) all the indexes
     m_idx_region = (16 + (m_hts ? n : n / 4) + 15) / 16 * 16;
-    m_CIDX = static_cast<uint8_t*>(m_bmem.alloc((m_hts ? 1 : 4) * m_idx_region));
-    m_DECODED = static_cast<int8_t*>(m_bmem.alloc(n));
-    m_YQ = static_cast<int8_t*>(m_bmem.alloc(n));
-    m_CNT = static_cast<int32_t*>(m_bmem.alloc(sizeof(int32_t) * symbol_blocks(static_cast<int>(n))));
-    m_TOTALS = static_cast<int32_t*>(m_bmem.alloc(sizeof(int32_t) * 4));
-    m_h_totals.reserve(16);
-    m_h_sym.reserve(n);
-    m_h_z.reserve(P64 * kChZ + 64);
-    m_h_idx.reserve((m_hts ? 1 : 4) * m_idx_region);
-    m_h_dec.reserve(n);
-}
-
-void DmcHtCodec::select_qp(int qp, hipStream_t st)
-{
-    copy_qp_rows({{m_cur_q_encoder, m_q_encoder, kChD}, {m_cur_q_decoder, m_q_decoder, kChD},
-                  {m_cur_q_feature, m_q_feature, kChD}}, qp, st);
+    alloc_symbol_buffers(n, m_hts ? 1 : 4, m_idx_region);
 }
 
 // ------------------------------------------------------------------------------------ networks
@@ -254,45 +200,31 @@ void DmcHtCodec::run_decoder(hipStream_t st)
     m_dec1.forward(View(cat, ld, 2 * kChD), t, View(m_CATM + kChM, kChM + kChD, kChD), g.H8, g.W8, m_s, st, c);
 }
 
+// one picture's head. HT-S: pictures 2j and 2j+1 share the trunk recon_head.conv1.j, computed here when need_trunk
+void DmcHtCodec::run_head(int i, bool need_trunk, half_t* head_out, hipStream_t st)
+{
+    const Geometry& g = m_g;
+    const View feature(m_CATM + kChM, kChM + kChD, kChD);
+    const View rc(m_RC, kChD, kChD), rt(m_RT, kChRecon, kChRecon);
+    if (m_hts && need_trunk) m_rh_common[i / 2].forward(feature, rc, g.H8, g.W8, m_s, st);
+    const FinCall fin(m_rh_head[i], head_out, kChSrcI);     // the head conv closes the chain
+    ChainCall c; c.fin = &fin;
+    m_rh[i].forward(m_hts ? rc : feature, rt, rt, g.H8, g.W8, m_s, st, c);
+}
+
 void DmcHtCodec::run_recon_head(half_t* x_hat, hipStream_t st)
 {
     const Geometry& g = m_g;
-    const View feature(m_CATM + kChM, kChM + kChD, kChD);
-    const View rc(m_RC, kChD, kChD), rt(m_RT, kChRecon, kChRecon);
     const size_t picture = static_cast<size_t>(g.P8()) * 64 * 3;
-    bool trunk_done = false;       // HT-S: pictures 2j and 2j+1 share the trunk recon_head.conv1.j
+    bool trunk_done = false;
     for (int i = 0; i < kFrames; ++i) {
         if (i % 2 == 0) trunk_done = false;
         if (!(m_recon_mask >> i & 1u)) continue;
-        View trunk = feature;
-        if (m_hts) {
-            if (!trunk_done) m_rh_common[i / 2].forward(feature, rc, g.H8, g.W8, m_s, st);
-            trunk_done = true;
-            trunk = rc;
-        }
         half_t* head = (i == kFrames - 1) ? m_FI : m_RH;    // the last head output doubles as the reset feature
-        const FinCall fin(m_rh_head[i], head, kChSrcI);     // the head conv closes the chain
-        ChainCall c; c.fin = &fin;
-        m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, c);
+        run_head(i, !trunk_done, head, st);
+        trunk_done = true;
         shuffle8(head, kChSrcI, g.H8, g.W8, 3, true, x_hat + i * picture, st);
     }
-}
-
-void DmcHtCodec::run_recon_reset(hipStream_t st)
-{
-    // forward_reset, dmc_hts_proxy.cpp:346-358
-    const Geometry& g = m_g;
-    const View feature(m_CATM + kChM, kChM + kChD, kChD);
-    const View rc(m_RC, kChD, kChD), rt(m_RT, kChRecon, kChRecon);
-    const int i = kFrames - 1;
-    View trunk = feature;
-    if (m_hts) {
-        m_rh_common[i / 2].forward(feature, rc, g.H8, g.W8, m_s, st);
-        trunk = rc;
-    }
-    const FinCall fin(m_rh_head[i], m_FI, kChSrcI);
-    ChainCall c; c.fin = &fin;
-    m_rh[i].forward(trunk, rt, rt, g.H8, g.W8, m_s, st, c);
 }
 
 // ------------------------------------------------------------------------------------ reference frame
@@ -309,10 +241,7 @@ void DmcHtCodec::add_ref_feature_from_frame(const half_t* frame, int height, int
         });
     }
     leave(user);
-    m_has_ref = true;
-    m_enc_ready = apply_adaptor;
-    m_memory_has_value = apply_adaptor;
-    m_has_feature_p = false;
+    m_flags.after_add_ref(apply_adaptor);
 }
 
 // ------------------------------------------------------------------------------------ compress
@@ -369,20 +298,17 @@ void DmcHtCodec::enc_stage0(hipStream_t st)
 int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool reset, hipStream_t user)
 {
     prepare(height, width);
-    if (!m_enc_ready) {
-        throw std::runtime_error("DMC-HT compress: no reference feature "
-                                 "(call add_ref_feature_from_frame(frame, true) first)");
-    }
+    require_encoder_ready("compress");
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8(x, height, width, 3 * kFrames, m_CATE, g.H8, g.W8, st, kChSrc + kChD);
     run_stage(kEnc0, st, [&] { enc_stage0(st); });
-    submit(st, [this, qp] { entropy_encode(qp); });
+    submit(st, [this, qp] { entropy_encode(qp, m_hts ? 1 : 4); });
     run_stage(kEnc1 + (reset ? 1 : 0), st, [&] {
         run_decoder(st);
         if (reset) {
-            run_recon_reset(st);
+            run_head(kFrames - 1, true, m_FI, st);       // forward_reset, dmc_hts_proxy.cpp:346-358: picture 7's head only
             run_fa_i(st);
         } else {
             run_fa_m(st);
@@ -390,7 +316,7 @@ int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool re
         run_fe(st);
     });
     leave(user);
-    m_has_feature_p = true;
+    m_flags.after_compress();
     wait_job();
     return m_ec_parallel;
 }
@@ -399,15 +325,7 @@ int DmcHtCodec::compress(const half_t* x, int height, int width, int qp, bool re
 void DmcHtCodec::estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept,
                                hipStream_t user)
 {
-    // every refusal comes before anything is touched: prepare() with another size would drop the temporal state
-    if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMC-HT estimate_bits: qp must be in [0, 63]");
-    if (!m_has_params || !m_enc_ready) {
-        throw std::runtime_error("DMC-HT estimate_bits: no reference feature "
-                                 "(call add_ref_feature_from_frame(frame, true) first)");
-    }
-    if (height <= 0 || width <= 0 || ceil_div(height, 16) * 2 != m_g.H8 || ceil_div(width, 16) * 2 != m_g.W8) {
-        throw std::invalid_argument("DMC-HT estimate_bits: the picture size is not the one of the temporal state");
-    }
+    check_probe(qp, height, width);
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
@@ -420,45 +338,17 @@ void DmcHtCodec::estimate_bits(const half_t* x, int height, int width, int qp, i
     leave(user);
 }
 
-void DmcHtCodec::entropy_encode(int qp)
-{
-    const Geometry& g = m_g;
-    const int groups = m_hts ? 1 : 4;
-    hip_check(hipMemcpyAsync(m_h_totals.get(), m_TOTALS, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, m_io_stream), "D2H totals");
-    const int nz = g.P64() * kChZ;
-    hip_check(hipMemcpyAsync(m_h_z.get(), m_ZI8, nz, hipMemcpyDeviceToHost, m_io_stream), "D2H z");
-    hip_check(hipStreamSynchronize(m_io_stream), "sync io");
-    int base[4] = { 0, 0, 0, 0 }, total = 0;
-    for (int k = 0; k < groups; ++k) {
-        base[k] = total;
-        total += m_h_totals[k];
-    }
-    if (total > 0) {
-        hip_check(hipMemcpyAsync(m_h_sym.get(), m_COMP, static_cast<size_t>(total) * 2, hipMemcpyDeviceToHost, m_io_stream), "D2H symbols");
-        hip_check(hipStreamSynchronize(m_io_stream), "sync io");
-    }
-    m_ec_parallel = ec_parallel_for(total);
-    m_enc.reset();
-    m_enc.set_parallel(m_ec_parallel);
-    for (int k = groups - 1; k >= 0; --k) m_enc.push_y(m_h_sym.get() + base[k], m_h_totals[k]);
-    m_enc.push_z(m_h_z.get(), nz, qp * kChZ, kChZ);
-    m_enc.flush();
-}
-
 // ------------------------------------------------------------------------------------ decompress
 void DmcHtCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int height, int width,
                             int ec_parallel, bool reset, half_t* x_hat, hipStream_t user)
 {
     prepare(height, width);
-    if (m_memory_has_value ? !m_has_feature_p : !m_has_ref) {
-        throw std::runtime_error("DMC-HT decompress: no reference feature "
-                                 "(call add_ref_feature_from_frame first)");
-    }
+    require_decoder_ready();
     const Geometry& g = m_g;
     const int ldc = 3 * kChY;
     hipStream_t st = enter(user);
     select_qp(qp, st);
-    const bool extend = m_memory_has_value;
+    const bool extend = m_flags.memory_has_value;
     run_stage(kDec0 + (extend ? 1 : 0), st, [&] {
         if (extend) run_fa_m(st);
         else run_fa_i(st);
@@ -483,26 +373,13 @@ void DmcHtCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int heig
             mask_dec_index(d, st);
             compact(m_IDX, 1, m_COND, m_CNT, ny, m_CIDX, m_TOTALS, 0, st);
         });
-        // (one copy for count + indexes in front of the context network was measured SLOWER here - LD 300 -> 271,
-        // HT-S 570 -> 541 pictures/s: the 192 KB copy sits in the stream in front of the context network's
-        // kernels; the two small copies with a synchronisation in between do not hold them up)
-        hip_check(hipMemcpyAsync(m_h_totals.get(), m_TOTALS, sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H totals");
-        hip_check(hipStreamSynchronize(st), "sync");
-        const int n = m_h_totals[0];
-        if (n > 0) {
-            hip_check(hipMemcpyAsync(m_h_idx.get(), m_CIDX, n, hipMemcpyDeviceToHost, st), "D2H indexes");
-            hip_check(hipEventRecord(m_ev_idx, st), "hipEventRecord");
-        }
+        const int n = fetch_total_and_indexes(st);
         // context network + the y-independent reduction run while the host decodes y
         run_stage(kDec2, st, [&] {
             run_fe(st);
             run_reduction(st);
         });
-        if (n > 0) {
-            hip_check(hipEventSynchronize(m_ev_idx), "hipEventSynchronize");
-            m_dec.decode_y(m_h_idx.get(), n, m_h_dec.get());
-            hip_check(hipMemcpyAsync(m_DECODED, m_h_dec.get(), n, hipMemcpyHostToDevice, st), "H2D symbols");
-        }
+        decode_y_and_upload(n, st);
         run_stage(kDecStep + 3, st, [&] {
             MaskStepDec d;
             d.decoded = m_DECODED; d.cond = m_COND; d.block_count = m_CNT; d.totals = m_TOTALS; d.yq = m_YQ;
@@ -574,10 +451,7 @@ void DmcHtCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int heig
         }
     }
     leave(user);
-    m_has_feature_p = true;
-    m_has_ref = true;
-    m_memory_has_value = !reset;
-    m_enc_ready = false;                   // ctx was advanced by this chunk; the encoder side must be re-seeded
+    m_flags.after_decompress(reset);       // ctx was advanced by this chunk; the encoder side must be re-seeded
 }
 
 // ------------------------------------------------------------------------------------ recon-head fan-out
@@ -592,7 +466,7 @@ void DmcHtCodec::set_recon_mask(unsigned mask)
 
 size_t DmcHtCodec::export_feature(void* dst, size_t cap, hipStream_t user)
 {
-    if (!m_has_params || m_g.H8 == 0 || !m_has_feature_p) throw std::runtime_error("DMC-HT export_feature: no feature_p yet");
+    if (!m_has_params || m_g.H8 == 0 || !m_flags.has_feature_p) throw std::runtime_error("DMC-HT export_feature: no feature_p yet");
     const Geometry& g = m_g;
     const size_t bytes = static_cast<size_t>(g.P8()) * kChD * sizeof(half_t);
     if (dst == nullptr) return bytes;
@@ -614,12 +488,12 @@ void DmcHtCodec::import_feature(const void* src, size_t bytes, int height, int w
     hipStream_t st = enter(user);
     replicate_pad(static_cast<const half_t*>(src), kChD, g.H8, g.W8, kChD, 0, 0, m_CATM + kChM, kChM + kChD, st);
     leave(user);
-    m_has_feature_p = true;
+    m_flags.has_feature_p = true;
 }
 
 void DmcHtCodec::run_recon_heads(unsigned mask, half_t* x_hat, hipStream_t user)
 {
-    if (!m_has_params || m_g.H8 == 0 || !m_has_feature_p) throw std::runtime_error("DMC-HT run_recon_heads: no feature_p");
+    if (!m_has_params || m_g.H8 == 0 || !m_flags.has_feature_p) throw std::runtime_error("DMC-HT run_recon_heads: no feature_p");
     hipStream_t st = enter(user);
     const unsigned keep = m_recon_mask;
     m_recon_mask = mask & 0xffu;
@@ -633,98 +507,41 @@ void DmcHtCodec::run_recon_heads(unsigned mask, half_t* x_hat, hipStream_t user)
     leave(user);
 }
 
-// ------------------------------------------------------------------------------------ state hand-off
-namespace {
-
-struct HtStateHeader {
-    uint32_t magic, h8, w8, flags;
-    uint32_t reserved[12];
-};
-constexpr uint32_t kHtMagic = 0x44434854;     // "DCHT"
-
-}  // namespace
+// ------------------------------------------------------------------------------------ state hand-off, debug
+std::vector<InterCodec::StatePart> DmcHtCodec::state_parts() const
+{
+    const size_t P8 = m_g.P8();
+    // reference feature, memory | feature_p, ctx (a channel slice)
+    return {{m_FI, kChSrcI, kChSrcI, P8}, {m_CATM, kChM + kChD, kChM + kChD, P8}, {m_CATE + kChSrc, kChD, kChSrc + kChD, P8}};
+}
 
 size_t DmcHtCodec::export_state(void* dst, size_t cap, hipStream_t user)
 {
-    if (!m_has_params || m_g.H8 == 0) throw std::runtime_error("DMC-HT export_state: no state yet");
-    const Geometry& g = m_g;
-    const size_t n_fi = static_cast<size_t>(g.P8()) * kChSrcI, n_catm = static_cast<size_t>(g.P8()) * (kChM + kChD),
-                 n_ctx = static_cast<size_t>(g.P8()) * kChD;
-    const size_t bytes = sizeof(HtStateHeader) + 2 * (n_fi + n_catm + n_ctx);
-    if (dst == nullptr) return bytes;
-    if (cap < bytes) throw std::invalid_argument("export_state: destination too small");
-    hipStream_t st = enter(user);
-    HtStateHeader h{};
-    h.magic = kHtMagic ^ (m_hts ? 1u : 0u); h.h8 = g.H8; h.w8 = g.W8;
-    h.flags = (m_has_ref ? 1u : 0u) | (m_enc_ready ? 2u : 0u) | (m_memory_has_value ? 4u : 0u) | (m_has_feature_p ? 8u : 0u);
-    char* out = static_cast<char*>(dst);
-    hip_check(hipMemcpyAsync(out, &h, sizeof(h), hipMemcpyHostToDevice, st), "state header");
-    hip_check(hipStreamSynchronize(st), "sync");
-    out += sizeof(h);
-    hip_check(hipMemcpyAsync(out, m_FI, 2 * n_fi, hipMemcpyDeviceToDevice, st), "state D2D");
-    out += 2 * n_fi;
-    hip_check(hipMemcpyAsync(out, m_CATM, 2 * n_catm, hipMemcpyDeviceToDevice, st), "state D2D");
-    out += 2 * n_catm;
-    hip_check(hipMemcpy2DAsync(out, 2 * kChD, m_CATE + kChSrc, 2 * (kChSrc + kChD), 2 * kChD, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
-    leave(user);
-    return bytes;
+    return InterCodec::export_state(state_magic(), state_parts(), dst, cap, user);
 }
 
 void DmcHtCodec::import_state(const void* src, size_t bytes, int height, int width, hipStream_t user)
 {
     prepare(height, width);
-    const Geometry& g = m_g;
-    const size_t n_fi = static_cast<size_t>(g.P8()) * kChSrcI, n_catm = static_cast<size_t>(g.P8()) * (kChM + kChD),
-                 n_ctx = static_cast<size_t>(g.P8()) * kChD;
-    if (bytes != sizeof(HtStateHeader) + 2 * (n_fi + n_catm + n_ctx)) {
-        throw std::invalid_argument("import_state: size does not match this picture size");
-    }
-    hipStream_t st = enter(user);
-    HtStateHeader h{};
-    const char* in = static_cast<const char*>(src);
-    hip_check(hipMemcpyAsync(&h, in, sizeof(h), hipMemcpyDeviceToHost, st), "state header");
-    hip_check(hipStreamSynchronize(st), "sync");
-    if (h.magic != (kHtMagic ^ (m_hts ? 1u : 0u)) || h.h8 != static_cast<uint32_t>(g.H8) || h.w8 != static_cast<uint32_t>(g.W8)) {
-        throw std::invalid_argument("import_state: not a state of this model structure and picture size");
-    }
-    in += sizeof(h);
-    hip_check(hipMemcpyAsync(m_FI, in, 2 * n_fi, hipMemcpyDeviceToDevice, st), "state D2D");
-    in += 2 * n_fi;
-    hip_check(hipMemcpyAsync(m_CATM, in, 2 * n_catm, hipMemcpyDeviceToDevice, st), "state D2D");
-    in += 2 * n_catm;
-    hip_check(hipMemcpy2DAsync(m_CATE + kChSrc, 2 * (kChSrc + kChD), in, 2 * kChD, 2 * kChD, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
-    leave(user);
-    m_has_ref = h.flags & 1u; m_enc_ready = h.flags & 2u; m_memory_has_value = h.flags & 4u; m_has_feature_p = h.flags & 8u;
+    InterCodec::import_state(state_magic(), "import_state: not a state of this model structure and picture size", state_parts(),
+                             src, bytes, user);
 }
 
-// ------------------------------------------------------------------------------------ debug
 size_t DmcHtCodec::debug_read(const std::string& name, void* dst, size_t cap, hipStream_t st)
 {
     const Geometry& g = m_g;
-    const void* src = nullptr;
-    size_t pixels = 0, ch_bytes = 0, pitch = 0;
-    auto view = [&](const void* p, int P, int c, int ld, int elem) {
-        src = p; pixels = P; ch_bytes = static_cast<size_t>(c) * elem; pitch = static_cast<size_t>(ld) * elem;
-    };
-    if (name == "y") view(m_Y, g.P16(), kChY, kChY, 2);
-    else if (name == "y_hat") view(m_CATSP, g.P16(), kChY, 2 * kChY, 2);
-    else if (name == "common") view(m_COMMON, g.P16(), 3 * kChY, 3 * kChY, 2);
-    else if (name == "z_i8") view(m_ZI8, g.P64(), kChZ, kChZ, 1);
-    else if (name == "memory") view(m_CATM, g.P8(), kChM, kChM + kChD, 2);
-    else if (name == "feature_p") view(m_CATM + kChM, g.P8(), kChD, kChM + kChD, 2);
-    else if (name == "ctx") view(m_CATE + kChSrc, g.P8(), kChD, kChSrc + kChD, 2);
-    else if (name == "feature_i") view(m_FI, g.P8(), kChSrcI, kChSrcI, 2);
-    else if (name == "symbols") view(m_COMP, 1, g.P16() * kChY, g.P16() * kChY, 2);
-    else if (name == "totals") view(m_TOTALS, 1, 4, 4, 4);
-    else throw std::invalid_argument("unknown debug tensor '" + name + "'");
-    const size_t bytes = pixels * ch_bytes;
-    if (dst != nullptr) {
-        if (cap < bytes) throw std::invalid_argument("debug_read: destination too small");
-        hip_check(hipStreamSynchronize(st), "sync");
-        hip_check(hipStreamSynchronize(m_cs), "sync");
-        hip_check(hipMemcpy2D(dst, ch_bytes, src, pitch, ch_bytes, pixels, hipMemcpyDeviceToHost), "debug D2H");
-    }
-    return bytes;
+    const size_t P8 = g.P8(), P16 = g.P16(), P64 = g.P64();
+    return InterCodec::debug_read({{"y", m_Y, P16, kChY, kChY, 2},
+                                   {"y_hat", m_CATSP, P16, kChY, 2 * kChY, 2},
+                                   {"common", m_COMMON, P16, 3 * kChY, 3 * kChY, 2},
+                                   {"z_i8", m_ZI8, P64, kChZ, kChZ, 1},
+                                   {"memory", m_CATM, P8, kChM, kChM + kChD, 2},
+                                   {"feature_p", m_CATM + kChM, P8, kChD, kChM + kChD, 2},
+                                   {"ctx", m_CATE + kChSrc, P8, kChD, kChSrc + kChD, 2},
+                                   {"feature_i", m_FI, P8, kChSrcI, kChSrcI, 2},
+                                   {"symbols", m_COMP, 1, g.P16() * kChY, g.P16() * kChY, 2},
+                                   {"totals", m_TOTALS, 1, 4, 4, 4}},
+                                  name, dst, cap, st);
 }
 
 }  // namespace dcvc

@@ -4,17 +4,16 @@
 // feature, context, temporal prior) stays resident in HBM between calls.
 #pragma once
 
-#include "codec/codec_base.h"
+#include "codec/inter_codec.h"
 
 namespace dcvc {
 
-class DmcLdCodec : public CodecBase {
+class DmcLdCodec : public InterCodec {
 public:
     // video_model_ld.py:16-21
-    static constexpr int kChSrc = 192, kChY = 128, kChZ = 128, kChD = 256, kChM = 256;
+    static constexpr int kChSrc = 192, kChY = 128, kChD = 256, kChM = 256;
 
     DmcLdCodec();
-    ~DmcLdCodec();
 
     // dmc_ld_proxy.cpp:595-639
     void set_param(const ParamStore& ps, float skip_thres);
@@ -49,18 +48,8 @@ public:
     void import_state(const void* src, size_t bytes, int height, int width, hipStream_t stream);
 
 private:
-    struct Geometry {
-        int H8 = 0, W8 = 0, H16 = 0, W16 = 0, H16p = 0, W16p = 0, H32 = 0, W32 = 0, H64 = 0, W64 = 0;
-        int P8() const { return H8 * W8; }
-        int P16() const { return H16 * W16; }
-        int P16p() const { return H16p * W16p; }
-        int P32() const { return H32 * W32; }
-        int P64() const { return H64 * W64; }
-        bool padded() const { return H16p != H16 || W16p != W16; }
-    };
-
     void prepare(int height, int width);
-    void select_qp(int qp, hipStream_t st);
+    std::vector<StatePart> state_parts() const;
     // sub-networks (operands are fixed views of the resident buffers, see prepare())
     // feed_fe: the feature extractor runs RIGHT behind this chain (nothing in between touches the scratch planes): the
     // chain's last launch also computes dc.0 of its first block (ChainCall::after), and run_fe is told so (dc0_done ->
@@ -76,13 +65,8 @@ private:
     void run_decoder(hipStream_t st);                 // y_hat, ctx -> feature_p
     void run_recon_head(half_t* x_hat, hipStream_t st);   // feature_p -> FI (+ x_hat)
     void enc_stage0(hipStream_t st);                  // x, ctx, temporal -> symbols, totals, z: all compress() codes
-    void entropy_encode(int qp);                      // worker thread
 
     // ---- parameters
-    DeviceArena m_wmem;
-    const half_t *m_q_encoder = nullptr, *m_q_decoder = nullptr, *m_q_feature = nullptr;
-    half_t *m_cur_q_encoder = nullptr, *m_cur_q_decoder = nullptr, *m_cur_q_feature = nullptr;
-    half_t* m_zeros = nullptr;
     DcbW m_fa_i[4], m_fa_m[4], m_fe[5];
     DcbW m_encb[3];               // encoder.conv1.0, .1 and encoder.conv2: one chain of three blocks, the last with the quant scale
     ConvKW m_enc_down;
@@ -100,13 +84,8 @@ private:
     FinW m_dec2;
     DcbW m_rh[3];
     FinW m_rh_head;
-    float m_skip_thres = 0.f;
-    bool m_has_params = false;
 
-    // ---- resident buffers (per resolution)
-    Geometry m_g;
-    DeviceArena m_bmem;
-    Scratch m_s;
+    // ---- resident buffers (per resolution, views into m_bmem)
     half_t* m_FI = nullptr;      // [P8][192]  reference feature: unshuffled I picture / recon-head output
     half_t* m_CATM = nullptr;    // [P8][512]  memory | feature_p          (feature_adaptor_m input)
     half_t* m_CATD = nullptr;    // [P8][512]  decoder.up out (x unshuffled at 64:256) | ctx
@@ -114,30 +93,12 @@ private:
     half_t* m_T2 = nullptr;
     half_t *m_Y = nullptr, *m_Ypad = nullptr;
     half_t *m_Z1 = nullptr, *m_Z2 = nullptr, *m_Z3 = nullptr, *m_ZH = nullptr;
-    int8_t* m_ZI8 = nullptr;
     half_t *m_H1 = nullptr, *m_H2 = nullptr, *m_HP = nullptr;
     half_t* m_TP = nullptr;      // [P16][256] temporal params: state, written by run_tpe alone
     half_t* m_PF = nullptr;      // [P16][384] hyper params | temporal params * q_feature: the fusion chain, in place
     half_t* m_CATSP = nullptr;   // [P16][512] y_hat | q_dec | scales | means
     half_t* m_SPT = nullptr;     // [P16][256]
     half_t* m_MEANS1 = nullptr;  // [P16][128]
-    int16_t *m_SYM = nullptr, *m_COMP = nullptr;
-    uint8_t *m_COND = nullptr, *m_IDX = nullptr, *m_CIDX = nullptr;
-    int8_t *m_DECODED = nullptr, *m_YQ = nullptr;
-    int32_t *m_CNT = nullptr, *m_TOTALS = nullptr;
-    Pinned<int32_t> m_h_totals;
-    Pinned<int16_t> m_h_sym;
-    Pinned<int8_t> m_h_z;
-    Pinned<uint8_t> m_h_idx;
-    Pinned<int8_t> m_h_dec;
-    hipEvent_t m_ev_idx = nullptr;
-    int m_ec_parallel = 1;
-
-    // ---- temporal state flags
-    bool m_has_ref = false;            // FI valid
-    bool m_enc_ready = false;          // memory, ctx and temporal params are those of the next picture to encode
-    bool m_memory_has_value = false;   // decoder: the next picture extends the memory (else restarts from FI)
-    bool m_has_feature_p = false;
 };
 
 }  // namespace dcvc

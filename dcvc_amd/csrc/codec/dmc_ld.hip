@@ -5,9 +5,6 @@
 #include "codec/dmc_ld.h"
 
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 
 namespace dcvc {
 
@@ -15,39 +12,22 @@ namespace {
 
 enum StageKey : int { kRef = 0, kEnc0 = 1, kEnc1 = 2 /* +reset */, kDec0 = 10 /* +memory_has_value */,
                       kDec1 = 12, kDec2 = 13, kDec3 = 14 };
+constexpr uint32_t kLdMagic = 0x44434c44;     // "DCLD"
 
 }  // namespace
 
-DmcLdCodec::DmcLdCodec()
+DmcLdCodec::DmcLdCodec() : InterCodec("DMC-LD")
 {
     // LD's kernels are short (4.2 ms of kernel time in ~350 launches per 1080p picture): measured on
     // MI355X, eager launches on the codec's stream beat hipGraph replay (139 vs 123 pictures/s), the
     // other codecs are neutral. set_use_graphs(true) switches back.
     m_use_graphs = false;
-    hip_check(hipEventCreateWithFlags(&m_ev_idx, hipEventDisableTiming), "hipEventCreate");
-}
-
-DmcLdCodec::~DmcLdCodec()
-{
-    quiesce();
-    if (m_ev_idx) (void)hipEventDestroy(m_ev_idx);
 }
 
 // ------------------------------------------------------------------------------------ set_param
 void DmcLdCodec::set_param(const ParamStore& ps, float skip_thres)
 {
-    quiesce();
-    clear_graphs();
-    m_wmem.release();
-    kernels_init();
-    m_skip_thres = skip_thres;
-    m_q_encoder = upload_qp_table(ps, m_wmem, "q_encoder", kChD);
-    m_q_decoder = upload_qp_table(ps, m_wmem, "q_decoder", kChD);
-    m_q_feature = upload_qp_table(ps, m_wmem, "q_feature", 2 * kChY);
-    m_cur_q_encoder = m_wmem.alloc_half(kChD);
-    m_cur_q_decoder = m_wmem.alloc_half(kChD);
-    m_cur_q_feature = m_wmem.alloc_half(2 * kChY);
-    m_zeros = m_wmem.alloc_half(2048);
+    begin_set_param(ps, skip_thres, kChD, 2 * kChY);
     auto chain = [&](DcbW* blocks, int n, const std::string& prefix) {
         for (int i = 0; i < n; ++i) blocks[i].load(ps, m_wmem, prefix + std::to_string(i) + ".");
     };
@@ -73,30 +53,14 @@ void DmcLdCodec::set_param(const ParamStore& ps, float skip_thres)
     m_dec2.load(ps, m_wmem, "decoder.conv2.");
     chain(m_rh, 3, "recon_head.conv.");
     m_rh_head.load(ps, m_wmem, "recon_head.head.");
-    load_cdf_tables(ps);
-    upload_code_length_tables(ps, m_wmem, kChZ, 1);      // for estimate_bits
-    m_has_params = true;
-    m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;
+    finish_set_param(ps);
 }
 
 // ------------------------------------------------------------------------------------ buffers
 void DmcLdCodec::prepare(int height, int width)
 {
-    if (!m_has_params) throw std::runtime_error("DMC-LD: set_param() has not been called");
-    if (height <= 0 || width <= 0) throw std::invalid_argument("DMC-LD: empty picture");
-    const int H8 = ceil_div(height, 16) * 2, W8 = ceil_div(width, 16) * 2;
-    if (m_g.H8 == H8 && m_g.W8 == W8) return;
-    quiesce();
-    clear_graphs();
-    m_bmem.release();
-    m_has_ref = m_enc_ready = m_memory_has_value = m_has_feature_p = false;   // the state had another size
-    Geometry g;
-    g.H8 = H8; g.W8 = W8;
-    g.H16 = H8 / 2; g.W16 = W8 / 2;
-    g.H16p = ceil_div(g.H16, 4) * 4; g.W16p = ceil_div(g.W16, 4) * 4;      // dmc_common.cpp:73-83
-    g.H32 = g.H16p / 2; g.W32 = g.W16p / 2;
-    g.H64 = g.H16p / 4; g.W64 = g.W16p / 4;
-    m_g = g;
+    if (!begin_prepare(height, width)) return;
+    const Geometry& g = m_g;
     auto H = [&](size_t n) { return m_bmem.alloc_half(n); };
     const size_t P8 = g.P8(), P16 = g.P16(), P16p = g.P16p(), P32 = g.P32(), P64 = g.P64();
     m_s.elems = std::max<size_t>(P8 * (kChM / 2), P16p * (3 * kChY / 2));
@@ -115,26 +79,7 @@ void DmcLdCodec::prepare(int height, int width)
     m_SPT = H(P16 * 2 * kChY);
     m_MEANS1 = H(P16 * kChY);
     const size_t n = P16 * kChY;
-    m_SYM = static_cast<int16_t*>(m_bmem.alloc(n * 2));
-    m_COMP = static_cast<int16_t*>(m_bmem.alloc(n * 2));
-    m_COND = static_cast<uint8_t*>(m_bmem.alloc(n / 8 + 8));
-    m_IDX = static_cast<uint8_t*>(m_bmem.alloc(n));
-    m_CIDX = static_cast<uint8_t*>(m_bmem.alloc(n));
-    m_DECODED = static_cast<int8_t*>(m_bmem.alloc(n));
-    m_YQ = static_cast<int8_t*>(m_bmem.alloc(n));
-    m_CNT = static_cast<int32_t*>(m_bmem.alloc(sizeof(int32_t) * symbol_blocks(static_cast<int>(n))));
-    m_TOTALS = static_cast<int32_t*>(m_bmem.alloc(sizeof(int32_t) * 4));
-    m_h_totals.reserve(16);
-    m_h_sym.reserve(n);
-    m_h_z.reserve(P64 * kChZ + 64);
-    m_h_idx.reserve(n);
-    m_h_dec.reserve(n);
-}
-
-void DmcLdCodec::select_qp(int qp, hipStream_t st)
-{
-    copy_qp_rows({{m_cur_q_encoder, m_q_encoder, kChD}, {m_cur_q_decoder, m_q_decoder, kChD},
-                  {m_cur_q_feature, m_q_feature, 2 * kChY}}, qp, st);
+    alloc_symbol_buffers(n, 1, n);      // the compacted indexes of the one round trip, no count in front
 }
 
 // ------------------------------------------------------------------------------------ networks
@@ -261,26 +206,20 @@ void DmcLdCodec::add_ref_feature_from_frame(const half_t* frame, int height, int
         });
     }
     leave(user);
-    m_has_ref = true;
-    m_enc_ready = apply_adaptor;
-    m_memory_has_value = apply_adaptor;
-    m_has_feature_p = false;
+    m_flags.after_add_ref(apply_adaptor);
 }
 
 // ------------------------------------------------------------------------------------ compress
 int DmcLdCodec::compress(const half_t* x, int height, int width, int qp, bool reset, hipStream_t user)
 {
     prepare(height, width);
-    if (!m_enc_ready) {
-        throw std::runtime_error("DMC-LD compress: no reference feature "
-                                 "(call add_ref_feature_from_frame(frame, true) first)");
-    }
+    require_encoder_ready("compress");
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8(x, height, width, 3, m_CATD + 64, g.H8, g.W8, st, kChD + kChM);   // x varies: outside the graph
     run_stage(kEnc0, st, [&] { enc_stage0(st); });
-    submit(st, [this, qp] { entropy_encode(qp); });
+    submit(st, [this, qp] { entropy_encode(qp, 1); });
     // decoder + temporal state update run on the GPU while the worker entropy-codes on the host
     run_stage(kEnc1 + (reset ? 1 : 0), st, [&] {
         run_decoder(st);
@@ -294,7 +233,7 @@ int DmcLdCodec::compress(const half_t* x, int height, int width, int qp, bool re
         run_tpe(st);
     });
     leave(user);
-    m_has_feature_p = true;
+    m_flags.after_compress();
     wait_job();
     return m_ec_parallel;
 }
@@ -324,15 +263,7 @@ void DmcLdCodec::enc_stage0(hipStream_t st)
 void DmcLdCodec::estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept,
                                hipStream_t user)
 {
-    // every refusal comes before anything is touched: prepare() with another size would drop the temporal state
-    if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMC-LD estimate_bits: qp must be in [0, 63]");
-    if (!m_has_params || !m_enc_ready) {
-        throw std::runtime_error("DMC-LD estimate_bits: no reference feature "
-                                 "(call add_ref_feature_from_frame(frame, true) first)");
-    }
-    if (height <= 0 || width <= 0 || ceil_div(height, 16) * 2 != m_g.H8 || ceil_div(width, 16) * 2 != m_g.W8) {
-        throw std::invalid_argument("DMC-LD estimate_bits: the picture size is not the one of the temporal state");
-    }
+    check_probe(qp, height, width);
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
@@ -344,51 +275,16 @@ void DmcLdCodec::estimate_bits(const half_t* x, int height, int width, int qp, i
     leave(user);
 }
 
-void DmcLdCodec::entropy_encode(int qp)
-{
-    static const bool trace = getenv("DCVC_TIMING") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (trace) {
-            fprintf(stderr, "[dcvc]   ld encode: %s at +%.0f us\n", what,
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-        }
-    };
-    // dmc_ld_proxy.cpp worker, Encode: y symbols then z
-    const Geometry& g = m_g;
-    hip_check(hipMemcpyAsync(m_h_totals.get(), m_TOTALS, sizeof(int32_t), hipMemcpyDeviceToHost, m_io_stream), "D2H totals");
-    const int nz = g.P64() * kChZ;
-    hip_check(hipMemcpyAsync(m_h_z.get(), m_ZI8, nz, hipMemcpyDeviceToHost, m_io_stream), "D2H z");
-    hip_check(hipStreamSynchronize(m_io_stream), "sync io");
-    const int total = m_h_totals[0];
-    lap("totals + z on the host (GPU stage 0 done)");
-    if (total > 0) {
-        hip_check(hipMemcpyAsync(m_h_sym.get(), m_COMP, static_cast<size_t>(total) * 2, hipMemcpyDeviceToHost, m_io_stream), "D2H symbols");
-        hip_check(hipStreamSynchronize(m_io_stream), "sync io");
-    }
-    lap("symbols on the host");
-    m_ec_parallel = ec_parallel_for(total);
-    m_enc.reset();
-    m_enc.set_parallel(m_ec_parallel);
-    m_enc.push_y(m_h_sym.get(), total);
-    m_enc.push_z(m_h_z.get(), nz, qp * kChZ, kChZ);
-    m_enc.flush();
-    lap("rANS done");
-}
-
 // ------------------------------------------------------------------------------------ decompress
 void DmcLdCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int height, int width,
                             int ec_parallel, bool reset, half_t* x_hat, hipStream_t user)
 {
     prepare(height, width);
-    if (m_memory_has_value ? !m_has_feature_p : !m_has_ref) {
-        throw std::runtime_error("DMC-LD decompress: no reference feature "
-                                 "(call add_ref_feature_from_frame first)");
-    }
+    require_decoder_ready();
     const Geometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
-    const bool extend = m_memory_has_value;
+    const bool extend = m_flags.memory_has_value;
     run_stage(kDec0 + (extend ? 1 : 0), st, [&] {
         if (extend) run_fa_m(st);
         else run_fa_i(st);
@@ -411,20 +307,10 @@ void DmcLdCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int heig
         mask_dec_index(d, st);
         compact(m_IDX, 1, m_COND, m_CNT, ny, m_CIDX, m_TOTALS, 0, st);
     });
-    hip_check(hipMemcpyAsync(m_h_totals.get(), m_TOTALS, sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H totals");
-    hip_check(hipStreamSynchronize(st), "sync");
-    const int n = m_h_totals[0];
-    if (n > 0) {
-        hip_check(hipMemcpyAsync(m_h_idx.get(), m_CIDX, n, hipMemcpyDeviceToHost, st), "D2H indexes");
-        hip_check(hipEventRecord(m_ev_idx, st), "hipEventRecord");
-    }
+    const int n = fetch_total_and_indexes(st);
     // the context network runs while the host decodes y (dmc_ld_proxy.cpp:556-560)
     run_stage(kDec2, st, [&] { run_fe(st); });
-    if (n > 0) {
-        hip_check(hipEventSynchronize(m_ev_idx), "hipEventSynchronize");
-        m_dec.decode_y(m_h_idx.get(), n, m_h_dec.get());
-        hip_check(hipMemcpyAsync(m_DECODED, m_h_dec.get(), n, hipMemcpyHostToDevice, st), "H2D symbols");
-    }
+    decode_y_and_upload(n, st);
     bind_stage_arg(kDec3, x_hat);
     run_stage(kDec3, st, [&] {
         MaskStepDec d;
@@ -441,115 +327,46 @@ void DmcLdCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int heig
         run_recon_head(x_hat, st);
     });
     leave(user);
-    m_has_feature_p = true;
-    m_has_ref = true;                      // the recon-head output is the reference feature after a reset
-    m_memory_has_value = !reset;
-    m_enc_ready = false;                   // the temporal params were consumed by this picture
+    m_flags.after_decompress(reset);       // the temporal params were consumed by this picture
 }
 
-// ------------------------------------------------------------------------------------ state hand-off
-namespace {
-
-struct StateHeader {
-    uint32_t magic, h8, w8, flags;
-    uint32_t reserved[12];
-};
-constexpr uint32_t kLdMagic = 0x44434c44;     // "DCLD"
-
-}  // namespace
+// ------------------------------------------------------------------------------------ state hand-off, debug
+std::vector<InterCodec::StatePart> DmcLdCodec::state_parts() const
+{
+    const size_t P8 = m_g.P8(), P16 = m_g.P16();
+    // reference feature, memory | feature_p, ctx (a channel slice), temporal prior
+    return {{m_FI, kChSrc, kChSrc, P8}, {m_CATM, kChM + kChD, kChM + kChD, P8}, {m_CATD + kChD, kChM, kChD + kChM, P8},
+            {m_TP, 2 * kChY, 2 * kChY, P16}};
+}
 
 size_t DmcLdCodec::export_state(void* dst, size_t cap, hipStream_t user)
 {
-    if (!m_has_params || m_g.H8 == 0) throw std::runtime_error("DMC-LD export_state: no state yet");
-    const Geometry& g = m_g;
-    const size_t n_fi = static_cast<size_t>(g.P8()) * kChSrc, n_catm = static_cast<size_t>(g.P8()) * (kChM + kChD),
-                 n_ctx = static_cast<size_t>(g.P8()) * kChM, n_tp = static_cast<size_t>(g.P16()) * 2 * kChY;
-    const size_t bytes = sizeof(StateHeader) + 2 * (n_fi + n_catm + n_ctx + n_tp);
-    if (dst == nullptr) return bytes;
-    if (cap < bytes) throw std::invalid_argument("export_state: destination too small");
-    hipStream_t st = enter(user);
-    StateHeader h{};
-    h.magic = kLdMagic; h.h8 = g.H8; h.w8 = g.W8;
-    h.flags = (m_has_ref ? 1u : 0u) | (m_enc_ready ? 2u : 0u) | (m_memory_has_value ? 4u : 0u) | (m_has_feature_p ? 8u : 0u);
-    char* out = static_cast<char*>(dst);
-    hip_check(hipMemcpyAsync(out, &h, sizeof(h), hipMemcpyHostToDevice, st), "state header");
-    hip_check(hipStreamSynchronize(st), "sync");          // the header lives on this stack frame
-    out += sizeof(h);
-    auto put = [&](const half_t* p, size_t n) {
-        hip_check(hipMemcpyAsync(out, p, 2 * n, hipMemcpyDeviceToDevice, st), "state D2D");
-        out += 2 * n;
-    };
-    put(m_FI, n_fi);
-    put(m_CATM, n_catm);
-    // ctx and the temporal prior are channel slices of wider buffers: dense copies
-    hip_check(hipMemcpy2DAsync(out, 2 * kChM, m_CATD + kChD, 2 * (kChD + kChM), 2 * kChM, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
-    out += 2 * n_ctx;
-    hip_check(hipMemcpy2DAsync(out, 4 * kChY, m_TP, 4 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
-    leave(user);
-    return bytes;
+    return InterCodec::export_state(kLdMagic, state_parts(), dst, cap, user);
 }
 
 void DmcLdCodec::import_state(const void* src, size_t bytes, int height, int width, hipStream_t user)
 {
     prepare(height, width);
-    const Geometry& g = m_g;
-    const size_t n_fi = static_cast<size_t>(g.P8()) * kChSrc, n_catm = static_cast<size_t>(g.P8()) * (kChM + kChD),
-                 n_ctx = static_cast<size_t>(g.P8()) * kChM, n_tp = static_cast<size_t>(g.P16()) * 2 * kChY;
-    if (bytes != sizeof(StateHeader) + 2 * (n_fi + n_catm + n_ctx + n_tp)) {
-        throw std::invalid_argument("import_state: size does not match this picture size");
-    }
-    hipStream_t st = enter(user);
-    StateHeader h{};
-    const char* in = static_cast<const char*>(src);
-    hip_check(hipMemcpyAsync(&h, in, sizeof(h), hipMemcpyDeviceToHost, st), "state header");
-    hip_check(hipStreamSynchronize(st), "sync");
-    if (h.magic != kLdMagic || h.h8 != static_cast<uint32_t>(g.H8) || h.w8 != static_cast<uint32_t>(g.W8)) {
-        throw std::invalid_argument("import_state: not a DMC-LD state of this picture size");
-    }
-    in += sizeof(h);
-    auto get = [&](half_t* p, size_t n) {
-        hip_check(hipMemcpyAsync(p, in, 2 * n, hipMemcpyDeviceToDevice, st), "state D2D");
-        in += 2 * n;
-    };
-    get(m_FI, n_fi);
-    get(m_CATM, n_catm);
-    hip_check(hipMemcpy2DAsync(m_CATD + kChD, 2 * (kChD + kChM), in, 2 * kChM, 2 * kChM, g.P8(), hipMemcpyDeviceToDevice, st), "state ctx");
-    in += 2 * n_ctx;
-    hip_check(hipMemcpy2DAsync(m_TP, 4 * kChY, in, 4 * kChY, 4 * kChY, g.P16(), hipMemcpyDeviceToDevice, st), "state temporal");
-    leave(user);
-    m_has_ref = h.flags & 1u; m_enc_ready = h.flags & 2u; m_memory_has_value = h.flags & 4u; m_has_feature_p = h.flags & 8u;
+    InterCodec::import_state(kLdMagic, "import_state: not a DMC-LD state of this picture size", state_parts(), src, bytes, user);
 }
 
-// ------------------------------------------------------------------------------------ debug
 size_t DmcLdCodec::debug_read(const std::string& name, void* dst, size_t cap, hipStream_t st)
 {
     const Geometry& g = m_g;
-    const void* src = nullptr;
-    size_t pixels = 0, ch_bytes = 0, pitch = 0;
-    auto view = [&](const void* p, int P, int c, int ld, int elem) {
-        src = p; pixels = P; ch_bytes = static_cast<size_t>(c) * elem; pitch = static_cast<size_t>(ld) * elem;
-    };
-    if (name == "y") view(m_Y, g.P16(), kChY, kChY, 2);
-    else if (name == "y_hat") view(m_CATSP, g.P16(), kChY, 4 * kChY, 2);
-    else if (name == "common") view(m_CATSP + kChY, g.P16(), 3 * kChY, 4 * kChY, 2);
-    else if (name == "means1") view(m_MEANS1, g.P16(), kChY, kChY, 2);
-    else if (name == "z_i8") view(m_ZI8, g.P64(), kChZ, kChZ, 1);
-    else if (name == "memory") view(m_CATM, g.P8(), kChM, kChM + kChD, 2);
-    else if (name == "feature_p") view(m_CATM + kChM, g.P8(), kChD, kChM + kChD, 2);
-    else if (name == "ctx") view(m_CATD + kChD, g.P8(), kChM, kChD + kChM, 2);
-    else if (name == "temporal") view(m_TP, g.P16(), 2 * kChY, 2 * kChY, 2);
-    else if (name == "feature_i") view(m_FI, g.P8(), kChSrc, kChSrc, 2);
-    else if (name == "symbols") view(m_COMP, 1, g.P16() * kChY, g.P16() * kChY, 2);
-    else if (name == "totals") view(m_TOTALS, 1, 4, 4, 4);
-    else throw std::invalid_argument("unknown debug tensor '" + name + "'");
-    const size_t bytes = pixels * ch_bytes;
-    if (dst != nullptr) {
-        if (cap < bytes) throw std::invalid_argument("debug_read: destination too small");
-        hip_check(hipStreamSynchronize(st), "sync");
-        hip_check(hipStreamSynchronize(m_cs), "sync");
-        hip_check(hipMemcpy2D(dst, ch_bytes, src, pitch, ch_bytes, pixels, hipMemcpyDeviceToHost), "debug D2H");
-    }
-    return bytes;
+    const size_t P8 = g.P8(), P16 = g.P16(), P64 = g.P64();
+    return InterCodec::debug_read({{"y", m_Y, P16, kChY, kChY, 2},
+                                   {"y_hat", m_CATSP, P16, kChY, 4 * kChY, 2},
+                                   {"common", m_CATSP + kChY, P16, 3 * kChY, 4 * kChY, 2},
+                                   {"means1", m_MEANS1, P16, kChY, kChY, 2},
+                                   {"z_i8", m_ZI8, P64, kChZ, kChZ, 1},
+                                   {"memory", m_CATM, P8, kChM, kChM + kChD, 2},
+                                   {"feature_p", m_CATM + kChM, P8, kChD, kChM + kChD, 2},
+                                   {"ctx", m_CATD + kChD, P8, kChM, kChD + kChM, 2},
+                                   {"temporal", m_TP, P16, 2 * kChY, 2 * kChY, 2},
+                                   {"feature_i", m_FI, P8, kChSrc, kChSrc, 2},
+                                   {"symbols", m_COMP, 1, g.P16() * kChY, g.P16() * kChY, 2},
+                                   {"totals", m_TOTALS, 1, 4, 4, 4}},
+                                  name, dst, cap, st);
 }
 
 }  // namespace dcvc

@@ -49,16 +49,9 @@ public:
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
 private:
-    struct Geometry {
+    struct BatchGeometry : Geometry {
         int N = 0;                  // pictures back to back in every buffer (a batch)
         int H = 0, W = 0;           // picture
-        int H8 = 0, W8 = 0, H16 = 0, W16 = 0, H16p = 0, W16p = 0, H32 = 0, W32 = 0, H64 = 0, W64 = 0;
-        int P8() const { return H8 * W8; }
-        int P16() const { return H16 * W16; }
-        int P16p() const { return H16p * W16p; }
-        int P32() const { return H32 * W32; }
-        int P64() const { return H64 * W64; }
-        bool padded() const { return H16p != H16 || W16p != W16; }
     };
 
     void prepare(int height, int width, int n);
@@ -99,7 +92,7 @@ private:
     bool m_has_params = false;
 
     // ---- per-resolution buffers
-    Geometry m_g;
+    BatchGeometry m_g;
     DeviceArena m_bmem;
     Scratch m_s;
     half_t *m_U = nullptr, *m_F = nullptr, *m_Y = nullptr, *m_Ypad = nullptr;

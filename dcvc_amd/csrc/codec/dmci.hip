@@ -81,15 +81,11 @@ void DmciCodec::prepare(int height, int width, int n)
     quiesce();
     clear_graphs();
     m_bmem.release();
-    m_g = Geometry();
-    Geometry g;
+    m_g = BatchGeometry();
+    BatchGeometry g;
+    static_cast<Geometry&>(g) = Geometry::of(height, width);
     g.N = n;
     g.H = height; g.W = width;
-    g.H8 = ceil_div(height, 16) * 2; g.W8 = ceil_div(width, 16) * 2;
-    g.H16 = g.H8 / 2; g.W16 = g.W8 / 2;
-    g.H16p = ceil_div(g.H16, 4) * 4; g.W16p = ceil_div(g.W16, 4) * 4;      // dmc_common.cpp:73-83
-    g.H32 = g.H16p / 2; g.W32 = g.W16p / 2;
-    g.H64 = g.H16p / 4; g.W64 = g.W16p / 4;
     auto H = [&](size_t count) { return m_bmem.alloc_half(count); };
     // every pixel count is that of the whole batch
     const size_t N = n;
@@ -139,7 +135,7 @@ void DmciCodec::select_qp(int qp, hipStream_t st)
 // ------------------------------------------------------------------------------------ networks
 void DmciCodec::run_encoder(hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     // dmci_proxy.cpp:92-105 (the per-channel q_scale_enc multiply is applied to the rounded
     // output of enc_1 inside its last conv's epilogue)
     // consecutive full-width blocks hand dc.0 over: block i's launch also computes dc.0 of block i+1, across the seam too
@@ -159,7 +155,7 @@ void DmciCodec::run_encoder(hipStream_t st)
 
 void DmciCodec::run_hyper_and_priors_enc(hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     if (g.padded()) {
         replicate_pad_b(m_Y, kChY, g.H16, g.W16, kChY, g.H16p - g.H16, g.W16p - g.W16, m_Ypad, kChY, g.N, st);
     }
@@ -174,7 +170,7 @@ void DmciCodec::run_hyper_and_priors_enc(hipStream_t st)
 
 void DmciCodec::run_priors_from_zhat(hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     m_hdec0.forward(View(m_ZH, kChZ, kChZ), View(m_H1a, kChZ, kChZ), View(m_H1, kChZ, kChZ), g.H64, g.W64, m_s, st);
     m_hdec1.forward(View(m_H1, kChZ, kChZ), View(m_H2a, kChZ, kChZ), View(m_H2, kChZ, kChZ), g.H32, g.W32, m_s, st);
     m_hdec2.forward(View(m_H2, kChZ, kChZ), View(m_HP, kChY, kChY), g.H16p, g.W16p, m_s, st);
@@ -199,7 +195,7 @@ void DmciCodec::run_priors_from_zhat(hipStream_t st)
 
 void DmciCodec::run_spatial_prior(int k, hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     const View ad(m_AD, 2 * kChY, 2 * kChY);
     const FinCall fin(m_sp3, m_SP, 2 * kChY);              // y_spatial_prior.conv.3 closes the chain
     ChainCall adaptor, sp;
@@ -212,7 +208,7 @@ void DmciCodec::run_spatial_prior(int k, hipStream_t st)
 
 void DmciCodec::run_decoder(half_t* x_hat, hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     // dmci_proxy.cpp:14-33
     const View d1(m_D1, kChEncDec, kChEncDec);
     const DcbW* after_up = m_dec_up.block.feeds(m_dec1[0]) ? &m_dec1[0] : nullptr;
@@ -228,7 +224,7 @@ void DmciCodec::run_decoder(half_t* x_hat, hipStream_t st)
 
 void DmciCodec::enc_stage0(hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     run_encoder(st);
     run_hyper_and_priors_enc(st);
     mul_channel(m_Y, kChY, m_cur_q_y_enc, m_Y, kChY, g.N * g.P16(), kChY, st);
@@ -294,7 +290,7 @@ void DmciCodec::estimate_bits(int n, const half_t* x, int height, int width, int
 {
     if (qp < 0 || qp >= kQpNum) throw std::invalid_argument("DMCI estimate_bits: qp must be in [0, 63]");
     prepare(height, width, n);
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
     pad_unshuffle8_b(x, height, width, 3, m_U, g.H8, g.W8, n, st);
@@ -309,7 +305,7 @@ void DmciCodec::entropy_encode(int qp)
 {
     // dmci_proxy.cpp:809-845: wait for the symbols, copy them out, code groups 3,2,1,0 then z
     // (a batch: every picture from its own totals, symbols and z into a stream of its own)
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     static const bool trace = getenv("DCVC_TIMING") != nullptr;
     const auto t_call = std::chrono::steady_clock::now();
     hip_check(hipMemcpyAsync(m_h_totals.get(), m_TOTALS, 4 * g.N * sizeof(int32_t), hipMemcpyDeviceToHost, m_io_stream), "D2H totals");
@@ -373,7 +369,7 @@ void DmciCodec::decompress_impl(int n, const uint8_t* const* bits, const size_t*
                                 int height, int width, half_t* x_hat, hipStream_t user)
 {
     prepare(height, width, n);
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     hipStream_t st = enter(user);
     select_qp(qp, st);
     const int nz = g.P64() * kChZ;
@@ -488,7 +484,7 @@ void DmciCodec::decompress_impl(int n, const uint8_t* const* bits, const size_t*
 // ------------------------------------------------------------------------------------ debug
 size_t DmciCodec::debug_read(const std::string& name, void* dst, size_t cap, hipStream_t st)
 {
-    const Geometry& g = m_g;
+    const BatchGeometry& g = m_g;
     const void* src = nullptr;
     size_t bytes = 0;
     if (name == "y") { src = m_Y; bytes = static_cast<size_t>(g.N) * g.P16() * kChY * 2; }

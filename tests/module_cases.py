@@ -593,9 +593,9 @@ def ht_decoder(H, W, k):
 
 
 def ht_recon_head(H, W):
-    # dmc_ht.hip run_recon_head / run_recon_reset: recon_head.conv1.j (full-width block from a slice into a dense buffer), then
+    # dmc_ht.hip run_head (one picture of run_recon_head; the reset path): recon_head.conv1.j (full-width block from a slice into a dense buffer), then
     # the head chain (adaptor 512 -> 256) with tmp == y and the 192-wide closing conv
-    return case("hts-recon-head", "dmc_ht.hip run_recon_head, run_recon_reset", H, W,
+    return case("hts-recon-head", "dmc_ht.hip run_head", H, W,
                 {"C": ("block", "i_512"), "R": ("chain", ["h_rh0", "h_256", "h_256"]), "RH": ("fin", "h_head")},
                 {"CATM": (1024, "g"), "RC": (512, "g"), "RT": (256, "g"), "FI": (192, "g")}, [V("CATM", 512, 512)],
                 [blk("C", V("CATM", 512, 512), V("RC", 512)),
@@ -766,7 +766,7 @@ CALL_SITES = [
     "dmc_ld.hip run_spatial_prior", "dmc_ld.hip run_decoder", "dmc_ld.hip run_recon_head",
     "dmc_ht.hip run_fa_i", "dmc_ht.hip run_fa_m, run_fe", "dmc_ht.hip run_tpe", "dmc_ht.hip run_encoder",
     "dmc_ht.hip run_hyper_encoder", "dmc_ht.hip run_common (hyper_decoder)", "dmc_ht.hip run_common (y_prior_fusion)",
-    "dmc_ht.hip run_spatial_prior", "dmc_ht.hip run_decoder", "dmc_ht.hip run_recon_head, run_recon_reset",
+    "dmc_ht.hip run_spatial_prior", "dmc_ht.hip run_decoder", "dmc_ht.hip run_head",
 ]
 
 

@@ -347,4 +347,31 @@ int dcvc_modtest_subpel_forward(dcvc_modtest* h, int module, void* x, int ldx, i
     });
 }
 
+long long dcvc_modtest_pack_stream(int kind, const void* w0, const void* w1, const void* w2, int a, int b, void* out, long long cap,
+                                   void* stream)
+{
+    long long halves = -1;
+    const int rc = dcvc::guarded([&] {
+        dcvc::kernels_init();
+        if (!w0 || !out || (kind == DCVC_MODTEST_PACK_MAIN && (!w1 || !w2))) throw std::invalid_argument("modtest: missing operand");
+        size_t n = 0;
+        switch (kind) {
+        case DCVC_MODTEST_PACK_MAIN: n = dcvc::dcb_nsplit_main_halves(a, b); break;
+        case DCVC_MODTEST_PACK_DC0: n = dcvc::dcb_nsplit_dc0_halves(a, b); break;
+        case DCVC_MODTEST_PACK_FIN: n = dcvc::dcb_nsplit_fin_halves(a, b); break;
+        case DCVC_MODTEST_PACK_ADAPTOR: n = dcvc::dcb_pair_adaptor_halves(a, b); break;
+        default: throw std::invalid_argument("modtest: no such stream kind");
+        }
+        if (static_cast<long long>(n) > cap) throw std::invalid_argument("modtest: the stream does not fit the buffer");
+        switch (kind) {
+        case DCVC_MODTEST_PACK_MAIN: dcvc::dcb_nsplit_pack_main(H(w0), H(w1), H(w2), a, b, H(out), S(stream)); break;
+        case DCVC_MODTEST_PACK_DC0: dcvc::dcb_nsplit_pack_dc0(H(w0), a, b, H(out), S(stream)); break;
+        case DCVC_MODTEST_PACK_FIN: dcvc::dcb_nsplit_pack_fin(H(w0), a, b, H(out), S(stream)); break;
+        default: dcvc::dcb_pair_pack_adaptor(H(w0), a, b, H(out), S(stream)); break;
+        }
+        halves = static_cast<long long>(n);
+    });
+    return rc == 0 ? halves : -1;
+}
+
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <vector>
 #include "dcvc_amd_ops.h"
 #include "kernels/ops.h"
 #include "rans/code_length.h"
@@ -361,25 +362,38 @@ struct NsplitPacked {
     }
 };
 
-void nsplit_check_shape(int c, int ci)
+// The four block entries' common part: the pack launches of the weights that are given (null: none) into their buffers
+struct NsplitStreams { dcvc::half_t* main = nullptr; dcvc::half_t* next = nullptr; dcvc::half_t* fin = nullptr; };
+void nsplit_pack(const NsplitStreams& out, const void* w3, const void* w0, const void* w2, const void* w1n, const void* wfin, int nfin,
+                 int c, int ci, hipStream_t st)
 {
-    if (!dcvc::dcb_nsplit_shape(c, ci)) {
-        throw std::invalid_argument("dcb_nsplit: (block width, inner width) must be (256, 256), (384, 384), (512, 512), (768, 768), (512, 256), (256, 128), (384, 192) or (192, 192)");
-    }
+    dcvc::dcb_nsplit_pack_main(H(w3), H(w0), H(w2), c, ci, out.main, st);
+    if (w1n != nullptr) dcvc::dcb_nsplit_pack_dc0(H(w1n), c, ci, out.next, st);
+    if (wfin != nullptr) dcvc::dcb_nsplit_pack_fin(H(wfin), c, nfin, out.fin, st);
 }
 
-void nsplit_launch(const dcvc::half_t* wmain, const dcvc::half_t* wnext, const void* t2, int ldt, const void* x, int ldx,
-                   const void* b3, const void* b0, const void* b2, const void* q, const void* q2, const void* b1n,
-                   void* t1n, int ldt1, void* y, int ldy, int pixels, int c, int ci, int shortcut, hipStream_t st)
-{
+// ... as temporaries that live exactly as long as a call's launches (stream-ordered, freed on every path out), named in its descriptor
+struct NsplitTemps {
+    AsyncBuf main;
+    std::unique_ptr<AsyncBuf> next, fin;
     dcvc::DcbNsplitDesc d;
-    d.t2 = H(t2); d.ldt = ldt; d.x = H(x); d.ldx = ldx;
-    d.wmain = wmain;
-    d.wnext = wnext;
-    d.b3 = H(b3); d.b0 = H(b0); d.b2 = H(b2); d.b1n = H(b1n); d.q = H(q); d.q2 = H(q2);
-    d.t1n = H(t1n); d.ldt1 = ldt1; d.y = H(y); d.ldy = ldy;
-    d.pixels = pixels; d.c = c; d.ci = ci; d.shortcut = shortcut != 0;
-    dcvc::dcb_nsplit(d, st);
+    NsplitTemps(const void* w3, const void* w0, const void* w2, const void* w1n, const void* wfin, int nfin, int c, int ci, hipStream_t st)
+        : main(dcvc::dcb_nsplit_main_halves(c, ci) * 2, st)
+    {
+        if (w1n != nullptr) next = std::make_unique<AsyncBuf>(dcvc::dcb_nsplit_dc0_halves(c, ci) * 2, st);
+        if (wfin != nullptr) fin = std::make_unique<AsyncBuf>(dcvc::dcb_nsplit_fin_halves(c, nfin) * 2, st);
+        const NsplitStreams out{main.half(), next ? next->half() : nullptr, fin ? fin->half() : nullptr};
+        nsplit_pack(out, w3, w0, w2, w1n, wfin, nfin, c, ci, st);
+        d.wmain = out.main; d.wnext = out.next; d.wfin = out.fin; d.nfin = fin ? nfin : 0; d.c = c; d.ci = ci;
+    }
+};
+
+// what every block launch takes besides its weights and its entry operand (t2 / t1)
+void nsplit_common(dcvc::DcbNsplitDesc& d, const void* x, int ldx, const void* b3, const void* b0, const void* b2, const void* q,
+                   const void* q2, void* y, int ldy, int pixels, int shortcut)
+{
+    d.x = H(x); d.ldx = ldx; d.b3 = H(b3); d.b0 = H(b0); d.b2 = H(b2); d.q = H(q); d.q2 = H(q2);
+    d.y = H(y); d.ldy = ldy; d.pixels = pixels; d.shortcut = shortcut != 0;
 }
 }  // namespace
 
@@ -390,19 +404,13 @@ int dcvc_dcb_nsplit(const void* t2, int ldt, const void* x, int ldx, const void*
 {
     return dcvc::guarded([&] {
         dcvc::kernels_init();
-        nsplit_check_shape(c, ci);
+        dcvc::dcb_nsplit_check_shape(c, ci);
         if (!w3 || !w0 || !w2) throw std::invalid_argument("dcb_nsplit: missing operand");
-        hipStream_t st = S(stream);
-        // packed copies live exactly as long as this call's launches: stream-ordered temporaries, freed on every path out
-        const AsyncBuf wmain(dcvc::dcb_nsplit_main_halves(c, ci) * 2, st);
-        dcvc::dcb_nsplit_pack_main(H(w3), H(w0), H(w2), c, ci, wmain.half(), st);
-        std::unique_ptr<AsyncBuf> wnext;
-        if (w1n != nullptr) {
-            wnext = std::make_unique<AsyncBuf>(dcvc::dcb_nsplit_dc0_halves(c, ci) * 2, st);
-            dcvc::dcb_nsplit_pack_dc0(H(w1n), c, ci, wnext->half(), st);
-        }
-        nsplit_launch(wmain.half(), wnext ? wnext->half() : nullptr, t2, ldt, x, ldx, b3, b0, b2, q, q2, b1n, t1n, ldt1, y, ldy,
-                      pixels, c, ci, shortcut, st);
+        NsplitTemps temps(w3, w0, w2, w1n, nullptr, 0, c, ci, S(stream));
+        dcvc::DcbNsplitDesc& d = temps.d;
+        nsplit_common(d, x, ldx, b3, b0, b2, q, q2, y, ldy, pixels, shortcut);
+        d.t2 = H(t2); d.ldt = ldt; d.b1n = H(b1n); d.t1n = H(t1n); d.ldt1 = ldt1;
+        dcvc::dcb_nsplit(d, S(stream));
     });
 }
 
@@ -443,22 +451,15 @@ int dcvc_dcb_nsplit_fin(const void* t2, int ldt, const void* x, int ldx, const v
 {
     return dcvc::guarded([&] {
         dcvc::kernels_init();
-        nsplit_check_shape(c, ci);
+        dcvc::dcb_nsplit_check_shape(c, ci);
         if (!w3 || !w0 || !w2 || !wfin || !bfin || !yfin) throw std::invalid_argument("dcb_nsplit_fin: missing operand");
         if (!dcvc::dcb_nsplit_fin_supported(c, ci, nfin)) throw std::invalid_argument("dcb_nsplit_fin: no kernel variant for this closing conv");
-        hipStream_t st = S(stream);
-        const AsyncBuf wmain(dcvc::dcb_nsplit_main_halves(c, ci) * 2, st);
-        dcvc::dcb_nsplit_pack_main(H(w3), H(w0), H(w2), c, ci, wmain.half(), st);
-        const AsyncBuf wf(dcvc::dcb_nsplit_fin_halves(c, nfin) * 2, st);
-        dcvc::dcb_nsplit_pack_fin(H(wfin), c, nfin, wf.half(), st);
-        dcvc::DcbNsplitDesc d;
-        d.t2 = H(t2); d.ldt = ldt; d.x = H(x); d.ldx = ldx;
-        d.wmain = wmain.half();
-        d.b3 = H(b3); d.b0 = H(b0); d.b2 = H(b2); d.q = H(q); d.q2 = H(q2);
-        d.y = H(y); d.ldy = ldy;
-        d.pixels = pixels; d.c = c; d.ci = ci; d.shortcut = shortcut != 0;
-        d.wfin = wf.half(); d.bfin = H(bfin); d.qfin = H(qfin); d.yfin = H(yfin); d.ldyfin = ldyfin; d.nfin = nfin;
-        dcvc::dcb_nsplit(d, st);
+        NsplitTemps temps(w3, w0, w2, nullptr, wfin, nfin, c, ci, S(stream));
+        dcvc::DcbNsplitDesc& d = temps.d;
+        nsplit_common(d, x, ldx, b3, b0, b2, q, q2, y, ldy, pixels, shortcut);
+        d.t2 = H(t2); d.ldt = ldt;
+        d.bfin = H(bfin); d.qfin = H(qfin); d.yfin = H(yfin); d.ldyfin = ldyfin;
+        dcvc::dcb_nsplit(d, S(stream));
     });
 }
 
@@ -475,32 +476,18 @@ int dcvc_dcb_nsplit_dw(const void* t1, int ldt, const void* wdw, int width, cons
 {
     return dcvc::guarded([&] {
         dcvc::kernels_init();
-        nsplit_check_shape(c, ci);
+        dcvc::dcb_nsplit_check_shape(c, ci);
         if (!t1 || !wdw || !w3 || !w0 || !w2) throw std::invalid_argument("dcb_nsplit_dw: missing operand");
         if (!dcvc::dcb_nsplit_dw_supported(c, ci, pixels)) throw std::invalid_argument("dcb_nsplit_dw: no kernel variant with the depthwise conv inside for this block shape");
         if (wfin != nullptr && !dcvc::dcb_nsplit_fin_supported(c, ci, nfin)) throw std::invalid_argument("dcb_nsplit_dw: no kernel variant for this closing conv");
         if (static_cast<long long>(pixels) * ldt * 2 >= (1LL << 31)) throw std::invalid_argument("dcb_nsplit_dw: dc.0's output must span less than 2 GiB (32-bit byte offsets inside the launch)");
-        hipStream_t st = S(stream);
-        const AsyncBuf wmain(dcvc::dcb_nsplit_main_halves(c, ci) * 2, st);
-        dcvc::dcb_nsplit_pack_main(H(w3), H(w0), H(w2), c, ci, wmain.half(), st);
-        std::unique_ptr<AsyncBuf> wnext, wf;
-        if (w1n != nullptr) {
-            wnext = std::make_unique<AsyncBuf>(dcvc::dcb_nsplit_dc0_halves(c, ci) * 2, st);
-            dcvc::dcb_nsplit_pack_dc0(H(w1n), c, ci, wnext->half(), st);
-        }
-        if (wfin != nullptr) {
-            wf = std::make_unique<AsyncBuf>(dcvc::dcb_nsplit_fin_halves(c, nfin) * 2, st);
-            dcvc::dcb_nsplit_pack_fin(H(wfin), c, nfin, wf->half(), st);
-        }
-        dcvc::DcbNsplitDesc d;
-        d.t1 = H(t1); d.ldt = ldt; d.wdw = H(wdw); d.width = width; d.x = H(x); d.ldx = ldx;
-        d.wmain = wmain.half();
-        d.wnext = wnext ? wnext->half() : nullptr;
-        d.b3 = H(b3); d.b0 = H(b0); d.b2 = H(b2); d.b1n = H(b1n); d.q = H(q); d.q2 = H(q2);
-        d.t1n = H(t1n); d.ldt1 = ldt1; d.y = H(y); d.ldy = ldy;
-        d.pixels = pixels; d.c = c; d.ci = ci; d.shortcut = shortcut != 0;
-        if (wf) { d.wfin = wf->half(); d.bfin = H(bfin); d.qfin = H(qfin); d.yfin = H(yfin); d.ldyfin = ldyfin; d.nfin = nfin; }
-        dcvc::dcb_nsplit(d, st);
+        NsplitTemps temps(w3, w0, w2, w1n, wfin, nfin, c, ci, S(stream));
+        dcvc::DcbNsplitDesc& d = temps.d;
+        nsplit_common(d, x, ldx, b3, b0, b2, q, q2, y, ldy, pixels, shortcut);
+        d.t1 = H(t1); d.ldt = ldt; d.wdw = H(wdw); d.width = width;
+        d.b1n = H(b1n); d.t1n = H(t1n); d.ldt1 = ldt1;
+        if (wfin != nullptr) { d.bfin = H(bfin); d.qfin = H(qfin); d.yfin = H(yfin); d.ldyfin = ldyfin; }
+        dcvc::dcb_nsplit(d, S(stream));
     });
 }
 
@@ -508,21 +495,15 @@ int dcvc_dcb_nsplit_pack(const void* w3, const void* w0, const void* w2, const v
 {
     return dcvc::guarded([&] {
         dcvc::kernels_init();
-        nsplit_check_shape(c, ci);
+        dcvc::dcb_nsplit_check_shape(c, ci);
         if (!w3 || !w0 || !w2 || !handle) throw std::invalid_argument("dcb_nsplit_pack: missing operand");
         auto pk = std::make_unique<NsplitPacked>();          // its destructor frees whatever has been allocated when a step below throws
         pk->c = c; pk->ci = ci;
         dcvc::hip_check(hipGetDevice(&pk->device), "hipGetDevice");
-        void* m = nullptr;
-        dcvc::hip_check(hipMalloc(&m, dcvc::dcb_nsplit_main_halves(c, ci) * 2), "hipMalloc(packed weights)");
-        pk->main = static_cast<dcvc::half_t*>(m);
-        dcvc::dcb_nsplit_pack_main(H(w3), H(w0), H(w2), c, ci, pk->main, S(stream));
-        if (w1n != nullptr) {
-            void* n = nullptr;
-            dcvc::hip_check(hipMalloc(&n, dcvc::dcb_nsplit_dc0_halves(c, ci) * 2), "hipMalloc(packed weights)");
-            pk->next = static_cast<dcvc::half_t*>(n);
-            dcvc::dcb_nsplit_pack_dc0(H(w1n), c, ci, pk->next, S(stream));
-        }
+        // (each buffer is the handle's as soon as it exists)
+        dcvc::hip_check(hipMalloc(reinterpret_cast<void**>(&pk->main), dcvc::dcb_nsplit_main_halves(c, ci) * 2), "hipMalloc(packed weights)");
+        if (w1n != nullptr) dcvc::hip_check(hipMalloc(reinterpret_cast<void**>(&pk->next), dcvc::dcb_nsplit_dc0_halves(c, ci) * 2), "hipMalloc(packed weights)");
+        nsplit_pack(NsplitStreams{pk->main, pk->next, nullptr}, w3, w0, w2, w1n, nullptr, 0, c, ci, S(stream));
         dcvc::hip_check(hipEventCreateWithFlags(&pk->packed, hipEventDisableTiming), "hipEventCreate");
         dcvc::hip_check(hipEventRecord(pk->packed, S(stream)), "hipEventRecord(packed)");
         pk->pack_stream = S(stream);
@@ -566,8 +547,11 @@ int dcvc_dcb_nsplit_packed(const void* handle, const void* t2, int ldt, const vo
             if (hipEventQuery(pk->packed) == hipSuccess) pk->settled = true;
             else dcvc::hip_check(hipStreamWaitEvent(S(stream), pk->packed, 0), "hipStreamWaitEvent(packed)");
         }
-        nsplit_launch(pk->main, with_next ? pk->next : nullptr, t2, ldt, x, ldx, b3, b0, b2, q, q2, b1n, t1n, ldt1, y, ldy, pixels,
-                      pk->c, pk->ci, shortcut, S(stream));
+        dcvc::DcbNsplitDesc d;
+        d.c = pk->c; d.ci = pk->ci; d.wmain = pk->main; d.wnext = with_next ? pk->next : nullptr;
+        nsplit_common(d, x, ldx, b3, b0, b2, q, q2, y, ldy, pixels, shortcut);
+        d.t2 = H(t2); d.ldt = ldt; d.b1n = H(b1n); d.t1n = H(t1n); d.ldt1 = ldt1;
+        dcvc::dcb_nsplit(d, S(stream));
     });
 }
 

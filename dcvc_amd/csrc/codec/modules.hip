@@ -121,7 +121,7 @@ void FinW::load(const ParamStore& ps, DeviceArena& mem, const std::string& prefi
 {
     conv.load(ps, mem, prefix);
     packed = nullptr;
-    if (conv.b != nullptr && conv.cin % 128 == 0 && conv.cout % 32 == 0 && conv.cout >= 128 && dcb_nsplit_waves() == 8) {
+    if (conv.b != nullptr && dcb_nsplit_fin_packable(conv.cin, conv.cout)) {
         packed = mem.alloc_half(dcb_nsplit_fin_halves(conv.cin, conv.cout));
         dcb_nsplit_pack_fin(conv.w, conv.cin, conv.cout, packed, nullptr);
         hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize(pack)");

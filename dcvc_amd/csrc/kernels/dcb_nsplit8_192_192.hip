@@ -5,10 +5,10 @@
 namespace dcvc {
 namespace nsplit8 {
 
-void run_192_192(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    run_shape8<192, 192>(p, wide, next, stream);
-}
+template void launch8<192, 192, 1, 0>(const NsParams&, hipStream_t);
+template void launch8<192, 192, 2, 0>(const NsParams&, hipStream_t);
+template void launch8<192, 192, 1, 1>(const NsParams&, hipStream_t);
+template void launch8<192, 192, 2, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

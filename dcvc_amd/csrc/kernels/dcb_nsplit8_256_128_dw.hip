@@ -6,19 +6,10 @@
 namespace dcvc {
 namespace nsplit8 {
 
-// the variants with a chain-closing conv in the NEXT slot: dcb_nsplit8_256_128_dw_fin.hip
-extern template void launch8<256, 128, 1, 128, 1>(const NsParams&, hipStream_t);
-extern template void launch8<256, 128, 2, 128, 1>(const NsParams&, hipStream_t);
-extern template void launch8<256, 128, 1, 192, 1>(const NsParams&, hipStream_t);
-extern template void launch8<256, 128, 2, 192, 1>(const NsParams&, hipStream_t);
-extern template void launch8<256, 128, 1, 256, 1>(const NsParams&, hipStream_t);
-extern template void launch8<256, 128, 2, 256, 1>(const NsParams&, hipStream_t);
-
-void run_256_128_dw(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    if (wide) run_px8_dw<256, 128, 2, 128, 192, 256>(p, next, stream);
-    else run_px8_dw<256, 128, 1, 128, 192, 256>(p, next, stream);
-}
+template void launch8<256, 128, 1, 0, 1>(const NsParams&, hipStream_t);
+template void launch8<256, 128, 2, 0, 1>(const NsParams&, hipStream_t);
+template void launch8<256, 128, 1, 1, 1>(const NsParams&, hipStream_t);
+template void launch8<256, 128, 2, 1, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

@@ -5,14 +5,10 @@
 namespace dcvc {
 namespace nsplit8 {
 
-// the variants with a chain-closing conv in the NEXT slot: dcb_nsplit8_384_192_fin.hip
-extern template void launch8<384, 192, 1, 384>(const NsParams&, hipStream_t);
-extern template void launch8<384, 192, 2, 384>(const NsParams&, hipStream_t);
-
-void run_384_192(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    run_shape8<384, 192, 384>(p, wide, next, stream);
-}
+template void launch8<384, 192, 1, 0>(const NsParams&, hipStream_t);
+template void launch8<384, 192, 2, 0>(const NsParams&, hipStream_t);
+template void launch8<384, 192, 1, 1>(const NsParams&, hipStream_t);
+template void launch8<384, 192, 2, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

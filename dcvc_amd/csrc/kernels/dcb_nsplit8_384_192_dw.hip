@@ -6,10 +6,9 @@
 namespace dcvc {
 namespace nsplit8 {
 
-void run_384_192_dw(const NsParams& p, int next, hipStream_t stream)
-{
-    run_px8_dw<384, 192, 1, 384>(p, next, stream);
-}
+template void launch8<384, 192, 1, 0, 1>(const NsParams&, hipStream_t);
+template void launch8<384, 192, 1, 1, 1>(const NsParams&, hipStream_t);
+template void launch8<384, 192, 1, 384, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

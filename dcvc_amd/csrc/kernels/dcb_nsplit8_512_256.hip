@@ -4,10 +4,10 @@
 namespace dcvc {
 namespace nsplit8 {
 
-void run_512_256(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    run_shape8<512, 256>(p, wide, next, stream);
-}
+template void launch8<512, 256, 1, 0>(const NsParams&, hipStream_t);
+template void launch8<512, 256, 2, 0>(const NsParams&, hipStream_t);
+template void launch8<512, 256, 1, 1>(const NsParams&, hipStream_t);
+template void launch8<512, 256, 2, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

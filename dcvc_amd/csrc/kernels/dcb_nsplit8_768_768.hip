@@ -4,13 +4,8 @@
 namespace dcvc {
 namespace nsplit8 {
 
-// the variants with a chain-closing conv in the NEXT slot: dcb_nsplit8_768_768_fin.hip
-extern template void launch8<768, 768, 1, 768>(const NsParams&, hipStream_t);
-
-void run_768_768(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    run_shape8<768, 768, 768>(p, wide, next, stream);
-}
+template void launch8<768, 768, 1, 0>(const NsParams&, hipStream_t);
+template void launch8<768, 768, 1, 1>(const NsParams&, hipStream_t);
 
 }  // namespace nsplit8
 }  // namespace dcvc

@@ -32,7 +32,8 @@
 // Otherwise: activations in LDS (A = [PX][CI], B = [PX][C], XOR-swizzled), persistent workgroups,
 // the next tile's t2 by LDS-DMA behind ffn.2's MFMAs, outputs stored straight from the epilogues' registers.
 #pragma once
-#include "dcb_nsplit_common.h"
+#include "dcb_shapes.h"
+#include "dcb_wave_share.h"
 
 namespace dcvc {
 namespace nsplit8 {
@@ -42,6 +43,8 @@ using nsplit::lds_dma16;
 using nsplit::NsParams;
 using nsplit::R;
 using nsplit::static_for;
+using nsplit::Ffn0Share;
+using nsplit::WaveShare;
 using nsplit::TABLE_BYTES;
 using nsplit::uint4v;
 
@@ -120,45 +123,40 @@ struct Lay {
 };
 
 // Per-wave tile / fragment counts. A "tile" = 32 output channels; a fragment = one MFMA "A" operand (32 channels x 16 k).
+// Who owns which tiles is dcb_wave_share.h's: the C-wide layers (dc.3, ffn.2) and dc.0 by SIMD pair where the width is a multiple
+// of 128 and by wave otherwise (192: the waves without a tile, 6 and 7, still walk a tile of ZERO weights and keep their results
+// to themselves), a chain-closing conv always by wave, ffn.0 in passes of two tiles.
 template <int C, int CI>
 struct Geo {
     static constexpr int KS_C = C / 16, KS_I = CI / 16;
-    static constexpr int QC = C / 128, QI = CI / 128;                  // tiles per SIMD pair of a C- / CI-wide layer
-    static constexpr int HI_C = (QC + 1) / 2, LO_C = QC / 2;           // ... of which wave w < 4 / wave w + 4
-    static constexpr int HI_I = (QI + 1) / 2, LO_I = QI / 2;
-    // CI a multiple of 128: dc.0's tiles by SIMD pair as the C-wide layers'; otherwise (CI = 192) by the rule of the closing
-    // convs below (waves 0 .. 3 one tile each, two of the waves 4 .. 7 one each)
-    static constexpr bool I_BY_PAIR = CI % 128 == 0;
-    // ffn.0: 4 CI / 32 tiles in pairs (a pair = 16 channels of t); the waves 0 .. 3 own P0_HI pairs each, 4 .. 7 P0_LO
-    // (equal but for CI = 192: 2 | 1)
-    static constexpr int PAIRS = CI / 16, P0_HI = (PAIRS + 7) / 8, P0_LO = (PAIRS - 4 * P0_HI) / 4;
+    static constexpr WaveShare share_c() { return WaveShare::block_layer(C); }
+    static constexpr WaveShare share_i() { return WaveShare::block_layer(CI); }
+    // the NEXT slot (0: none, 1: dc.0 of the next block, NN > 1: closing conv of width NN)
+    static constexpr WaveShare share_next(int next) { return next > 1 ? WaveShare::by_wave(next) : share_i(); }
+    // (the names block_body and pair_body read; the values are the share header's. QC .. LO_I mean "per SIMD pair" and are valid
+    // only where C_BY_PAIR / I_BY_PAIR holds - the bodies read them under that condition alone; nf_hi .. act_lo are the by-wave rule)
+    static constexpr bool I_BY_PAIR = share_i().by_pair, C_BY_PAIR = share_c().by_pair;
+    static constexpr int QC = share_c().hi + share_c().lo, QI = share_i().hi + share_i().lo;     // by pair: tiles per SIMD pair
+    static constexpr int HI_C = share_c().hi, LO_C = share_c().lo, HI_I = share_i().hi, LO_I = share_i().lo;
+    static constexpr int nf_hi(int nn) { return WaveShare::by_wave(nn).hi; }
+    static constexpr int nf_lo(int nn) { return WaveShare::by_wave(nn).lo; }
+    static constexpr int act_lo(int nn) { return WaveShare::by_wave(nn).act; }
+    static constexpr int P0_HI = Ffn0Share(CI).hi, P0_LO = Ffn0Share(CI).lo;       // ffn.0 tile pairs per wave
     static constexpr int TP = 2;                                        // passes of 2 tiles
     static constexpr int n0(bool hiw) { return 2 * (hiw ? P0_HI : P0_LO); }      // ffn.0 tiles per wave
     static constexpr int np(bool hiw) { return hiw ? P0_HI : P0_LO; }
-    // C a multiple of 128: the C-wide layers' tiles by SIMD pair; otherwise (C = 192) by the closing convs' rule - the waves
-    // without a tile (6, 7) still walk a tile of ZERO weights through dc.3 / ffn.2 (one barrier sequence, one ring discipline)
-    // and keep their results to themselves
-    static constexpr bool C_BY_PAIR = C % 128 == 0;
-    static constexpr bool EVEN = HI_C == LO_C && HI_I == LO_I && I_BY_PAIR && C_BY_PAIR && P0_HI == P0_LO;
-    static constexpr int nt_c(bool hiw) { return C_BY_PAIR ? (hiw ? HI_C : LO_C) : (nt_f(C, hiw) > 0 ? nt_f(C, hiw) : 0); }
-    static constexpr int nt_i(bool hiw) { return I_BY_PAIR ? (hiw ? HI_I : LO_I) : nt_f(CI, hiw); }
+    static constexpr bool EVEN = C_BY_PAIR && I_BY_PAIR && share_c().even() && share_i().even() && P0_HI == P0_LO;
+    static constexpr int nt_c(bool hiw) { return share_c().tiles_of(!hiw); }
+    static constexpr int nt_i(bool hiw) { return share_i().tiles_of(!hiw); }
     static constexpr int f_dc3(bool hiw) { return nt_c(hiw) * KS_I; }
     static constexpr int f_ffn0(bool hiw) { return n0(hiw) * KS_C; }
     static constexpr int f_main(bool hiw) { return 2 * f_dc3(hiw) + f_ffn0(hiw); }
     static constexpr int f_dc0(bool hiw) { return nt_i(hiw) * KS_C; }
-    // a chain-closing conv of width NN (C -> NN, NN / 32 tiles): the waves 0 .. 3 own nf_hi tiles each, of the waves 4 .. 7 the
-    // first act_lo own nf_lo each (NN = 192: 1 | 1, two active; NN = 128: 1 | 0). Wave w < 4: tiles [w nf_hi, ...), wave w >= 4:
-    // tiles [4 nf_hi + (w - 4) nf_lo, ...).
-    static constexpr int nf_hi(int nn) { return (nn / 32 + 7) / 8; }
-    static constexpr int nf_lo(int nn) { return nn / 32 - 4 * nf_hi(nn) <= 0 ? 0 : (nn / 32 - 4 * nf_hi(nn) + 3) / 4; }
-    static constexpr int act_lo(int nn) { return nf_lo(nn) == 0 ? 0 : (nn / 32 - 4 * nf_hi(nn)) / nf_lo(nn); }
-    static constexpr int nt_f(int nn, bool hiw) { return hiw ? nf_hi(nn) : nf_lo(nn); }
-    static constexpr bool fin_ok(int nn) { return nn % 32 == 0 && nn >= 128 && 4 * nf_hi(nn) + act_lo(nn) * nf_lo(nn) == nn / 32; }
-    // tiles / fragments of the NEXT slot (0: none, 1: dc.0 of the next block, NN > 1: closing conv of width NN)
-    static constexpr int nt_next(int next, bool hiw) { return next == 0 ? 0 : next == 1 ? nt_i(hiw) : nt_f(next, hiw); }
+    static constexpr bool fin_ok(int nn) { return WaveShare::by_wave(nn).covers(nn); }
+    static constexpr int nt_next(int next, bool hiw) { return next == 0 ? 0 : share_next(next).tiles_of(!hiw); }
     static constexpr int f_next(int next, bool hiw) { return nt_next(next, hiw) * KS_C; }
-    static constexpr bool even(int next) { return EVEN && (next <= 1 || (nf_hi(next) == nf_lo(next) && act_lo(next) == 4)); }
-    static_assert(C % 64 == 0 && CI % 64 == 0 && 4 * (P0_HI + P0_LO) == PAIRS && P0_LO >= 1, "channel counts the eight waves can share");
+    static constexpr bool even(int next) { return EVEN && (next <= 1 || WaveShare::by_wave(next).even()); }
+    static_assert(C % 64 == 0 && Ffn0Share(CI).covers(CI), "channel counts the eight waves can share");
 };
 
 template <int C, int CI, int PXT, int NEXT, int DW, bool HIW>
@@ -826,7 +824,8 @@ dcb_nsplit8_kernel(const NsParams p)
     }
 }
 
-template <int C, int CI, int PXT, int NEXT, int DW = 0>
+// (declared in dcb_shapes.h; instantiated explicitly, one unit per shape and variant group: dcb_nsplit8_<shape>[_dw][_fin].hip)
+template <int C, int CI, int PXT, int NEXT, int DW>
 void launch8(const NsParams& p, hipStream_t stream)
 {
     auto kern = dcb_nsplit8_kernel<C, CI, PXT, NEXT, DW>;
@@ -865,47 +864,6 @@ void launch8(const NsParams& p, hipStream_t stream)
     }
     hip_check(hipGetLastError(), "dcb_nsplit8 launch");
 }
-
-// `next`: 0 = nothing behind ffn.2, 1 = dc.0 of the next block, NN > 1 = the chain's closing conv of width NN (one of FINS...)
-template <int C, int CI, int PXT, int... FINS>
-void run_px8(const NsParams& p, int next, hipStream_t stream)
-{
-    if (next == 0) { launch8<C, CI, PXT, 0>(p, stream); return; }
-    if (next == 1) { launch8<C, CI, PXT, 1>(p, stream); return; }
-    const bool hit = ((next == FINS ? (launch8<C, CI, PXT, FINS>(p, stream), true) : false) || ... || false);
-    if (!hit) throw std::invalid_argument("dcb_nsplit8: no instantiation for a closing conv of width " + std::to_string(next));
-}
-
-// the same with the block's depthwise conv inside the launch (DW = 1)
-template <int C, int CI, int PXT, int... FINS>
-void run_px8_dw(const NsParams& p, int next, hipStream_t stream)
-{
-    if (next == 0) { launch8<C, CI, PXT, 0, 1>(p, stream); return; }
-    if (next == 1) { launch8<C, CI, PXT, 1, 1>(p, stream); return; }
-    const bool hit = ((next == FINS ? (launch8<C, CI, PXT, FINS, 1>(p, stream), true) : false) || ... || false);
-    if (!hit) throw std::invalid_argument("dcb_nsplit8: no instantiation for a closing conv of width " + std::to_string(next));
-}
-
-template <int C, int CI, int... FINS>
-void run_shape8(const NsParams& p, bool wide, int next, hipStream_t stream)
-{
-    if constexpr (C < 768) {
-        if (wide) { run_px8<C, CI, 2, FINS...>(p, next, stream); return; }
-    }
-    run_px8<C, CI, 1, FINS...>(p, next, stream);
-}
-
-// dcb_nsplit8_<shape>.hip
-void run_256_128(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_256_128_dw(const NsParams& p, bool wide, int next, hipStream_t stream);      // depthwise conv inside: dcb_nsplit8_256_128_dw.hip
-void run_384_192_dw(const NsParams& p, int next, hipStream_t stream);                 // ... 32-pixel workgroups only: dcb_nsplit8_384_192_dw.hip
-void run_256_256(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_192_192(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_384_192(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_384_384(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_512_256(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_512_512(const NsParams& p, bool wide, int next, hipStream_t stream);
-void run_768_768(const NsParams& p, bool wide, int next, hipStream_t stream);
 
 }  // namespace nsplit8
 }  // namespace dcvc

@@ -1,5 +1,5 @@
 // dcb_nsplit_common.h - what the block kernel (dcb_nsplit8_kernel.h) and the adaptor + dc.0 kernel (dcb_pair8_kernel.h) share:
-// the launch parameters, the LDS-DMA piece, the compile-time loop. (Until round 6 these lived in dcb_nsplit_kernel.h, round 3's
+// the launch parameters, the workgroup-size threshold, the LDS-DMA piece, the compile-time loop. (Until round 6 these lived in dcb_nsplit_kernel.h, round 3's
 // 4-wave form of the block kernel - the 8-wave kernel's A/B partner through rounds 4 and 5, retired in round 6: git history.)
 #pragma once
 #include "arith.h"
@@ -17,6 +17,9 @@
 namespace dcvc {
 
 const float4* wsilu_table_device();      // conv_gemm.hip
+
+// both block kernels: 64-pixel workgroups when they fill the chip (picture resolution / 8), 32 otherwise (/ 16: 255 workgroups at 1080p)
+constexpr int DCB_WIDE_PIXELS = 64 * 200;
 
 namespace nsplit {
 

@@ -4,11 +4,7 @@
 namespace dcvc {
 namespace pair8 {
 
-void run_c192(const PairParams& p, int cin, int ci, bool wide, hipStream_t stream)
-{
-    if (cin == 384 && ci == 192) { run_pair<384, 192, 192>(p, wide, stream); return; }
-    throw std::invalid_argument("dcb_pair8: no instantiation for this shape");
-}
+template void run_pair<384, 192, 192>(const PairParams&, bool, hipStream_t);
 
 }  // namespace pair8
 }  // namespace dcvc

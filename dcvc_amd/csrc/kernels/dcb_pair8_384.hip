@@ -4,11 +4,7 @@
 namespace dcvc {
 namespace pair8 {
 
-void run_c384(const PairParams& p, int cin, int ci, bool wide, hipStream_t stream)
-{
-    if (cin == 192 && ci == 384) { run_pair<192, 384, 384>(p, wide, stream); return; }
-    throw std::invalid_argument("dcb_pair8: no instantiation for this shape");
-}
+template void run_pair<192, 384, 384>(const PairParams&, bool, hipStream_t);
 
 }  // namespace pair8
 }  // namespace dcvc

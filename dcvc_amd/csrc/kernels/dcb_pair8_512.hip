@@ -4,14 +4,10 @@
 namespace dcvc {
 namespace pair8 {
 
-void run_c512(const PairParams& p, int cin, int ci, bool wide, hipStream_t stream)
-{
-    if (cin == 256 && ci == 512) { run_pair<256, 512, 512>(p, wide, stream); return; }
-    if (cin == 512 && ci == 512) { run_pair<512, 512, 512>(p, wide, stream); return; }
-    if (cin == 192 && ci == 512) { run_pair<192, 512, 512>(p, wide, stream); return; }
-    if (cin == 192 && ci == 256) { run_pair<192, 512, 256>(p, wide, stream); return; }
-    throw std::invalid_argument("dcb_pair8: no instantiation for this shape");
-}
+template void run_pair<256, 512, 512>(const PairParams&, bool, hipStream_t);
+template void run_pair<512, 512, 512>(const PairParams&, bool, hipStream_t);
+template void run_pair<192, 512, 512>(const PairParams&, bool, hipStream_t);
+template void run_pair<192, 512, 256>(const PairParams&, bool, hipStream_t);
 
 }  // namespace pair8
 }  // namespace dcvc

@@ -25,17 +25,6 @@ using nsplit8::Geo;
 using nsplit8::NTHREADS;
 using nsplit8::RING;
 
-struct PairParams {
-    const half_t* x; int ldx;        // [M][ldx], first CIN channels
-    const half8* wa;                 // packed adaptor weights (dcb_pair_pack_adaptor)
-    const half8* w1;                 // packed dc.0 weights (dcb_nsplit_pack_dc0 of the block)
-    const half_t* ba; const half_t* b1;
-    const float4* wsilu;
-    half_t* y; int ldy;              // `in` [M][ldy], C channels
-    half_t* t1; int ldt1;            // dc.0 output [M][ldt1], CI channels
-    int M;
-};
-
 template <int CIN, int C, int CI, int PXT>
 struct Lay {
     static constexpr int CINP = (CIN + 127) / 128 * 128;              // LDS rows in groups of 16 chunks
@@ -329,6 +318,7 @@ void launch_pair(const PairParams& p, hipStream_t stream)
     hip_check(hipGetLastError(), "dcb_pair8 launch");
 }
 
+// (declared in dcb_shapes.h; instantiated explicitly in dcb_pair8_<C>.hip)
 template <int CIN, int C, int CI>
 void run_pair(const PairParams& p, bool wide, hipStream_t stream)
 {

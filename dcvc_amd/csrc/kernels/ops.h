@@ -76,8 +76,8 @@ void conv1x1(const Conv1x1Desc& d, hipStream_t stream);
 // Bit-identical to conv1x1(dc.3) + conv1x1(ffn.0, wsilu, chunk_add) + conv1x1(ffn.2) [+ conv1x1(dc.0, wsilu)].
 // Activations in LDS, every wave owns a quarter of
 // the output channels and streams ITS weight fragments straight from L2 out of a pre-packed per-wave stream
-// (dcb_nsplit_pack_main / _dc0, packed once at set_param time). (c, ci) = (block width, inner width cdc = cffn):
-// (256, 256), (384, 384), (512, 512), (768, 768), and the half-width `dcb2` blocks (512, 256), (256, 128). Bit-identical to
+// (dcb_nsplit_pack_main / _dc0, packed once at set_param time). (c, ci) = (block width, inner width cdc = cffn): the rows of
+// BLOCK_SHAPES (kernels/dcb_shapes.h), full-width and the half-width `dcb2` blocks. Bit-identical to
 // the launch sequence. y may alias x (a workgroup reads and writes only its own pixels).
 struct DcbNsplitDesc {
     const half_t* t2 = nullptr; int ldt = 0;
@@ -103,8 +103,8 @@ struct DcbNsplitDesc {
     const half_t* t1 = nullptr; const half_t* wdw = nullptr; int width = 0;
 };
 bool dcb_nsplit_dw_supported(int c, int ci, int pixels);      // (256, 128); (384, 192) on 32-pixel workgroups. DCVC_NSPLIT_DW=0: never (A/B)
-int dcb_nsplit_waves();                                      // 8
 bool dcb_nsplit_shape(int c, int ci);                         // a shape the kernel is instantiated for
+void dcb_nsplit_check_shape(int c, int ci);                   // throws std::invalid_argument naming the shapes there are
 bool dcb_nsplit_supported(int c, int cdc, int cffn);          // DCVC_NSPLIT: 0 = off, 1 = full-width blocks only (A/B)
 size_t dcb_nsplit_main_halves(int c, int ci);
 size_t dcb_nsplit_dc0_halves(int c, int ci);
@@ -112,6 +112,7 @@ void dcb_nsplit_pack_main(const half_t* w3, const half_t* w0, const half_t* w2, 
 void dcb_nsplit_pack_dc0(const half_t* w1, int c, int ci, half_t* out, hipStream_t stream);
 bool dcb_nsplit_fin_supported(int c, int ci, int nn);        // a closing conv of width nn behind a (c, ci) block in one launch
 size_t dcb_nsplit_fin_halves(int c, int nn);
+bool dcb_nsplit_fin_packable(int c, int nn);                 // a closing conv [nn][c] dcb_nsplit_pack_fin takes (FinW::load packs exactly these)
 void dcb_nsplit_pack_fin(const half_t* w /* [nn][c] */, int c, int nn, half_t* out, hipStream_t stream);
 void dcb_nsplit(const DcbNsplitDesc& d, hipStream_t stream);
 void dcb_nsplit_timeline_buffer(long long* device_buffer);    // tuning aid: [workgroups][32] shader-clock stamps

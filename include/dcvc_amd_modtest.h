@@ -81,6 +81,17 @@ int dcvc_modtest_upsample_forward(dcvc_modtest* h, int module, void* x, int ldx,
 int dcvc_modtest_subpel_forward(dcvc_modtest* h, int module, void* x, int ldx, int cx, void* y, int ldy, int cy, int H, int W,
                                 void* up_tmp, int with_zeros, int n, void* stream);
 
+/* The block kernels' packed weight streams (tests/test_block_pack_gpu.py): packs device weights into the device buffer `out`
+ * (cap halves) on `stream` and returns the stream's size in halves, or -1. No handle, no allocation, no synchronisation.
+ * (a, b) = (c, ci) for MAIN (w0 = dc.3 [c][ci], w1 = ffn.0 [4 ci][c], w2 = ffn.2 [c][ci]) and DC0 (w0 [ci][c]), (c, nn) for
+ * FIN (w0 [nn][c]), (cin, c) for ADAPTOR (w0 [c][cin]); w1, w2 null but for MAIN */
+#define DCVC_MODTEST_PACK_MAIN    0
+#define DCVC_MODTEST_PACK_DC0     1
+#define DCVC_MODTEST_PACK_FIN     2
+#define DCVC_MODTEST_PACK_ADAPTOR 3
+long long dcvc_modtest_pack_stream(int kind, const void* w0, const void* w1, const void* w2, int a, int b, void* out, long long cap,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

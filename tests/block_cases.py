@@ -36,17 +36,6 @@ def nsplit8_instantiations():
                 continue                                    # a declaration: instantiated in its _fin unit
             a = _ints(m.group(2))
             keys.add(("nsplit8", a[0], a[1], a[2], a[3], a[4] if len(a) > 4 else 0))
-        for m in re.finditer(r"run_shape8<([\d,\s]+)>", src):
-            a = _ints(m.group(1))
-            C, CI, fins = a[0], a[1], a[2:]
-            for pxt in ((1, 2) if C < 768 else (1,)):
-                for nx in [0, 1] + fins:
-                    keys.add(("nsplit8", C, CI, pxt, nx, 0))
-        for m in re.finditer(r"run_px8_dw<([\d,\s]+)>", src):
-            a = _ints(m.group(1))
-            C, CI, pxt, fins = a[0], a[1], a[2], a[3:]
-            for nx in [0, 1] + fins:
-                keys.add(("nsplit8", C, CI, pxt, nx, 1))
     return keys
 
 

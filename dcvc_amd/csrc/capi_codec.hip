@@ -7,6 +7,7 @@
 #include "kernels/arith.h"
 
 #include <cstring>
+#include <string>
 
 struct dcvc_dmci {
     dcvc::DmciCodec codec;
@@ -144,6 +145,15 @@ int64_t estimate_symbols(H* c)
     return guarded_size([&] {
         if (c == nullptr || c->est_kept < 0) throw std::invalid_argument("estimate_symbols: no size probe yet");
         return c->est_kept;
+    });
+}
+
+template <typename H>
+int reconstruct(H* c, const char* entry, void* x_hat, void* stream)
+{
+    return dcvc::guarded([&] {
+        if (c == nullptr || x_hat == nullptr) throw std::invalid_argument(std::string(entry) + ": null codec or x_hat pointer");
+        c->codec.reconstruct(static_cast<dcvc::half_t*>(x_hat), hip_stream(stream));
     });
 }
 
@@ -337,6 +347,8 @@ int dcvc_dmcld_estimate_bits(dcvc_dmcld* c, const void* x, int height, int width
 
 int64_t dcvc_dmcld_estimate_symbols(dcvc_dmcld* c) { return estimate_symbols(c); }
 
+int dcvc_dmcld_reconstruct(dcvc_dmcld* c, void* x_hat, void* stream) { return reconstruct(c, "dcvc_dmcld_reconstruct", x_hat, stream); }
+
 int64_t dcvc_dmcld_export_state(dcvc_dmcld* c, void* dst, size_t cap, void* stream) { return export_state(c, dst, cap, stream); }
 
 int dcvc_dmcld_import_state(dcvc_dmcld* c, const void* src, size_t bytes, int height, int width, void* stream)
@@ -398,6 +410,8 @@ int dcvc_dmcht_estimate_bits(dcvc_dmcht* c, const void* x, int height, int width
 }
 
 int64_t dcvc_dmcht_estimate_symbols(dcvc_dmcht* c) { return estimate_symbols(c); }
+
+int dcvc_dmcht_reconstruct(dcvc_dmcht* c, void* x_hat, void* stream) { return reconstruct(c, "dcvc_dmcht_reconstruct", x_hat, stream); }
 
 int64_t dcvc_dmcht_export_state(dcvc_dmcht* c, void* dst, size_t cap, void* stream) { return export_state(c, dst, cap, stream); }
 

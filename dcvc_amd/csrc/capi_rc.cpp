@@ -75,6 +75,17 @@ int dcvc_rc_pick_qp_near(dcvc_rc_estimate_fn estimate, void* user, int64_t budge
     return e < 0 ? e : qp;
 }
 
+int dcvc_rc_pick_qp_for_quality(dcvc_rc_quality_fn measure, void* user, double target, int start, int qp_min, int qp_max,
+                                int* trials)
+{
+    int qp = -1;
+    const int e = dcvc::guarded([&] {
+        if (measure == nullptr) throw std::invalid_argument("pick_qp_for_quality: null measure");
+        qp = dcvc::pick_qp_for_quality([&](int q) { return measure(q, user); }, target, start, qp_min, qp_max, trials);
+    });
+    return e < 0 ? e : qp;
+}
+
 int64_t dcvc_rc_unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits, int horizon,
                                  int n)
 {

@@ -13,6 +13,7 @@
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
+//               [--target-psnr DB [--qp-min 0] [--qp-max 63]] [--quality-log log.json]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
@@ -77,6 +78,24 @@
 //               that start value plus --rc-intra-bonus, and their bits count as spent. --rc-log: "mode": "probe", P units
 //               with probes >= 1 and predicted_bytes, I units with probes 0 and null. All-intra runs ignore the flag (they
 //               probe already); the stream format and the decoder do not change.
+//               --quality-log FILE (encode, any rate mode): the encoder measures every coded unit's reconstruction - an
+//               I picture's intra x_hat, a P unit's pictures from dcvc_dmcld_reconstruct / dcvc_dmcht_reconstruct, which leave the
+//               temporal state as it is - against the source samples it uploaded (with --scale: the resampled planes, at the coded
+//               size), on the device, with the calls and geometry decode --ref uses for the source type and depth (8-bit yuv420:
+//               dcvc_x_to_pix(DCVC_PIX_YUV420P, 8) -> dcvc_sse_ws, where the decoder sums fp16 planes on the host: the same values
+//               summed in another order). The log: {target_psnr | null, qp_min, qp_max, width, height, src_type, bit_depth, units:
+//               [{type, first_picture, pictures, qp, trials, bytes, psnr, frame_psnr, frame_psnr_y, _u, _v (YUV only)}],
+//               ave_all_frame_psnr, total_trials}. frame_psnr is the decoder's log's: (6 Y + U + V) / 8, or the RGB PSNR; a unit's
+//               psnr is the mean over the pictures it really holds (not the padding pictures of a ragged last chunk). The output
+//               file does not change by a byte.
+//               --target-psnr DB [--qp-min 0] [--qp-max 63] (encode): every unit is coded at the smallest q_index in the range whose
+//               trial coding meets DB (its psnr above >= DB), qp_max when none does: dcvc_rc_pick_qp_for_quality from the previous
+//               unit's q_index of the same type (--qp-i for the first of each): gallop, then bisection, 2 trials when the q_index
+//               stays, at most 12. An I trial is dcvc_dmci_compress; a P unit's state is exported once, every trial after the first
+//               imports it, then compress, reconstruct, measure. The unit is the chosen trial's stream, and the encoder goes on from
+//               the state behind that trial (kept from the last trial that met). Picture types, the reset rule and --scene-cut work
+//               as without the flag; the container carries every unit's q_index: decode needs no option. Refused: a target that is
+//               not finite or not positive, --target-bpp, --qp-p, --batch above 1, --qp-min above --qp-max.
 //               --scene-cut T [--scene-min-gap G] [--scene-log log.json] (encode, one-picture inter model = LD): an I picture
 //               where the source changes scene. Every source picture is converted first and measured on
 //               the device (dcvc_luma_sad: 8-bit luma of x, sum of absolute differences against the previous picture);
@@ -150,6 +169,7 @@
 #include <cstring>
 #include <filesystem>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -747,6 +767,7 @@ RateArgs rate_args(const Args& a, int batch)
     RateArgs r;
     if (!a.has("target-bpp")) {
         for (const char* k : {"qp-min", "qp-max", "rc-horizon", "rc-intra-bonus", "rc-log", "rc-mode"}) {
+            if (a.has("target-psnr") && (std::strcmp(k, "qp-min") == 0 || std::strcmp(k, "qp-max") == 0)) continue;      // quality_args
             if (a.has(k)) die(std::string("--") + k + " needs --target-bpp");
         }
         return r;
@@ -770,6 +791,37 @@ RateArgs rate_args(const Args& a, int batch)
     if (mode != "feedback" && mode != "probe") die("--rc-mode must be feedback or probe, got " + mode);
     r.probe = mode == "probe";
     return r;
+}
+
+// --target-psnr with --qp-min / --qp-max, and --quality-log, refused before anything touches the device
+struct QualityArgs {
+    bool target_on = false;
+    double target = 0;
+    int qp_min = 0, qp_max = 63;
+    std::string log;
+    bool on() const { return target_on || !log.empty(); }
+};
+
+QualityArgs quality_args(const Args& a, int batch)
+{
+    QualityArgs q;
+    q.log = a.str("quality-log");
+    if (a.has("quality-log") && q.log.empty()) die("--quality-log needs a file name");
+    if (!a.has("target-psnr")) return q;
+    q.target_on = true;
+    const std::string s = a.str("target-psnr");
+    char* end = nullptr;
+    q.target = strtod(s.c_str(), &end);
+    if (s.empty() || *end != '\0' || !std::isfinite(q.target) || !(q.target > 0)) {
+        die("--target-psnr must be a positive number of dB, got " + s);
+    }
+    if (a.has("target-bpp")) die("--target-psnr cannot be combined with --target-bpp: a unit is coded to a quality or to a rate");
+    if (a.has("qp-p")) die("--target-psnr cannot be combined with --qp-p: the search chooses the q_index of the P units");
+    if (batch > 1) die("--target-psnr cannot be combined with --batch above 1: a batch has one q_index");
+    q.qp_min = int_arg(a, "qp-min", 0, 0, 63);
+    q.qp_max = int_arg(a, "qp-max", 63, 0, 63);
+    if (q.qp_min > q.qp_max) die("--qp-min " + std::to_string(q.qp_min) + " is above --qp-max " + std::to_string(q.qp_max));
+    return q;
 }
 
 // --scene-cut and its companions; what the flags alone decide is refused before a model is loaded
@@ -1182,6 +1234,102 @@ void x_hat_to_picture(const Geometry& g, const DeviceBuffers& b, const char* xh,
     }
 }
 
+// --quality-log / --target-psnr: the encoder's own measurement of a reconstruction against the source samples
+// it uploaded, with the calls and the geometry decode --ref uses for the source type and depth; every sum stays on the device.
+// 8-bit YUV420, where the decoder sums fp16 planes on the host: dcvc_x_to_pix(DCVC_PIX_YUV420P, 8) -> dcvc_sse_ws, fp32 planes
+// that hold the same values.
+struct PictureQuality {
+    double psnr = 0, y = 0, u = 0, v = 0;
+};
+
+struct QualityMeter {
+    uint8_t* src = nullptr;        // per slot: the source picture as planar samples (RGB: u8 [3][H][W]; YUV: Y, Cb, Cr planes)
+    void* dist = nullptr;          // the reconstruction's distortion planes: fp16 [3][H][W] (RGB), fp32 [H][W] + [2][Hc][Wc] (YUV)
+    double* sse = nullptr;
+    double* h_sse = nullptr;       // pinned
+    void* ws = nullptr;
+    long long ws_bytes = 0;
+    void create(const Geometry& g, int slots)
+    {
+        hip_ok(hipMalloc(&src, g.frame_bytes() * static_cast<size_t>(slots)), "hipMalloc");
+        hip_ok(hipMalloc(&dist, g.rgb ? g.y_bytes() * 6 : (g.y_bytes() + g.uv_bytes()) * 4), "hipMalloc");
+        hip_ok(hipMalloc(&sse, 3 * sizeof(double)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+        ws_bytes = g.rgb ? dcvc_sse_workspace_bytes(3, g.H, g.W)
+                         : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.Hc(), g.Wc()));
+        hip_ok(hipMalloc(&ws, static_cast<size_t>(ws_bytes)), "hipMalloc");
+    }
+    // the picture in the staging planes b.yuv8 (at the coded size: behind --scale's resampler) -> slot; in stream order
+    void capture(const Geometry& g, const DeviceBuffers& b, int slot)
+    {
+        uint8_t* dst = src + g.frame_bytes() * static_cast<size_t>(slot);
+        if (g.rgb) {
+            abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, dst, b.st), "rgb_to_x (planar source)");
+        } else if (g.pix()) {
+            abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, nullptr, 3, dst, b.st), "pix_to_x (planar source)");
+        } else {
+            hip_ok(hipMemcpyAsync(dst, b.yuv8, g.frame_bytes(), hipMemcpyDeviceToDevice, b.st), "D2D");
+        }
+    }
+    // x_hat (fp16 [rows][g.Wp][3]) against the source in `slot`; waits for the stream
+    PictureQuality measure(const Geometry& g, const char* xh, int slot, hipStream_t st)
+    {
+        const uint8_t* s = src + g.frame_bytes() * static_cast<size_t>(slot);
+        PictureQuality q;
+        if (g.rgb) {
+            const size_t plane = g.y_bytes();
+            if (g.cs) abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, dist, nullptr, g.matrix, g.range, g.yuv_depth, st), "x_to_rgb_cs");
+            else abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, dist, nullptr, st), "x_to_rgb");
+            abi_ok(dcvc_sse_ws(s, DCVC_SAMPLE_U8, dist, DCVC_SAMPLE_F16, 3, g.H, g.W, g.W, static_cast<long long>(plane), sse, ws, ws_bytes, st),
+                   "sse");
+            hip_ok(hipMemcpyAsync(h_sse, sse, 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            q.psnr = psnr_of_sse((h_sse[0] + h_sse[1]) + h_sse[2], 3.0 * static_cast<double>(plane));
+            return q;
+        }
+        const size_t ny = g.y_bytes(), nc = static_cast<size_t>(g.Hc()) * g.Wc(), es = g.hbd() ? 2 : 1;
+        const int dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const double peak = static_cast<double>((1 << g.bit_depth) - 1);
+        if (g.pix()) abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, dist, nullptr, st), "x_to_pix");
+        else if (g.hbd()) abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, dist, nullptr, st), "x_to_yuv420p16");
+        else abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, DCVC_PIX_YUV420P, 8, dist, nullptr, st), "x_to_pix");
+        const char* dist_uv = static_cast<const char*>(dist) + ny * 4;
+        abi_ok(dcvc_sse_ws(s, dt, dist, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), sse, ws, ws_bytes, st), "sse (Y)");
+        abi_ok(dcvc_sse_ws(s + ny * es, dt, dist_uv, DCVC_SAMPLE_F32, 2, g.Hc(), g.Wc(), g.Wc(), static_cast<long long>(nc), sse + 1, ws,
+                           ws_bytes, st), "sse (U, V)");
+        hip_ok(hipMemcpyAsync(h_sse, sse, 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        q.y = psnr_of_sse(h_sse[0], static_cast<double>(ny), peak);
+        q.u = psnr_of_sse(h_sse[1], static_cast<double>(nc), peak);
+        q.v = psnr_of_sse(h_sse[2], static_cast<double>(nc), peak);
+        q.psnr = (6 * q.y + q.u + q.v) / 8;
+        return q;
+    }
+    void destroy()
+    {
+        for (void* d : {static_cast<void*>(src), dist, static_cast<void*>(sse), ws}) {
+            if (d) hip_ok(hipFree(d), "hipFree");
+        }
+        if (h_sse) hip_ok(hipHostFree(h_sse), "hipHostFree");
+        *this = QualityMeter{};
+    }
+};
+
+// one coded unit in --quality-log
+struct QualityUnit {
+    bool intra = false;
+    int first_picture = 0, qp = 0, trials = 0;
+    long long bytes = 0;
+    double psnr = 0;
+    std::vector<PictureQuality> pictures;
+};
+
+// dcvc_rc_pick_qp_for_quality's callback: the trial coding of a unit at qp -> its quality
+struct QualityTrial {
+    std::function<double(int)> run;
+    static double call(int qp, void* user) { return static_cast<QualityTrial*>(user)->run(qp); }
+};
+
 // one source picture in --scene-log
 struct ScenePicture {
     long long sad = 0;
@@ -1202,6 +1350,7 @@ int encode(const Args& a)
 {
     const int batch = batch_arg(a);
     const SceneArgs scene = scene_args(a, batch);
+    const QualityArgs quality = quality_args(a, batch);
     const RateArgs rate = rate_args(a, batch);
     const ColourArgs colour = colour_args(a);
     HashRun hash;
@@ -1265,6 +1414,14 @@ int encode(const Args& a)
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
     DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
+    // --quality-log / --target-psnr: every converted picture's source samples stay on the device, one slot per picture of a unit
+    QualityMeter meter;
+    if (quality.on()) meter.create(g, std::max(delay, batch));
+    std::vector<QualityUnit> quality_units;
+    void* trial_state = nullptr;           // --target-psnr: the inter codec's state in front of a P unit's trials
+    long long trial_state_bytes = 0;
+    void* kept_dev = nullptr;              // ... and what the last trial that met left: the intra x_hat, or the inter codec's state
+    size_t kept_cap = 0;
     // --hash-log: the intra encoder's reconstruction as the decoder would write it, with the source's type and depth at the
     // coded size
     hash.begin(src_type_name(type), depth);
@@ -1336,6 +1493,7 @@ int encode(const Args& a)
     // ... or, with --rc-mode probe, search every P unit's q_index on the inter model's probe (rate_control.code_sequence_probed)
     const bool rate_probe = rate.on && !rate_search && rate.probe;
     int start_q = qp_i, pictures_coded = 0;
+    int quality_start_i = qp_i, quality_start_p = qp_i;      // --target-psnr: the previous unit's q_index, per type
     dcvc_rc* ctl = nullptr;
     if (rate.on && !rate_search && !rate_probe) {
         ctl = dcvc_rc_create(rate.target_bpp, pixels, qp_i, rate.horizon, rate.intra_bonus, rate.qp_min, rate.qp_max, 0.049);
@@ -1388,6 +1546,7 @@ int encode(const Args& a)
         bool intra = is_intra_picture(idx, intra_period);
         if (scd) {
             load_picture();
+            if (quality.on()) meter.capture(g, b, 0);
             convert(static_cast<char*>(b.x), 3, true, idx > 0);
             ScenePicture sp;
             sp.sad = idx > 0 ? static_cast<long long>(*b.h_sad) : 0;
@@ -1408,6 +1567,7 @@ int encode(const Args& a)
             for (int j = 0; j < nb; ++j) {
                 char* dst = static_cast<char*>(b.x) + slot * j;
                 load_picture();
+                if (quality.on()) meter.capture(g, b, j);
                 convert(dst, 3);
             }
             int ecs[16];
@@ -1421,6 +1581,13 @@ int encode(const Args& a)
                 if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
                 if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, xh, g.Hp, g.Wp, 1, b.st), "add_ref");
                 if (hash.on()) hash_x_hat(xh);
+                if (quality.on()) {
+                    QualityUnit qu;
+                    qu.intra = true; qu.first_picture = idx + j; qu.qp = qp_i; qu.bytes = nbytes;
+                    qu.pictures.push_back(meter.measure(g, xh, j, b.st));
+                    qu.psnr = qu.pictures[0].psnr;
+                    quality_units.push_back(qu);
+                }
                 put_unit(true, qp_i, ecs[j], 0, payload);
             }
             idx += nb;
@@ -1432,6 +1599,7 @@ int encode(const Args& a)
         for (int j = 0; j < slots && !scd; ++j) {
             char* dst = static_cast<char*>(b.x) + 6 * j;
             if (j < want) load_picture();      // a short last chunk repeats its final picture (test_video.py:104-110)
+            if (quality.on() && j < want) meter.capture(g, b, j);
             convert(dst, ldx);
         }
         int ec = 0, reset = 0, qp = qp_i;
@@ -1458,7 +1626,126 @@ int encode(const Args& a)
             ru.predicted_bytes = p.bytes.at(qp);
             start_q = qp;
         }
-        if (intra) {
+        // --quality-log / --target-psnr: the unit's reconstruction measured on the device. An I picture's is the intra x_hat; a P
+        // unit's comes from dcvc_dmc*_reconstruct, which leaves the temporal state as it is. The padding pictures of a ragged
+        // last chunk (slots want .. delay - 1) do not count.
+        QualityUnit qu;
+        qu.intra = intra; qu.first_picture = idx;
+        auto code_intra = [&](int q) {
+            ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, q, pad_b, pad_r, b.x_hat, b.st);
+            abi_ok(ec, "intra compress");
+            nbytes = dcvc_dmci_get_stream(c.intra, nullptr, 0);
+            payload.resize(static_cast<size_t>(nbytes));
+            abi_ok(dcvc_dmci_get_stream(c.intra, payload.data(), payload.size()), "get_stream");
+        };
+        auto code_inter = [&](int q) {
+            if (c.ld) {
+                ec = dcvc_dmcld_compress(c.ld, b.x, g.H, g.W, q, reset, pad_b, pad_r, b.st);
+                abi_ok(ec, "inter compress");
+                nbytes = dcvc_dmcld_get_stream(c.ld, nullptr, 0);
+                payload.resize(static_cast<size_t>(nbytes));
+                abi_ok(dcvc_dmcld_get_stream(c.ld, payload.data(), payload.size()), "get_stream");
+            } else {
+                ec = dcvc_dmcht_compress(c.ht, b.x, g.H, g.W, q, reset, pad_b, pad_r, b.st);
+                abi_ok(ec, "inter compress");
+                nbytes = dcvc_dmcht_get_stream(c.ht, nullptr, 0);
+                payload.resize(static_cast<size_t>(nbytes));
+                abi_ok(dcvc_dmcht_get_stream(c.ht, payload.data(), payload.size()), "get_stream");
+            }
+        };
+        auto measure_unit = [&]() {
+            if (!intra) {
+                abi_ok(c.ld ? dcvc_dmcld_reconstruct(c.ld, b.x_hat, b.st) : dcvc_dmcht_reconstruct(c.ht, b.x_hat, b.st), "reconstruct");
+            }
+            qu.pictures.clear();
+            double sum = 0;
+            for (int j = 0; j < want; ++j) {
+                const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
+                qu.pictures.push_back(meter.measure(g, xh, j, b.st));
+                sum += qu.pictures.back().psnr;
+            }
+            qu.psnr = sum / want;
+            return qu.psnr;
+        };
+        if (!intra) reset = (reset_interval > 0 && (idx + delay) % reset_interval == 1) ? 1 : 0;
+        if (quality.target_on) {
+            // rate_control.code_sequence_quality: the smallest q_index in [--qp-min, --qp-max] whose trial coding meets the target,
+            // searched from the previous unit's q_index of the same type (--qp-i for the first). A P unit's trials all start from
+            // the state exported once in front of them. The unit is the chosen trial - the last trial that met, or the last
+            // trial when none did: every trial that meets leaves its stream, its figures and what the encoder goes on from (the
+            // intra x_hat; the inter codec's state behind it) in `kept`, and a chosen trial that was not the last one is put
+            // back from there. Coding it again from the same state would give the same bytes and costs a compress.
+            int& start = intra ? quality_start_i : quality_start_p;
+            int last_q = -1;
+            bool first = true;
+            if (!intra) {
+                const long long sb = c.ld ? dcvc_dmcld_export_state(c.ld, nullptr, 0, b.st) : dcvc_dmcht_export_state(c.ht, nullptr, 0, b.st);
+                abi_ok(sb, "export_state");
+                if (sb != trial_state_bytes) {
+                    if (trial_state) hip_ok(hipFree(trial_state), "hipFree");
+                    hip_ok(hipMalloc(&trial_state, static_cast<size_t>(sb)), "hipMalloc");
+                    trial_state_bytes = sb;
+                }
+                abi_ok(c.ld ? dcvc_dmcld_export_state(c.ld, trial_state, static_cast<size_t>(sb), b.st)
+                            : dcvc_dmcht_export_state(c.ht, trial_state, static_cast<size_t>(sb), b.st), "export_state");
+            }
+            auto restore = [&]() {
+                abi_ok(c.ld ? dcvc_dmcld_import_state(c.ld, trial_state, static_cast<size_t>(trial_state_bytes), g.H, g.W, b.st)
+                            : dcvc_dmcht_import_state(c.ht, trial_state, static_cast<size_t>(trial_state_bytes), g.H, g.W, b.st), "import_state");
+            };
+            const size_t kept_bytes = intra ? static_cast<size_t>(g.Hp) * g.Wp * 3 * 2 : static_cast<size_t>(trial_state_bytes);
+            if (kept_bytes > kept_cap) {
+                if (kept_dev) hip_ok(hipFree(kept_dev), "hipFree");
+                hip_ok(hipMalloc(&kept_dev, kept_bytes), "hipMalloc");
+                kept_cap = kept_bytes;
+            }
+            int kept_q = -1, kept_ec = 0;
+            std::vector<uint8_t> kept_payload;
+            QualityUnit kept_unit;
+            QualityTrial trial;
+            trial.run = [&](int q) {
+                if (intra) {
+                    code_intra(q);
+                } else {
+                    if (!first) restore();
+                    code_inter(q);
+                }
+                first = false;
+                last_q = q;
+                const double got = measure_unit();
+                if (got >= quality.target) {
+                    kept_q = q; kept_ec = ec; kept_payload = payload; kept_unit = qu;
+                    if (intra) {
+                        hip_ok(hipMemcpyAsync(kept_dev, b.x_hat, kept_bytes, hipMemcpyDeviceToDevice, b.st), "D2D");
+                    } else {
+                        abi_ok(c.ld ? dcvc_dmcld_export_state(c.ld, kept_dev, kept_bytes, b.st) : dcvc_dmcht_export_state(c.ht, kept_dev, kept_bytes, b.st),
+                               "export_state");
+                    }
+                }
+                return got;
+            };
+            int trials = 0;
+            qp = dcvc_rc_pick_qp_for_quality(QualityTrial::call, &trial, quality.target, start, quality.qp_min, quality.qp_max, &trials);
+            abi_ok(qp, "quality search");
+            if (qp != last_q && qp == kept_q) {
+                ec = kept_ec; payload = kept_payload; qu = kept_unit;
+                if (intra) {
+                    hip_ok(hipMemcpyAsync(b.x_hat, kept_dev, kept_bytes, hipMemcpyDeviceToDevice, b.st), "D2D");
+                } else {
+                    abi_ok(c.ld ? dcvc_dmcld_import_state(c.ld, kept_dev, kept_bytes, g.H, g.W, b.st)
+                                : dcvc_dmcht_import_state(c.ht, kept_dev, kept_bytes, g.H, g.W, b.st), "import_state");
+                }
+            } else if (qp != last_q) {
+                die("quality search: the chosen q_index " + std::to_string(qp) + " is neither the last trial nor the last that met");
+            }
+            qu.trials = trials;
+            start = qp;
+            if (intra) {
+                if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (hash.on()) hash_x_hat(static_cast<const char*>(b.x_hat));
+            }
+        } else if (intra) {
             ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, qp, pad_b, pad_r, b.x_hat, b.st);
             abi_ok(ec, "intra compress");
             nbytes = dcvc_dmci_get_stream(c.intra, nullptr, 0);
@@ -1469,7 +1756,6 @@ int encode(const Args& a)
             if (hash.on()) hash_x_hat(static_cast<const char*>(b.x_hat));
         } else {
             if (!ctl && !rate_probe) qp = qp_p;
-            reset = (reset_interval > 0 && (idx + delay) % reset_interval == 1) ? 1 : 0;
             if (c.ld) {
                 ec = dcvc_dmcld_compress(c.ld, b.x, g.H, g.W, qp, reset, pad_b, pad_r, b.st);
                 abi_ok(ec, "inter compress");
@@ -1483,6 +1769,11 @@ int encode(const Args& a)
                 payload.resize(static_cast<size_t>(nbytes));
                 abi_ok(dcvc_dmcht_get_stream(c.ht, payload.data(), payload.size()), "get_stream");
             }
+        }
+        if (quality.on()) {
+            if (!quality.target_on) measure_unit();
+            qu.qp = qp; qu.bytes = static_cast<long long>(payload.size());
+            quality_units.push_back(qu);
         }
         put_unit(intra, qp, ec, reset, payload);
         if (rate.on) {
@@ -1545,6 +1836,46 @@ int encode(const Args& a)
             js += "]}\n";
             FILE* lf = fopen(rate.log.c_str(), "wb");
             if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + rate.log);
+            fclose(lf);
+        }
+    }
+    if (quality.on()) {
+        if (trial_state) hip_ok(hipFree(trial_state), "hipFree");
+        if (kept_dev) hip_ok(hipFree(kept_dev), "hipFree");
+        meter.destroy();
+        double sum = 0;
+        long long count = 0, total_trials = 0;
+        for (const QualityUnit& u : quality_units) {
+            for (const PictureQuality& q : u.pictures) sum += q.psnr;
+            count += static_cast<long long>(u.pictures.size());
+            total_trials += u.trials;
+        }
+        const double ave = count ? sum / static_cast<double>(count) : 0.0;
+        if (quality.target_on) {
+            printf("quality: target %.4f dB, coded %.4f dB in %zu units, %lld trial codings\n", quality.target, ave, quality_units.size(),
+                   total_trials);
+        }
+        if (!quality.log.empty()) {
+            std::string js = "{\"target_psnr\": " + (quality.target_on ? jnum(quality.target) : std::string("null")) +
+                             ", \"qp_min\": " + std::to_string(quality.qp_min) + ", \"qp_max\": " + std::to_string(quality.qp_max) +
+                             ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) + ", \"src_type\": \"" +
+                             src_type_name(type) + "\", \"bit_depth\": " + std::to_string(depth) + ", \"units\": [";
+            for (size_t i = 0; i < quality_units.size(); ++i) {
+                const QualityUnit& u = quality_units[i];
+                std::vector<double> all, py, pu, pv;
+                for (const PictureQuality& q : u.pictures) {
+                    all.push_back(q.psnr); py.push_back(q.y); pu.push_back(q.u); pv.push_back(q.v);
+                }
+                js += std::string(i ? ", " : "") + "{\"type\": \"" + (u.intra ? "I" : "P") + "\", \"first_picture\": " +
+                      std::to_string(u.first_picture) + ", \"pictures\": " + std::to_string(u.pictures.size()) + ", \"qp\": " +
+                      std::to_string(u.qp) + ", \"trials\": " + std::to_string(u.trials) + ", \"bytes\": " + std::to_string(u.bytes) +
+                      ", \"psnr\": " + jnum(u.psnr) + ", \"frame_psnr\": " + jlist(all);
+                if (!rgb) js += ", \"frame_psnr_y\": " + jlist(py) + ", \"frame_psnr_u\": " + jlist(pu) + ", \"frame_psnr_v\": " + jlist(pv);
+                js += "}";
+            }
+            js += "], \"ave_all_frame_psnr\": " + jnum(ave) + ", \"total_trials\": " + std::to_string(total_trials) + "}\n";
+            FILE* lf = fopen(quality.log.c_str(), "wb");
+            if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + quality.log);
             fclose(lf);
         }
     }

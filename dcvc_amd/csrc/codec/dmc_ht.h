@@ -40,6 +40,11 @@ public:
     // Not in the reference: the size probe, as DmcLdCodec::estimate_bits. x as for compress.
     void estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept, hipStream_t stream);
 
+    // Not in the reference: the encoder-side reconstruction, as DmcLdCodec::reconstruct. All 8 pictures of
+    // the chunk whose feature_p the object holds, whatever set_recon_mask says; x_hat as for decompress. Every head output,
+    // picture 7's too, goes to RH: FI is state.
+    void reconstruct(half_t* x_hat, hipStream_t stream);
+
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
     // Temporal state (reference feature, memory | feature_p, ctx + validity flags) as one flat DEVICE
@@ -103,7 +108,7 @@ private:
     half_t* m_TI = nullptr;      // [P8][512]   memory * q_feature
     half_t* m_RC = nullptr;      // [P8][512]   recon head: shared trunk of a picture pair (HT-S)
     half_t* m_RT = nullptr;      // [P8][256]   recon head: per-picture chain
-    half_t* m_RH = nullptr;      // [P8][192]   recon head: head output of pictures 0..6
+    half_t* m_RH = nullptr;      // [P8][192]   recon head: head output of pictures 0..6 (reconstruct(): of all 8)
     half_t* m_UPT = nullptr;     // biased upsampler temporary (HT-L)
     half_t *m_Y = nullptr, *m_Ypad = nullptr;
     half_t *m_Z1 = nullptr, *m_Z2 = nullptr, *m_Z3 = nullptr, *m_ZH = nullptr;

@@ -10,7 +10,7 @@ namespace dcvc {
 namespace {
 
 enum StageKey : int { kRef = 0, kEnc0 = 1, kEnc1 = 2 /* +reset */, kDec0 = 10 /* +memory_has_value */,
-                      kDec1 = 12, kDec2 = 13, kDecStep = 20 /* +k */ };
+                      kDec1 = 12, kDec2 = 13, kDecStep = 20 /* +k */, kRecon = 30 };
 
 }  // namespace
 
@@ -504,6 +504,25 @@ void DmcHtCodec::run_recon_heads(unsigned mask, half_t* x_hat, hipStream_t user)
         throw;
     }
     m_recon_mask = keep;
+    leave(user);
+}
+
+// ------------------------------------------------------------------------------------ encoder-side reconstruction
+void DmcHtCodec::reconstruct(half_t* x_hat, hipStream_t user)
+{
+    require_feature_p("reconstruct");
+    const Geometry& g = m_g;
+    const size_t picture = static_cast<size_t>(g.P8()) * 64 * 3;
+    hipStream_t st = enter(user);
+    bind_stage_arg(kRecon, x_hat);
+    // reads feature_p; writes RC, RT, the scratch planes, RH and x_hat: none of them state, none read by a later stage
+    // before it is written. The launches are those of run_recon_head with the full mask, picture 7's head into RH.
+    run_stage(kRecon, st, [&] {
+        for (int i = 0; i < kFrames; ++i) {
+            run_head(i, i % 2 == 0, m_RH, st);
+            shuffle8(m_RH, kChSrcI, g.H8, g.W8, 3, true, x_hat + i * picture, st);
+        }
+    });
     leave(user);
 }
 

@@ -38,6 +38,14 @@ public:
     // other than the temporal state's.
     void estimate_bits(const half_t* x, int height, int width, int qp, int64_t units[2], int64_t* kept, hipStream_t stream);
 
+    // Not in the reference: the encoder-side reconstruction. The picture of the unit whose feature_p the
+    // object holds - after compress, after decompress, after import_state of such a state - bit-identical to what
+    // decompress of that unit's stream writes. x_hat: device fp16 [H16*16][W16*16][3]. A stage of its own (the recon head
+    // into a scratch plane, shuffle8) that reads feature_p and writes no state: export_state gives the bytes it gave
+    // before, and every later call gives what it gives without this one. Refused, with nothing touched: no parameters,
+    // no feature_p yet.
+    void reconstruct(half_t* x_hat, hipStream_t stream);
+
     size_t debug_read(const std::string& name, void* dst, size_t cap, hipStream_t stream);
 
     // Temporal state as one flat DEVICE buffer (reference feature, memory | feature_p, ctx, temporal
@@ -63,7 +71,7 @@ private:
     void run_priors(hipStream_t st);                  // z_hat, temporal -> common params (the temporal prior is only read)
     void run_spatial_prior(hipStream_t st);           // [y_hat | common] -> means of step 1
     void run_decoder(hipStream_t st);                 // y_hat, ctx -> feature_p
-    void run_recon_head(half_t* x_hat, hipStream_t st);   // feature_p -> FI (+ x_hat)
+    void run_recon_head(half_t* head, half_t* x_hat, hipStream_t st);   // feature_p -> head: FI or RHS (+ x_hat)
     void enc_stage0(hipStream_t st);                  // x, ctx, temporal -> symbols, totals, z: all compress() codes
 
     // ---- parameters
@@ -99,6 +107,7 @@ private:
     half_t* m_CATSP = nullptr;   // [P16][512] y_hat | q_dec | scales | means
     half_t* m_SPT = nullptr;     // [P16][256]
     half_t* m_MEANS1 = nullptr;  // [P16][128]
+    half_t* m_RHS = nullptr;     // [P8][192]  reconstruct(): its head output (FI is state)
 };
 
 }  // namespace dcvc

@@ -11,7 +11,7 @@ namespace dcvc {
 namespace {
 
 enum StageKey : int { kRef = 0, kEnc0 = 1, kEnc1 = 2 /* +reset */, kDec0 = 10 /* +memory_has_value */,
-                      kDec1 = 12, kDec2 = 13, kDec3 = 14 };
+                      kDec1 = 12, kDec2 = 13, kDec3 = 14, kRecon = 30 };
 constexpr uint32_t kLdMagic = 0x44434c44;     // "DCLD"
 
 }  // namespace
@@ -80,6 +80,7 @@ void DmcLdCodec::prepare(int height, int width)
     m_MEANS1 = H(P16 * kChY);
     const size_t n = P16 * kChY;
     alloc_symbol_buffers(n, 1, n);      // the compacted indexes of the one round trip, no count in front
+    m_RHS = H(P8 * kChSrc);             // last: every other buffer keeps the address it had without it
 }
 
 // ------------------------------------------------------------------------------------ networks
@@ -181,14 +182,14 @@ void DmcLdCodec::run_decoder(hipStream_t st)
     run_dcb_chain(m_dec1, 3, View(m_CATD, kChD + kChM, kChD + kChM), t, t, g.H8, g.W8, m_s, st, c);
 }
 
-void DmcLdCodec::run_recon_head(half_t* x_hat, hipStream_t st)
+void DmcLdCodec::run_recon_head(half_t* head, half_t* x_hat, hipStream_t st)
 {
     const Geometry& g = m_g;
     const View t(m_T, kChD, kChD);
-    const FinCall fin(m_rh_head, m_FI, kChSrc);            // the head output doubles as the reference feature after a reset
+    const FinCall fin(m_rh_head, head, kChSrc);            // into FI the head output doubles as the reference feature after a reset
     ChainCall c; c.tmp2 = View(m_T2, kChD, kChD); c.fin = &fin;
     run_dcb_chain(m_rh, 3, View(m_CATM + kChM, kChM + kChD, kChD), t, t, g.H8, g.W8, m_s, st, c);
-    if (x_hat != nullptr) shuffle8(m_FI, kChSrc, g.H8, g.W8, 3, true, x_hat, st);
+    if (x_hat != nullptr) shuffle8(head, kChSrc, g.H8, g.W8, 3, true, x_hat, st);
 }
 
 // ------------------------------------------------------------------------------------ reference frame
@@ -224,7 +225,7 @@ int DmcLdCodec::compress(const half_t* x, int height, int width, int qp, bool re
     run_stage(kEnc1 + (reset ? 1 : 0), st, [&] {
         run_decoder(st);
         if (reset) {
-            run_recon_head(nullptr, st);     // forward_reset, dmc_ld_proxy.cpp:297-305
+            run_recon_head(m_FI, nullptr, st);     // forward_reset, dmc_ld_proxy.cpp:297-305
             run_fa_i(st, true);
         } else {
             run_fa_m(st, true);
@@ -324,10 +325,22 @@ void DmcLdCodec::decompress(const uint8_t* bits, size_t nbytes, int qp, int heig
         d.means = m_MEANS1; d.ldm = kChY; d.step = 1;
         mask_step_dec(d, st);
         run_decoder(st);
-        run_recon_head(x_hat, st);
+        run_recon_head(m_FI, x_hat, st);
     });
     leave(user);
     m_flags.after_decompress(reset);       // the temporal params were consumed by this picture
+}
+
+// ------------------------------------------------------------------------------------ encoder-side reconstruction
+void DmcLdCodec::reconstruct(half_t* x_hat, hipStream_t user)
+{
+    require_feature_p("reconstruct");
+    hipStream_t st = enter(user);
+    bind_stage_arg(kRecon, x_hat);
+    // reads feature_p (the second half of CATM: run_fa_m rewrote the memory half alone); writes the chain temporaries, the
+    // scratch planes, RHS and x_hat - nothing export_state carries, nothing a later stage reads before writing it
+    run_stage(kRecon, st, [&] { run_recon_head(m_RHS, x_hat, st); });
+    leave(user);
 }
 
 // ------------------------------------------------------------------------------------ state hand-off, debug

@@ -43,6 +43,8 @@ protected:
     };
     void require_encoder_ready(const char* what) const;      // compress / estimate_bits
     void require_decoder_ready() const;
+    // reconstruct: parameters and a feature_p (compress, decompress or import_state of such a state left it)
+    void require_feature_p(const char* what) const;
     // estimate_bits: qp, encoder-side state, picture size. Every refusal comes before anything is touched: prepare() with
     // another size would drop the temporal state.
     void check_probe(int qp, int height, int width) const;

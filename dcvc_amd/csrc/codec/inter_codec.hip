@@ -35,6 +35,14 @@ void InterCodec::require_decoder_ready() const
     }
 }
 
+void InterCodec::require_feature_p(const char* what) const
+{
+    if (!m_has_params) throw std::runtime_error(m_name + " " + what + ": set_param() has not been called");
+    if (m_g.H8 == 0 || !m_flags.has_feature_p) {
+        throw std::runtime_error(m_name + " " + what + ": no feature_p yet (compress, decompress or import_state first)");
+    }
+}
+
 void InterCodec::check_probe(int qp, int height, int width) const
 {
     if (qp < 0 || qp >= kQpNum) throw std::invalid_argument(m_name + " estimate_bits: qp must be in [0, 63]");

@@ -114,6 +114,23 @@ int pick_qp_near(const std::function<int64_t(int)>& estimate, int64_t budget_bit
     return lo < qp_min ? qp_min : lo;
 }
 
+int pick_qp_for_quality(const std::function<double(int)>& measure, double target, int start, int qp_min, int qp_max, int* trials)
+{
+    if (qp_min > qp_max) throw std::invalid_argument("pick_qp_for_quality: qp_min above qp_max");
+    const int flip = qp_min + qp_max;
+    const int s = std::min(qp_max, std::max(qp_min, start));
+    // reflected index r = flip - q: "meets" falls where "fits" falls, 0 bits against a budget of 0
+    const int r = pick_qp_near([&](int rq) -> int64_t {
+        const double quality = measure(flip - rq);
+        if (std::isnan(quality)) {
+            if (trials) *trials += 1;             // pick_qp_near counts a probe when it returns
+            throw std::runtime_error("pick_qp_for_quality: the trial failed");
+        }
+        return quality >= target ? 0 : 1;
+    }, 0, flip - s, qp_min, qp_max, trials);
+    return flip - r;
+}
+
 int64_t unit_budget_bits(double target_bpp, double pixels_per_picture, int pictures_coded, int64_t spent_bits, int horizon, int n)
 {
     if (horizon < 1 || n < 0) throw std::invalid_argument("unit_budget_bits: horizon must be positive, n not negative");

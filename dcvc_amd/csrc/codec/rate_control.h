@@ -41,6 +41,13 @@ int pick_qp_for_budget(const std::function<int64_t(int)>& estimate, int64_t budg
 // most 2 ceil(log2(qp_max - qp_min + 2)) + 1 in any range (12 over 0 .. 63).
 int pick_qp_near(const std::function<int64_t(int)>& estimate, int64_t budget_bits, int start, int qp_min, int qp_max, int* probes);
 
+// The mirror image, for coding to a quality: the smallest bracketed q_index whose trial meets, measure(qp) >=
+// target (NaN = failure, thrown). pick_qp_near under the index reflection q -> qp_min + qp_max - q, "fits" = "meets": s is
+// tried; it meets: gallop downward with step 1, 2, 4, ... to the first value that does not meet or to qp_min; it does not:
+// gallop upward to the first value that meets or to qp_max; then the bisection. qp_max when nothing meets. The same trial
+// counts: none twice, 2 when the answer is start, at most 12 over 0 .. 63. trials (may be null) receives their number.
+int pick_qp_for_quality(const std::function<double(int)>& measure, double target, int start, int qp_min, int qp_max, int* trials);
+
 // Budget of a P unit of n pictures in a run towards target_bpp, from what TargetBpp::update aims at: with share =
 // target_bpp * pixels_per_picture, want = max((share * (pictures_coded + horizon) - spent_bits) / horizon, share / 64) bits
 // per picture; floor(want * n) in double arithmetic.

@@ -248,6 +248,11 @@ class DMC(CompressionModel):
     def estimate_bits(self, x, qp, padding_b, padding_r):
         return self._ensure_proxy().estimate_bits(x, qp, padding_b, padding_r)
 
+    # not in the reference: the encoder-side reconstruction - x_hat of the unit just coded (HT: a list of 8),
+    # what decompress() of its stream gives, without touching the temporal state
+    def reconstruct(self, height, width):
+        return self._ensure_proxy().reconstruct(height, width)
+
 
 class DMCHT(DMC):
     """video_model_ht.py:320-470 (inference subset): the hierarchical inter models, 8 pictures per

@@ -91,6 +91,7 @@ _LD = dict(
     estimate_bits=_lib.fn("dcvc_dmcld_estimate_bits", _ci,
                           [_vp, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
     estimate_symbols=_lib.fn("dcvc_dmcld_estimate_symbols", ctypes.c_int64, [_vp]),
+    reconstruct=_lib.fn("dcvc_dmcld_reconstruct", _ci, [_vp, _vp, _vp]),
 )
 
 _HT = dict(
@@ -113,6 +114,7 @@ _HT = dict(
     estimate_bits=_lib.fn("dcvc_dmcht_estimate_bits", _ci,
                           [_vp, _vp, _ci, _ci, _ci, _ci, _ci, ctypes.POINTER(ctypes.c_int64), _vp]),
     estimate_symbols=_lib.fn("dcvc_dmcht_estimate_symbols", ctypes.c_int64, [_vp]),
+    reconstruct=_lib.fn("dcvc_dmcht_reconstruct", _ci, [_vp, _vp, _vp]),
 )
 
 _DTYPES = {torch.float16: 0, torch.float32: 1, torch.int32: 2}
@@ -326,6 +328,15 @@ class DMCLDProxy(_Proxy):
                                      ctypes.c_void_p(x_hat.data_ptr()), _stream_ptr()))
         return x_hat
 
+    def reconstruct(self, height, width):
+        """Not part of the reference surface: the encoder-side reconstruction. x_hat of the picture whose
+        feature_p the object holds (after compress, decompress or import_state), bit-identical to decompress() of that
+        picture's stream; proxy-owned like decompress()'s. The temporal state and every later call stay as they are."""
+        device = torch.device("cuda", torch.cuda.current_device())
+        x_hat = self._out_buffer(int(height), int(width), device)
+        _lib.check(_LD["reconstruct"](self._h, ctypes.c_void_p(x_hat.data_ptr()), _stream_ptr()))
+        return x_hat
+
 
 def _estimate_bits_inter(self, x, qp, padding_b, padding_r):
     """Not part of the reference surface: the size probe. What compress(x, qp, reset, ...) would spend
@@ -391,6 +402,18 @@ class _DMCHTProxy(_Proxy):
                                      1 if reset_feature_memory else 0,
                                      ctypes.c_void_p(self._x_hat.data_ptr()), _stream_ptr()))
         return self._pictures(self._recon_mask)
+
+    def reconstruct(self, height, width):
+        """Not part of the reference surface: the encoder-side reconstruction -> list of 8 x_hat, the pictures
+        of the chunk whose feature_p the object holds, bit-identical to decompress() of that chunk's stream. Always all 8,
+        whatever set_recon_mask() says; proxy-owned like decompress()'s."""
+        device = torch.device("cuda", torch.cuda.current_device())
+        h16, w16 = (int(height) + 15) // 16 * 16, (int(width) + 15) // 16 * 16
+        if self._x_hat is None or tuple(self._x_hat.shape) != (self.FRAMES, 3, h16, w16) or self._x_hat.device != device:
+            self._x_hat = torch.empty((self.FRAMES, 3, h16, w16), dtype=torch.float16, device=device).contiguous(
+                memory_format=torch.channels_last)
+        _lib.check(_HT["reconstruct"](self._h, ctypes.c_void_p(self._x_hat.data_ptr()), _stream_ptr()))
+        return self._pictures(0xFF)
 
     _recon_mask = 0xFF
 

@@ -281,6 +281,79 @@ def code_sequence_probed(frame_count, frames_per_p, code_intra, code_inter, prob
     return units
 
 
+# ---- coding to a quality. The native tool has the same search (csrc/codec/rate_control.cpp,
+# dcvc_rc_pick_qp_for_quality) and the same loop (dcvc encode --target-psnr); the tests hold them against each other.
+
+def pick_qp_for_quality(measure, target, start, qp_min=0, qp_max=63, trace=None):
+    """Smallest q_index whose trial coding meets a quality: measure(qp) -> quality, "meets" = measure(qp) >= target. The
+    mirror image of pick_qp_near, and built on it through the index reflection q -> qp_min + qp_max - q with "fits" =
+    "meets":
+
+    s = start clamped to the range is tried. It meets: gallop downward - max(s - 1, qp_min), then 2, 4, ... further down from
+    the last value that met - to the first value that does not meet, or until qp_min met. It does not: gallop upward in the
+    same way to the first value that meets, or until qp_max did not. Then the bracket is bisected. The answer is the smallest
+    bracketed q_index that meets, qp_max when nothing meets. pick_qp_near's counts: no q_index tried twice, 2 trials when the
+    answer is start, at most 12 over 0 .. 63. A real model's quality rises with the q_index; nothing here assumes it.
+    `trace`, a list, receives (qp, quality) of every trial. A NaN quality raises ValueError."""
+    if qp_min > qp_max:
+        raise ValueError("qp_min above qp_max")
+    flip = qp_min + qp_max
+
+    def misses(r):
+        quality = float(measure(flip - r))
+        if trace is not None:
+            trace.append((flip - r, quality))
+        if math.isnan(quality):
+            raise ValueError("pick_qp_for_quality: the trial failed")
+        return 0 if quality >= target else 1
+
+    s = min(qp_max, max(qp_min, int(start)))
+    return flip - pick_qp_near(misses, 0, flip - s, qp_min, qp_max)
+
+
+def code_sequence_quality(frame_count, frames_per_p, trial_intra, trial_inter, commit, target, qp_i=32, qp_min=0, qp_max=63,
+                          intra_period=-1, reset_interval=32, force_intra=False, log=None, intra_at=None):
+    """code_sequence with every unit coded at the smallest q_index whose trial coding meets `target` (dcvc encode
+    --target-psnr): pick_qp_for_quality on trial codings, start = the q_index of the previous unit of the same type (qp_i
+    for the first of each type).
+
+    trial_intra(frame_idx, qp) -> quality             codes the I picture as a trial and measures its reconstruction
+    trial_inter(frame_idx, n, qp, reset, first) -> quality
+                                                      codes the P unit (n existing pictures) as a trial and measures its
+                                                      reconstruction over those n pictures. Every trial of a unit starts
+                                                      from the temporal state in front of the unit: the caller exports it
+                                                      when `first` is true and imports it before every later trial
+    commit(is_intra, frame_idx, n, qp, reset, last_qp) -> bytes-like
+                                                      the unit is the trial at qp: its stream, and the codec state behind
+                                                      that trial from here on (an I picture: add_ref with its x_hat).
+                                                      last_qp is the q_index of the last trial: when it is not qp the
+                                                      caller kept that trial's stream and state, or codes it again from
+                                                      the same state - the bytes are the same.
+    `log`, a list, receives per unit {type, qp, trials, trace}; `intra_at` as in code_sequence. Returns what code_sequence
+    returns."""
+    units, idx = [], 0
+    start = {True: int(qp_i), False: int(qp_i)}
+    while idx < frame_count:
+        intra = idx == 0 or force_intra or intra_period == 1 or (intra_period > 1 and idx != 1 and idx % intra_period == 1)
+        if intra_at is not None:
+            intra = bool(intra_at(idx, intra))
+        n = 1 if intra else min(frames_per_p, frame_count - idx)
+        reset = (not intra) and reset_interval > 0 and (idx + frames_per_p) % reset_interval == 1
+        trace = []
+        if intra:
+            measure = lambda q: trial_intra(idx, q)
+        else:
+            measure = lambda q: trial_inter(idx, n, q, reset, not trace)
+        qp = pick_qp_for_quality(measure, target, start[intra], qp_min, qp_max, trace=trace)
+        payload = commit(intra, idx, n, qp, reset, trace[-1][0])
+        start[intra] = qp
+        units.append((intra, qp, reset, payload))
+        if log is not None:
+            log.append(dict(type="I" if intra else "P", qp=qp, trials=len(trace), trace=trace))
+        idx += 1 if intra else frames_per_p
+    return units
+
+
 def intra_budget_bits(target_bpp, pixels_per_picture, k, spent_bits):
     """Budget of picture k (0-based) of an all-intra run: what k + 1 pictures may take together minus what the first k
     took, floored at a quarter of one picture's share."""

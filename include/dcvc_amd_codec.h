@@ -147,6 +147,16 @@ int dcvc_dmcld_estimate_bits(dcvc_dmcld* c, const void* x, int height, int width
                              int64_t* out_units, void* stream);
 int64_t dcvc_dmcld_estimate_symbols(dcvc_dmcld* c);
 
+/* Not part of the reference surface: the encoder-side reconstruction. The picture of the unit whose
+ * feature_p the object holds: after dcvc_dmcld_compress, after dcvc_dmcld_decompress, or after dcvc_dmcld_import_state of
+ * such a state. x_hat: device fp16 [ceil16(height)][ceil16(width)][3], bit-identical to what dcvc_dmcld_decompress of that
+ * unit's stream writes. One stage of its own - the recon head into a scratch plane, then the pixel shuffle - that reads
+ * feature_p and writes no state: dcvc_dmcld_export_state gives the bytes it gave before, every later compress,
+ * estimate_bits and decompress gives what it gives without the call, and their stages (and graphs) are the ones they
+ * were. Refused, with nothing touched: a null handle or x_hat, no parameters set, no feature_p yet (e.g. right after
+ * add_ref_feature_from_frame). */
+int dcvc_dmcld_reconstruct(dcvc_dmcld* c, void* x_hat, void* stream);
+
 /* Not part of the reference surface - hand-off of a GOP to another GPU (north_star: temporal
  * context exchanged point-to-point over xGMI): the temporal state (reference feature, memory,
  * last decoded feature, context, temporal prior, validity flags) as ONE flat device buffer that
@@ -188,6 +198,10 @@ int dcvc_dmcht_decompress(dcvc_dmcht* c, const uint8_t* bit_stream, size_t nbyte
 int dcvc_dmcht_estimate_bits(dcvc_dmcht* c, const void* x, int height, int width, int qp, int padding_b, int padding_r,
                              int64_t* out_units, void* stream);
 int64_t dcvc_dmcht_estimate_symbols(dcvc_dmcht* c);
+/* Not part of the reference surface: the encoder-side reconstruction of a chunk, as dcvc_dmcld_reconstruct. x_hat: 8 x
+ * [ceil16(height)][ceil16(width)][3] back to back, always all 8 pictures, whatever dcvc_dmcht_set_recon_mask says; every
+ * head output (picture 7's too) goes to a scratch plane, not to the reference feature. */
+int dcvc_dmcht_reconstruct(dcvc_dmcht* c, void* x_hat, void* stream);
 /* GOP hand-off between GPUs, as dcvc_dmcld_export_state / _import_state */
 int64_t dcvc_dmcht_export_state(dcvc_dmcht* c, void* dst, size_t cap, void* stream);
 int dcvc_dmcht_import_state(dcvc_dmcht* c, const void* src, size_t bytes, int height, int width, void* stream);

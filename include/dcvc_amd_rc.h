@@ -1,6 +1,6 @@
 /* Rate control of the dcvc tool (no reference counterpart): the one-pass controller towards a target rate and the
  * q_index search on a size probe. Host code only, no GPU. dcvc_amd/rate_control.py is the same arithmetic in Python
- * (TargetBpp, pick_qp_for_budget, intra_budget_bits); the two are tested against each other.
+ * (TargetBpp, pick_qp_for_budget, pick_qp_for_quality, intra_budget_bits); the two are tested against each other.
  *
  * Errors: a negative return code, message through dcvc_last_error() (dcvc_amd_ops.h). */
 #ifndef DCVC_AMD_RC_H
@@ -42,6 +42,18 @@ int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t
  * most 4 within 2 of it, at most 2 ceil(log2(qp_max - qp_min + 2)) + 1 (12 over 0 .. 63). */
 int dcvc_rc_pick_qp_near(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int start, int qp_min, int qp_max,
                          int* probes);
+/* Coding to a quality, the mirror image of dcvc_rc_pick_qp_near: the smallest q_index whose trial meets the
+ * target. measure(qp, user) = the quality of a trial coding at qp (NaN = failure); qp "meets" when measure >= target.
+ * s = start clamped to [qp_min, qp_max] is tried first; if it meets, max(s - 1, qp_min), then 2, 4, ... further down from the
+ * last value that met, until one does not meet or qp_min met; if it does not, upward in the same way until one meets or
+ * qp_max did not; then the bracket is bisected. Returns the smallest bracketed q_index that meets, qp_max when nothing
+ * meets: it is dcvc_rc_pick_qp_near under the index reflection q -> qp_min + qp_max - q with "fits" = "meets", so the
+ * trial counts are its probe counts: no q_index tried twice, 2 trials when the answer is start, at most 12 over 0 .. 63.
+ * The quality of a real model rises with the q_index; the function does not assume it, its result is defined by the
+ * procedure. *trials (may be NULL) receives the number of trials. Negative on failure. */
+typedef double (*dcvc_rc_quality_fn)(int qp, void* user);
+int dcvc_rc_pick_qp_for_quality(dcvc_rc_quality_fn measure, void* user, double target, int start, int qp_min, int qp_max,
+                                int* trials);
 /* Budget of a P unit of n pictures: share = target_bpp * pixels, want = max((share * (pictures_coded + horizon) -
  * spent_bits) / horizon, share / 64) (what dcvc_rc_update steers towards), floor(want * n), in double arithmetic.
  * Negative on failure (horizon < 1, n < 0). */

@@ -652,6 +652,40 @@ int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H_, int W_, int fmt, in
     });
 }
 
+namespace {
+
+// the operands of the dcvc_msssim* entries and of the dcvc_sse* entries: n_planes pairs of H x W planes
+dcvc::MsssimDesc msssim_desc(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
+                             long long plane_stride, double* out, double data_range = 255.0)
+{
+    dcvc::MsssimDesc d;
+    d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+    d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+    d.data_range = data_range;
+    return d;
+}
+
+dcvc::SseDesc sse_desc(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
+                       long long plane_stride, double* out)
+{
+    dcvc::SseDesc d;
+    d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
+    d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+    return d;
+}
+
+dcvc::RgbToXDesc rgb_source(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H_, int W_,
+                             void* x, int ldx, void* planar)
+{
+    dcvc::RgbToXDesc d;
+    d.src = static_cast<const uint8_t*>(src);
+    d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
+    d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint8_t*>(planar);
+    return d;
+}
+
+}  // namespace
+
 int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_,
                 int row_stride, long long plane_stride, double* out, void* stream)
 {
@@ -662,9 +696,7 @@ int dcvc_msssim(const void* src, int src_dtype, const void* rec, int rec_dtype, 
                 throw std::invalid_argument("msssim: sample type must be DCVC_SAMPLE_U8 or DCVC_SAMPLE_F16");
             }
         }
-        dcvc::MsssimDesc d;
-        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
-        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        const dcvc::MsssimDesc d = msssim_desc(src, src_dtype, rec, rec_dtype, n_planes, H_, W_, row_stride, plane_stride, out);
         dcvc::msssim_validate(d);      // before the workspace is sized: a bad geometry never reaches the allocator
         const AsyncBuf ws(dcvc::msssim_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(msssim workspace)");
         dcvc::msssim(d, ws.p, S(stream));
@@ -675,10 +707,7 @@ int dcvc_msssim_range(const void* src, int src_dtype, const void* rec, int rec_d
                       int row_stride, long long plane_stride, double data_range, double* out, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::MsssimDesc d;
-        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
-        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
-        d.data_range = data_range;
+        const dcvc::MsssimDesc d = msssim_desc(src, src_dtype, rec, rec_dtype, n_planes, H_, W_, row_stride, plane_stride, out, data_range);
         dcvc::msssim_validate(d);
         const AsyncBuf ws(dcvc::msssim_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(msssim workspace)");
         dcvc::msssim(d, ws.p, S(stream));
@@ -695,10 +724,7 @@ int dcvc_msssim_range_ws(const void* src, int src_dtype, const void* rec, int re
                          long long plane_stride, double data_range, double* out, void* workspace, long long workspace_bytes, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::MsssimDesc d;
-        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
-        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
-        d.data_range = data_range;
+        const dcvc::MsssimDesc d = msssim_desc(src, src_dtype, rec, rec_dtype, n_planes, H_, W_, row_stride, plane_stride, out, data_range);
         dcvc::msssim_validate(d);
         if (workspace == nullptr || workspace_bytes < 0 ||
             static_cast<unsigned long long>(workspace_bytes) < dcvc::msssim_workspace_bytes(n_planes, H_, W_)) {
@@ -713,11 +739,7 @@ int dcvc_rgb_to_x(const void* src, long long row_stride, long long pixel_stride,
                   void* x, int ldx, void* planar, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::RgbToXDesc d;
-        d.src = static_cast<const uint8_t*>(src);
-        d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
-        d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint8_t*>(planar);
-        dcvc::rgb_to_x(d, S(stream));
+        dcvc::rgb_to_x(rgb_source(src, row_stride, pixel_stride, channel_stride, H_, W_, x, ldx, planar), S(stream));
     });
 }
 
@@ -732,11 +754,8 @@ int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stri
                      void* x, int ldx, void* planar, int matrix, int range, int yuv_bit_depth, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::RgbToXDesc d;
-        d.src = static_cast<const uint8_t*>(src);
-        d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
-        d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint8_t*>(planar);
-        dcvc::rgb_to_x_cs(d, dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
+        dcvc::rgb_to_x_cs(rgb_source(src, row_stride, pixel_stride, channel_stride, H_, W_, x, ldx, planar),
+                          dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
     });
 }
 
@@ -753,9 +772,7 @@ int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int
              long long plane_stride, double* out, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::SseDesc d;
-        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
-        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        const dcvc::SseDesc d = sse_desc(src, src_dtype, rec, rec_dtype, n_planes, H_, W_, row_stride, plane_stride, out);
         dcvc::sse_validate(d);         // before the workspace is sized: a bad geometry never reaches the allocator
         const AsyncBuf ws(dcvc::sse_workspace_bytes(n_planes, H_, W_), S(stream), "hipMallocAsync(sse workspace)");
         dcvc::sse(d, ws.p, S(stream));
@@ -772,9 +789,7 @@ int dcvc_sse_ws(const void* src, int src_dtype, const void* rec, int rec_dtype, 
                 long long plane_stride, double* out, void* workspace, long long workspace_bytes, void* stream)
 {
     return dcvc::guarded([&] {
-        dcvc::SseDesc d;
-        d.src = src; d.src_dtype = src_dtype; d.rec = rec; d.rec_dtype = rec_dtype;
-        d.n_planes = n_planes; d.H = H_; d.W = W_; d.row_stride = row_stride; d.plane_stride = plane_stride; d.out = out;
+        const dcvc::SseDesc d = sse_desc(src, src_dtype, rec, rec_dtype, n_planes, H_, W_, row_stride, plane_stride, out);
         dcvc::sse_validate(d);
         if (workspace == nullptr || workspace_bytes < 0 ||
             static_cast<unsigned long long>(workspace_bytes) < dcvc::sse_workspace_bytes(n_planes, H_, W_)) {

@@ -6,7 +6,7 @@
 // stream container, decode the container again, write the reconstruction, log bits and PSNR - as a
 // native tool on top of the C ABI only (include/dcvc_amd_codec.h, _ops.h, _stream.h, _image.h). No Python, no
 // torch: weights come from a .dcvw file (python -m dcvc_amd.export_weights), pictures travel as u8
-// planes and are converted on the device (frame_io.hip, rgb_io.hip).
+// planes and are converted on the device (picture_yuv.hip, rgb_cs.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
 //               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] -o out.bin
@@ -21,7 +21,7 @@
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
-//               (dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
+//               (dcvc_pix_to_x / dcvc_x_to_pix with DCVC_PIX_YUV420P: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
 //               stream does not carry it: decode with the depth the source had. PSNR per plane is 10 log10(max_val^2 / mse)
 //               over fp32 distortion planes, summed on the device (dcvc_sse_ws), and --calc-ssim uses data_range = max_val;
 //               the log has the 8-bit YUV420 log's keys.
@@ -29,7 +29,7 @@
 //               one file (ffmpeg -pix_fmt rgb24 -f rawvideo), -W / -H required to encode; png = -i (encode), --ref and -o
 //               are directories of im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-45; the writer uses
 //               im00001.png, ...), the size is taken from the first picture and every picture must have it. RGB is
-//               converted with BT.709 on the device (dcvc_rgb_to_x / dcvc_x_to_rgb, test_video.py:55-64, 87-122,
+//               converted with BT.709 on the device (dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs, test_video.py:55-64, 87-122,
 //               366-370); the log then holds the RGB PSNR (dcvc_sse, calc_psnr over 3 H W samples) and, with --calc-ssim,
 //               the mean of the three planes' MS-SSIM (calc_msssim_rgb), without _y / _u / _v keys. Both sides must be
 //               even, and >= 88 for --calc-ssim.
@@ -109,8 +109,8 @@
 //               count, so a chunk cannot be cut short at a scene change. The stream format and the decoder do not change.
 //               --scale WxH (encode, yuv420): code the clip at W x H instead of the source's -W x -H. The uploaded
 //               u8 / u16 planes are resampled on the device (dcvc_resample_planes, integer Lanczos-3: Y in one call, U and V
-//               in one call, every plane on its own with the centre-aligned rule) before dcvc_yuv420_to_x / _yuv420p16_to_x
-//               read them; the parameter set carries W x H and everything behind - --batch, --target-bpp, --scene-cut -
+//               in one call, every plane on its own with the centre-aligned rule) before dcvc_pix_to_x
+//               reads them; the parameter set carries W x H and everything behind - --batch, --target-bpp, --scene-cut -
 //               sees a clip of that size. W and H positive and even, each side's ratio in [1/8, 8]; the source size gives
 //               the file of a run without the flag. RGB sources are not resampled yet.
 //               --out-size WxH (decode, yuv420): the reconstruction's integer samples (what -o writes at the coded size) are
@@ -143,8 +143,8 @@
 //               Y 16..235, C 16..240 times 2^(B-8) on the scale of B-bit samples, v / (2^B - 1): --yuv-depth (8..16,
 //               default 8, only with --range limited) is the depth of the YUV pictures the stream stands for, e.g. 10 to
 //               look at a stream coded from yuv420 --bit-depth 10. The defaults, bt709 and full, are the reference's
-//               conversion: a run without the flags issues dcvc_rgb_to_x / dcvc_x_to_rgb as before, a run with any of them
-//               dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs, which give the same bytes at bt709 / full. The stream carries none of
+//               conversion: every run issues dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs, with bt709 / full when no flag is given, which is
+//               what dcvc_rgb_to_x / dcvc_x_to_rgb compute. The stream carries none of
 //               this: decode with the flags of the encode, and verify a manifest with the flags it was hashed with. With
 //               any of the flags the JSON log gains color_matrix, color_range and color_yuv_depth. Refused: an unknown
 //               name, a depth outside 8..16 or without --range limited, and any of the flags with a YUV source type, where
@@ -318,14 +318,13 @@ struct Geometry {
     int H = 0, W = 0, Hp = 0, Wp = 0;      // picture, padded to multiples of 16
     bool rgb = false;                      // 8-bit RGB pictures (--src-type rgb24 / png) instead of YUV420
     int bit_depth = 8;                     // YUV420: 9..16 = uint16 samples (--bit-depth)
-    // --src-type yuv422 / yuv444 / nv12 / p010: a DCVC_PIX_* layout at any depth, on the picture path of dcvc_pix_to_x /
-    // dcvc_x_to_pix; -1: YUV420 planes or RGB on the paths that were here before
+    // --src-type yuv422 / yuv444 / nv12 / p010: a DCVC_PIX_* layout at any depth, with fp32 distortion planes and the metrics
+    // on the device at 8 bits too; -1: YUV420 planes (8 bits: fp16 distortion planes, summed on the host) or RGB
     int pix_fmt = -1;
-    // RGB with --matrix / --range / --yuv-depth: dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs with these; without: the BT.709 / full
-    // range entry points that were here before
-    bool cs = false;
+    // RGB: what dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs are given (--matrix / --range / --yuv-depth; without: BT.709 / full range)
     int matrix = DCVC_MATRIX_BT709, range = DCVC_RANGE_FULL, yuv_depth = 8;
     bool pix() const { return pix_fmt >= 0; }
+    int yuv_fmt() const { return pix() ? pix_fmt : DCVC_PIX_YUV420P; }      // the layout the conversion calls are given
     bool hbd() const { return bit_depth > 8; }
     int Hc() const { return pix_fmt == DCVC_PIX_YUV422P || pix_fmt == DCVC_PIX_YUV444P ? H : H / 2; }      // a chroma plane's sides
     int Wc() const { return pix_fmt == DCVC_PIX_YUV444P ? W : W / 2; }
@@ -733,7 +732,7 @@ struct ColourArgs {
     bool on = false;       // any of the three flags given
     int matrix = DCVC_MATRIX_BT709, range = DCVC_RANGE_FULL, yuv_depth = 8;
     std::string matrix_name = "bt709", range_name = "full";
-    void apply(Geometry& g) const { g.cs = on; g.matrix = matrix; g.range = range; g.yuv_depth = yuv_depth; }
+    void apply(Geometry& g) const { g.matrix = matrix; g.range = range; g.yuv_depth = yuv_depth; }
 };
 
 ColourArgs colour_args(const Args& a)
@@ -1218,18 +1217,12 @@ void x_hat_to_picture(const Geometry& g, const DeviceBuffers& b, const char* xh,
     char* y16 = static_cast<char*>(b.y16);
     if (g.rgb) {
         // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
-        if (g.cs) {
-            abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, g.matrix, g.range, g.yuv_depth, b.st), "x_to_rgb_cs");
-        } else {
-            abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, b.st), "x_to_rgb");
-        }
-    } else if (g.pix()) {
+        abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, g.matrix, g.range, g.yuv_depth, b.st), "x_to_rgb_cs");
+    } else if (g.pix() || g.hbd()) {
         // fp32 distortion planes [H][W] + [2][Hc][Wc] in y16, the output samples in file layout in out8
-        abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_pix");
-    } else if (g.hbd()) {
-        // fp32 distortion planes [H][W] + [2][H/2][W/2] in y16, the writer's u16 samples in out8
-        abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_yuv420p16");
+        abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.yuv_fmt(), g.bit_depth, y16, samples ? b.out8 : nullptr, b.st), "x_to_pix");
     } else {
+        // 8-bit YUV420: fp16 distortion planes, which the decode log sums on the host
         abi_ok(dcvc_x_to_yuv420(xh, g.Wp, g.H, g.W, y16, y16 + g.y_bytes() * 2, b.out8, b.out8 + g.y_bytes(), b.st), "x_to_yuv420");
     }
 }
@@ -1264,7 +1257,8 @@ struct QualityMeter {
     {
         uint8_t* dst = src + g.frame_bytes() * static_cast<size_t>(slot);
         if (g.rgb) {
-            abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, dst, b.st), "rgb_to_x (planar source)");
+            abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, dst, g.matrix, g.range, g.yuv_depth, b.st),
+                   "rgb_to_x_cs (planar source)");
         } else if (g.pix()) {
             abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, nullptr, 3, dst, b.st), "pix_to_x (planar source)");
         } else {
@@ -1278,8 +1272,7 @@ struct QualityMeter {
         PictureQuality q;
         if (g.rgb) {
             const size_t plane = g.y_bytes();
-            if (g.cs) abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, dist, nullptr, g.matrix, g.range, g.yuv_depth, st), "x_to_rgb_cs");
-            else abi_ok(dcvc_x_to_rgb(xh, g.Wp, g.H, g.W, dist, nullptr, st), "x_to_rgb");
+            abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, dist, nullptr, g.matrix, g.range, g.yuv_depth, st), "x_to_rgb_cs");
             abi_ok(dcvc_sse_ws(s, DCVC_SAMPLE_U8, dist, DCVC_SAMPLE_F16, 3, g.H, g.W, g.W, static_cast<long long>(plane), sse, ws, ws_bytes, st),
                    "sse");
             hip_ok(hipMemcpyAsync(h_sse, sse, 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H");
@@ -1290,9 +1283,7 @@ struct QualityMeter {
         const size_t ny = g.y_bytes(), nc = static_cast<size_t>(g.Hc()) * g.Wc(), es = g.hbd() ? 2 : 1;
         const int dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
         const double peak = static_cast<double>((1 << g.bit_depth) - 1);
-        if (g.pix()) abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.pix_fmt, g.bit_depth, dist, nullptr, st), "x_to_pix");
-        else if (g.hbd()) abi_ok(dcvc_x_to_yuv420p16(xh, g.Wp, g.H, g.W, g.bit_depth, dist, nullptr, st), "x_to_yuv420p16");
-        else abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, DCVC_PIX_YUV420P, 8, dist, nullptr, st), "x_to_pix");
+        abi_ok(dcvc_x_to_pix(xh, g.Wp, g.H, g.W, g.yuv_fmt(), g.bit_depth, dist, nullptr, st), "x_to_pix");
         const char* dist_uv = static_cast<const char*>(dist) + ny * 4;
         abi_ok(dcvc_sse_ws(s, dt, dist, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), sse, ws, ws_bytes, st), "sse (Y)");
         abi_ok(dcvc_sse_ws(s + ny * es, dt, dist_uv, DCVC_SAMPLE_F32, 2, g.Hc(), g.Wc(), g.Wc(), static_cast<long long>(nc), sse + 1, ws,
@@ -1461,16 +1452,10 @@ int encode(const Args& a)
     // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
     int luma_turn = 0;
     auto convert = [&](char* dst, int ldx, bool measure = false, bool has_prev = false) {
-        if (rgb && g.cs) {
+        if (rgb) {
             abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, g.matrix, g.range, g.yuv_depth, b.st), "rgb_to_x_cs");
-        } else if (rgb) {
-            abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, b.st), "rgb_to_x");
-        } else if (g.pix()) {
-            abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, dst, ldx, nullptr, b.st), "pix_to_x");
-        } else if (g.hbd()) {
-            abi_ok(dcvc_yuv420p16_to_x(b.yuv8, b.yuv8 + g.y_bytes() * 2, g.H, g.W, g.bit_depth, dst, ldx, b.st), "yuv420p16_to_x");
         } else {
-            abi_ok(dcvc_yuv420_to_x(b.yuv8, b.yuv8 + g.y_bytes(), g.H, g.W, dst, ldx, b.st), "yuv420_to_x");
+            abi_ok(dcvc_pix_to_x(b.yuv8, g.yuv_fmt(), g.bit_depth, g.H, g.W, dst, ldx, nullptr, b.st), "pix_to_x");
         }
         if (measure) {
             abi_ok(dcvc_luma_sad(dst, ldx, g.H, g.W, has_prev ? b.luma8[luma_turn ^ 1] : nullptr, b.luma8[luma_turn], b.sad, b.st),
@@ -2183,7 +2168,8 @@ int decode(const Args& a)
                 // how the runtime stages a pageable copy or recycles a stream-ordered allocation)
                 const size_t plane = g.y_bytes();
                 hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
-                abi_ok(dcvc_rgb_to_x(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, b.src8, b.st), "rgb_to_x (planar source)");
+                abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, b.src8, g.matrix, g.range, g.yuv_depth, b.st),
+                       "rgb_to_x_cs (planar source)");
                 abi_ok(dcvc_sse_ws(b.src8, DCVC_SAMPLE_U8, y16, DCVC_SAMPLE_F16, 3, g.H, g.W, g.W, static_cast<long long>(plane), b.sse,
                                    b.sse_ws, b.sse_ws_bytes, b.st), "sse");
                 hip_ok(hipMemcpyAsync(b.h_sse, b.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");

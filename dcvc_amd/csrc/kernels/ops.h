@@ -255,39 +255,31 @@ void mul_channel(const half_t* x, int ldx, const half_t* q, half_t* y, int ldy, 
 void scale_clamped(const half_t* x, int ldx, const half_t* q, int ldq, half_t* y, int ldy, int pixels,
                    int C, bool reciprocal, hipStream_t stream);
 
-// ---------------------------------------------------------------- picture I/O (frame_io.hip)
-// 8-bit YUV420 planes (y [H][W], uv [2][H/2][W/2]) -> x fp16, 3 channels per pixel at pixel
-// stride ldx (3 for one picture, 24 + a channel offset for a chunk of 8): nearest-neighbour
-// chroma, x = fp16(fp16(v / 255) - 0.5)   (test_video.py:69-123, transforms.py:69-80)
-void yuv420_to_x(const uint8_t* y, const uint8_t* uv, int H, int W, half_t* x, int ldx, hipStream_t stream);
-// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as YUV420: fp16 planes scaled to
-// 0..255 (what get_distortion measures, test_video.py:32-45) and / or u8 planes (what the writer
-// stores, test_video.py:356-363: Y rounded half-to-even, U/V truncated). Null outputs are skipped.
-void x_to_yuv420(const half_t* x, int row_pixels, int H, int W, half_t* y16, half_t* uv16, uint8_t* y8,
-                 uint8_t* uv8, hipStream_t stream);
-
-// ---------------------------------------------------------------- high-bit-depth picture I/O (frame_io16.hip)
-// uint16 YUV420 planes of bit depth 9..16 (y [H][W], uv [2][H/2][W/2]) -> x fp16 at pixel stride ldx, as yuv420_to_x:
-// nearest-neighbour chroma, x = fp16(fp16(fp32(v) / fp32(max_val)) - 0.5) with max_val = 2^b - 1 (DCVC-FM's YUVReader).
-void yuv420p16_to_x(const uint16_t* y, const uint16_t* uv, int H, int W, int bit_depth, half_t* x, int ldx, hipStream_t stream);
-// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as fp32 distortion planes [H][W] + [2][H/2][W/2]
-// (clamp(t * max_val, 0, max_val), t as x_to_yuv420 computes it before its * 255) and / or uint16 samples (rint of those,
-// half to even, all three planes: DCVC-FM's YUVWriter). Null outputs are skipped.
-void x_to_yuv420p16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* yuv, hipStream_t stream);
-
-// ---------------------------------------------------------------- other chroma formats (frame_io_fmt.hip)
+// ---------------------------------------------------------------- YUV pictures (picture_yuv.hip)
 // One picture in file layout - Y [H][W], then Cb / Cr as planes [2][Hc][Wc] or, for NV12, interleaved [Hc][Wc][2] - of 8-bit
 // (u8) or 9..16-bit (u16: LSB-aligned in the planar formats, in the high bits for NV12 = P010 / P012 / P016) samples.
 constexpr int kPixYuv420p = 0, kPixYuv422p = 1, kPixYuv444p = 2, kPixNv12 = 3;      // DCVC_PIX_*
 // samples of one picture; throws for an unknown format or sides that are not positive and even
 long long pix_picture_samples(int fmt, int H, int W);
-// -> x fp16 at pixel stride ldx (yuv420_to_x's / yuv420p16_to_x's arithmetic per sample, nearest-neighbour chroma) and / or
-// `planar`: the picture as LSB-aligned planar samples (Y, Cb, Cr at the format's subsampling). One of the two may be null.
+// -> x fp16, 3 channels per pixel at pixel stride ldx (3 for one picture, 24 + a channel offset for a chunk of 8):
+// nearest-neighbour chroma, x = fp16(fp16(fp32(v) / fp32(max_val)) - 0.5) with max_val = 2^b - 1 (test_video.py:69-123,
+// transforms.py:69-80; DCVC-FM's YUVReader) and / or `planar`: the picture as LSB-aligned planar samples (Y, Cb, Cr at the
+// format's subsampling). One of the two may be null.
 void pix_to_x(const void* src, int fmt, int bit_depth, int H, int W, half_t* x, int ldx, void* planar, hipStream_t stream);
-// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as planar fp32 distortion planes [H][W] + [2][Hc][Wc] and / or
-// the samples in file layout (rint, half to even; the 4:2:0 layouts at 8 bits truncate Cb / Cr as x_to_yuv420 does). Chroma:
-// the mean of the 1, 2 or 2 x 2 luma positions of fp16(x_hat + 0.5), summed in fp32 and rounded to fp16 once.
+// x_hat fp16 [rows][row_pixels][3] -> the top-left H x W picture as planar fp32 distortion planes [H][W] + [2][Hc][Wc] (what
+// get_distortion measures, test_video.py:32-45: scaled to 0..max_val and clamped) and / or the samples in file layout (rint,
+// half to even: DCVC-FM's YUVWriter; the 4:2:0 layouts at 8 bits truncate Cb / Cr as the reference's writer does,
+// test_video.py:356-363). Chroma: the mean of the 1, 2 or 2 x 2 luma positions of fp16(x_hat + 0.5), summed in fp32 and
+// rounded to fp16 once. Null outputs are skipped.
 void x_to_pix(const half_t* x, int row_pixels, int H, int W, int fmt, int bit_depth, float* dist, void* out, hipStream_t stream);
+// The 4:2:0 planar forms of the two with the planes handed over one by one (y [H][W], uv [2][H/2][W/2]); the same kernels
+// and bits. 8 bits: the distortion planes are fp16 (the same values), and each of the four outputs may be null.
+void yuv420_to_x(const uint8_t* y, const uint8_t* uv, int H, int W, half_t* x, int ldx, hipStream_t stream);
+void x_to_yuv420(const half_t* x, int row_pixels, int H, int W, half_t* y16, half_t* uv16, uint8_t* y8,
+                 uint8_t* uv8, hipStream_t stream);
+// 9..16 bits: dist and yuv are whole pictures, [H][W] + [2][H/2][W/2]
+void yuv420p16_to_x(const uint16_t* y, const uint16_t* uv, int H, int W, int bit_depth, half_t* x, int ldx, hipStream_t stream);
+void x_to_yuv420p16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* yuv, hipStream_t stream);
 
 // ---------------------------------------------------------------- MS-SSIM (msssim.hip)
 // metrics.py:27-91 calc_msssim of n_planes pairs of H x W planes (u8 or fp16 samples in 0..255; src and rec share row_stride
@@ -309,7 +301,7 @@ void msssim_validate(const MsssimDesc& d);       // throws std::invalid_argument
 size_t msssim_workspace_bytes(int n_planes, int H, int W);
 void msssim(const MsssimDesc& d, void* workspace, hipStream_t stream);
 
-// ---------------------------------------------------------------- RGB pictures (rgb_io.hip)
+// ---------------------------------------------------------------- RGB pictures (rgb_cs.hip)
 // test_video.py:87-122 + transforms.py:17-27 (BT.709 rgb2ycbcr): u8 RGB read through (row, pixel, channel) strides in bytes
 // (packed HWC: 3W, 3, 1; planar CHW: W, 1, H*W) -> x fp16 at pixel stride ldx (3 channels written; 3 for one picture, 24
 // for the slots of an 8-picture chunk) and / or a planar u8 copy [3][H][W] of the source. Either output may be null.
@@ -325,11 +317,9 @@ void rgb_to_x(const RgbToXDesc& d, hipStream_t stream);
 // H x W picture as planar fp16 [3][H][W] in 0..255 (the distortion planes) and / or packed u8 HWC (rint of those, the
 // writer's pixels). Null outputs are skipped.
 void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, hipStream_t stream);
-void rgb_validate(int H, int W, const char* what);      // throws std::invalid_argument: sides not positive and even, or too large
-// ---------------------------------------------------------------- RGB pictures, other matrices and ranges (rgb_cs.hip)
 // rgb_to_x / x_to_rgb with the colour matrix (DCVC_MATRIX_*) and range (DCVC_RANGE_*) chosen; yuv_bit_depth (8..16) is the
 // depth b of the YUV samples x stands for (x = v / (2^b - 1) - 0.5), which places the limited-range levels. Layouts, null
-// rules and refusals are those of the two functions above; BT.709 / full range gives their bits.
+// rules and refusals are those of the two functions above, which are these at BT.709 / full range.
 constexpr int kMatrixBt601 = 0, kMatrixBt709 = 1, kMatrixBt2020 = 2;
 constexpr int kRangeFull = 0, kRangeLimited = 1;
 struct ColourSpace {
@@ -337,6 +327,8 @@ struct ColourSpace {
 };
 void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream);
 void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream);
+
+// ---------------------------------------------------------------- SSE (sse.hip)
 // metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8, fp16, u16 or fp32 samples; src and rec share
 // row_stride and plane_stride, in samples) -> out[plane] (device). Per-workgroup partials in the workspace
 // (sse_workspace_bytes), reduced by a second launch in a fixed order.

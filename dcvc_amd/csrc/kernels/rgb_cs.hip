@@ -1,24 +1,34 @@
 // rgb_cs.hip - 8-bit RGB pictures <-> the codec's fp16 NHWC picture tensor with a chosen colour matrix (BT.601, BT.709,
-// BT.2020 non-constant luminance) and range (full, or limited: Y 16..235, C 16..240 scaled to the YUV bit depth).
+// BT.2020 non-constant luminance) and range (full, or limited: Y 16..235, C 16..240 scaled to the YUV bit depth): one kernel
+// to x and one from x behind rgb_to_x / x_to_rgb (BT.709 / full range) and rgb_to_x_cs / x_to_rgb_cs.
 //
-// No reference counterpart beyond BT.709 / full range, which is rgb_io.hip's conversion (transforms.py:17-27, 53-66) and
-// which these kernels reproduce bit for bit: the op sequences are rgb_io.hip's with the matrix constants as arguments and,
-// in limited range, one multiply and one add (to x) or one subtract and one multiply (to RGB) per channel between the
-// matrix and the fp16 rounding. DESIGN.md 20 has the definition; tests/colour_np.py restates it in numpy.
+// Reference at BT.709 / full range (a chain of torch ops on the GPU): test_video.py:87-122 get_src_frame with
+// transforms.py:17-27 rgb2ycbcr (x.float() / 255, y = Kr r + Kg g + Kb b, cb / cr = 0.5 (b|r - y) / (1 - Kb|Kr) + 0.5,
+// clamp(0, 1), .half(), - 0.5), test_video.py:55-64 get_distortion with transforms.py:53-66 ycbcr2rgb (x_hat + 0.5 in fp16,
+// then in fp32 r = y + (2 - 2 Kr)(cr - 0.5), b = y + (2 - 2 Kb)(cb - 0.5), g = (y - Kr r - Kb b) / Kg, clamp(0, 1), .half(),
+// then clamp(* 255, 0, 255) in fp16), :366-370 the writer (.round().byte()). torch's GPU true division by a CPU scalar is
+// a * (1 / b) with the reciprocal rounded to fp32 (measured on MI355X over all 2^24 colours, DESIGN.md "RGB sources"); the
+// kernels follow it, as that is what the reference computes on a GPU. The other matrices have no reference counterpart: the
+// same op sequences with other constants and, in limited range, one multiply and one add (to x) or one subtract and one
+// multiply (to RGB) per channel between the matrix and the fp16 rounding. DESIGN.md 20 has the definition; tests/colour_np.py
+// restates it in numpy.
 //
-// Every step is one fp32 operation (the library builds with -ffp-contract=off: no v_fma) and every constant is the fp32
-// value of a double expression, computed on the host (colour_consts) and passed by value in the kernel argument: the
-// constants are wave-uniform and sit in SGPRs. The range is a template switch, so the full-range kernels hold no extra
-// operation. Layout and access modes are rgb_io.hip's: one thread per 8 pixels of a row, 8- / 16-byte accesses where the
-// layout allows them, element accesses elsewhere.
+// Every torch op rounds on its own, so every step is one fp32 operation (the library builds with -ffp-contract=off: no
+// v_fma) and every constant is the fp32 value of the Python double (expression) it stands for, computed on the host
+// (colour_consts) and passed by value in the kernel argument: the constants are wave-uniform and sit in SGPRs. The range is
+// a template switch, so the full-range kernels hold no extra operation.
+//
+// HBM-bound passes, one thread per 8 pixels of a row. A template switch picks 8- / 16-byte accesses where the layout
+// allows them (packed HWC or planar CHW u8 input, packed x at ldx == 3, rows of a multiple of 8 pixels, aligned bases)
+// and element accesses elsewhere (the slots of an 8-picture chunk at ldx = 24, odd-multiple-of-2 widths).
 #include "arith.h"
-#include "ops.h"
+#include "picture_io.h"
 
 namespace dcvc {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kPictureThreads;
 constexpr float kInv255 = 1.0f / 255.0f;                              // x.float() / 255.0
 
 // what the two kernels read: the matrix (8 values) and the limited-range levels (6 values; unused in full range)
@@ -74,19 +84,19 @@ __device__ __forceinline__ void pixel_to_x(const ColourConsts& k, unsigned r8, u
     o[2] = to_half(static_cast<float>(to_half(clampf(cr, 0.f, 1.f))) - 0.5f);
 }
 
-// load modes of rgb_to_x_cs
+// load modes of rgb_to_x
 constexpr int kLoadScalar = 0, kLoadPacked = 1, kLoadPlanar = 2;
 
 // one thread = 8 consecutive pixels of a row. LOAD: kLoadPacked (pixel stride 3, channel stride 1: 3 x 8-B loads),
 // kLoadPlanar (pixel stride 1: one 8-B load per channel) or kLoadScalar (any strides). VEC_X: x at ldx == 3, 3 x 16-B
 // stores. Vector modes need W % 8 == 0 and aligned rows (checked by the host).
 template <int LOAD, bool VEC_X, bool LIMITED>
-__global__ void __launch_bounds__(kThreads) rgb_to_x_cs_kernel(const uint8_t* __restrict__ src, long long rs, long long ps,
+__global__ void __launch_bounds__(kThreads) rgb_to_x_kernel(const uint8_t* __restrict__ src, long long rs, long long ps,
                                                                long long cs, int H, int W, half_t* __restrict__ x, int ldx,
                                                                uint8_t* __restrict__ planar, const ColourConsts k)
 {
     const unsigned wv = (W + 7) >> 3;
-    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (rgb_validate)
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (picture_validate)
     if (i >= static_cast<unsigned>(H) * wv) return;
     const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
     const int n = min(8, W - w0);
@@ -176,12 +186,12 @@ __device__ __forceinline__ uint8_t to_u8(half_t v)
 // one thread = 8 consecutive pixels of a row. VEC: row_pixels % 8 == 0, W % 8 == 0, aligned bases: 3 x 16-B loads,
 // one 16-B store per fp16 plane, 3 x 8-B stores of packed u8.
 template <bool VEC, bool LIMITED>
-__global__ void __launch_bounds__(kThreads) x_to_rgb_cs_kernel(const half_t* __restrict__ x, int row_pixels, int H, int W,
+__global__ void __launch_bounds__(kThreads) x_to_rgb_kernel(const half_t* __restrict__ x, int row_pixels, int H, int W,
                                                                half_t* __restrict__ rgb16, uint8_t* __restrict__ rgb8,
                                                                const ColourConsts k)
 {
     const unsigned wv = (W + 7) >> 3;
-    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (rgb_validate)
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (picture_validate)
     if (i >= static_cast<unsigned>(H) * wv) return;
     const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
     const int n = min(8, W - w0);
@@ -226,14 +236,6 @@ __global__ void __launch_bounds__(kThreads) x_to_rgb_cs_kernel(const half_t* __r
     }
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-unsigned grid_of(int H, int W)
-{
-    const long long n = static_cast<long long>(H) * ((W + 7) / 8);
-    return static_cast<unsigned>((n + kThreads - 1) / kThreads);
-}
-
 void colour_validate(const ColourSpace& cs, const char* what)
 {
     if (cs.matrix != kMatrixBt601 && cs.matrix != kMatrixBt709 && cs.matrix != kMatrixBt2020) {
@@ -252,36 +254,40 @@ void launch_to_x(const RgbToXDesc& d, bool limited, const ColourConsts& k, hipSt
 {
     const dim3 grid(grid_of(d.H, d.W)), block(kThreads);
     if (limited) {
-        hipLaunchKernelGGL((rgb_to_x_cs_kernel<LOAD, VEC_X, true>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+        hipLaunchKernelGGL((rgb_to_x_kernel<LOAD, VEC_X, true>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
                            d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k);
     } else {
-        hipLaunchKernelGGL((rgb_to_x_cs_kernel<LOAD, VEC_X, false>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+        hipLaunchKernelGGL((rgb_to_x_kernel<LOAD, VEC_X, false>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
                            d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k);
     }
 }
 
-}  // namespace
-
-void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream)
+// the three (stride, extent) pairs must not overlap: sorted by stride, each stride covers the previous dimension
+void stride_check(const RgbToXDesc& d, const std::string& what)
 {
-    rgb_validate(d.H, d.W, "rgb_to_x_cs");
-    colour_validate(cs, "rgb_to_x_cs");
-    if (d.src == nullptr) throw std::invalid_argument("rgb_to_x_cs: no source picture");
-    if (d.x == nullptr && d.planar == nullptr) throw std::invalid_argument("rgb_to_x_cs: neither x nor the planar copy requested");
-    if (d.x != nullptr && d.ldx < 3) throw std::invalid_argument("rgb_to_x_cs: the pixel stride of x must be >= 3");
-    // the three (stride, extent) pairs must not overlap: sorted by stride, each stride covers the previous dimension
     long long st[3] = {d.channel_stride, d.pixel_stride, d.row_stride}, ex[3] = {3, d.W, d.H};
     for (int q = 0; q < 3; ++q) {
-        if (st[q] <= 0) throw std::invalid_argument("rgb_to_x_cs: the source strides must be positive");
+        if (st[q] <= 0) throw std::invalid_argument(what + ": the source strides must be positive");
     }
     for (int a = 0; a < 3; ++a)
         for (int b = a + 1; b < 3; ++b)
             if (st[b] < st[a]) { std::swap(st[a], st[b]); std::swap(ex[a], ex[b]); }
     if (st[1] < st[0] * ex[0] || st[2] < st[1] * ex[1]) {
-        throw std::invalid_argument("rgb_to_x_cs: source strides too small (row " + std::to_string(d.row_stride) + ", pixel " +
+        throw std::invalid_argument(what + ": source strides too small (row " + std::to_string(d.row_stride) + ", pixel " +
                                     std::to_string(d.pixel_stride) + ", channel " + std::to_string(d.channel_stride) +
                                     " for " + std::to_string(d.W) + "x" + std::to_string(d.H) + ")");
     }
+}
+
+// what: the entry's name, the prefix of its refusals
+void to_x(const RgbToXDesc& d, const ColourSpace& cs, const std::string& what, hipStream_t stream)
+{
+    picture_validate(d.H, d.W, what.c_str());
+    colour_validate(cs, what.c_str());
+    if (d.src == nullptr) throw std::invalid_argument(what + ": no source picture");
+    if (d.x == nullptr && d.planar == nullptr) throw std::invalid_argument(what + ": neither x nor the planar copy requested");
+    if (d.x != nullptr && d.ldx < 3) throw std::invalid_argument(what + ": the pixel stride of x must be >= 3");
+    stride_check(d, what);
     const bool rows8 = d.W % 8 == 0 && d.row_stride % 8 == 0 && aligned(d.src, 8) && (d.planar == nullptr || aligned(d.planar, 8));
     int load = kLoadScalar;
     if (rows8 && d.pixel_stride == 3 && d.channel_stride == 1) load = kLoadPacked;
@@ -294,26 +300,43 @@ void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream)
     else if (load == kLoadPlanar && vec_x) launch_to_x<kLoadPlanar, true>(d, limited, k, stream);
     else if (load == kLoadPlanar) launch_to_x<kLoadPlanar, false>(d, limited, k, stream);
     else launch_to_x<kLoadScalar, false>(d, limited, k, stream);
-    hip_check(hipGetLastError(), "rgb_to_x_cs launch");
+    hip_check(hipGetLastError(), (what + " launch").c_str());
 }
 
-void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream)
+void from_x(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, const std::string& what,
+            hipStream_t stream)
 {
-    rgb_validate(H, W, "x_to_rgb_cs");
-    colour_validate(cs, "x_to_rgb_cs");
-    if (x == nullptr) throw std::invalid_argument("x_to_rgb_cs: no x_hat");
-    if (row_pixels < W) throw std::invalid_argument("x_to_rgb_cs: the rows of x_hat are shorter than the picture");
+    picture_validate(H, W, what.c_str());
+    colour_validate(cs, what.c_str());
+    if (x == nullptr) throw std::invalid_argument(what + ": no x_hat");
+    if (row_pixels < W) throw std::invalid_argument(what + ": the rows of x_hat are shorter than the picture");
     const bool vec = row_pixels % 8 == 0 && W % 8 == 0 && aligned(x, 16) && (rgb16 == nullptr || aligned(rgb16, 16)) &&
                      (rgb8 == nullptr || aligned(rgb8, 8));
     if (rgb16 == nullptr && rgb8 == nullptr) return;
     const bool limited = cs.range == kRangeLimited;
     const ColourConsts k = colour_consts(cs);
     const dim3 grid(grid_of(H, W)), block(kThreads);
-    if (vec && limited) hipLaunchKernelGGL((x_to_rgb_cs_kernel<true, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
-    else if (vec) hipLaunchKernelGGL((x_to_rgb_cs_kernel<true, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
-    else if (limited) hipLaunchKernelGGL((x_to_rgb_cs_kernel<false, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
-    else hipLaunchKernelGGL((x_to_rgb_cs_kernel<false, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
-    hip_check(hipGetLastError(), "x_to_rgb_cs launch");
+    if (vec && limited) hipLaunchKernelGGL((x_to_rgb_kernel<true, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else if (vec) hipLaunchKernelGGL((x_to_rgb_kernel<true, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else if (limited) hipLaunchKernelGGL((x_to_rgb_kernel<false, true>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    else hipLaunchKernelGGL((x_to_rgb_kernel<false, false>), grid, block, 0, stream, x, row_pixels, H, W, rgb16, rgb8, k);
+    hip_check(hipGetLastError(), (what + " launch").c_str());
+}
+
+}  // namespace
+
+void rgb_to_x(const RgbToXDesc& d, hipStream_t stream) { to_x(d, ColourSpace{}, "rgb_to_x", stream); }
+
+void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream) { to_x(d, cs, "rgb_to_x_cs", stream); }
+
+void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, hipStream_t stream)
+{
+    from_x(x, row_pixels, H, W, rgb16, rgb8, ColourSpace{}, "x_to_rgb", stream);
+}
+
+void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream)
+{
+    from_x(x, row_pixels, H, W, rgb16, rgb8, cs, "x_to_rgb_cs", stream);
 }
 
 }  // namespace dcvc

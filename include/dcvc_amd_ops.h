@@ -191,11 +191,13 @@ int dcvc_scale_clamped(const void* x, int ldx, const void* q, int ldq, void* y, 
 /* Picture I/O on the device, replacing the host-side numpy/scipy/torch chains of the harness.
  * test_video.py:69-123 get_src_frame (+ transforms.py:69-80 ycbcr420_to_444_np, order 0):
  *   y: u8 [H][W], uv: u8 [2][H/2][W/2] (device) -> x fp16 at pixel stride ldx (3 channels written):
- *   nearest chroma, x = fp16(fp16(v / 255) - 0.5). */
+ *   nearest chroma, x = fp16(fp16(v / 255) - 0.5). H, W positive and even, ldx >= 3, no NULL operand: refused otherwise.
+ *   The same kernels as dcvc_pix_to_x / dcvc_x_to_pix at DCVC_PIX_YUV420P, 8 bits, behind separate plane pointers. */
 int dcvc_yuv420_to_x(const void* y, const void* uv, int H, int W, void* x, int ldx, void* stream);
 /* test_video.py:32-45 get_distortion and :356-363 (decoded-picture writer):
  *   x_hat fp16 [rows][row_pixels][3] -> top-left H x W picture; y16/uv16: fp16 planes in 0..255,
- *   y8/uv8: u8 planes (Y rounded half-to-even, U/V truncated as the reference does). Null = skip. */
+ *   y8/uv8: u8 planes (Y rounded half-to-even, U/V truncated as the reference does). Each of the four: NULL = skip;
+ *   with all four NULL the call returns 0 without a launch. */
 int dcvc_x_to_yuv420(const void* x_hat, int row_pixels, int H, int W, void* y16, void* uv16, void* y8,
                      void* uv8, void* stream);
 
@@ -238,7 +240,7 @@ int dcvc_pix_to_x(const void* src, int fmt, int bit_depth, int H, int W, void* x
  *   decodes to the same samples in both 4:2:0 layouts; 4:2:2 and 4:4:4 have no reference writer and round). P010 stores
  *   s << (16 - b). Either output may be NULL; with both NULL the call returns 0 without a launch.
  * DCVC_PIX_YUV420P and DCVC_PIX_NV12 give the bits of dcvc_yuv420_to_x, dcvc_x_to_yuv420, dcvc_yuv420p16_to_x and
- * dcvc_x_to_yuv420p16, up to the layout. */
+ * dcvc_x_to_yuv420p16, up to the layout: those four run the kernels of these two. */
 int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H, int W, int fmt, int bit_depth, void* dist32, void* out, void* stream);
 
 /* sample types of dcvc_msssim (U8, F16) and of dcvc_sse / dcvc_sse_ws / dcvc_msssim_range (all four; 2 is unassigned) */
@@ -293,7 +295,7 @@ int dcvc_x_to_rgb(const void* x_hat, int row_pixels, int H, int W, void* rgb16, 
  *   pb = (0.5 (b - y)) * (1.0f / fp32(1 - Kb));  pr = (0.5 (r - y)) * (1.0f / fp32(1 - Kr))
  *   full: Y = y, Cb = pb + 0.5, Cr = pr + 0.5;  limited: Y = y * ry + lo, Cb = pb * rc + mid, Cr = pr * rc + mid
  *   x_k = fp16(fp32(fp16(clamp(., 0, 1))) - 0.5)
- * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_rgb_to_x's sequence and gives its bits. Refused before any launch:
+ * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_rgb_to_x (the same kernel). Refused before any launch:
  * an unknown matrix or range, a depth outside 8..16, and everything dcvc_rgb_to_x refuses. */
 int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int H, int W,
                      void* x, int ldx, void* planar, int matrix, int range, int yuv_bit_depth, void* stream);
@@ -302,7 +304,7 @@ int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stri
  *   full: y = Y, pb = Cb - 0.5, pr = Cr - 0.5;  limited: y = (Y - lo) * iy, pb = (Cb - mid) * ic, pr = (Cr - mid) * ic
  *   r = y + fp32(2 - 2 Kr) * pr;  b = y + fp32(2 - 2 Kb) * pb;  g = ((y - Kr r) - Kb b) * (1.0f / fp32(Kg))
  *   rgb16_k = clamp(fp16(fp32(fp16(clamp(., 0, 1))) * 255), 0, 255);  rgb8 = rint(rgb16) (half to even), NaN -> 0
- * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_x_to_rgb's sequence and gives its bits. Over all 2^24 colours
+ * At DCVC_MATRIX_BT709 / DCVC_RANGE_FULL this is dcvc_x_to_rgb (the same kernel). Over all 2^24 colours
  * dcvc_x_to_rgb_cs(dcvc_rgb_to_x_cs(c)) = c for every matrix, in full range and in limited range at every depth. */
 int dcvc_x_to_rgb_cs(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8,
                      int matrix, int range, int yuv_bit_depth, void* stream);

@@ -1,4 +1,4 @@
-"""Picture I/O kernels (frame_io.hip) on a real MI355X against the oracle / reference vectors."""
+"""Picture I/O kernels (picture_yuv.hip through dcvc_yuv420_to_x / dcvc_x_to_yuv420) on a real MI355X against the oracle / reference vectors."""
 import ctypes
 import os
 

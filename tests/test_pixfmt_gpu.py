@@ -2,7 +2,9 @@
 formats at 8, 10 and 16 bits; sizes on the element path and on the vector path, one thread to several workgroups; ldx 3 and 24
 (a chunk slot: channels 3..23 untouched); row_pixels W, W + 8 and W + 1; bases aligned and offset by one sample; every sample
 code; every fp16 bit pattern as x_hat; P010 sources with non-zero low bits; guard bands around every output; and YUV420P /
-NV12 against the existing dcvc_yuv420_to_x, dcvc_x_to_yuv420, dcvc_yuv420p16_to_x and dcvc_x_to_yuv420p16."""
+NV12 against the existing dcvc_yuv420_to_x, dcvc_x_to_yuv420, dcvc_yuv420p16_to_x and dcvc_x_to_yuv420p16, which run the same
+two kernels behind separate plane pointers: those entries with planes allocated apart and offset, every subset of
+dcvc_x_to_yuv420's four outputs, and dcvc_x_to_yuv420p16 with one output."""
 import ctypes
 
 import numpy as np
@@ -202,6 +204,96 @@ def test_420_layouts_equal_the_existing_kernels(bits):
             assert np.array_equal(dist, want_d.view(np.uint32)), fmt
             ys, cs = pn.unpack(samples, fmt, bits, H, W)
             assert np.concatenate([ys.ravel(), cs.ravel()]).astype(samples.dtype).tobytes() == want_s.tobytes(), fmt
+
+
+PLANE_SIZES = SIZES[:4]        # one thread; element path; vector path; several rows
+
+
+def _planes_to_x(y, uv, bits, ldx, ch, uv_off):
+    """dcvc_yuv420_to_x / dcvc_yuv420p16_to_x with y and uv allocated apart, uv behind uv_off samples, x at channel offset ch of
+    pixels of ldx halfs -> x [H W, 3] as uint16 bits, with every other element of x checked"""
+    H, W = y.shape
+    keep_y, yp = _src(np.ascontiguousarray(y).ravel())
+    keep_uv, up = _src(np.ascontiguousarray(uv).ravel(), uv_off)
+    xo = Out((H * W - 1) * ldx + 3, 2, ch)
+    if bits == 8:
+        _lib.check(_f("dcvc_yuv420_to_x", [vp, vp, ci, ci, vp, ci, vp])(yp, up, H, W, xo.ptr(), ldx, _st()))
+    else:
+        _lib.check(_f("dcvc_yuv420p16_to_x", [vp, vp, ci, ci, ci, vp, ci, vp])(yp, up, H, W, bits, xo.ptr(), ldx, _st()))
+    torch.cuda.synchronize()
+    xb = xo.body(np.uint16)
+    idx = (np.arange(H * W)[:, None] * ldx + np.arange(3)).ravel()
+    rest = np.ones(xb.size, bool)
+    rest[idx] = False
+    assert np.all(xb[rest] == SENT16), "x was written outside the three channels"
+    return xb[idx].reshape(H * W, 3)
+
+
+@pytest.mark.parametrize("H,W", PLANE_SIZES, ids=["%dx%d" % s for s in PLANE_SIZES])
+@pytest.mark.parametrize("bits", BITS)
+def test_separate_planes_to_x(bits, H, W):
+    pic = _picture(pn.YUV420P, bits, H, W, seed=5)
+    y, uv = pn.unpack(pic, pn.YUV420P, bits, H, W)
+    want = _bits16(pn.to_x(pic, pn.YUV420P, bits, H, W)).reshape(H * W, 3)
+    for uv_off in (0, 1):                      # both planes 16-B aligned; uv not 8-B aligned
+        for ldx, ch in ((3, 0), (24, 15)):     # one picture; a chunk slot
+            assert np.array_equal(_planes_to_x(y, uv, bits, ldx, ch, uv_off), want), (uv_off, ldx, ch)
+
+
+def _x_to_yuv420(x_hat, H, W, mask):
+    """dcvc_x_to_yuv420 with the outputs of `mask` (bit 0: y16, 1: uv16, 2: y8, 3: uv8) non-null -> their contents (None for a
+    null one), guard bands checked"""
+    keep, xp = _src(np.ascontiguousarray(x_hat).reshape(-1).view(np.uint16))
+    ny, nc = H * W, H * W // 2
+    outs = [Out(n, es) if mask >> k & 1 else None for k, (n, es) in enumerate(((ny, 2), (nc, 2), (ny, 1), (nc, 1)))]
+    fn = _f("dcvc_x_to_yuv420", [vp, ci, ci, ci, vp, vp, vp, vp, vp])
+    _lib.check(fn(xp, x_hat.shape[1], H, W, *[o.ptr() if o else None for o in outs], _st()))
+    torch.cuda.synchronize()
+    return [o.body(v) if o else None for o, v in zip(outs, (np.uint16, np.uint16, np.uint8, np.uint8))]
+
+
+def _want_yuv420(x_hat, H, W):
+    """pn.from_x at (YUV420P, 8): the fp32 planes cast to fp16 (exact) and the samples, as [y16, uv16, y8, uv8]"""
+    d, s = pn.from_x(x_hat, H, W, pn.YUV420P, 8)
+    d16 = d.astype(np.float16)
+    assert np.array_equal(d16.astype(np.float32), d)
+    return [_bits16(d16[:H * W]), _bits16(d16[H * W:]), s[:H * W], s[H * W:]]
+
+
+@pytest.mark.parametrize("H,W", PLANE_SIZES, ids=["%dx%d" % s for s in PLANE_SIZES])
+def test_x_to_yuv420_every_subset_of_outputs(H, W):
+    for extra in (0, 8, 1):
+        x_hat = _x_hat(H + 2, W + extra, seed=6)
+        full = _x_to_yuv420(x_hat, H, W, 15)
+        for got, want in zip(full, _want_yuv420(x_hat, H, W)):
+            assert np.array_equal(got, want), extra
+        for mask in range(1, 15):
+            for k, got in enumerate(_x_to_yuv420(x_hat, H, W, mask)):
+                assert (got is None) == (not mask >> k & 1)
+                assert got is None or np.array_equal(got, full[k]), (extra, mask, k)
+
+
+def test_x_to_yuv420_every_fp16_pattern():
+    x_hat = pn.all_halfs()
+    for got, want in zip(_x_to_yuv420(x_hat, 256, 256, 15), _want_yuv420(x_hat, 256, 256)):
+        assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("H,W", PLANE_SIZES, ids=["%dx%d" % s for s in PLANE_SIZES])
+@pytest.mark.parametrize("bits", [10, 16])
+def test_x_to_yuv420p16_one_output(bits, H, W):
+    x_hat = _x_hat(H + 2, W, seed=7)
+    want_d, want_s = pn.from_x(x_hat, H, W, pn.YUV420P, bits)
+    keep, xp = _src(np.ascontiguousarray(x_hat).reshape(-1).view(np.uint16))
+    fn = _f("dcvc_x_to_yuv420p16", [vp, ci, ci, ci, ci, vp, vp, vp])
+    n = H * W * 3 // 2
+    for dist, yuv in ((Out(n, 4), None), (None, Out(n, 2)), (None, Out(n, 2, 1))):      # dist only; yuv only; yuv behind one sample
+        _lib.check(fn(xp, x_hat.shape[1], H, W, bits, dist.ptr() if dist else None, yuv.ptr() if yuv else None, _st()))
+        torch.cuda.synchronize()
+        if dist:
+            assert np.array_equal(dist.body(np.uint32), want_d.view(np.uint32))
+        else:
+            assert np.array_equal(yuv.body(np.uint16), want_s), yuv.off
 
 
 def test_python_wrappers():

@@ -1,6 +1,7 @@
 """dcvc_pix_to_x, dcvc_x_to_pix and dcvc_pix_picture_samples refuse a bad argument before any device work: every call below
 passes never-dereferenced pointers on a box without a GPU, must return < 0 and must name its entry point in dcvc_last_error
-(the pattern of test_ops_refusals_cpu.py)."""
+(the pattern of test_ops_refusals_cpu.py). The 8-bit YUV420 entries and the plain RGB entries, which forward to the same code,
+refuse under their own names."""
 import ctypes
 
 import pytest
@@ -99,3 +100,59 @@ def test_picture_samples():
 
 def test_every_entry_point_of_the_group_is_tried():
     assert {r[0] for r in REFUSED} == set(SIG)
+
+
+ll = cll
+FORWARDS = {
+    "yuv420_to_x": [vp, vp, ci, ci, vp, ci, vp],
+    "x_to_yuv420": [vp, ci, ci, ci, vp, vp, vp, vp, vp],
+    "rgb_to_x": [vp, ll, ll, ll, ci, ci, vp, ci, vp, vp],
+    "x_to_rgb": [vp, ci, ci, ci, vp, vp, vp],
+}
+
+
+def _yuv_to_x(y=P, uv=P2, H=16, W=24, x=P3, ldx=3):
+    return (y, uv, H, W, x, ldx, NULL)
+
+
+def _x_to_yuv(x=P, row=24, H=16, W=24, y16=P2, uv16=P2, y8=P3, uv8=P3):
+    return (x, row, H, W, y16, uv16, y8, uv8, NULL)
+
+
+FORWARDS_REFUSED = [
+    ("yuv420_to_x", _yuv_to_x(H=15), "odd height"),
+    ("yuv420_to_x", _yuv_to_x(W=23), "odd width"),
+    ("yuv420_to_x", _yuv_to_x(H=0), "no rows"),
+    ("yuv420_to_x", _yuv_to_x(ldx=2), "ldx below 3"),
+    ("yuv420_to_x", _yuv_to_x(y=NULL), "null y"),
+    ("yuv420_to_x", _yuv_to_x(uv=NULL), "null uv"),
+    ("yuv420_to_x", _yuv_to_x(x=NULL), "null x"),
+    ("yuv420_to_x", _yuv_to_x(H=1 << 18, W=1 << 17), "beyond the 32-bit thread index"),
+    ("x_to_yuv420", _x_to_yuv(H=15), "odd height"),
+    ("x_to_yuv420", _x_to_yuv(W=23, row=23), "odd width"),
+    ("x_to_yuv420", _x_to_yuv(W=0), "no columns"),
+    ("x_to_yuv420", _x_to_yuv(row=22), "row_pixels below W"),
+    ("x_to_yuv420", _x_to_yuv(x=NULL), "null x_hat"),
+    ("x_to_yuv420", _x_to_yuv(H=1 << 18, W=1 << 17, row=1 << 17), "beyond the 32-bit thread index"),
+    ("rgb_to_x", (P, 72, 3, 1, 15, 24, P2, 3, NULL, NULL), "odd height"),
+    ("rgb_to_x", (P, 72, 3, 1, 16, 24, P2, 2, NULL, NULL), "ldx below 3"),
+    ("rgb_to_x", (NULL, 72, 3, 1, 16, 24, P2, 3, NULL, NULL), "null source"),
+    ("rgb_to_x", (P, 71, 3, 1, 16, 24, P2, 3, NULL, NULL), "rows overlap"),
+    ("rgb_to_x", (P, 72, 3, 0, 16, 24, P2, 3, NULL, NULL), "channel stride 0"),
+    ("x_to_rgb", (P, 24, 16, 23, P2, P3, NULL), "odd width"),
+    ("x_to_rgb", (P, 22, 16, 24, P2, P3, NULL), "row_pixels below W"),
+    ("x_to_rgb", (NULL, 24, 16, 24, P2, P3, NULL), "null x_hat"),
+]
+
+
+@pytest.mark.parametrize("name,args,why", FORWARDS_REFUSED, ids=["%s-%s" % (r[0], r[2].replace(" ", "_")) for r in FORWARDS_REFUSED])
+def test_forwarding_entries_refuse_under_their_own_names(name, args, why):
+    from dcvc_amd import _lib
+    assert len(args) == len(FORWARDS[name])
+    assert _lib.fn("dcvc_" + name, ci, FORWARDS[name])(*args) < 0, why
+    assert _err().startswith(name + ":"), _err()        # rgb_to_x: / x_to_rgb:, not the _cs entries'
+
+
+def test_x_to_yuv420_with_no_output_returns_0_without_a_launch():
+    from dcvc_amd import _lib
+    assert _lib.fn("dcvc_x_to_yuv420", ci, FORWARDS["x_to_yuv420"])(*_x_to_yuv(y16=NULL, uv16=NULL, y8=NULL, uv8=NULL)) == 0

@@ -1,4 +1,4 @@
-"""The RGB picture kernels (rgb_io.hip through dcvc_amd.rgb) on a real MI355X, against the reference's op chains evaluated by
+"""The RGB picture kernels (rgb_cs.hip and sse.hip through dcvc_amd.rgb) on a real MI355X, against the reference's op chains evaluated by
 torch on the GPU (test_video.py:55-64, 87-122; transforms.py:17-27, 53-66) and against the numpy restatement in the same
 division convention (tests/rgb_np.py, div="recip"): bit for bit on all 2^24 colours in packed, planar and chunk-slot layouts,
 on random and clamp-edge x_hat with padded rows; the fp64 sums of squares against numpy, their reproducibility across runs

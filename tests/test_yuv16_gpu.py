@@ -1,4 +1,4 @@
-"""The high-bit-depth YUV420 kernels (frame_io16.hip through dcvc_amd.yuv16) on a real MI355X, against the numpy restatement
+"""The high-bit-depth YUV420 kernels (picture_yuv.hip through dcvc_amd.yuv16) on a real MI355X, against the numpy restatement
 (tests/yuv16_np.py): yuv420p16_to_x bit for bit over every code at 10, 12 and 16 bits in the packed (ldx = 3) and chunk-slot
 layouts, x_to_yuv420p16 bit for bit on random and clamp-edge x_hat with padded rows, the fp64 sums of squares with u16 / fp32
 samples against numpy and their reproducibility, dcvc_msssim_range at 255 against dcvc_msssim, 10-bit MS-SSIM against a

@@ -5,7 +5,8 @@ Per picture at 1920x1080 and 3840x2160, as tools/rgb_bench.py measures (its _tim
 back-to-back calls after a warm-up, over enough distinct buffers - > 512 MB in all - that the bytes come from HBM). Three
 variants per direction - "old" (the entry point without _cs), "bt709_full" and "bt2020_limited_10" (the _cs entry point) -
 take turns over --rounds rounds, so a drift of the machine falls on all three; each entry is the median over every batch of
-its variant, and "ratio_to_old" is that median over the old entry point's. All variants move the same bytes.
+its variant, and "ratio_to_old" is that median over the old entry point's. All variants move the same bytes. Since the
+picture kernels were merged (profiles/picture_io_merge.json) "old" and "bt709_full" run the same kernel.
 
 Needs the GPU. Usage: python tools/colour_bench.py [--batch 20] [--reps 10] [--rounds 3] [--out profiles/colour_bench.json]
 """

@@ -10,7 +10,8 @@ method is tools/rgb_bench.py's and tools/yuv16_bench.py's:
   * in the same run the existing planar 4:2:0 kernels at the same size and depth (dcvc_yuv420_to_x / dcvc_x_to_yuv420 at 8
     bits, dcvc_yuv420p16_to_x / dcvc_x_to_yuv420p16 at 10), whose bytes NV12 / P010 and yuv420p move exactly (the 8-bit
     dcvc_x_to_yuv420 writes fp16 planes, 3 H W bytes, where dcvc_x_to_pix writes fp32 ones, 6 H W), and each new-to-planar
-    ratio of the medians.
+    ratio of the medians. Since the picture kernels were merged (profiles/picture_io_merge.json) those entry points run the
+    kernels of dcvc_pix_to_x / dcvc_x_to_pix, so the two columns time the same kernel.
 
 Needs the GPU. Usage: python tools/pixfmt_bench.py [--batch 20] [--reps 30] [--out profiles/pixfmt_bench.json]
 """

@@ -652,6 +652,30 @@ int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H_, int W_, int fmt, in
     });
 }
 
+int dcvc_wire_carrier(int wire)
+{
+    int fmt = -1;
+    const int rc = dcvc::guarded([&] { fmt = dcvc::wire_carrier(wire); });
+    return rc < 0 ? rc : fmt;
+}
+
+long long dcvc_wire_picture_bytes(int wire, int bit_depth, int H_, int W_)
+{
+    long long n = -1;
+    const int rc = dcvc::guarded([&] { n = dcvc::wire_picture_bytes(wire, bit_depth, H_, W_); });
+    return rc < 0 ? rc : n;
+}
+
+int dcvc_wire_unpack(const void* src, int wire, int bit_depth, int H_, int W_, void* carrier, void* stream)
+{
+    return dcvc::guarded([&] { dcvc::wire_unpack(src, wire, bit_depth, H_, W_, carrier, S(stream)); });
+}
+
+int dcvc_wire_pack(const void* carrier, int wire, int bit_depth, int H_, int W_, void* dst, void* stream)
+{
+    return dcvc::guarded([&] { dcvc::wire_pack(carrier, wire, bit_depth, H_, W_, dst, S(stream)); });
+}
+
 namespace {
 
 // the operands of the dcvc_msssim* entries and of the dcvc_sse* entries: n_planes pairs of H x W planes

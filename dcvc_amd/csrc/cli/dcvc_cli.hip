@@ -9,14 +9,14 @@
 // planes and are converted on the device (picture_yuv.hip, rgb_cs.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
-//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] -o out.bin
+//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
 //               [--target-psnr DB [--qp-min 0] [--qp-max 63]] [--quality-log log.json]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
@@ -41,6 +41,20 @@
 //               source's planar samples against those planes, peak = max_val), --calc-ssim from dcvc_msssim_range_ws
 //               (every plane's sides >= 88). The log is the YUV420 log: (6 Y + U + V) / 8 for every format,
 //               frame_pixel_num = H W. --scale / --out-size are refused for them: not resampled yet.
+//               --src-type nv21 | nv16 | p210 | uyvy | yuy2 | y210 | v210: wire formats, the layouts capture cards,
+//               cameras and hardware decoders hand over, for -i (encode), --ref and -o. nv21: Y, then Cr Cb pairs (8 bits); nv16:
+//               Y, then rows of Cb Cr pairs at full height; uyvy: Cb Y0 Cr Y1 bytes (8 bits); yuy2: Y0 Cb Y1 Cr; v210: 6 pixels in
+//               four 32-bit words of three 10-bit fields, rows of 128 ceil(W / 48) bytes (10 bits). nv16 and yuy2 take --bit-depth
+//               8|9..16, u16 samples with the value in the high bits above 8 (p210 = nv16 --bit-depth 10, y210 = yuy2 --bit-depth
+//               10); another depth than the one a name stands for is refused. Each picture read is unpacked on the device
+//               (dcvc_wire_unpack, one launch) into the buffer where a picture of the carrier type - nv12 for nv21, yuv422 for
+//               the others - lands, and the run is the carrier type's from there: stream, --batch, --target-bpp, --target-psnr,
+//               --quality-log, --scene-cut, metrics and the JSON log are those of the carrier clip, byte for byte. On decode
+//               dcvc_x_to_pix writes the carrier picture and dcvc_wire_pack (one launch) the picture -o writes and --hash-log /
+//               --verify-hash hash (encode --hash-log too); unused bits, the fields of a v210 group past W and the row padding
+//               are zero. The manifest carries nv21, nv16, uyvy, yuy2 or v210, with two segments (Y, the interleaved chroma) for
+//               nv21 / nv16 and the whole picture as one for the others. Refused before a model is loaded: --scale / --out-size
+//               (not resampled yet), -i / --ref / -o names ending in .y4m, --matrix / --range.
 //               A -i, --ref or -o name ending in .y4m is a YUV4MPEG2 file (a file without the magic is refused). Encode:
 //               the header supplies -W -H, the source type and the bit depth, flags that disagree are refused; a C420*
 //               file takes the yuv420 path (its stream equals the raw file's). Decode: the flags, or - with both absent -
@@ -323,6 +337,9 @@ struct Geometry {
     int pix_fmt = -1;
     // RGB: what dcvc_rgb_to_x_cs / dcvc_x_to_rgb_cs are given (--matrix / --range / --yuv-depth; without: BT.709 / full range)
     int matrix = DCVC_MATRIX_BT709, range = DCVC_RANGE_FULL, yuv_depth = 8;
+    // --src-type nv21 / nv16 / p210 / uyvy / yuy2 / y210 / v210: the DCVC_WIRE_* layout of the files, beside
+    // pix_fmt, its carrier, which everything between dcvc_wire_unpack and dcvc_wire_pack sees; -1: the files hold pix_fmt
+    int wire = -1;
     bool pix() const { return pix_fmt >= 0; }
     int yuv_fmt() const { return pix() ? pix_fmt : DCVC_PIX_YUV420P; }      // the layout the conversion calls are given
     bool hbd() const { return bit_depth > 8; }
@@ -332,9 +349,17 @@ struct Geometry {
     size_t uv_bytes() const { return static_cast<size_t>(Hc()) * Wc() * 2; }      // samples of the U and V planes
     // one picture: u8 or u16 YUV planes (NV12: interleaved chroma), or packed RGB (u8 planes [3][H][W] on the device)
     size_t frame_bytes() const { return rgb ? 3 * y_bytes() : (y_bytes() + uv_bytes()) * (hbd() ? 2 : 1); }
+    // one picture of -i, --ref and -o, and what the hashes cover: frame_bytes(), or the wire format's picture
+    size_t file_bytes() const
+    {
+        if (wire < 0) return frame_bytes();
+        const long long n = dcvc_wire_picture_bytes(wire, bit_depth, H, W);
+        abi_ok(n, "wire picture");
+        return static_cast<size_t>(n);
+    }
 };
 
-Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8, int pix_fmt = -1)
+Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8, int pix_fmt = -1, int wire = -1)
 {
     if (rgb && (H <= 0 || W <= 0 || (H & 1) || (W & 1))) {
         die("picture size must be positive and even (RGB pictures are coded as YUV420 is: even sides), got " +
@@ -346,6 +371,7 @@ Geometry geometry(int H, int W, bool rgb = false, int bit_depth = 8, int pix_fmt
     g.rgb = rgb;
     g.bit_depth = bit_depth;
     g.pix_fmt = pix_fmt;
+    g.wire = wire;
     return g;
 }
 
@@ -506,15 +532,36 @@ PngDir png_dir(const std::string& dir)
 
 enum class SrcType { Yuv420, Rgb24, Png, Yuv422, Yuv444, Nv12 };
 
+// the DCVC_WIRE_* layout a --src-type name stands for (p210 = nv16, y210 = yuy2, both at 10 bits), -1 for the other names
+int wire_of(const std::string& s)
+{
+    return s == "nv21" ? DCVC_WIRE_NV21 : s == "nv16" || s == "p210" ? DCVC_WIRE_NV16 : s == "uyvy" ? DCVC_WIRE_UYVY :
+           s == "yuy2" || s == "y210" ? DCVC_WIRE_YUY2 : s == "v210" ? DCVC_WIRE_V210 : -1;
+}
+
+const char* wire_name(int wire)
+{
+    return wire == DCVC_WIRE_NV21 ? "nv21" : wire == DCVC_WIRE_NV16 ? "nv16" : wire == DCVC_WIRE_UYVY ? "uyvy" :
+           wire == DCVC_WIRE_YUY2 ? "yuy2" : "v210";
+}
+
+// the one depth a wire format's name stands for; 0: the name leaves it to --bit-depth (nv16, yuy2) or is no wire format
+int wire_fixed_depth(const std::string& s)
+{
+    return s == "p210" || s == "y210" || s == "v210" ? 10 : s == "uyvy" || s == "nv21" ? 8 : 0;
+}
+
+// a wire format's name gives the type of its carrier: the run is that type's behind dcvc_wire_unpack and up to dcvc_wire_pack
 SrcType src_type(const std::string& s)
 {
+    if (wire_of(s) >= 0) return dcvc_wire_carrier(wire_of(s)) == DCVC_PIX_NV12 ? SrcType::Nv12 : SrcType::Yuv422;
     if (s == "yuv420") return SrcType::Yuv420;
     if (s == "rgb24") return SrcType::Rgb24;
     if (s == "png") return SrcType::Png;
     if (s == "yuv422") return SrcType::Yuv422;
     if (s == "yuv444") return SrcType::Yuv444;
     if (s == "nv12" || s == "p010") return SrcType::Nv12;      // p010 = nv12 --bit-depth 10 (bit_depth_arg)
-    die("unknown --src-type " + s + " (yuv420, yuv422, yuv444, nv12, p010, rgb24 or png)");
+    die("unknown --src-type " + s + " (yuv420, yuv422, yuv444, nv12, p010, nv21, nv16, p210, uyvy, yuy2, y210, v210, rgb24 or png)");
 }
 
 // the DCVC_PIX_* layout of the types that take the picture path of dcvc_pix_to_x / dcvc_x_to_pix; -1 for the others
@@ -648,13 +695,23 @@ bool is_intra_picture(int idx, int intra_period)
 int bit_depth_arg(const Args& a, SrcType type)
 {
     const bool p010 = a.str("src-type") == "p010";
-    if (!a.has("bit-depth")) return p010 ? 10 : 8;
+    // the wire formats with one depth: p210, y210 and v210 hold 10-bit samples, uyvy and nv21 8-bit ones
+    const int fixed = wire_fixed_depth(a.str("src-type"));
+    if (!a.has("bit-depth")) return p010 ? 10 : fixed ? fixed : 8;
     const std::string s = a.str("bit-depth");
     if (type == SrcType::Rgb24 || type == SrcType::Png) die("--bit-depth is for --src-type yuv420 only (RGB sources are 8-bit)");
     char* end = nullptr;
     const long v = strtol(s.c_str(), &end, 10);
     if (s.empty() || *end != '\0' || v < 8 || v > 16) die("--bit-depth must be 8 or 9..16, got " + s);
     if (p010 && v != 10) die("--src-type p010 is nv12 at 10 bits: --bit-depth " + s + " disagrees (use --src-type nv12 --bit-depth " + s + ")");
+    if (fixed && v != fixed) {
+        const std::string t = a.str("src-type");
+        if (t == "p210" || t == "y210") {
+            const std::string base = t == "p210" ? "nv16" : "yuy2";
+            die("--src-type " + t + " is " + base + " at 10 bits: --bit-depth " + s + " disagrees (use --src-type " + base + " --bit-depth " + s + ")");
+        }
+        die("--src-type " + t + " holds " + std::to_string(fixed) + "-bit samples: --bit-depth " + s + " disagrees");
+    }
     return static_cast<int>(v);
 }
 
@@ -663,6 +720,60 @@ const char* src_type_name(SrcType t)
     return t == SrcType::Yuv420 ? "yuv420" : t == SrcType::Yuv422 ? "yuv422" : t == SrcType::Yuv444 ? "yuv444" : t == SrcType::Nv12 ? "nv12" :
            t == SrcType::Rgb24 ? "rgb24" : "png";
 }
+
+// --src-type nv21 | nv16 | p210 | uyvy | yuy2 | y210 | v210: the DCVC_WIRE_* layout of the run's files, -1 for the other types.
+// What the flags alone decide is refused before a model is loaded: a depth the format does not have, and Y4M files.
+int wire_arg(const Args& a, bool encoding)
+{
+    const std::string t = a.str("src-type");
+    const int wire = wire_of(t);
+    if (wire < 0) return -1;
+    bit_depth_arg(a, src_type(t));
+    for (const char* k : {"i", "ref", "o"}) {
+        if ((std::strcmp(k, "i") != 0 || encoding) && a.has(k) && is_y4m_name(a.str(k))) {
+            die(std::string(k[0] == 'r' ? "--" : "-") + k + " " + a.str(k) + ": Y4M has no tag for --src-type " + t + "; use a raw file");
+        }
+    }
+    return wire;
+}
+
+// the file's pictures of a wire format, beside the carrier pictures in DeviceBuffers: one launch converts each way
+struct WireStage {
+    uint8_t* in = nullptr;         // a picture of -i or --ref, in front of dcvc_wire_unpack
+    uint8_t* h_in = nullptr;       // pinned
+    uint8_t* out = nullptr;        // dcvc_wire_pack's picture: what -o writes and the hashes cover
+    uint8_t* h_out = nullptr;      // pinned
+    void create(const Geometry& g)
+    {
+        destroy();                 // a stream may switch parameter sets
+        if (g.wire < 0) return;
+        hip_ok(hipMalloc(&in, g.file_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&out, g.file_bytes()), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_in), g.file_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.file_bytes(), hipHostMallocDefault), "hipHostMalloc");
+    }
+    // the picture in h_in -> `carrier`, where an upload of the carrier type's picture lands
+    void upload(const Geometry& g, uint8_t* carrier, hipStream_t st) const
+    {
+        hip_ok(hipMemcpyAsync(in, h_in, g.file_bytes(), hipMemcpyHostToDevice, st), "H2D");
+        abi_ok(dcvc_wire_unpack(in, g.wire, g.bit_depth, g.H, g.W, carrier, st), "wire_unpack");
+    }
+    // the carrier picture dcvc_x_to_pix wrote -> out
+    void pack(const Geometry& g, const uint8_t* carrier, hipStream_t st) const
+    {
+        abi_ok(dcvc_wire_pack(carrier, g.wire, g.bit_depth, g.H, g.W, out, st), "wire_pack");
+    }
+    void destroy()
+    {
+        for (uint8_t* d : {in, out}) {
+            if (d) hip_ok(hipFree(d), "hipFree");
+        }
+        for (uint8_t* h : {h_in, h_out}) {
+            if (h) hip_ok(hipHostFree(h), "hipHostFree");
+        }
+        *this = WireStage{};
+    }
+};
 
 Y4mSource y4m_source(const PictureFile& pf, const Args& a, bool check_size)
 {
@@ -885,7 +996,7 @@ SizeArg size_arg(const Args& a, const char* key)
     const std::string flag = std::string("--") + key;
     const std::string type = a.str("src-type", "yuv420");
     if (type == "rgb24" || type == "png") die(flag + " is for --src-type yuv420: RGB sources are not resampled yet");
-    if (type == "yuv422" || type == "yuv444" || type == "nv12" || type == "p010") {
+    if (type == "yuv422" || type == "yuv444" || type == "nv12" || type == "p010" || wire_of(type) >= 0) {
         die(flag + " is for --src-type yuv420: " + type + " sources are not resampled yet");
     }
     if (!parse_size(a.str(key), z.W, z.H)) die(flag + " must be WxH with both sides positive and even, got " + a.str(key));
@@ -1062,9 +1173,11 @@ HashManifest read_manifest(const std::string& path)
     }
     m.src_type = h[4];
     m.depth = static_cast<int>(v[0]); m.W = static_cast<int>(v[1]); m.H = static_cast<int>(v[2]);
-    const bool packed = m.src_type == "rgb24" || m.src_type == "png";
-    const size_t planes = packed ? 1 : m.src_type == "nv12" ? 2 : 3;
-    if (!packed && m.src_type != "nv12" && m.src_type != "yuv420" && m.src_type != "yuv422" && m.src_type != "yuv444") {
+    // one segment: the packed pixels (RGB; uyvy, yuy2, v210); two: Y and the interleaved chroma
+    const bool packed = m.src_type == "rgb24" || m.src_type == "png" || m.src_type == "uyvy" || m.src_type == "yuy2" || m.src_type == "v210";
+    const bool semi = m.src_type == "nv12" || m.src_type == "nv21" || m.src_type == "nv16";
+    const size_t planes = packed ? 1 : semi ? 2 : 3;
+    if (!packed && !semi && m.src_type != "yuv420" && m.src_type != "yuv422" && m.src_type != "yuv444") {
         bad("unknown source type " + m.src_type);
     }
     if (lines.size() < 2 || lines.back()[0] != "sequence") bad("no sequence line at the end");
@@ -1092,6 +1205,15 @@ int hash_segments(const Geometry& g, long long* off, long long* len)
         return 1;
     }
     const long long es = g.hbd() ? 2 : 1, y = static_cast<long long>(g.y_bytes()) * es, uv = static_cast<long long>(g.uv_bytes()) * es;
+    if (g.wire >= 0) {
+        // the wire picture: Y and the interleaved chroma (nv21, nv16), or the whole picture (uyvy, yuy2, v210)
+        const long long total = static_cast<long long>(g.file_bytes());
+        const bool semi = g.wire == DCVC_WIRE_NV21 || g.wire == DCVC_WIRE_NV16;
+        off[0] = 0; len[0] = semi ? y : total;
+        if (!semi) return 1;
+        off[1] = y; len[1] = total - y;
+        return 2;
+    }
     off[0] = 0; len[0] = y;
     if (g.pix_fmt == DCVC_PIX_NV12) {
         off[1] = y; len[1] = uv;
@@ -1153,7 +1275,7 @@ struct HashRun {
         fprintf(stderr, "dcvc: --verify-hash: %s\n", what.c_str());
         exit(3);
     }
-    // one output picture on the device (g.frame_bytes() bytes in file layout); waits for the stream
+    // one output picture on the device (g.file_bytes() bytes in file layout); waits for the stream
     void picture(const uint8_t* dev, const Geometry& g, hipStream_t st)
     {
         long long off[3], len[3];
@@ -1172,7 +1294,7 @@ struct HashRun {
                 mismatch("picture " + std::to_string(idx) + " was decoded, " + verify + " holds " + std::to_string(expect.pictures.size()) + " pictures");
             }
             const HashPicture& e = expect.pictures[idx];
-            const char* names = g.rgb ? "P" : "YUV";      // P: the packed pixels; nv12: Y and the interleaved chroma
+            const char* names = n == 1 ? "P" : "YUV";      // P: the packed pixels; nv12, nv21, nv16: Y and the interleaved chroma
             for (int k = 0; k < n; ++k) {
                 if (e.planes[static_cast<size_t>(k)] != p.planes[static_cast<size_t>(k)]) {
                     mismatch("picture " + std::to_string(idx) + ", plane " + std::to_string(k) + " (" + (n == 2 && k == 1 ? "UV" : std::string(1, names[k])) +
@@ -1181,8 +1303,8 @@ struct HashRun {
             }
             if (e.crc != p.crc) mismatch("picture " + std::to_string(idx) + ", whole picture: expected " + hex8(e.crc) + ", got " + hex8(p.crc));
         }
-        got.sequence = dcvc_crc32_combine(got.sequence, p.crc, static_cast<long long>(g.frame_bytes()));
-        got.total_bytes += static_cast<long long>(g.frame_bytes());
+        got.sequence = dcvc_crc32_combine(got.sequence, p.crc, static_cast<long long>(g.file_bytes()));
+        got.total_bytes += static_cast<long long>(g.file_bytes());
         got.pictures.push_back(p);
     }
     void finish()
@@ -1352,6 +1474,7 @@ int encode(const Args& a)
     SrcType type = src_type(a.str("src-type", "yuv420"));
     int depth = bit_depth_arg(a, type);
     const SizeArg scale = size_arg(a, "scale");
+    const int wire = wire_arg(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
@@ -1377,7 +1500,7 @@ int encode(const Args& a)
         die("--src-type rgb24 needs -W and -H");
     }
     // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
-    Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type));
+    Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type), wire);
     if (rgb) colour.apply(gs);
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
@@ -1400,7 +1523,7 @@ int encode(const Args& a)
         total = pngs.count();
     } else {
         if (!src_file.f) src_file.open(a.str("i"));
-        total = src_file.count(gs.frame_bytes());
+        total = src_file.count(gs.file_bytes());
     }
     const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
@@ -1415,11 +1538,16 @@ int encode(const Args& a)
     size_t kept_cap = 0;
     // --hash-log: the intra encoder's reconstruction as the decoder would write it, with the source's type and depth at the
     // coded size
-    hash.begin(src_type_name(type), depth);
+    // a wire format's source pictures are unpacked into b.yuv8, where the carrier type's upload lands, and the hashed
+    // reconstruction is packed: everything between the two is the carrier type's run
+    WireStage ws;
+    ws.create(g);
+    hash.begin(wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
     hash.size(g.W, g.H);
     auto hash_x_hat = [&](const char* xh) {
         x_hat_to_picture(g, b, xh, true);
-        hash.picture(b.out8, g, b.st);
+        if (wire >= 0) ws.pack(g, b.out8, b.st);
+        hash.picture(wire >= 0 ? ws.out : b.out8, g, b.st);
     };
     // --scale: the source picture's own staging, pinned and on the device, in front of b.yuv8
     Resampler rs;
@@ -1440,6 +1568,11 @@ int encode(const Args& a)
             if (!src_file.read(h_full, gs.frame_bytes())) die("short read");
             hip_ok(hipMemcpyAsync(d_full, h_full, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
             rs.run(d_full, b.yuv8, b.st);
+            return;
+        }
+        if (wire >= 0) {
+            if (!src_file.read(ws.h_in, g.file_bytes())) die("short read");
+            ws.upload(g, b.yuv8, b.st);
             return;
         }
         if (type == SrcType::Png) {
@@ -1773,6 +1906,7 @@ int encode(const Args& a)
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
     src_file.close();
+    ws.destroy();
     if (scale.on) {
         rs.destroy();
         hip_ok(hipHostFree(h_full), "hipHostFree");
@@ -1891,6 +2025,7 @@ int decode(const Args& a)
     const ColourArgs colour = colour_args(a);
     HashRun hash;
     hash.parse(a, false);
+    const int wire = wire_arg(a, false);
     if (rec_y4m) {
         const std::string t = a.str("src-type");
         if (t == "nv12" || t == "p010") die("-o " + a.str("o") + ": Y4M has no tag for interleaved chroma (--src-type " + t + "); write a raw file");
@@ -1925,7 +2060,7 @@ int decode(const Args& a)
     if (out_size.on && pix_fmt >= 0) {
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
     }
-    hash.begin(src_type_name(type), depth);
+    hash.begin(wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
     FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
     // -o *.y4m: the header once the first picture's size is known, then a FRAME line in front of every picture
@@ -1960,6 +2095,9 @@ int decode(const Args& a)
     dcvc::stream::SpsTable sps;
     Geometry g;
     DeviceBuffers b;
+    // a wire format: --ref's pictures are unpacked into b.yuv8, where the carrier type's upload lands, and the carrier picture in
+    // b.out8 is packed into what -o writes and the hashes cover
+    WireStage ws;
     bool have_buffers = false;
     std::vector<uint8_t> src;
     // --out-size: the output pictures' geometry and their buffers, beside the coded size's (which follow the stream)
@@ -2022,9 +2160,10 @@ int decode(const Args& a)
             if (out_size.on) check_ratio("--out-size", s->width, s->height, go.W, go.H);
             hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
-            g = geometry(s->height, s->width, rgb, depth, pix_fmt);
+            g = geometry(s->height, s->width, rgb, depth, pix_fmt, wire);
             if (rgb) colour.apply(g);
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
+            ws.create(g);
             if (out_size.on) so.create(g, go, has_ref, calc_ssim);
             src.resize(g.frame_bytes());
             have_buffers = true;
@@ -2143,15 +2282,20 @@ int decode(const Args& a)
             // the source first: when it ends inside a chunk, the remaining pictures of the chunk are the encoder's
             // padding (repeats of the final picture) and must reach neither the log nor rec.yuv
             if (has_ref) {
-                uint8_t* sp = rgb || g.hbd() || g.pix() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
-                const bool got = png ? ref_pngs.read(sp, g) : ref_file.read(sp, g.frame_bytes());
+                uint8_t* sp = wire >= 0 ? ws.h_in : rgb || g.hbd() || g.pix() ? b.h_src : src.data();      // RGB, high bit depth: straight into pinned memory
+                const bool got = png ? ref_pngs.read(sp, g) : ref_file.read(sp, g.file_bytes());
                 if (!got) {
                     if (j > 0 && !intra) { source_ended = true; break; }      // (an I batch: as its pictures one by one)
                     die("reference file is shorter than the stream");
                 }
             }
-            if (hash.on()) hash.picture(b.out8, g, b.st);
-            if (has_rec) {
+            if (wire >= 0 && (has_rec || hash.on())) ws.pack(g, b.out8, b.st);
+            if (hash.on()) hash.picture(wire >= 0 ? ws.out : b.out8, g, b.st);
+            if (has_rec && wire >= 0) {
+                hip_ok(hipMemcpyAsync(ws.h_out, ws.out, g.file_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                hip_ok(hipStreamSynchronize(b.st), "sync");
+                if (fwrite(ws.h_out, 1, g.file_bytes(), rec) != g.file_bytes()) die("short write");
+            } else if (has_rec) {
                 hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 if (png) {
@@ -2189,7 +2333,8 @@ int decode(const Args& a)
                 const double peak = static_cast<double>((1 << g.bit_depth) - 1);
                 const uint8_t* src_uv = b.src8 + ny * es;
                 const char* dist_uv = y16 + ny * 4;
-                hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                if (wire >= 0) ws.upload(g, b.yuv8, b.st);
+                else hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
                 abi_ok(dcvc_pix_to_x(b.yuv8, g.pix_fmt, g.bit_depth, g.H, g.W, nullptr, 3, b.src8, b.st), "pix_to_x (planar source)");
                 abi_ok(dcvc_sse_ws(b.src8, dt, y16, DCVC_SAMPLE_F32, 1, g.H, g.W, g.W, static_cast<long long>(ny), b.sse, b.sse_ws,
                                    b.sse_ws_bytes, b.st), "sse (Y)");
@@ -2269,6 +2414,7 @@ int decode(const Args& a)
         }
     }
     if (have_buffers) free_buffers(b);
+    ws.destroy();
     so.destroy();
     if (rec) fclose(rec);
     ref_file.close();

@@ -281,6 +281,19 @@ void x_to_yuv420(const half_t* x, int row_pixels, int H, int W, half_t* y16, hal
 void yuv420p16_to_x(const uint16_t* y, const uint16_t* uv, int H, int W, int bit_depth, half_t* x, int ldx, hipStream_t stream);
 void x_to_yuv420p16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* yuv, hipStream_t stream);
 
+// ---------------------------------------------------------------- wire formats (wire_formats.hip)
+// Capture and file layouts in front of pix_to_x and behind x_to_pix: NV21 (8 bits), NV16 / P210 and YUY2 / Y210 (8..16 bits,
+// u16 samples in the high bits), UYVY (8 bits) and v210 (10 bits in 32-bit words, rows of 128 ceil(W / 48) bytes).
+constexpr int kWireNv21 = 0, kWireNv16 = 1, kWireUyvy = 2, kWireYuy2 = 3, kWireV210 = 4;      // DCVC_WIRE_*
+// the kPix* layout that holds a wire format's samples at its subsampling (NV12 for NV21, else YUV422P); throws for an unknown one
+int wire_carrier(int wire);
+// file bytes of one picture; throws for an unknown format, a depth the format does not have, sides that are not positive and even
+long long wire_picture_bytes(int wire, int bit_depth, int H, int W);
+// src (one wire picture) -> carrier (one picture in the carrier's file layout, as pix_to_x takes it) and back; one launch each.
+// Throw before the launch: null operands, what wire_picture_bytes refuses, ranges that overlap.
+void wire_unpack(const void* src, int wire, int bit_depth, int H, int W, void* carrier, hipStream_t stream);
+void wire_pack(const void* carrier, int wire, int bit_depth, int H, int W, void* dst, hipStream_t stream);
+
 // ---------------------------------------------------------------- MS-SSIM (msssim.hip)
 // metrics.py:27-91 calc_msssim of n_planes pairs of H x W planes (u8 or fp16 samples in 0..255; src and rec share row_stride
 // and plane_stride, in samples), fp64 after the load; out[plane] (device, fp64). The workspace (msssim_workspace_bytes) holds the

@@ -243,6 +243,35 @@ int dcvc_pix_to_x(const void* src, int fmt, int bit_depth, int H, int W, void* x
  * dcvc_x_to_yuv420p16, up to the layout: those four run the kernels of these two. */
 int dcvc_x_to_pix(const void* x_hat, int row_pixels, int H, int W, int fmt, int bit_depth, void* dist32, void* out, void* stream);
 
+/* Wire formats (no reference counterpart): the layouts capture cards, cameras and hardware decoders hand over,
+ * converted to and from a carrier - the DCVC_PIX_* layout that holds the same samples at the same subsampling - in a pass of
+ * its own in front of dcvc_pix_to_x and behind dcvc_x_to_pix. One picture, little-endian:
+ *   DCVC_WIRE_NV21  Y [H][W], then [H/2][W/2][2] as Cr, Cb; 8 bits; carrier DCVC_PIX_NV12 (the pairs swapped)
+ *   DCVC_WIRE_NV16  Y [H][W], then [H][W/2][2] as Cb, Cr; 8 bits, or 9..16: u16 with the value in the high b bits (P210)
+ *   DCVC_WIRE_UYVY  [H][W/2] x (Cb, Y0, Cr, Y1) bytes; 8 bits
+ *   DCVC_WIRE_YUY2  [H][W/2] x (Y0, Cb, Y1, Cr); 8 bits, or 9..16: u16 with the value in the high b bits (Y210 / Y212 / Y216)
+ *   DCVC_WIRE_V210  rows of 128 ceil(W / 48) bytes; 6 pixels in four 32-bit words, three 10-bit fields each at bits 0-9, 10-19,
+ *                   20-29: w0 = Cb0 Y0 Cr0, w1 = Y1 Cb2 Y2, w2 = Cr2 Y3 Cb4, w3 = Y4 Cr4 Y5; 10 bits
+ * The last four have the carrier DCVC_PIX_YUV422P. `carrier` is one picture in the carrier's file layout, what dcvc_pix_to_x
+ * takes and dcvc_x_to_pix writes: u8 at 8 bits, u16 above, LSB-aligned for DCVC_PIX_YUV422P.
+ *   unpack: high-aligned samples are read as v >> (16 - b), v210 fields with & 1023; the low bits, bits 30-31, fields past W and
+ *   the row padding are ignored. Samples above max_val are neither checked nor masked.
+ *   pack: high-aligned samples are stored as (s << (16 - b)) & 0xFFFF, v210 fields as s & 1023; bits 30-31, the fields of a
+ *   last group past W and the row padding are written as zero: every byte of dcvc_wire_picture_bytes is defined.
+ *   pack(unpack(p)) == p for a p whose ignored bits are zero, unpack(pack(c)) == c for a c with samples <= max_val.
+ * One launch per call on `stream`, no allocation, no host synchronisation. Refused before the launch (dcvc_last_error names
+ * the wire entry): a NULL operand, an unknown format, a depth the format does not have, sides that are not positive and even,
+ * a picture too large for 32-bit thread indices, source and destination ranges that overlap. */
+#define DCVC_WIRE_NV21 0
+#define DCVC_WIRE_NV16 1
+#define DCVC_WIRE_UYVY 2
+#define DCVC_WIRE_YUY2 3
+#define DCVC_WIRE_V210 4
+int       dcvc_wire_carrier(int wire);                                    /* DCVC_PIX_*, < 0: unknown; host only */
+long long dcvc_wire_picture_bytes(int wire, int bit_depth, int H, int W); /* file bytes of one picture, < 0: refused; host only */
+int dcvc_wire_unpack(const void* src, int wire, int bit_depth, int H, int W, void* carrier, void* stream);
+int dcvc_wire_pack(const void* carrier, int wire, int bit_depth, int H, int W, void* dst, void* stream);
+
 /* sample types of dcvc_msssim (U8, F16) and of dcvc_sse / dcvc_sse_ws / dcvc_msssim_range (all four; 2 is unassigned) */
 #define DCVC_SAMPLE_U8  0
 #define DCVC_SAMPLE_F16 1

@@ -792,6 +792,27 @@ int dcvc_x_to_rgb_cs(const void* x_hat, int row_pixels, int H_, int W_, void* rg
     });
 }
 
+int dcvc_rgb16_to_x_cs(const void* src, long long row_stride, long long pixel_stride, long long channel_stride, int bit_depth, int H_,
+                       int W_, void* x, int ldx, void* planar16, int matrix, int range, int yuv_bit_depth, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::Rgb16ToXDesc d;
+        d.src = static_cast<const uint16_t*>(src);
+        d.row_stride = row_stride; d.pixel_stride = pixel_stride; d.channel_stride = channel_stride;
+        d.bit_depth = bit_depth; d.H = H_; d.W = W_; d.x = H(x); d.ldx = ldx; d.planar = static_cast<uint16_t*>(planar16);
+        dcvc::rgb16_to_x_cs(d, dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
+    });
+}
+
+int dcvc_x_to_rgb16_cs(const void* x_hat, int row_pixels, int H_, int W_, int bit_depth, void* dist32, void* rgb16u, int matrix,
+                       int range, int yuv_bit_depth, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::x_to_rgb16_cs(H(x_hat), row_pixels, H_, W_, bit_depth, static_cast<float*>(dist32), static_cast<uint16_t*>(rgb16u),
+                            dcvc::ColourSpace{matrix, range, yuv_bit_depth}, S(stream));
+    });
+}
+
 int dcvc_sse(const void* src, int src_dtype, const void* rec, int rec_dtype, int n_planes, int H_, int W_, int row_stride,
              long long plane_stride, double* out, void* stream)
 {

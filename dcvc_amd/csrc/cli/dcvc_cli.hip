@@ -1,4 +1,4 @@
-// dcvc - standalone DCVC-UF encoder / decoder for 8- to 16-bit YUV (4:2:0, 4:2:2, 4:4:4, NV12 / P010, Y4M) and 8-bit RGB pictures on
+// dcvc - standalone DCVC-UF encoder / decoder for 8- to 16-bit YUV (4:2:0, 4:2:2, 4:4:4, NV12 / P010, Y4M) and 8- to 16-bit RGB pictures on
 // an MI355X.
 //
 // The codec without the research harness: what test_video.py:166-399 (run_one_point_with_stream)
@@ -9,14 +9,14 @@
 // planes and are converted on the device (picture_yuv.hip, rgb_cs.hip).
 //
 //   dcvc encode --intra I.dcvw [--inter P.dcvw] -i in.yuv -W 1920 -H 1080 [-n frames] --qp-i 32 [--qp-p 32]
-//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png] [--bit-depth 8|9..16] -o out.bin
+//               [--intra-period -1] [--reset-interval 32] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] -o out.bin
 //               [--target-bpp B [--qp-min 0] [--qp-max 63] [--rc-horizon 8] [--rc-intra-bonus 0] [--rc-log log.json]
 //                [--rc-mode feedback|probe]]
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
 //               [--target-psnr DB [--qp-min 0] [--qp-max 63]] [--quality-log log.json]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
-//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png] [--bit-depth 8|9..16] [--out-size WxH]
+//               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
@@ -33,6 +33,16 @@
 //               366-370); the log then holds the RGB PSNR (dcvc_sse, calc_psnr over 3 H W samples) and, with --calc-ssim,
 //               the mean of the three planes' MS-SSIM (calc_msssim_rgb), without _y / _u / _v keys. Both sides must be
 //               even, and >= 88 for --calc-ssim.
+//               --src-type rgb48 | png16: RGB above 8 bits, everywhere rgb24 / png are (-i, --ref, -o; --batch,
+//               --target-bpp, --target-psnr, --quality-log, --scene-cut, --matrix / --range / --yuv-depth, --hash-log /
+//               --verify-hash). rgb48 = packed u16 little-endian pictures back to back (ffmpeg -pix_fmt rgb48le -f rawvideo),
+//               --bit-depth 9..16 (default 16), values LSB-aligned in 0..2^b - 1, -W / -H required to encode; png16 =
+//               directories of 16-bit PNGs under png's naming rules, depth 16 (another --bit-depth is refused, and so is an
+//               8-bit file in the directory, with its name). Converted by dcvc_rgb16_to_x_cs / dcvc_x_to_rgb16_cs; the RGB
+//               PSNR is 10 log10(max_val^2 / mse) over 3 H W samples (dcvc_sse_ws, the source's planar u16 copy against fp32
+//               distortion planes) and --calc-ssim the mean of three dcvc_msssim_range_ws calls with data_range = max_val;
+//               the log has the rgb24 log's keys. The manifest carries rgb48 or png16 with one segment of 6 H W bytes.
+//               Refused before a model is loaded: --bit-depth 8, --scale / --out-size, names ending in .y4m, odd sides.
 //               --src-type yuv422 | yuv444 | nv12 | p010, each with --bit-depth 8|9..16 (p010 = nv12 --bit-depth 10):
 //               4:2:2 and 4:4:4 planar pictures (Y, Cb, Cr planes; u16 samples LSB-aligned as yuv4xxp10le) and NV12 (Y, then
 //               interleaved Cb Cr rows; above 8 bits the value sits in the high bits, P010 / P012 / P016) for -i (encode),
@@ -330,8 +340,8 @@ Codecs make_codecs(const std::string& intra_path, const std::string& inter_path)
 // ------------------------------------------------------------------------------------ pictures
 struct Geometry {
     int H = 0, W = 0, Hp = 0, Wp = 0;      // picture, padded to multiples of 16
-    bool rgb = false;                      // 8-bit RGB pictures (--src-type rgb24 / png) instead of YUV420
-    int bit_depth = 8;                     // YUV420: 9..16 = uint16 samples (--bit-depth)
+    bool rgb = false;                      // RGB pictures (--src-type rgb24 / png: 8 bits; rgb48 / png16: 9..16) instead of YUV420
+    int bit_depth = 8;                     // 9..16 = uint16 samples (--bit-depth)
     // --src-type yuv422 / yuv444 / nv12 / p010: a DCVC_PIX_* layout at any depth, with fp32 distortion planes and the metrics
     // on the device at 8 bits too; -1: YUV420 planes (8 bits: fp16 distortion planes, summed on the host) or RGB
     int pix_fmt = -1;
@@ -343,12 +353,13 @@ struct Geometry {
     bool pix() const { return pix_fmt >= 0; }
     int yuv_fmt() const { return pix() ? pix_fmt : DCVC_PIX_YUV420P; }      // the layout the conversion calls are given
     bool hbd() const { return bit_depth > 8; }
+    bool rgb16() const { return rgb && hbd(); }      // --src-type rgb48 / png16: dcvc_rgb16_to_x_cs / dcvc_x_to_rgb16_cs, fp32 distortion planes
     int Hc() const { return pix_fmt == DCVC_PIX_YUV422P || pix_fmt == DCVC_PIX_YUV444P ? H : H / 2; }      // a chroma plane's sides
     int Wc() const { return pix_fmt == DCVC_PIX_YUV444P ? W : W / 2; }
     size_t y_bytes() const { return static_cast<size_t>(H) * W; }                 // samples of the Y plane
     size_t uv_bytes() const { return static_cast<size_t>(Hc()) * Wc() * 2; }      // samples of the U and V planes
-    // one picture: u8 or u16 YUV planes (NV12: interleaved chroma), or packed RGB (u8 planes [3][H][W] on the device)
-    size_t frame_bytes() const { return rgb ? 3 * y_bytes() : (y_bytes() + uv_bytes()) * (hbd() ? 2 : 1); }
+    // one picture: u8 or u16 YUV planes (NV12: interleaved chroma), or packed RGB (planes [3][H][W] on the device), u8 or u16
+    size_t frame_bytes() const { return (rgb ? 3 * y_bytes() : y_bytes() + uv_bytes()) * (hbd() ? 2 : 1); }
     // one picture of -i, --ref and -o, and what the hashes cover: frame_bytes(), or the wire format's picture
     size_t file_bytes() const
     {
@@ -428,6 +439,11 @@ DeviceBuffers make_buffers(const Geometry& g, int frames, bool ssim = false, boo
                                : std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.Hc(), g.Wc()));
         hip_ok(hipMalloc(&b.sse_ws, static_cast<size_t>(b.sse_ws_bytes)), "hipMalloc");
     }
+    if (ssim && g.rgb16()) {
+        // R, G and B one after the other on the same workspace
+        b.ssim_ws_bytes = dcvc_msssim_workspace_bytes(1, g.H, g.W);
+        hip_ok(hipMalloc(&b.ssim_ws, static_cast<size_t>(b.ssim_ws_bytes)), "hipMalloc");
+    }
     if (ssim && g.pix()) {
         b.ssim_ws_bytes = std::max(dcvc_msssim_workspace_bytes(1, g.H, g.W), dcvc_msssim_workspace_bytes(2, g.Hc(), g.Wc()));
         hip_ok(hipMalloc(&b.ssim_ws, static_cast<size_t>(b.ssim_ws_bytes)), "hipMalloc");
@@ -485,6 +501,14 @@ double psnr_of_sse(double se, double n, double peak = 255.0)
 
 // a directory of PNG pictures im1.png, im2.png, ... or im00001.png, ... (video_reader.py:10-45 PNGReader; its naming
 // rule: im1.png present -> no padding, else im00001.png present -> 5 digits, else an error)
+// the size of a picture of --src-type png16; an 8-bit file is refused with its name
+void png16_info(const std::string& p, int& w, int& h)
+{
+    int depth = 0;
+    abi_ok(dcvc_png_info2(p.c_str(), &w, &h, &depth), "png read");
+    if (depth != 16) die(p + " is an " + std::to_string(depth) + "-bit PNG: --src-type png16 reads 16-bit pictures (--src-type png reads 8-bit ones)");
+}
+
 struct PngDir {
     std::string dir;
     int pad = 5, next = 1;
@@ -507,12 +531,14 @@ struct PngDir {
         if (!exists(next)) return false;
         const std::string p = path(next++);
         int w = 0, h = 0;
-        abi_ok(dcvc_png_info(p.c_str(), &w, &h), "png read");
+        if (g.rgb16()) png16_info(p, w, h);
+        else abi_ok(dcvc_png_info(p.c_str(), &w, &h), "png read");
         if (w != g.W || h != g.H) {
             die(p + " is " + std::to_string(w) + "x" + std::to_string(h) + ", the sequence is " + std::to_string(g.W) + "x" +
                 std::to_string(g.H));
         }
-        abi_ok(dcvc_png_read_rgb(p.c_str(), buf, g.frame_bytes(), &w, &h), "png read");
+        if (g.rgb16()) abi_ok(dcvc_png_read_rgb16(p.c_str(), buf, g.frame_bytes(), &w, &h), "png read");
+        else abi_ok(dcvc_png_read_rgb(p.c_str(), buf, g.frame_bytes(), &w, &h), "png read");
         return true;
     }
 };
@@ -530,7 +556,11 @@ PngDir png_dir(const std::string& dir)
     die(dir + ": unknown image naming convention (im1.png or im00001.png expected)");
 }
 
-enum class SrcType { Yuv420, Rgb24, Png, Yuv422, Yuv444, Nv12 };
+enum class SrcType { Yuv420, Rgb24, Png, Yuv422, Yuv444, Nv12, Rgb48, Png16 };
+
+bool is_rgb(SrcType t) { return t == SrcType::Rgb24 || t == SrcType::Png || t == SrcType::Rgb48 || t == SrcType::Png16; }
+bool is_png(SrcType t) { return t == SrcType::Png || t == SrcType::Png16; }
+bool is_rgb_name(const std::string& t) { return t == "rgb24" || t == "png" || t == "rgb48" || t == "png16"; }
 
 // the DCVC_WIRE_* layout a --src-type name stands for (p210 = nv16, y210 = yuy2, both at 10 bits), -1 for the other names
 int wire_of(const std::string& s)
@@ -558,10 +588,12 @@ SrcType src_type(const std::string& s)
     if (s == "yuv420") return SrcType::Yuv420;
     if (s == "rgb24") return SrcType::Rgb24;
     if (s == "png") return SrcType::Png;
+    if (s == "rgb48") return SrcType::Rgb48;
+    if (s == "png16") return SrcType::Png16;
     if (s == "yuv422") return SrcType::Yuv422;
     if (s == "yuv444") return SrcType::Yuv444;
     if (s == "nv12" || s == "p010") return SrcType::Nv12;      // p010 = nv12 --bit-depth 10 (bit_depth_arg)
-    die("unknown --src-type " + s + " (yuv420, yuv422, yuv444, nv12, p010, nv21, nv16, p210, uyvy, yuy2, y210, v210, rgb24 or png)");
+    die("unknown --src-type " + s + " (yuv420, yuv422, yuv444, nv12, p010, nv21, nv16, p210, uyvy, yuy2, y210, v210, rgb24, png, rgb48 or png16)");
 }
 
 // the DCVC_PIX_* layout of the types that take the picture path of dcvc_pix_to_x / dcvc_x_to_pix; -1 for the others
@@ -697,8 +729,16 @@ int bit_depth_arg(const Args& a, SrcType type)
     const bool p010 = a.str("src-type") == "p010";
     // the wire formats with one depth: p210, y210 and v210 hold 10-bit samples, uyvy and nv21 8-bit ones
     const int fixed = wire_fixed_depth(a.str("src-type"));
-    if (!a.has("bit-depth")) return p010 ? 10 : fixed ? fixed : 8;
+    if (!a.has("bit-depth")) return p010 ? 10 : fixed ? fixed : type == SrcType::Rgb48 || type == SrcType::Png16 ? 16 : 8;
     const std::string s = a.str("bit-depth");
+    if (type == SrcType::Rgb48 || type == SrcType::Png16) {
+        char* e16 = nullptr;
+        const long v16 = strtol(s.c_str(), &e16, 10);
+        const bool number = !s.empty() && *e16 == '\0';
+        if (type == SrcType::Png16 && (!number || v16 != 16)) die("--src-type png16 holds 16-bit samples: --bit-depth " + s + " disagrees");
+        if (!number || v16 < 9 || v16 > 16) die("--src-type rgb48 takes --bit-depth 9..16 (8-bit RGB pictures are --src-type rgb24), got " + s);
+        return static_cast<int>(v16);
+    }
     if (type == SrcType::Rgb24 || type == SrcType::Png) die("--bit-depth is for --src-type yuv420 only (RGB sources are 8-bit)");
     char* end = nullptr;
     const long v = strtol(s.c_str(), &end, 10);
@@ -718,7 +758,7 @@ int bit_depth_arg(const Args& a, SrcType type)
 const char* src_type_name(SrcType t)
 {
     return t == SrcType::Yuv420 ? "yuv420" : t == SrcType::Yuv422 ? "yuv422" : t == SrcType::Yuv444 ? "yuv444" : t == SrcType::Nv12 ? "nv12" :
-           t == SrcType::Rgb24 ? "rgb24" : "png";
+           t == SrcType::Rgb24 ? "rgb24" : t == SrcType::Rgb48 ? "rgb48" : t == SrcType::Png16 ? "png16" : "png";
 }
 
 // --src-type nv21 | nv16 | p210 | uyvy | yuy2 | y210 | v210: the DCVC_WIRE_* layout of the run's files, -1 for the other types.
@@ -735,6 +775,19 @@ int wire_arg(const Args& a, bool encoding)
         }
     }
     return wire;
+}
+
+// --src-type rgb48 | png16: what the flags alone decide is refused before a model is loaded: the depth, Y4M names, odd sizes
+void rgb16_arg(const Args& a, bool encoding)
+{
+    const std::string t = a.str("src-type");
+    if (t != "rgb48" && t != "png16") return;
+    bit_depth_arg(a, src_type(t));
+    for (const char* k : {"i", "ref", "o"}) {
+        if ((std::strcmp(k, "i") != 0 || encoding) && a.has(k) && is_y4m_name(a.str(k))) {
+            die(std::string(k[0] == 'r' ? "--" : "-") + k + " " + a.str(k) + ": a Y4M file holds YUV pictures, not --src-type " + t);
+        }
+    }
 }
 
 // the file's pictures of a wire format, beside the carrier pictures in DeviceBuffers: one launch converts each way
@@ -866,7 +919,7 @@ ColourArgs colour_args(const Args& a)
     }
     // a Y4M -i or --ref cannot make the type RGB: a header that disagrees with --src-type is refused
     const std::string t = a.str("src-type", "yuv420");
-    if (t != "rgb24" && t != "png") {
+    if (!is_rgb_name(t)) {
         die("--matrix, --range and --yuv-depth are for --src-type rgb24 and png: " + t + " pictures are not converted");
     }
     return c;
@@ -995,7 +1048,7 @@ SizeArg size_arg(const Args& a, const char* key)
     if (!a.has(key)) return z;
     const std::string flag = std::string("--") + key;
     const std::string type = a.str("src-type", "yuv420");
-    if (type == "rgb24" || type == "png") die(flag + " is for --src-type yuv420: RGB sources are not resampled yet");
+    if (is_rgb_name(type)) die(flag + " is for --src-type yuv420: RGB sources are not resampled yet");
     if (type == "yuv422" || type == "yuv444" || type == "nv12" || type == "p010" || wire_of(type) >= 0) {
         die(flag + " is for --src-type yuv420: " + type + " sources are not resampled yet");
     }
@@ -1174,7 +1227,7 @@ HashManifest read_manifest(const std::string& path)
     m.src_type = h[4];
     m.depth = static_cast<int>(v[0]); m.W = static_cast<int>(v[1]); m.H = static_cast<int>(v[2]);
     // one segment: the packed pixels (RGB; uyvy, yuy2, v210); two: Y and the interleaved chroma
-    const bool packed = m.src_type == "rgb24" || m.src_type == "png" || m.src_type == "uyvy" || m.src_type == "yuy2" || m.src_type == "v210";
+    const bool packed = is_rgb_name(m.src_type) || m.src_type == "uyvy" || m.src_type == "yuy2" || m.src_type == "v210";
     const bool semi = m.src_type == "nv12" || m.src_type == "nv21" || m.src_type == "nv16";
     const size_t planes = packed ? 1 : semi ? 2 : 3;
     if (!packed && !semi && m.src_type != "yuv420" && m.src_type != "yuv422" && m.src_type != "yuv444") {
@@ -1337,7 +1390,11 @@ struct HashRun {
 void x_hat_to_picture(const Geometry& g, const DeviceBuffers& b, const char* xh, bool samples)
 {
     char* y16 = static_cast<char*>(b.y16);
-    if (g.rgb) {
+    if (g.rgb16()) {
+        // fp32 [3][H][W] (the distortion planes) in y16, the writer's packed u16 pixels in out8
+        abi_ok(dcvc_x_to_rgb16_cs(xh, g.Wp, g.H, g.W, g.bit_depth, y16, samples ? b.out8 : nullptr, g.matrix, g.range, g.yuv_depth, b.st),
+               "x_to_rgb16_cs");
+    } else if (g.rgb) {
         // rgb16 [3][H][W] fp16 (the distortion planes) in y16, the writer's packed u8 pixels in out8
         abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, y16, samples ? b.out8 : nullptr, g.matrix, g.range, g.yuv_depth, b.st), "x_to_rgb_cs");
     } else if (g.pix() || g.hbd()) {
@@ -1358,8 +1415,8 @@ struct PictureQuality {
 };
 
 struct QualityMeter {
-    uint8_t* src = nullptr;        // per slot: the source picture as planar samples (RGB: u8 [3][H][W]; YUV: Y, Cb, Cr planes)
-    void* dist = nullptr;          // the reconstruction's distortion planes: fp16 [3][H][W] (RGB), fp32 [H][W] + [2][Hc][Wc] (YUV)
+    uint8_t* src = nullptr;        // per slot: the source picture as planar samples (RGB: u8 or u16 [3][H][W]; YUV: Y, Cb, Cr planes)
+    void* dist = nullptr;          // the reconstruction's distortion planes: fp16 (8-bit RGB) or fp32 [3][H][W], fp32 [H][W] + [2][Hc][Wc] (YUV)
     double* sse = nullptr;
     double* h_sse = nullptr;       // pinned
     void* ws = nullptr;
@@ -1367,7 +1424,7 @@ struct QualityMeter {
     void create(const Geometry& g, int slots)
     {
         hip_ok(hipMalloc(&src, g.frame_bytes() * static_cast<size_t>(slots)), "hipMalloc");
-        hip_ok(hipMalloc(&dist, g.rgb ? g.y_bytes() * 6 : (g.y_bytes() + g.uv_bytes()) * 4), "hipMalloc");
+        hip_ok(hipMalloc(&dist, g.rgb16() ? g.y_bytes() * 12 : g.rgb ? g.y_bytes() * 6 : (g.y_bytes() + g.uv_bytes()) * 4), "hipMalloc");
         hip_ok(hipMalloc(&sse, 3 * sizeof(double)), "hipMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
         ws_bytes = g.rgb ? dcvc_sse_workspace_bytes(3, g.H, g.W)
@@ -1378,7 +1435,10 @@ struct QualityMeter {
     void capture(const Geometry& g, const DeviceBuffers& b, int slot)
     {
         uint8_t* dst = src + g.frame_bytes() * static_cast<size_t>(slot);
-        if (g.rgb) {
+        if (g.rgb16()) {
+            abi_ok(dcvc_rgb16_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.bit_depth, g.H, g.W, nullptr, 3, dst, g.matrix, g.range, g.yuv_depth, b.st),
+                   "rgb16_to_x_cs (planar source)");
+        } else if (g.rgb) {
             abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, nullptr, 3, dst, g.matrix, g.range, g.yuv_depth, b.st),
                    "rgb_to_x_cs (planar source)");
         } else if (g.pix()) {
@@ -1392,6 +1452,16 @@ struct QualityMeter {
     {
         const uint8_t* s = src + g.frame_bytes() * static_cast<size_t>(slot);
         PictureQuality q;
+        if (g.rgb16()) {
+            const size_t plane = g.y_bytes();
+            abi_ok(dcvc_x_to_rgb16_cs(xh, g.Wp, g.H, g.W, g.bit_depth, dist, nullptr, g.matrix, g.range, g.yuv_depth, st), "x_to_rgb16_cs");
+            abi_ok(dcvc_sse_ws(s, DCVC_SAMPLE_U16, dist, DCVC_SAMPLE_F32, 3, g.H, g.W, g.W, static_cast<long long>(plane), sse, ws, ws_bytes, st),
+                   "sse");
+            hip_ok(hipMemcpyAsync(h_sse, sse, 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            q.psnr = psnr_of_sse((h_sse[0] + h_sse[1]) + h_sse[2], 3.0 * static_cast<double>(plane), static_cast<double>((1 << g.bit_depth) - 1));
+            return q;
+        }
         if (g.rgb) {
             const size_t plane = g.y_bytes();
             abi_ok(dcvc_x_to_rgb_cs(xh, g.Wp, g.H, g.W, dist, nullptr, g.matrix, g.range, g.yuv_depth, st), "x_to_rgb_cs");
@@ -1475,6 +1545,7 @@ int encode(const Args& a)
     int depth = bit_depth_arg(a, type);
     const SizeArg scale = size_arg(a, "scale");
     const int wire = wire_arg(a, true);
+    rgb16_arg(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
@@ -1487,17 +1558,18 @@ int encode(const Args& a)
             die(std::string("--scale is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
         }
     }
-    const bool rgb = type == SrcType::Rgb24 || type == SrcType::Png;
+    const bool rgb = is_rgb(type);
     PngDir pngs;
-    if (type == SrcType::Png) {
+    if (is_png(type)) {
         // the size of the first picture; -W / -H, when given, must agree with it
         pngs = png_dir(a.str("i"));
-        abi_ok(dcvc_png_info(pngs.path(1).c_str(), &pic_w, &pic_h), "png info");
+        if (type == SrcType::Png16) png16_info(pngs.path(1), pic_w, pic_h);
+        else abi_ok(dcvc_png_info(pngs.path(1).c_str(), &pic_w, &pic_h), "png info");
         if ((a.has("W") && a.num("W", 0) != pic_w) || (a.has("H") && a.num("H", 0) != pic_h)) {
             die(pngs.path(1) + " is " + std::to_string(pic_w) + "x" + std::to_string(pic_h) + ", not the -W x -H given");
         }
     } else if (rgb && (!a.has("W") || !a.has("H"))) {
-        die("--src-type rgb24 needs -W and -H");
+        die(std::string("--src-type ") + src_type_name(type) + " needs -W and -H");
     }
     // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
     Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type), wire);
@@ -1519,7 +1591,7 @@ int encode(const Args& a)
     const int delay = c.frames_per_p;
     if (intra_period > 1 && intra_period % delay != 0) die("intra period must be a multiple of the chunk size");
     long long total = 0;
-    if (type == SrcType::Png) {
+    if (is_png(type)) {
         total = pngs.count();
     } else {
         if (!src_file.f) src_file.open(a.str("i"));
@@ -1575,7 +1647,7 @@ int encode(const Args& a)
             ws.upload(g, b.yuv8, b.st);
             return;
         }
-        if (type == SrcType::Png) {
+        if (is_png(type)) {
             if (!pngs.read(b.h_yuv, g)) die("short read");
         } else if (!src_file.read(b.h_yuv, g.frame_bytes())) {
             die("short read");
@@ -1585,7 +1657,10 @@ int encode(const Args& a)
     // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
     int luma_turn = 0;
     auto convert = [&](char* dst, int ldx, bool measure = false, bool has_prev = false) {
-        if (rgb) {
+        if (g.rgb16()) {
+            abi_ok(dcvc_rgb16_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.bit_depth, g.H, g.W, dst, ldx, nullptr, g.matrix, g.range, g.yuv_depth, b.st),
+                   "rgb16_to_x_cs");
+        } else if (rgb) {
             abi_ok(dcvc_rgb_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.H, g.W, dst, ldx, nullptr, g.matrix, g.range, g.yuv_depth, b.st), "rgb_to_x_cs");
         } else {
             abi_ok(dcvc_pix_to_x(b.yuv8, g.yuv_fmt(), g.bit_depth, g.H, g.W, dst, ldx, nullptr, b.st), "pix_to_x");
@@ -2026,10 +2101,11 @@ int decode(const Args& a)
     HashRun hash;
     hash.parse(a, false);
     const int wire = wire_arg(a, false);
+    rgb16_arg(a, false);
     if (rec_y4m) {
         const std::string t = a.str("src-type");
         if (t == "nv12" || t == "p010") die("-o " + a.str("o") + ": Y4M has no tag for interleaved chroma (--src-type " + t + "); write a raw file");
-        if (t == "rgb24" || t == "png") die("-o " + a.str("o") + ": a Y4M file holds YUV pictures, not --src-type " + t);
+        if (is_rgb_name(t)) die("-o " + a.str("o") + ": a Y4M file holds YUV pictures, not --src-type " + t);
     }
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
     std::vector<uint8_t> bin;
@@ -2043,7 +2119,7 @@ int decode(const Args& a)
     SrcType type = src_type(a.str("src-type", "yuv420"));
     int depth = bit_depth_arg(a, type);
     const bool has_rec = a.has("o"), has_ref = a.has("ref");
-    const bool png = type == SrcType::Png;
+    const bool png = is_png(type);
     // raw or Y4M files (the YUV types, rgb24), or directories of PNG pictures. --ref *.y4m: its header supplies the source
     // type and the bit depth when the flags do not, and must agree with them when they do
     PictureFile ref_file;
@@ -2055,7 +2131,7 @@ int decode(const Args& a)
             if (!has_fps) { fps_num = ref_file.info.fps_num; fps_den = ref_file.info.fps_den; }
         }
     }
-    const bool rgb = type == SrcType::Rgb24 || type == SrcType::Png;
+    const bool rgb = is_rgb(type);
     const int pix_fmt = pix_fmt_of(type);
     if (out_size.on && pix_fmt >= 0) {
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
@@ -2298,14 +2374,38 @@ int decode(const Args& a)
             } else if (has_rec) {
                 hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
-                if (png) {
+                if (png && g.rgb16()) {
+                    abi_ok(dcvc_png_write_rgb16(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
+                } else if (png) {
                     abi_ok(dcvc_png_write_rgb(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
                 } else {
                     rec_frame(g);
                     if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) die("short write");
                 }
             }
-            if (has_ref && rgb) {
+            if (has_ref && g.rgb16()) {
+                // the RGB branch below at 9..16 bits: the source's planar u16 copy against the fp32 planes, data range max_val;
+                // MS-SSIM plane by plane on the tool's own workspace
+                const size_t plane = g.y_bytes();
+                const double peak = static_cast<double>((1 << g.bit_depth) - 1);
+                hip_ok(hipMemcpyAsync(b.yuv8, b.h_src, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                abi_ok(dcvc_rgb16_to_x_cs(b.yuv8, 3LL * g.W, 3, 1, g.bit_depth, g.H, g.W, nullptr, 3, b.src8, g.matrix, g.range, g.yuv_depth,
+                                          b.st), "rgb16_to_x_cs (planar source)");
+                abi_ok(dcvc_sse_ws(b.src8, DCVC_SAMPLE_U16, y16, DCVC_SAMPLE_F32, 3, g.H, g.W, g.W, static_cast<long long>(plane), b.sse,
+                                   b.sse_ws, b.sse_ws_bytes, b.st), "sse");
+                hip_ok(hipMemcpyAsync(b.h_sse, b.sse, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (calc_ssim) {
+                    for (size_t q = 0; q < 3; ++q) {
+                        abi_ok(dcvc_msssim_range_ws(b.src8 + q * plane * 2, DCVC_SAMPLE_U16, y16 + q * plane * 4, DCVC_SAMPLE_F32, 1, g.H, g.W,
+                                                    g.W, static_cast<long long>(plane), peak, b.ssim + q, b.ssim_ws, b.ssim_ws_bytes, b.st),
+                               "msssim (R, G, B)");
+                    }
+                    hip_ok(hipMemcpyAsync(b.h_ssim, b.ssim, 3 * sizeof(double), hipMemcpyDeviceToHost, b.st), "D2H");
+                }
+                hip_ok(hipStreamSynchronize(b.st), "sync");
+                psnr.push_back(psnr_of_sse((b.h_sse[0] + b.h_sse[1]) + b.h_sse[2], 3.0 * static_cast<double>(plane), peak));
+                if (calc_ssim) ssim.push_back(((0.0 + b.h_ssim[0]) + b.h_ssim[1] + b.h_ssim[2]) / 3);
+            } else if (has_ref && rgb) {
                 // get_distortion (png branch): calc_psnr over the 3 H W samples from the device's sums of squares; the
                 // source's planar copy next to the fp16 planes for dcvc_sse and dcvc_msssim
                 // (the copy leaves from pinned memory, and the workspace is the tool's own: nothing in this loop depends on

@@ -1,4 +1,5 @@
-// png.cpp - PNG <-> packed RGB24 on the host (include/dcvc_amd_image.h), with zlib for the deflate stream.
+// png.cpp - PNG <-> packed RGB24, and 16-bit PNG <-> packed u16 RGB (rgb48), on the host (include/dcvc_amd_image.h), with zlib
+// for the deflate stream.
 //
 // The reference's PNGReader / PNGWriter (src/utils/video_reader.py:10-45, video_writer.py:9-30) go through PIL:
 // Image.open(path).convert('RGB') and Image.fromarray(rgb).save(path). The contract kept here is pixel equality with
@@ -67,8 +68,9 @@ int channels_of(int colour)
     }
 }
 
-// signature + IHDR (the first chunk, CRC checked); refuses what the reader does not decode
-Header parse_header(const std::string& path, const std::vector<uint8_t>& d)
+// signature + IHDR (the first chunk, CRC checked); refuses what the reader does not decode. want_depth: 8 (the RGB24 entry
+// points), 16 (the rgb48 ones) or 0 (either: dcvc_png_info2)
+Header parse_header(const std::string& path, const std::vector<uint8_t>& d, int want_depth = 8)
 {
     if (d.size() < 8 || std::memcmp(d.data(), kSignature, 8) != 0) fail(path, "not a PNG file");
     if (d.size() < 8 + 8 + 13 + 4) fail(path, "truncated (header)");
@@ -85,7 +87,10 @@ Header parse_header(const std::string& path, const std::vector<uint8_t>& d)
     }
     hd.width = static_cast<int>(w); hd.height = static_cast<int>(h);
     if (channels_of(hd.colour) == 0) fail(path, "unknown colour type " + std::to_string(hd.colour));
-    if (hd.depth != 8) fail(path, "bit depth " + std::to_string(hd.depth) + " is not supported (8-bit PNG only)");
+    if (want_depth == 8 && hd.depth != 8) fail(path, "bit depth " + std::to_string(hd.depth) + " is not supported (8-bit PNG only)");
+    if (want_depth == 16 && hd.depth != 16) fail(path, "bit depth " + std::to_string(hd.depth) + " is not supported (16-bit PNG only)");
+    if (want_depth == 0 && hd.depth != 8 && hd.depth != 16) fail(path, "bit depth " + std::to_string(hd.depth) + " is not supported (8- or 16-bit PNG)");
+    if (hd.depth == 16 && hd.colour == 3) fail(path, "a palette picture cannot have bit depth 16");
     if (p[10] != 0 || p[11] != 0) fail(path, "unknown compression or filter method");
     if (hd.interlace != 0) fail(path, "interlaced PNG is not supported");
     return hd;
@@ -97,13 +102,16 @@ uint8_t paeth(int a, int b, int c)
     return static_cast<uint8_t>(pa <= pb && pa <= pc ? a : (pb <= pc ? b : c));
 }
 
-void decode(const std::string& path, uint8_t* rgb, size_t capacity, int* width, int* height)
+// depth 8: rgb is packed u8; depth 16: packed native u16 (the file's samples are big-endian)
+void decode(const std::string& path, uint8_t* rgb, size_t capacity, int* width, int* height, int depth = 8)
 {
     const std::vector<uint8_t> d = read_file(path, 0);
-    const Header hd = parse_header(path, d);
+    const Header hd = parse_header(path, d, depth);
     const size_t W = static_cast<size_t>(hd.width), H = static_cast<size_t>(hd.height);
-    if (W * H * 3 > capacity) fail(path, "picture " + std::to_string(W) + "x" + std::to_string(H) + " does not fit the buffer");
-    const int ch = channels_of(hd.colour);
+    const size_t bs = depth == 16 ? 2 : 1;          // bytes per sample
+    if (W * H * 3 * bs > capacity) fail(path, "picture " + std::to_string(W) + "x" + std::to_string(H) + " does not fit the buffer");
+    const int chans = channels_of(hd.colour);
+    const int ch = chans * static_cast<int>(bs);    // the filter unit: bytes per pixel (2, 4, 6 or 8 at 16 bits)
     std::vector<uint8_t> idat, plte;
     bool ended = false;
     size_t pos = 8;
@@ -132,7 +140,7 @@ void decode(const std::string& path, uint8_t* rgb, size_t capacity, int* width, 
     }
     if (idat.empty()) fail(path, "no image data");
     if (hd.colour == 3 && plte.empty()) fail(path, "palette picture without PLTE");
-    // inflate into the filtered rows: exactly H * (1 + W * ch) bytes
+    // inflate into the filtered rows: exactly H * (1 + W * ch) bytes, ch bytes per pixel
     const size_t stride = W * ch, raw_bytes = H * (1 + stride);
     std::vector<uint8_t> raw(raw_bytes);
     if (idat.size() > 0xffffffffu || raw_bytes > 0xffffffffu) fail(path, "image data too large");
@@ -170,6 +178,19 @@ void decode(const std::string& path, uint8_t* rgb, size_t capacity, int* width, 
         default: fail(path, "unknown row filter " + std::to_string(f) + " in row " + std::to_string(y));
         }
         prev = cur;
+        if (depth == 16) {
+            // grey is replicated and alpha dropped, as at 8 bits; big-endian samples -> native u16
+            uint16_t* o16 = reinterpret_cast<uint16_t*>(rgb) + y * W * 3;
+            const bool grey = chans < 3;
+            for (size_t x = 0; x < W; ++x) {
+                const uint8_t* px = cur + x * static_cast<size_t>(ch);
+                for (int q = 0; q < 3; ++q) {
+                    const uint8_t* sp = px + (grey ? 0 : 2 * q);
+                    o16[3 * x + static_cast<size_t>(q)] = static_cast<uint16_t>((sp[0] << 8) | sp[1]);
+                }
+            }
+            continue;
+        }
         uint8_t* o = rgb + y * W * 3;
         switch (hd.colour) {
         case 2: std::memcpy(o, cur, stride); break;
@@ -230,6 +251,41 @@ void encode(const std::string& path, const uint8_t* rgb, int width, int height)
     if (fclose(f) != 0 || !ok) fail(path, "write error");
 }
 
+// colour type 2, 16 bits: big-endian samples, filter 1 (Sub) on every row with the 6-byte pixel as its unit
+void encode16(const std::string& path, const uint16_t* rgb, int width, int height)
+{
+    if (width <= 0 || height <= 0 || width > DCVC_PNG_MAX_SIDE || height > DCVC_PNG_MAX_SIDE) {
+        fail(path, "picture size " + std::to_string(width) + "x" + std::to_string(height) + " out of range");
+    }
+    if (rgb == nullptr) fail(path, "no pixels");
+    const size_t W = static_cast<size_t>(width), H = static_cast<size_t>(height), stride = 6 * W;
+    std::vector<uint8_t> raw(H * (1 + stride)), line(stride);
+    for (size_t y = 0; y < H; ++y) {
+        const uint16_t* s = rgb + y * 3 * W;
+        for (size_t i = 0; i < 3 * W; ++i) { line[2 * i] = uint8_t(s[i] >> 8); line[2 * i + 1] = uint8_t(s[i]); }
+        uint8_t* o = raw.data() + y * (1 + stride);
+        o[0] = 1;
+        for (size_t i = 0; i < 6; ++i) o[1 + i] = line[i];
+        for (size_t i = 6; i < stride; ++i) o[1 + i] = uint8_t(line[i] - line[i - 6]);
+    }
+    if (raw.size() > 0xffffffffu) fail(path, "image data too large");
+    uLongf zlen = compressBound(static_cast<uLong>(raw.size()));
+    std::vector<uint8_t> z(zlen);
+    if (compress2(z.data(), &zlen, raw.data(), static_cast<uLong>(raw.size()), DCVC_PNG_ZLIB_LEVEL) != Z_OK) fail(path, "deflate failed");
+    std::vector<uint8_t> out(kSignature, kSignature + 8);
+    uint8_t ihdr[13] = {};
+    for (int k = 0; k < 4; ++k) { ihdr[k] = uint8_t(W >> (24 - 8 * k)); ihdr[4 + k] = uint8_t(H >> (24 - 8 * k)); }
+    ihdr[8] = 16; ihdr[9] = 2;
+    out.reserve(zlen + 64);
+    put_chunk(out, "IHDR", ihdr, 13);
+    put_chunk(out, "IDAT", z.data(), zlen);
+    put_chunk(out, "IEND", nullptr, 0);
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) fail(path, "cannot write");
+    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (fclose(f) != 0 || !ok) fail(path, "write error");
+}
+
 }  // namespace
 
 extern "C" {
@@ -257,6 +313,35 @@ int dcvc_png_write_rgb(const char* path, const void* rgb, int width, int height)
     return dcvc::guarded([&] {
         if (path == nullptr) throw std::invalid_argument("png_write_rgb: null path");
         encode(path, static_cast<const uint8_t*>(rgb), width, height);
+    });
+}
+
+int dcvc_png_info2(const char* path, int* width, int* height, int* bit_depth)
+{
+    return dcvc::guarded([&] {
+        if (path == nullptr || width == nullptr || height == nullptr || bit_depth == nullptr) throw std::invalid_argument("png_info2: null argument");
+        const Header hd = parse_header(path, read_file(path, 8 + 8 + 13 + 4), 0);
+        *width = hd.width;
+        *height = hd.height;
+        *bit_depth = hd.depth;
+    });
+}
+
+int dcvc_png_read_rgb16(const char* path, void* rgb16, size_t capacity, int* width, int* height)
+{
+    return dcvc::guarded([&] {
+        if (path == nullptr || rgb16 == nullptr || width == nullptr || height == nullptr) throw std::invalid_argument("png_read_rgb16: null argument");
+        if (reinterpret_cast<uintptr_t>(rgb16) & 1) throw std::invalid_argument("png_read_rgb16: the pixel buffer must be 2-byte aligned");
+        decode(path, static_cast<uint8_t*>(rgb16), capacity, width, height, 16);
+    });
+}
+
+int dcvc_png_write_rgb16(const char* path, const void* rgb16, int width, int height)
+{
+    return dcvc::guarded([&] {
+        if (path == nullptr) throw std::invalid_argument("png_write_rgb16: null path");
+        if (reinterpret_cast<uintptr_t>(rgb16) & 1) throw std::invalid_argument("png_write_rgb16: the pixel buffer must be 2-byte aligned");
+        encode16(path, static_cast<const uint16_t*>(rgb16), width, height);
     });
 }
 

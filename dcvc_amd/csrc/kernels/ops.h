@@ -340,6 +340,21 @@ struct ColourSpace {
 };
 void rgb_to_x_cs(const RgbToXDesc& d, const ColourSpace& cs, hipStream_t stream);
 void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream);
+// 9..16-bit RGB: u16 samples, LSB-aligned in 0..max_val = 2^bit_depth - 1, strides in samples; the unit value
+// is fp32(v) / fp32(max_val), a correctly rounded division, and from there on the 8-bit conversion. planar: u16 [3][H][W].
+struct Rgb16ToXDesc {
+    const uint16_t* src = nullptr;
+    long long row_stride = 0, pixel_stride = 0, channel_stride = 0;
+    int bit_depth = 16;
+    int H = 0, W = 0;
+    half_t* x = nullptr; int ldx = 3;
+    uint16_t* planar = nullptr;
+};
+void rgb16_to_x_cs(const Rgb16ToXDesc& d, const ColourSpace& cs, hipStream_t stream);
+// x_hat -> dist32: planar fp32 [3][H][W] = clamp(fp32(fp16(clamp(rgb, 0, 1))) * max_val, 0, max_val), the distortion planes,
+// and / or rgb16u: packed u16 [H][W][3] = rint of those (half to even, NaN -> 0). One of the two may be null, not both.
+void x_to_rgb16_cs(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist32, uint16_t* rgb16u, const ColourSpace& cs,
+                   hipStream_t stream);
 
 // ---------------------------------------------------------------- SSE (sse.hip)
 // metrics.py:10-24's fp64 sum of squared differences of n_planes pairs of H x W planes (u8, fp16, u16 or fp32 samples; src and rec share

@@ -21,6 +21,12 @@
 // HBM-bound passes, one thread per 8 pixels of a row. A template switch picks 8- / 16-byte accesses where the layout
 // allows them (packed HWC or planar CHW u8 input, packed x at ldx == 3, rows of a multiple of 8 pixels, aligned bases)
 // and element accesses elsewhere (the slots of an 8-picture chunk at ldx = 24, odd-multiple-of-2 widths).
+//
+// 9..16-bit RGB (u16 samples, LSB-aligned, max_val = 2^b - 1) goes through a second kernel pair behind
+// rgb16_to_x_cs / x_to_rgb16_cs with the same constants and the same per-pixel matrix code: to x, c = fp32(v) / fp32(max_val)
+// is a correctly rounded division, as the 16-bit YUV reader's; from x, the distortion planes are fp32,
+// clamp(fp32(t) * max_val, 0, max_val) with t = fp16(clamp(rgb, 0, 1)), as fp16 cannot hold a 10-bit sample, and the written
+// sample is rint of that. The accesses are 16 bytes wide where the 8-bit pair's are 8.
 #include "arith.h"
 #include "picture_io.h"
 
@@ -62,11 +68,10 @@ ColourConsts colour_consts(const ColourSpace& cs)
 // torch.clamp: NaN passes through
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// one RGB pixel -> the three fp16 channels of x
+// one RGB pixel on the unit scale (sample / max_val) -> the three fp16 channels of x
 template <bool LIMITED>
-__device__ __forceinline__ void pixel_to_x(const ColourConsts& k, unsigned r8, unsigned g8, unsigned b8, half_t* o)
+__device__ __forceinline__ void unit_to_x(const ColourConsts& k, float r, float g, float b, half_t* o)
 {
-    const float r = static_cast<float>(r8) * kInv255, g = static_cast<float>(g8) * kInv255, b = static_cast<float>(b8) * kInv255;
     float y = (k.kr * r + k.kg * g) + k.kb * b;
     const float pb = (0.5f * (b - y)) * k.inv_1mkb;
     const float pr = (0.5f * (r - y)) * k.inv_1mkr;
@@ -82,6 +87,20 @@ __device__ __forceinline__ void pixel_to_x(const ColourConsts& k, unsigned r8, u
     o[0] = to_half(static_cast<float>(to_half(clampf(y, 0.f, 1.f))) - 0.5f);
     o[1] = to_half(static_cast<float>(to_half(clampf(cb, 0.f, 1.f))) - 0.5f);
     o[2] = to_half(static_cast<float>(to_half(clampf(cr, 0.f, 1.f))) - 0.5f);
+}
+
+// 8 bits: x.float() / 255.0 is a multiply by the fp32 reciprocal
+template <bool LIMITED>
+__device__ __forceinline__ void pixel_to_x(const ColourConsts& k, unsigned r8, unsigned g8, unsigned b8, half_t* o)
+{
+    unit_to_x<LIMITED>(k, static_cast<float>(r8) * kInv255, static_cast<float>(g8) * kInv255, static_cast<float>(b8) * kInv255, o);
+}
+
+// 9..16 bits: a true division, correctly rounded (the library builds with -fno-fast-math), as the 16-bit YUV reader's
+template <bool LIMITED>
+__device__ __forceinline__ void pixel16_to_x(const ColourConsts& k, float maxv, unsigned r, unsigned g, unsigned b, half_t* o)
+{
+    unit_to_x<LIMITED>(k, static_cast<float>(r) / maxv, static_cast<float>(g) / maxv, static_cast<float>(b) / maxv, o);
 }
 
 // load modes of rgb_to_x
@@ -148,9 +167,9 @@ __global__ void __launch_bounds__(kThreads) rgb_to_x_kernel(const uint8_t* __res
     }
 }
 
-// one pixel of x_hat -> the three fp16 distortion samples (0..255)
+// one pixel of x_hat -> t = fp16(clamp(rgb, 0, 1)) of its three channels
 template <bool LIMITED>
-__device__ __forceinline__ void x_to_pixel(const ColourConsts& k, const half_t* p, half_t* o)
+__device__ __forceinline__ void x_to_unit(const ColourConsts& k, const half_t* p, half_t* t)
 {
     float y = static_cast<float>(to_half(static_cast<float>(p[0]) + 0.5f));              // x_hat + 0.5 (fp16)
     const float cb = static_cast<float>(to_half(static_cast<float>(p[1]) + 0.5f));
@@ -167,13 +186,32 @@ __device__ __forceinline__ void x_to_pixel(const ColourConsts& k, const half_t* 
     const float r = y + k.c2m2kr * pr;
     const float b = y + k.c2m2kb * pb;
     const float g = ((y - k.kr * r) - k.kb * b) * k.inv_kg;
-    const float rgb[3] = {r, g, b};
+    t[0] = to_half(clampf(r, 0.f, 1.f));                                                     // .to(fp16)
+    t[1] = to_half(clampf(g, 0.f, 1.f));
+    t[2] = to_half(clampf(b, 0.f, 1.f));
+}
+
+// one pixel of x_hat -> the three fp16 distortion samples (0..255)
+template <bool LIMITED>
+__device__ __forceinline__ void x_to_pixel(const ColourConsts& k, const half_t* p, half_t* o)
+{
+    half_t t[3];
+    x_to_unit<LIMITED>(k, p, t);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-        const half_t t = to_half(clampf(rgb[q], 0.f, 1.f));                                  // .to(fp16)
-        const float s = static_cast<float>(to_half(static_cast<float>(t) * 255.0f));           // * 255 (fp16)
+        const float s = static_cast<float>(to_half(static_cast<float>(t[q]) * 255.0f));        // * 255 (fp16)
         o[q] = to_half(clampf(s, 0.f, 255.f));                                                  // clamp(0, 255), exact
     }
+}
+
+// 9..16 bits: the three fp32 distortion samples (0..max_val)
+template <bool LIMITED>
+__device__ __forceinline__ void x_to_pixel16(const ColourConsts& k, float maxv, const half_t* p, float* o)
+{
+    half_t t[3];
+    x_to_unit<LIMITED>(k, p, t);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) o[q] = clampf(static_cast<float>(t[q]) * maxv, 0.f, maxv);
 }
 
 // .round().byte(): half to even (the samples are in 0..255; NaN, which no clamp removes, is written as 0)
@@ -236,6 +274,130 @@ __global__ void __launch_bounds__(kThreads) x_to_rgb_kernel(const half_t* __rest
     }
 }
 
+// ---------------------------------------------------------------- 9..16 bits
+// one thread = 8 consecutive pixels of a row of u16 samples. LOAD: kLoadPacked (3 x 16-B loads), kLoadPlanar (one 16-B load
+// per channel) or kLoadScalar (any strides, element by element). VEC_X: x at ldx == 3, 3 x 16-B stores. Vector modes need
+// W % 8 == 0 and 16-byte aligned rows (checked by the host); the planar copy then goes out in one 16-B store per channel.
+template <int LOAD, bool VEC_X, bool LIMITED>
+__global__ void __launch_bounds__(kThreads) rgb16_to_x_kernel(const uint16_t* __restrict__ src, long long rs, long long ps,
+                                                                 long long cs, int H, int W, half_t* __restrict__ x, int ldx,
+                                                                 uint16_t* __restrict__ planar, const ColourConsts k, float maxv)
+{
+    const unsigned wv = (W + 7) >> 3;
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (picture_validate)
+    if (i >= static_cast<unsigned>(H) * wv) return;
+    const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
+    const uint16_t* row = src + h * rs + w0 * ps;
+    const size_t plane = static_cast<size_t>(H) * W, o = static_cast<size_t>(h) * W + w0;
+    if constexpr (LOAD == kLoadScalar) {
+        const int n = min(8, W - w0);
+        for (int e = 0; e < n; ++e) {
+            const unsigned r = row[e * ps], g = row[e * ps + cs], b = row[e * ps + 2 * cs];
+            if (planar) {
+                planar[o + e] = static_cast<uint16_t>(r);
+                planar[plane + o + e] = static_cast<uint16_t>(g);
+                planar[2 * plane + o + e] = static_cast<uint16_t>(b);
+            }
+            if (x) pixel16_to_x<LIMITED>(k, maxv, r, g, b, x + (o + e) * ldx);
+        }
+    } else {
+        uint4 c[3];                                                // c[q]: the 8 samples of channel q
+        uint16_t* cw = reinterpret_cast<uint16_t*>(c);
+        if constexpr (LOAD == kLoadPacked) {
+            uint4 v[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) v[q] = reinterpret_cast<const uint4*>(row)[q];
+            const uint16_t* s = reinterpret_cast<const uint16_t*>(v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) cw[q * 8 + e] = s[3 * e + q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) c[q] = *reinterpret_cast<const uint4*>(row + q * cs);
+        }
+        if (planar) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<uint4*>(planar + q * plane + o) = c[q];
+        }
+        if (x) {
+            half_t* xo = x + o * ldx;
+            if constexpr (VEC_X) {
+                half8 v[3];
+                half_t* hv = reinterpret_cast<half_t*>(v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) pixel16_to_x<LIMITED>(k, maxv, cw[e], cw[8 + e], cw[16 + e], hv + 3 * e);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) reinterpret_cast<half8*>(xo)[q] = v[q];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) pixel16_to_x<LIMITED>(k, maxv, cw[e], cw[8 + e], cw[16 + e], xo + e * ldx);
+            }
+        }
+    }
+}
+
+// .round() to u16: half to even (the samples are in 0..max_val; NaN, which no clamp removes, is written as 0)
+__device__ __forceinline__ uint16_t to_u16(float f) { return f == f ? static_cast<uint16_t>(rintf(f)) : 0; }
+
+// one thread = 8 consecutive pixels of a row. VEC: row_pixels % 8 == 0, W % 8 == 0, aligned bases: 3 x 16-B loads, two 16-B
+// stores per fp32 plane, 3 x 16-B stores of packed u16.
+template <bool VEC, bool LIMITED>
+__global__ void __launch_bounds__(kThreads) x_to_rgb16_kernel(const half_t* __restrict__ x, int row_pixels, int H, int W,
+                                                                 float* __restrict__ dist, uint16_t* __restrict__ out,
+                                                                 const ColourConsts k, float maxv)
+{
+    const unsigned wv = (W + 7) >> 3;
+    const unsigned i = blockIdx.x * kThreads + threadIdx.x;      // < 2^31 (picture_validate)
+    if (i >= static_cast<unsigned>(H) * wv) return;
+    const int h = static_cast<int>(i / wv), w0 = static_cast<int>(i - h * wv) * 8;
+    const half_t* p = x + (static_cast<size_t>(h) * row_pixels + w0) * 3;
+    const size_t plane = static_cast<size_t>(H) * W, o = static_cast<size_t>(h) * W + w0;
+    if constexpr (VEC) {
+        half8 in[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) in[q] = reinterpret_cast<const half8*>(p)[q];
+        const half_t* hin = reinterpret_cast<const half_t*>(in);
+        float4 d[3][2];                                            // d[q]: the 8 distortion samples of channel q
+        float* df = reinterpret_cast<float*>(d);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float t[3];
+            x_to_pixel16<LIMITED>(k, maxv, hin + 3 * e, t);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) df[q * 8 + e] = t[q];
+        }
+        if (dist) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                reinterpret_cast<float4*>(dist + q * plane + o)[0] = d[q][0];
+                reinterpret_cast<float4*>(dist + q * plane + o)[1] = d[q][1];
+            }
+        }
+        if (out) {
+            uint4 v[3];
+            uint16_t* s = reinterpret_cast<uint16_t*>(v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) s[3 * e + q] = to_u16(df[q * 8 + e]);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) reinterpret_cast<uint4*>(out + o * 3)[q] = v[q];
+        }
+    } else {
+        const int n = min(8, W - w0);
+        for (int e = 0; e < n; ++e) {
+            float t[3];
+            x_to_pixel16<LIMITED>(k, maxv, p + 3 * e, t);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                if (dist) dist[q * plane + o + e] = t[q];
+                if (out) out[(o + e) * 3 + q] = to_u16(t[q]);
+            }
+        }
+    }
+}
+
 void colour_validate(const ColourSpace& cs, const char* what)
 {
     if (cs.matrix != kMatrixBt601 && cs.matrix != kMatrixBt709 && cs.matrix != kMatrixBt2020) {
@@ -263,7 +425,8 @@ void launch_to_x(const RgbToXDesc& d, bool limited, const ColourConsts& k, hipSt
 }
 
 // the three (stride, extent) pairs must not overlap: sorted by stride, each stride covers the previous dimension
-void stride_check(const RgbToXDesc& d, const std::string& what)
+template <typename Desc>
+void stride_check(const Desc& d, const std::string& what)
 {
     long long st[3] = {d.channel_stride, d.pixel_stride, d.row_stride}, ex[3] = {3, d.W, d.H};
     for (int q = 0; q < 3; ++q) {
@@ -323,6 +486,74 @@ void from_x(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_
     hip_check(hipGetLastError(), (what + " launch").c_str());
 }
 
+float depth_max_val(int bit_depth, const std::string& what)
+{
+    if (bit_depth < 9 || bit_depth > 16) {
+        throw std::invalid_argument(what + ": the bit depth must be in 9..16 (8-bit pictures go through the u8 entry points), got " +
+                                    std::to_string(bit_depth));
+    }
+    return static_cast<float>((1 << bit_depth) - 1);      // exact in fp32
+}
+
+template <int LOAD, bool VEC_X>
+void launch_to_x16(const Rgb16ToXDesc& d, bool limited, const ColourConsts& k, float maxv, hipStream_t stream)
+{
+    const dim3 grid(grid_of(d.H, d.W)), block(kThreads);
+    if (limited) {
+        hipLaunchKernelGGL((rgb16_to_x_kernel<LOAD, VEC_X, true>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+                           d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k, maxv);
+    } else {
+        hipLaunchKernelGGL((rgb16_to_x_kernel<LOAD, VEC_X, false>), grid, block, 0, stream, d.src, d.row_stride, d.pixel_stride,
+                           d.channel_stride, d.H, d.W, d.x, d.ldx, d.planar, k, maxv);
+    }
+}
+
+void to_x16(const Rgb16ToXDesc& d, const ColourSpace& cs, const std::string& what, hipStream_t stream)
+{
+    picture_validate(d.H, d.W, what.c_str());
+    const float maxv = depth_max_val(d.bit_depth, what);
+    colour_validate(cs, what.c_str());
+    if (d.src == nullptr) throw std::invalid_argument(what + ": no source picture");
+    if (d.x == nullptr && d.planar == nullptr) throw std::invalid_argument(what + ": neither x nor the planar copy requested");
+    if (d.x != nullptr && d.ldx < 3) throw std::invalid_argument(what + ": the pixel stride of x must be >= 3");
+    stride_check(d, what);
+    // strides in samples: 8 samples are the 16 bytes of one access
+    const bool rows8 = d.W % 8 == 0 && d.row_stride % 8 == 0 && aligned(d.src, 16) && (d.planar == nullptr || aligned(d.planar, 16));
+    int load = kLoadScalar;
+    if (rows8 && d.pixel_stride == 3 && d.channel_stride == 1) load = kLoadPacked;
+    else if (rows8 && d.pixel_stride == 1 && d.channel_stride % 8 == 0) load = kLoadPlanar;
+    const bool vec_x = d.x != nullptr && load != kLoadScalar && d.ldx == 3 && aligned(d.x, 16);
+    const bool limited = cs.range == kRangeLimited;
+    const ColourConsts k = colour_consts(cs);
+    if (load == kLoadPacked && vec_x) launch_to_x16<kLoadPacked, true>(d, limited, k, maxv, stream);
+    else if (load == kLoadPacked) launch_to_x16<kLoadPacked, false>(d, limited, k, maxv, stream);
+    else if (load == kLoadPlanar && vec_x) launch_to_x16<kLoadPlanar, true>(d, limited, k, maxv, stream);
+    else if (load == kLoadPlanar) launch_to_x16<kLoadPlanar, false>(d, limited, k, maxv, stream);
+    else launch_to_x16<kLoadScalar, false>(d, limited, k, maxv, stream);
+    hip_check(hipGetLastError(), (what + " launch").c_str());
+}
+
+void from_x16(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist, uint16_t* out, const ColourSpace& cs,
+              const std::string& what, hipStream_t stream)
+{
+    picture_validate(H, W, what.c_str());
+    const float maxv = depth_max_val(bit_depth, what);
+    colour_validate(cs, what.c_str());
+    if (x == nullptr) throw std::invalid_argument(what + ": no x_hat");
+    if (dist == nullptr && out == nullptr) throw std::invalid_argument(what + ": neither the distortion planes nor the samples requested");
+    if (row_pixels < W) throw std::invalid_argument(what + ": the rows of x_hat are shorter than the picture");
+    const bool vec = row_pixels % 8 == 0 && W % 8 == 0 && aligned(x, 16) && (dist == nullptr || aligned(dist, 16)) &&
+                     (out == nullptr || aligned(out, 16));
+    const bool limited = cs.range == kRangeLimited;
+    const ColourConsts k = colour_consts(cs);
+    const dim3 grid(grid_of(H, W)), block(kThreads);
+    if (vec && limited) hipLaunchKernelGGL((x_to_rgb16_kernel<true, true>), grid, block, 0, stream, x, row_pixels, H, W, dist, out, k, maxv);
+    else if (vec) hipLaunchKernelGGL((x_to_rgb16_kernel<true, false>), grid, block, 0, stream, x, row_pixels, H, W, dist, out, k, maxv);
+    else if (limited) hipLaunchKernelGGL((x_to_rgb16_kernel<false, true>), grid, block, 0, stream, x, row_pixels, H, W, dist, out, k, maxv);
+    else hipLaunchKernelGGL((x_to_rgb16_kernel<false, false>), grid, block, 0, stream, x, row_pixels, H, W, dist, out, k, maxv);
+    hip_check(hipGetLastError(), (what + " launch").c_str());
+}
+
 }  // namespace
 
 void rgb_to_x(const RgbToXDesc& d, hipStream_t stream) { to_x(d, ColourSpace{}, "rgb_to_x", stream); }
@@ -337,6 +568,14 @@ void x_to_rgb(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint
 void x_to_rgb_cs(const half_t* x, int row_pixels, int H, int W, half_t* rgb16, uint8_t* rgb8, const ColourSpace& cs, hipStream_t stream)
 {
     from_x(x, row_pixels, H, W, rgb16, rgb8, cs, "x_to_rgb_cs", stream);
+}
+
+void rgb16_to_x_cs(const Rgb16ToXDesc& d, const ColourSpace& cs, hipStream_t stream) { to_x16(d, cs, "rgb16_to_x_cs", stream); }
+
+void x_to_rgb16_cs(const half_t* x, int row_pixels, int H, int W, int bit_depth, float* dist32, uint16_t* rgb16u, const ColourSpace& cs,
+                   hipStream_t stream)
+{
+    from_x16(x, row_pixels, H, W, bit_depth, dist32, rgb16u, cs, "x_to_rgb16_cs", stream);
 }
 
 }  // namespace dcvc

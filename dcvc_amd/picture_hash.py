@@ -12,7 +12,8 @@ The manifest is text, one line per picture::
     sequence <crc8hex> <total bytes>
 
 A picture's CRC is over its bytes in raw file layout (what ``-o`` writes), the plane CRCs are over Y, U, V (planar types), Y
-and the interleaved chroma (nv12) or the packed pixels (rgb24, png); ``sequence`` is the CRC of all pictures back to back.
+and the interleaved chroma (nv12) or the packed pixels (rgb24, png; rgb48 at 9..16 bits and png16 at 16: little-endian u16
+samples, 6 H W bytes); ``sequence`` is the CRC of all pictures back to back.
 """
 import ctypes
 import re
@@ -26,7 +27,7 @@ _SIGS = {
     "dcvc_crc32_combine": (_u32, [_u32, _u32, _ll]),
 }
 MAX_SEGMENTS = 16
-SRC_TYPES = ("yuv420", "yuv422", "yuv444", "nv12", "rgb24", "png")
+SRC_TYPES = ("yuv420", "yuv422", "yuv444", "nv12", "rgb24", "png", "rgb48", "png16")
 _HEX = re.compile(r"^[0-9a-f]{8}$")
 _DEC = re.compile(r"^(0|[1-9][0-9]*)$")
 
@@ -75,6 +76,8 @@ def plane_bytes(src_type, bit_depth, width, height):
     hw = width * height
     if src_type in ("rgb24", "png"):
         return [3 * hw]
+    if src_type in ("rgb48", "png16"):
+        return [6 * hw]
     es = 2 if bit_depth > 8 else 1
     if src_type == "nv12":
         return [hw * es, hw // 2 * es]
@@ -136,6 +139,8 @@ def parse_manifest(text):
         raise ValueError("manifest: bad source type or numbers in the header: %r" % lines[0])
     depth, width, height = (int(v) for v in head[5:])
     if not 8 <= depth <= 16 or width < 1 or height < 1 or (head[4] in ("rgb24", "png") and depth != 8):
+        raise ValueError("manifest: bad bit depth or size in the header: %r" % lines[0])
+    if (head[4] == "rgb48" and depth < 9) or (head[4] == "png16" and depth != 16):
         raise ValueError("manifest: bad bit depth or size in the header: %r" % lines[0])
     lens = plane_bytes(head[4], depth, width, height)
     if len(lines) < 2 or not lines[-1].startswith("sequence "):

@@ -1,4 +1,4 @@
-/* dcvc_amd_image.h - picture files on the host: PNG pictures as packed 8-bit RGB (RGB24), and YUV4MPEG2 (.y4m) headers (below).
+/* dcvc_amd_image.h - picture files on the host: PNG pictures as packed 8-bit RGB (RGB24) or 16-bit RGB (rgb48), and YUV4MPEG2 (.y4m) headers (below).
  *
  * The reference reads and writes its RGB test sequences as PNG files through PIL (src/utils/video_reader.py:10-45
  * PNGReader: Image.open(path).convert('RGB'); src/utils/video_writer.py:9-30 PNGWriter: Image.fromarray(rgb).save(path)).
@@ -27,6 +27,18 @@ int dcvc_png_info(const char* path, int* width, int* height);
 int dcvc_png_read_rgb(const char* path, void* rgb, size_t capacity, int* width, int* height);
 /* writes packed [height][width][3] u8 as a PNG file */
 int dcvc_png_write_rgb(const char* path, const void* rgb, int width, int height);
+
+/* 16-bit PNG <-> packed u16 RGB (rgb48: native-endian samples in memory; the file's are big-endian). No reference counterpart.
+ *   reader: bit depth 16; colour types 0, 2, 4 and 6 (grey replicated, alpha dropped, as at 8 bits); all five row filters with
+ *           the 16-bit filter unit (2, 4, 6 or 8 bytes per pixel); any number of IDAT chunks, every CRC checked. Interlaced
+ *           and 8-bit files are refused. sBIT is ignored: a 16-bit PNG is always depth 16.
+ *   writer: colour type 2, 16-bit, not interlaced, filter 1 (Sub) on every row, zlib level DCVC_PNG_ZLIB_LEVEL.
+ * dcvc_png_info2 is dcvc_png_info for both kinds of file: bit_depth receives 8 or 16. */
+int dcvc_png_info2(const char* path, int* width, int* height, int* bit_depth);
+/* decodes a 16-bit PNG file into rgb16 (packed [height][width][3] u16, capacity bytes, 2-byte aligned) */
+int dcvc_png_read_rgb16(const char* path, void* rgb16, size_t capacity, int* width, int* height);
+/* writes packed [height][width][3] u16 as a 16-bit PNG file */
+int dcvc_png_write_rgb16(const char* path, const void* rgb16, int width, int height);
 
 /* YUV4MPEG2 (.y4m) headers, host only; the pictures behind them are raw planar samples (DCVC_PIX_* layouts of
  * include/dcvc_amd_ops.h, LSB-aligned u16 little-endian above 8 bits), each behind a "FRAME" line.

@@ -337,6 +337,25 @@ int dcvc_rgb_to_x_cs(const void* src, long long row_stride, long long pixel_stri
  * dcvc_x_to_rgb_cs(dcvc_rgb_to_x_cs(c)) = c for every matrix, in full range and in limited range at every depth. */
 int dcvc_x_to_rgb_cs(const void* x_hat, int row_pixels, int H, int W, void* rgb16, void* rgb8,
                      int matrix, int range, int yuv_bit_depth, void* stream);
+/* 9..16-bit RGB pictures (rgb48: film scans, HDR stills, screen capture; no reference counterpart). Samples are
+ * u16, LSB-aligned in 0..max_val = 2^bit_depth - 1; strides are in samples (packed HWC: 3W, 3, 1; planar CHW: W, 1, H*W). The
+ * conversion is dcvc_rgb_to_x_cs's from the unit value on, which here is a true division:
+ *   r, g, b = fp32(u16) / fp32(max_val), correctly rounded (as dcvc_yuv420p16_to_x; not a reciprocal multiply); samples above
+ *   max_val are neither masked nor checked;  y, pb, pr, the levels and x_k as dcvc_rgb_to_x_cs
+ *   planar16: u16 [3][H][W] copy of the source (for the metrics). Either output may be NULL, not both.
+ * NULL rules, stride rules and stream order are dcvc_rgb_to_x_cs's. Refused before any launch, with the function's name in
+ * the message: a bit depth outside 9..16 (8-bit pictures have one definition, dcvc_rgb_to_x_cs's), both outputs NULL, an
+ * unknown matrix or range, a yuv_bit_depth outside 8..16, strides that are not positive or overlap, ldx < 3. */
+int dcvc_rgb16_to_x_cs(const void* src, long long row_stride, long long pixel_stride, long long channel_stride,
+                       int bit_depth, int H, int W, void* x, int ldx, void* planar16,
+                       int matrix, int range, int yuv_bit_depth, void* stream);
+/* The inverse: dcvc_x_to_rgb_cs up to t_k = fp16(clamp(rgb_k, 0, 1)), then
+ *   dist32_k = clamp(fp32(t_k) * fp32(max_val), 0, max_val) (NaN passes through): fp32 [3][H][W], the distortion planes (fp16
+ *   cannot hold a 10-bit sample);  rgb16u: packed u16 [H][W][3] = rint(dist32) (half to even), NaN -> 0.
+ * Either output may be NULL, not both. Refused as above, and row_pixels < W. x is fp16, so above about 11 bits neighbouring
+ * codes share an x: dcvc_x_to_rgb16_cs(dcvc_rgb16_to_x_cs(c)) = c holds for part of the colours only. */
+int dcvc_x_to_rgb16_cs(const void* x_hat, int row_pixels, int H, int W, int bit_depth,
+                       void* dist32, void* rgb16u, int matrix, int range, int yuv_bit_depth, void* stream);
 /* metrics.py:10-24 calc_psnr's fp64 sum of squared differences, one value per plane: n_planes planes of H x W samples (u8,
  * fp16, u16 or fp32; DCVC_SAMPLE_*), src and rec sharing the geometry (row_stride, plane_stride in samples). out: device memory, n_planes
  * doubles, written asynchronously on `stream`. Per-workgroup partials reduced in a fixed order: the same bits on every run and

@@ -198,7 +198,7 @@ def build_cli(verbose=False):
     """The standalone encoder / decoder (dcvc_amd/bin/dcvc): host code on top of the C ABI, linked
     against libdcvc_amd.so next to it."""
     os.makedirs(os.path.dirname(CLI_BIN), exist_ok=True)
-    cmd = [_hipcc()] + COMMON + ["-x", "hip"] + HIP_FLAGS + [CLI_SRC, "-x", "none", "-o", CLI_BIN, "-L", PKG, "-ldcvc_amd",
+    cmd = [_hipcc()] + COMMON + ["-x", "hip"] + HIP_FLAGS + [CLI_SRC, "-x", "none", "-o", CLI_BIN, "-L", PKG, "-ldcvc_amd", "-lpthread",
                                                        "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib"]
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -15,10 +15,35 @@
 //               [--scene-cut T [--scene-min-gap 8] [--scene-log log.json]] [--scale WxH] [--hash-log hashes.txt]
 //               [--target-psnr DB [--qp-min 0] [--qp-max 63]] [--quality-log log.json]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
+//               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
+//               [--in-format raw|y4m] [--out-format raw|y4m]                                               (-i - | --ref - | -o -: pipes)
+//               Pipes: "-" names stdin for -i (and for decode --ref) and stdout for -o; a FIFO, /dev/stdin or any other
+//               name that is no regular file (fstat, S_ISREG) works in the same places. Such a source is read front to back and
+//               never seeked; a regular file keeps its count up front and every refusal. A name cannot end in .y4m there, so
+//               --in-format raw|y4m (encode -i, decode --ref) and --out-format raw|y4m (decode -o) say it; the default is by name.
+//               Encoding from a pipe is driven by the end of the input (-n still caps it): the pictures of the last P unit, the
+//               padding of a ragged last chunk and a short last --batch follow what was read, and the stream is the regular
+//               file's byte for byte. A trailing partial raw picture is dropped with a warning; a Y4M pipe that ends inside a
+//               picture ends the run with status 2 after the units of the whole pictures have been written. When -o is a pipe,
+//               or with --flush-units 1, encode writes every parameter set and unit as soon as it is complete and keeps only
+//               the byte count; decode reads every stream unit by unit (dcvc_stream_next_unit: the units of one codec call plus
+//               one of lookahead in memory) and flushes a piped -o after every picture. With -o - every message goes to stderr.
+//               SIGPIPE is ignored: a write that fails with EPIPE ends the run with status 1 and one line.
+//               --read-ahead N (encode, 0..8; default 0 for a regular -i: the loop as it was; 2 for a pipe): one reader thread
+//               fills a ring of N + 1 pinned host slots with read() alone while the main thread codes; the upload leaves from
+//               the slot on the one stream, and the slot goes back after the synchronisation behind the conversion. No second
+//               stream, no other launch: only the host's read overlaps the coding. The stream does not depend on N.
+//               --latency-log FILE (encode): {units: [{type, first_picture, pictures, qp, bytes, read_ms, out_ms}], pictures,
+//               bytes}; bytes counts a parameter set in front of the unit, read_ms is when the unit's last source picture was
+//               whole in host memory, out_ms when its bytes had been handed to the OS (a regular -o without --flush-units: the
+//               one write at the end), both in steady_clock milliseconds since the run started.
+//               Refused before a model is loaded: "-" or a non-regular name with --src-type png | png16 (directories), -i -
+//               with --ref -, a log named "-", --in-format / --out-format other than raw | y4m or y4m with a type a .y4m name
+//               is refused for, --read-ahead outside 0..8, and --read-ahead / --flush-units / --latency-log on decode.
 //               --bit-depth (the YUV types; default 8): 9..16 = uint16 little-endian samples (yuv420p10le, ...; 3 H W bytes
 //               per picture) for -i (encode), --ref and -o, read and written as DCVC-FM's YUVReader / YUVWriter do
 //               (dcvc_pix_to_x / dcvc_x_to_pix with DCVC_PIX_YUV420P: v / max_val, max_val = 2^b - 1; rint(clamp(t max_val))). The
@@ -188,6 +213,8 @@
 
 #include <chrono>
 #include <cmath>
+#include <condition_variable>
+#include <csignal>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -195,9 +222,16 @@
 #include <fstream>
 #include <functional>
 #include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
+
+#include <cerrno>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 namespace {
 
@@ -205,6 +239,62 @@ namespace {
 {
     fprintf(stderr, "dcvc: %s\n", msg.c_str());
     exit(2);
+}
+
+// where the tool's messages go: stdout, or stderr when stdout carries data (-o -)
+FILE* g_msg = stdout;
+
+// ------------------------------------------------------------------------------------ pipes
+// "-" names stdin (-i, --ref) or stdout (-o); any other name that is no regular file - a FIFO, /dev/stdin - is read and
+// written the same way: front to back, never seeking. fstat decides, not an attempt to seek.
+bool is_dash(const std::string& p) { return p == "-"; }
+
+bool fd_is_regular(int fd)
+{
+    struct stat st;
+    return fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
+}
+
+// a name that exists and is neither a regular file nor a directory, or "-"
+bool names_a_pipe(const std::string& p)
+{
+    if (is_dash(p)) return true;
+    struct stat st;
+    return stat(p.c_str(), &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode);
+}
+
+// a write to a pipe whose reader has gone ends the run with status 1 (SIGPIPE is ignored)
+[[noreturn]] void output_closed(const std::string& name)
+{
+    fprintf(stderr, "dcvc: -o %s: the reader closed the pipe\n", name.c_str());
+    exit(1);
+}
+
+// every byte, or false with errno set
+bool write_all(int fd, const uint8_t* p, size_t n)
+{
+    while (n > 0) {
+        const ssize_t k = write(fd, p, n);
+        if (k < 0 && errno == EINTR) continue;
+        if (k < 0) return false;
+        p += k;
+        n -= static_cast<size_t>(k);
+    }
+    return true;
+}
+
+// up to n bytes, short only at the end of the input; -1 on a read error
+ssize_t read_upto(int fd, uint8_t* p, size_t n)
+{
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t k = read(fd, p + got, n - got);
+        if (k < 0 && errno == EINTR) continue;
+        if (k < 0) return -1;
+        if (k == 0) break;
+        got += static_cast<size_t>(k);
+    }
+    return static_cast<ssize_t>(got);
 }
 
 void hip_ok(hipError_t e, const char* what)
@@ -604,70 +694,117 @@ int pix_fmt_of(SrcType t)
 
 bool is_y4m_name(const std::string& path) { return path.size() >= 4 && path.compare(path.size() - 4, 4, ".y4m") == 0; }
 
-// A file of pictures back to back: raw, or Y4M (a name ending in .y4m: one header line, then a "FRAME...\n" line in front of
-// every picture; a file without the magic is refused).
+// A file of pictures back to back: raw, or Y4M (a name ending in .y4m, or --in-format y4m: one header line, then a "FRAME...\n"
+// line in front of every picture; a file without the magic is refused). Read front to back through a buffer of its own, so
+// that stdin ("-"), a FIFO or any other non-regular file serves as well: the reader never seeks. A regular
+// file is also counted up front (count), with positioned reads that leave the reader where it is.
 struct PictureFile {
-    FILE* f = nullptr;
-    std::string path;
-    bool y4m = false;
+    enum Status { Picture, End, Broken };      // Broken: `error` says why (a Y4M source that ends inside a picture, a bad FRAME line)
+    int fd = -1;
+    std::string path;                          // as the messages name it
+    bool y4m = false, regular = true;
     dcvc_y4m_info info{};
-    void open(const std::string& p)
+    std::vector<uint8_t> buf;                  // bytes read ahead of the pictures: header and FRAME lines
+    size_t pos = 0, end = 0;
+    size_t partial = 0;                        // End: bytes of a trailing partial raw picture
+    std::string error;
+    // format: "" = by name, "raw" or "y4m" (--in-format)
+    void open(const std::string& p, const std::string& format = "")
     {
-        path = p;
-        f = fopen(p.c_str(), "rb");
-        if (!f) die("cannot open " + p);
-        if (!is_y4m_name(p)) return;
-        y4m = true;
-        char head[1024];
-        const size_t n = fread(head, 1, sizeof(head), f);
-        if (dcvc_y4m_parse_header(head, n, &info) < 0) die(p + " is no Y4M file: " + dcvc_last_error());
-        fseek(f, static_cast<long>(info.header_bytes), SEEK_SET);
+        path = is_dash(p) ? "stdin" : p;
+        fd = is_dash(p) ? 0 : ::open(p.c_str(), O_RDONLY);
+        if (fd < 0) die("cannot open " + p);
+        regular = fd_is_regular(fd);
+        buf.resize(1024);
+        y4m = format.empty() ? is_y4m_name(p) : format == "y4m";
+        if (!y4m) return;
+        const size_t n = fill_line();
+        if (dcvc_y4m_parse_header(buf.data() + pos, n, &info) < 0) die(path + " is no Y4M file: " + dcvc_last_error());
+        pos += static_cast<size_t>(info.header_bytes);
     }
-    // the "FRAME...\n" line at the file position; false at the end of the file
-    bool frame_line()
+    // reads until the buffer holds a whole line, 1024 bytes or the end of the input; the bytes it holds
+    size_t fill_line()
     {
-        char line[1024];
-        const long at = ftell(f);
-        const size_t n = fread(line, 1, sizeof(line), f);
-        if (n == 0) return false;
-        const int len = dcvc_y4m_frame_header_bytes(line, n);
-        if (len < 0) die(path + ": no FRAME line where a picture should start (" + dcvc_last_error() + ")");
-        fseek(f, at + len, SEEK_SET);
-        return true;
+        if (pos > 0) {
+            std::memmove(buf.data(), buf.data() + pos, end - pos);
+            end -= pos;
+            pos = 0;
+        }
+        size_t scanned = 0;
+        for (;;) {
+            if (std::memchr(buf.data() + scanned, '\n', end - scanned) != nullptr || end == buf.size()) return end;
+            scanned = end;
+            ssize_t k;
+            do k = ::read(fd, buf.data() + end, buf.size() - end); while (k < 0 && errno == EINTR);
+            if (k <= 0) return end;
+            end += static_cast<size_t>(k);
+        }
     }
-    // pictures in the file; a Y4M file that ends inside a picture is refused. The position is left at the first picture.
+    // pictures in a regular file; a Y4M file that ends inside a picture is refused. The reader's position is not touched.
     long long count(size_t frame_bytes)
     {
-        fseek(f, 0, SEEK_END);
-        const long long size = ftell(f);
-        long long n = 0;
-        if (!y4m) {
-            n = size / static_cast<long long>(frame_bytes);
-        } else {
-            fseek(f, static_cast<long>(info.header_bytes), SEEK_SET);
-            while (frame_line()) {
-                if (ftell(f) + static_cast<long long>(frame_bytes) > size) {
-                    die(path + " ends inside picture " + std::to_string(n + 1) + " (" + std::to_string(frame_bytes) + " bytes each)");
-                }
-                fseek(f, static_cast<long>(frame_bytes), SEEK_CUR);
-                ++n;
+        struct stat st;
+        if (fstat(fd, &st) != 0) die("cannot read " + path);
+        const long long size = st.st_size;
+        if (!y4m) return size / static_cast<long long>(frame_bytes);
+        long long n = 0, at = info.header_bytes;
+        char line[1024];
+        for (;;) {
+            const ssize_t got = pread(fd, line, sizeof(line), at);
+            if (got <= 0) return n;
+            const int len = dcvc_y4m_frame_header_bytes(line, static_cast<size_t>(got));
+            if (len < 0) die(path + ": no FRAME line where a picture should start (" + dcvc_last_error() + ")");
+            at += len;
+            if (at + static_cast<long long>(frame_bytes) > size) {
+                die(path + " ends inside picture " + std::to_string(n + 1) + " (" + std::to_string(frame_bytes) + " bytes each)");
             }
+            at += static_cast<long long>(frame_bytes);
+            ++n;
         }
-        fseek(f, y4m ? static_cast<long>(info.header_bytes) : 0, SEEK_SET);
-        return n;
+    }
+    // the next picture. Calls nothing that dies and nothing from HIP: the read-ahead thread runs it.
+    Status next(uint8_t* dst, size_t frame_bytes)
+    {
+        if (y4m) {
+            const size_t n = fill_line();
+            if (n == 0) return End;
+            const int len = dcvc_y4m_frame_header_bytes(buf.data(), n);
+            if (len < 0) {
+                error = path + ": no FRAME line where a picture should start (" + dcvc_last_error() + ")";
+                return Broken;
+            }
+            pos += static_cast<size_t>(len);
+        }
+        size_t got = std::min(end - pos, frame_bytes);
+        std::memcpy(dst, buf.data() + pos, got);
+        pos += got;
+        if (got < frame_bytes) {
+            const ssize_t k = read_upto(fd, dst + got, frame_bytes - got);
+            if (k < 0) {
+                error = "cannot read " + path + ": " + strerror(errno);
+                return Broken;
+            }
+            got += static_cast<size_t>(k);
+        }
+        if (got == frame_bytes) return Picture;
+        if (y4m) {
+            error = path + " ends inside a picture";
+            return Broken;
+        }
+        partial = got;
+        return End;
     }
     // the next picture; false when the file has ended (a Y4M file inside a picture: refused)
-    bool read(uint8_t* buf, size_t frame_bytes)
+    bool read(uint8_t* dst, size_t frame_bytes)
     {
-        if (y4m && !frame_line()) return false;
-        const size_t got = fread(buf, 1, frame_bytes, f);
-        if (y4m && got != frame_bytes) die(path + " ends inside a picture");
-        return got == frame_bytes;
+        const Status s = next(dst, frame_bytes);
+        if (s == Broken) die(error);
+        return s == Picture;
     }
     void close()
     {
-        if (f) fclose(f);
-        f = nullptr;
+        if (fd > 0) ::close(fd);
+        fd = -1;
     }
 };
 
@@ -805,10 +942,10 @@ struct WireStage {
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_in), g.file_bytes(), hipHostMallocDefault), "hipHostMalloc");
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.file_bytes(), hipHostMallocDefault), "hipHostMalloc");
     }
-    // the picture in h_in -> `carrier`, where an upload of the carrier type's picture lands
-    void upload(const Geometry& g, uint8_t* carrier, hipStream_t st) const
+    // the picture in h_in (or in `from`, a read-ahead slot) -> `carrier`, where an upload of the carrier type's picture lands
+    void upload(const Geometry& g, uint8_t* carrier, hipStream_t st, const uint8_t* from = nullptr) const
     {
-        hip_ok(hipMemcpyAsync(in, h_in, g.file_bytes(), hipMemcpyHostToDevice, st), "H2D");
+        hip_ok(hipMemcpyAsync(in, from ? from : h_in, g.file_bytes(), hipMemcpyHostToDevice, st), "H2D");
         abi_ok(dcvc_wire_unpack(in, g.wire, g.bit_depth, g.H, g.W, carrier, st), "wire_unpack");
     }
     // the carrier picture dcvc_x_to_pix wrote -> out
@@ -889,6 +1026,61 @@ int int_arg(const Args& a, const std::string& key, int def, int lo, int hi)
         die("--" + key + " must be in " + std::to_string(lo) + ".." + std::to_string(hi) + ", got " + s);
     }
     return static_cast<int>(v);
+}
+
+// -i / --ref / -o on pipes, --in-format / --out-format, --read-ahead, --flush-units, --latency-log: what the
+// flags alone decide is refused before a model is loaded
+struct PipeArgs {
+    std::string in_format, out_format;      // "" = by name, "raw" or "y4m"
+    int read_ahead = 0;                     // encode: pinned slots filled ahead of the coder by a reader thread; 0: today's loop
+    bool flush_units = false;               // encode: every unit is written and flushed as soon as it is complete
+    std::string latency_log;
+    bool in_is_y4m(const std::string& name) const { return in_format.empty() ? is_y4m_name(name) : in_format == "y4m"; }
+    bool out_is_y4m(const std::string& name) const { return out_format.empty() ? is_y4m_name(name) : out_format == "y4m"; }
+};
+
+PipeArgs pipe_args(const Args& a, bool encoding)
+{
+    PipeArgs p;
+    const std::string t = a.str("src-type", "yuv420");
+    for (const char* k : {"in-format", "out-format"}) {
+        if (!a.has(k)) continue;
+        const std::string v = a.str(k), flag = std::string("--") + k;
+        if (v != "raw" && v != "y4m") die(flag + " must be raw or y4m, got " + v);
+        if (encoding && k[0] == 'o') die("--out-format is a decoder flag: it names the format of the pictures -o writes");
+        if (v != "y4m") continue;
+        // the types a name ending in .y4m is refused for, in that path's words
+        if (wire_of(t) >= 0) die(flag + " y4m: Y4M has no tag for --src-type " + t + "; use a raw file");
+        if (t == "nv12" || t == "p010") die(flag + " y4m: Y4M has no tag for interleaved chroma (--src-type " + t + "); use a raw file");
+        if (is_rgb_name(t)) die(flag + " y4m: a Y4M file holds YUV pictures, not --src-type " + t);
+    }
+    p.in_format = a.str("in-format");
+    p.out_format = a.str("out-format");
+    if (t == "png" || t == "png16") {
+        for (const char* k : {"i", "ref", "o"}) {
+            if ((std::strcmp(k, "i") == 0 && !encoding) || !a.has(k) || !names_a_pipe(a.str(k))) continue;
+            die(std::string(k[0] == 'r' ? "--" : "-") + k + " " + a.str(k) + ": --src-type " + t + " reads and writes a directory of PNG pictures, not a pipe");
+        }
+        if (a.has("in-format") || a.has("out-format")) die("--in-format / --out-format are for raw and Y4M files: --src-type " + t + " is a directory of PNG pictures");
+    }
+    if (a.has("ref") && is_dash(a.str("i")) && is_dash(a.str("ref"))) die("-i - together with --ref -: stdin carries one of the two");
+    for (const char* k : {"json", "rc-log", "scene-log", "quality-log", "hash-log", "latency-log"}) {
+        if (a.has(k) && is_dash(a.str(k))) {
+            die(std::string("--") + k + " -: a log goes to a file of its own" + (a.has("o") && is_dash(a.str("o")) ? " (-o - has the standard output)" : ""));
+        }
+    }
+    if (!encoding) {
+        for (const char* k : {"read-ahead", "flush-units", "latency-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+        }
+        return p;
+    }
+    p.read_ahead = int_arg(a, "read-ahead", -1, 0, 8);
+    if (p.read_ahead > 0 && (t == "png" || t == "png16")) die("--read-ahead reads raw and Y4M sources ahead: --src-type " + t + " is a directory of PNG pictures");
+    p.flush_units = int_arg(a, "flush-units", 0, 0, 1) != 0;
+    p.latency_log = a.str("latency-log");
+    if (a.has("latency-log") && p.latency_log.empty()) die("--latency-log needs a file name");
+    return p;
 }
 
 // --matrix, --range, --yuv-depth: the colour conversion of RGB sources, refused before anything touches the device
@@ -1380,7 +1572,7 @@ struct HashRun {
                 mismatch("sequence: expected " + hex8(expect.sequence) + " over " + std::to_string(expect.total_bytes) + " bytes, got " +
                          hex8(got.sequence) + " over " + std::to_string(got.total_bytes));
             }
-            printf("verified %zu pictures against %s: sequence %s\n", got.pictures.size(), verify.c_str(), hex8(got.sequence).c_str());
+            fprintf(g_msg, "verified %zu pictures against %s: sequence %s\n", got.pictures.size(), verify.c_str(), hex8(got.sequence).c_str());
         }
     }
 };
@@ -1528,6 +1720,86 @@ struct RateUnit {
     long long predicted_bytes = -1, bytes = 0;      // -1: no prediction (the feedback loop does not probe)
 };
 
+// --read-ahead N: one reader thread fills a ring of N + 1 pinned host slots with the source's pictures while the
+// main thread codes. The main thread allocates and frees the slots and makes every HIP call; the thread only reads
+// (PictureFile::next) and hands slots over under a mutex and a condition variable. A slot goes back to the thread once the
+// upload that read it has completed.
+struct ReadAhead {
+    struct Slot {
+        uint8_t* p = nullptr;      // pinned
+        bool full = false;
+        PictureFile::Status status = PictureFile::End;
+        double read_ms = 0;        // when the picture was complete in host memory, since the run started
+    };
+    std::vector<Slot> slots;
+    size_t head = 0, tail = 0;     // the next slot the coder takes, the next the reader fills
+    std::mutex m;
+    std::condition_variable cv;
+    bool stop = false;
+    std::thread th;
+    // at most `limit` pictures of `bytes` bytes are read; the first slot that is no picture (the end, a broken source) is the last
+    void start(PictureFile& f, size_t bytes, int n_slots, int limit, std::chrono::steady_clock::time_point t0)
+    {
+        slots.resize(static_cast<size_t>(n_slots));
+        for (Slot& s : slots) hip_ok(hipHostMalloc(reinterpret_cast<void**>(&s.p), bytes, hipHostMallocDefault), "hipHostMalloc");
+        th = std::thread([this, &f, bytes, limit, t0] {
+            for (int k = 0; k < limit; ++k) {
+                Slot* s = nullptr;
+                {
+                    std::unique_lock<std::mutex> lk(m);
+                    cv.wait(lk, [&] { return stop || !slots[tail].full; });
+                    if (stop) return;
+                    s = &slots[tail];
+                }
+                const PictureFile::Status status = f.next(s->p, bytes);
+                const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                {
+                    std::lock_guard<std::mutex> lk(m);
+                    s->status = status; s->read_ms = ms; s->full = true;
+                    tail = (tail + 1) % slots.size();
+                }
+                cv.notify_all();
+                if (status != PictureFile::Picture) return;
+            }
+        });
+    }
+    // the next slot in reading order, once it is full; it stays the coder's until release()
+    Slot& take()
+    {
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return slots[head].full; });
+        return slots[head];
+    }
+    void release()
+    {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            slots[head].full = false;
+            head = (head + 1) % slots.size();
+        }
+        cv.notify_all();
+    }
+    void finish()
+    {
+        {
+            std::lock_guard<std::mutex> lk(m);
+            stop = true;
+        }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+        for (Slot& s : slots) hip_ok(hipHostFree(s.p), "hipHostFree");
+        slots.clear();
+    }
+};
+
+// one coded unit in --latency-log
+struct LatencyUnit {
+    bool intra = false;
+    int first_picture = 0, pictures = 0, qp = 0;
+    long long bytes = 0;                  // a parameter set written in front of the unit included
+    double read_ms = 0, out_ms = 0;
+};
+
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
@@ -1538,6 +1810,8 @@ int encode(const Args& a)
     const ColourArgs colour = colour_args(a);
     HashRun hash;
     hash.parse(a, true);
+    const PipeArgs pipe = pipe_args(a, true);
+    if (is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the stream
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
     }
@@ -1549,8 +1823,8 @@ int encode(const Args& a)
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
-    if (is_y4m_name(a.str("i"))) {
-        src_file.open(a.str("i"));
+    if (pipe.in_is_y4m(a.str("i"))) {
+        src_file.open(a.str("i"), pipe.in_format);
         const Y4mSource y = y4m_source(src_file, a, true);
         type = y.type; depth = y.depth;
         pic_w = src_file.info.width; pic_h = src_file.info.height;
@@ -1594,12 +1868,15 @@ int encode(const Args& a)
     if (is_png(type)) {
         total = pngs.count();
     } else {
-        if (!src_file.f) src_file.open(a.str("i"));
-        total = src_file.count(gs.file_bytes());
+        if (src_file.fd < 0) src_file.open(a.str("i"), pipe.in_format);
+        // a pipe's length is unknown: the loop below learns the clip's end from the reader, -n still caps it
+        total = src_file.regular ? src_file.count(gs.file_bytes()) : (1 << 30);
     }
-    const int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
+    const bool piped_in = !is_png(type) && !src_file.regular;
+    // pictures to code; from a pipe: an upper bound until the input ends
+    int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
-    DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
+    const int read_ahead = pipe.read_ahead >= 0 ? pipe.read_ahead : piped_in ? 2 : 0;    DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
     // --quality-log / --target-psnr: every converted picture's source samples stay on the device, one slot per picture of a unit
     QualityMeter meter;
     if (quality.on()) meter.create(g, std::max(delay, batch));
@@ -1633,26 +1910,76 @@ int encode(const Args& a)
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
+    // -o on a pipe ("-", a FIFO), or --flush-units 1: every parameter set and unit is written as soon as it is complete, and `out`
+    // holds one unit at a time; a regular file without the flag is written once at the end
+    const std::string out_name = a.str("o");
+    const bool streaming = names_a_pipe(out_name) || pipe.flush_units;
+    int out_fd = -1;
+    if (streaming) {
+        out_fd = is_dash(out_name) ? 1 : ::open(out_name.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (out_fd < 0) die("cannot write " + out_name);
+    }
+    long long out_bytes = 0;               // bytes handed to out_fd
+    std::vector<LatencyUnit> latency;
     const auto t0 = std::chrono::steady_clock::now();
-    // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx)
-    auto load_picture = [&]() {
-        if (scale.on) {
-            if (!src_file.read(h_full, gs.frame_bytes())) die("short read");
-            hip_ok(hipMemcpyAsync(d_full, h_full, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
-            rs.run(d_full, b.yuv8, b.st);
-            return;
+    auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    // --read-ahead: the source's pictures arrive in the ring's pinned slots instead of the one pinned buffer of each path
+    ReadAhead ra;
+    if (read_ahead > 0) ra.start(src_file, gs.file_bytes(), read_ahead + 1, frame_num, t0);
+    bool slot_held = false;                // a slot whose upload is in flight: released behind convert()'s synchronisation
+    double last_read_ms = 0;               // when the last source picture was complete in host memory
+    std::string input_error;               // a pipe that broke off inside a picture: the run ends as at the end of the input, with status 2
+    bool input_done = false;               // a pipe has ended: what was read is the clip
+    auto source_ended = [&](PictureFile::Status st) {
+        if (!piped_in) die(st == PictureFile::Broken ? src_file.error : "short read");
+        input_done = true;
+        if (st == PictureFile::Broken) {
+            input_error = src_file.error;
+        } else if (src_file.partial > 0) {
+            fprintf(stderr, "dcvc: warning: %s ends with %zu bytes that are no whole picture (%zu bytes each): dropped\n",
+                    src_file.path.c_str(), src_file.partial, gs.file_bytes());
         }
-        if (wire >= 0) {
-            if (!src_file.read(ws.h_in, g.file_bytes())) die("short read");
-            ws.upload(g, b.yuv8, b.st);
-            return;
+    };
+    // the next picture of -i in pinned memory - `own`, or a read-ahead slot; nullptr when a pipe has ended
+    auto next_source = [&](uint8_t* own) -> const uint8_t* {
+        if (read_ahead > 0) {
+            ReadAhead::Slot& s = ra.take();
+            if (s.status != PictureFile::Picture) {
+                source_ended(s.status);
+                return nullptr;
+            }
+            slot_held = true;
+            last_read_ms = s.read_ms;
+            return s.p;
         }
+        const PictureFile::Status st = src_file.next(own, gs.file_bytes());
+        if (st != PictureFile::Picture) {
+            source_ended(st);
+            return nullptr;
+        }
+        last_read_ms = now_ms();
+        return own;
+    };
+    // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx).
+    // false: the input has ended (a pipe; a regular file was counted)
+    auto load_picture = [&]() -> bool {
         if (is_png(type)) {
             if (!pngs.read(b.h_yuv, g)) die("short read");
-        } else if (!src_file.read(b.h_yuv, g.frame_bytes())) {
-            die("short read");
+            last_read_ms = now_ms();
+            hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            return true;
         }
-        hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+        const uint8_t* h = next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv);
+        if (h == nullptr) return false;
+        if (scale.on) {
+            hip_ok(hipMemcpyAsync(d_full, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            rs.run(d_full, b.yuv8, b.st);
+        } else if (wire >= 0) {
+            ws.upload(g, b.yuv8, b.st, h);
+        } else {
+            hip_ok(hipMemcpyAsync(b.yuv8, h, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+        }
+        return true;
     };
     // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
     int luma_turn = 0;
@@ -1672,12 +1999,30 @@ int encode(const Args& a)
             luma_turn ^= 1;
         }
         hip_ok(hipStreamSynchronize(b.st), "sync");      // the staging buffers are reused
+        if (slot_held) ra.release();                     // ... and so is the read-ahead slot the upload read
+        slot_held = false;
     };
-    auto put_unit = [&](bool intra, int qp, int ec, int reset, const std::vector<uint8_t>& pl) {
+    // the unit of `pictures` source pictures from first_picture on, the last of them read at read_ms
+    auto put_unit = [&](bool intra, int qp, int ec, int reset, const std::vector<uint8_t>& pl, int first_picture, int pictures, double read_ms) {
+        const size_t before = out.size();
         bool is_new = false;
         const int sps_id = sps.id_for(g.H, g.W, is_new);
         if (is_new) dcvc::stream::put_sps(out, sps_id, g.H, g.W);
         dcvc::stream::put_ip(out, intra, sps_id, qp, ec, reset != 0, pl.data(), pl.size());
+        LatencyUnit lu;
+        lu.intra = intra; lu.first_picture = first_picture; lu.pictures = pictures; lu.qp = qp; lu.read_ms = read_ms;
+        lu.bytes = static_cast<long long>(out.size() - before);
+        if (streaming) {
+            // write() hands the bytes to the OS: nothing of them stays in a buffer of the tool's
+            if (!write_all(out_fd, out.data(), out.size())) {
+                if (errno == EPIPE) output_closed(out_name);
+                die("cannot write " + out_name);
+            }
+            out_bytes += static_cast<long long>(out.size());
+            out.clear();
+            lu.out_ms = now_ms();
+        }
+        if (!pipe.latency_log.empty()) latency.push_back(lu);
     };
     // --target-bpp: all-intra runs search the q_index of every picture on the size probe, runs with an inter model follow the
     // feedback controller (rate_control.code_sequence with TargetBpp)
@@ -1735,10 +2080,10 @@ int encode(const Args& a)
         if (!scd) die(std::string("scene cut: ") + dcvc_last_error());
     }
     int idx = 0;
-    while (idx < frame_num) {
+    while (idx < frame_num && !input_done) {
         bool intra = is_intra_picture(idx, intra_period);
         if (scd) {
-            load_picture();
+            if (!load_picture()) break;
             if (quality.on()) meter.capture(g, b, 0);
             convert(static_cast<char*>(b.x), 3, true, idx > 0);
             ScenePicture sp;
@@ -1755,14 +2100,18 @@ int encode(const Args& a)
         }
         if (intra && batch > 1) {
             // up to `batch` intra pictures in one call, each in its own slot [H][W][3]; the units go out in picture order
-            const int nb = std::min(batch, frame_num - idx);
+            int nb = std::min(batch, frame_num - idx);
             const size_t slot = static_cast<size_t>(g.H) * g.W * 3 * 2, slot_hat = static_cast<size_t>(g.Hp) * g.Wp * 3 * 2;
+            double read_ms[16];
             for (int j = 0; j < nb; ++j) {
                 char* dst = static_cast<char*>(b.x) + slot * j;
-                load_picture();
+                if (!load_picture()) nb = j;      // a pipe ended: a short last batch
+                if (j >= nb) break;
+                read_ms[j] = last_read_ms;
                 if (quality.on()) meter.capture(g, b, j);
                 convert(dst, 3);
             }
+            if (nb == 0) break;
             int ecs[16];
             abi_ok(dcvc_dmci_compress_batch(c.intra, nb, b.x, g.H, g.W, qp_i, pad_b, pad_r, b.x_hat, ecs, b.st), "intra compress");
             for (int j = 0; j < nb; ++j) {
@@ -1781,20 +2130,23 @@ int encode(const Args& a)
                     qu.psnr = qu.pictures[0].psnr;
                     quality_units.push_back(qu);
                 }
-                put_unit(true, qp_i, ecs[j], 0, payload);
+                put_unit(true, qp_i, ecs[j], 0, payload, idx + j, 1, read_ms[j]);
             }
             idx += nb;
             continue;
         }
-        const int want = intra ? 1 : std::min(delay, frame_num - idx);
+        int want = intra ? 1 : std::min(delay, frame_num - idx);
         const int slots = intra ? 1 : delay;
         const int ldx = 3 * slots;
         for (int j = 0; j < slots && !scd; ++j) {
             char* dst = static_cast<char*>(b.x) + 6 * j;
-            if (j < want) load_picture();      // a short last chunk repeats its final picture (test_video.py:104-110)
+            // a short last chunk repeats its final picture (test_video.py:104-110); a pipe that ends inside the chunk makes it one
+            if (j < want && !load_picture()) want = j;
+            if (want == 0) break;
             if (quality.on() && j < want) meter.capture(g, b, j);
             convert(dst, ldx);
         }
+        if (want == 0) break;
         int ec = 0, reset = 0, qp = qp_i;
         long long nbytes = 0;
         RateUnit ru;
@@ -1968,7 +2320,7 @@ int encode(const Args& a)
             qu.qp = qp; qu.bytes = static_cast<long long>(payload.size());
             quality_units.push_back(qu);
         }
-        put_unit(intra, qp, ec, reset, payload);
+        put_unit(intra, qp, ec, reset, payload, idx, want, last_read_ms);
         if (rate.on) {
             if (ctl) abi_ok(dcvc_rc_update(ctl, 8.0 * payload.size(), want, intra ? 1 : 0), "rate control");
             spent_bits += 8LL * static_cast<long long>(payload.size());
@@ -1980,6 +2332,9 @@ int encode(const Args& a)
         idx += want;
     }
     hip_ok(hipStreamSynchronize(b.st), "sync");
+    if (read_ahead > 0) ra.finish();
+    frame_num = idx;                       // from a pipe: the pictures the input held
+    if (frame_num == 0) die(input_error.empty() ? "no pictures to code" : input_error);
     src_file.close();
     ws.destroy();
     if (scale.on) {
@@ -1993,8 +2348,8 @@ int encode(const Args& a)
         dcvc_scd_destroy(scd);
         int cuts = 0;
         for (const ScenePicture& sp : scene_pictures) cuts += sp.reason && std::strcmp(sp.reason, "cut") == 0;
-        printf("scene cut: threshold %s, min gap %d, %d of %zu pictures coded as I pictures at a cut\n", jnum(scene.threshold).c_str(),
-               scene.min_gap, cuts, scene_pictures.size());
+        fprintf(g_msg, "scene cut: threshold %s, min gap %d, %d of %zu pictures coded as I pictures at a cut\n", jnum(scene.threshold).c_str(),
+                scene.min_gap, cuts, scene_pictures.size());
         if (!scene.log.empty()) {
             std::string js = "{\"threshold\": " + jnum(scene.threshold) + ", \"min_gap\": " + std::to_string(scene.min_gap) +
                              ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) + ", \"pictures\": [";
@@ -2013,7 +2368,7 @@ int encode(const Args& a)
     }
     if (rate.on) {
         const double achieved = static_cast<double>(spent_bits) / (static_cast<double>(frame_num) * pixels);
-        printf("rate control: target %.4f bpp, coded %.4f bpp in %zu units\n", rate.target_bpp, achieved, rate_units.size());
+        fprintf(g_msg, "rate control: target %.4f bpp, coded %.4f bpp in %zu units\n", rate.target_bpp, achieved, rate_units.size());
         if (!rate.log.empty()) {
             std::string js = "{\"target_bpp\": " + jnum(rate.target_bpp) + ", \"achieved_bpp\": " + jnum(achieved) +
                              ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) +
@@ -2046,8 +2401,8 @@ int encode(const Args& a)
         }
         const double ave = count ? sum / static_cast<double>(count) : 0.0;
         if (quality.target_on) {
-            printf("quality: target %.4f dB, coded %.4f dB in %zu units, %lld trial codings\n", quality.target, ave, quality_units.size(),
-                   total_trials);
+            fprintf(g_msg, "quality: target %.4f dB, coded %.4f dB in %zu units, %lld trial codings\n", quality.target, ave, quality_units.size(),
+                    total_trials);
         }
         if (!quality.log.empty()) {
             std::string js = "{\"target_psnr\": " + (quality.target_on ? jnum(quality.target) : std::string("null")) +
@@ -2073,14 +2428,78 @@ int encode(const Args& a)
             fclose(lf);
         }
     }
-    FILE* of = fopen(a.str("o").c_str(), "wb");
-    if (!of || fwrite(out.data(), 1, out.size(), of) != out.size()) die("cannot write " + a.str("o"));
-    fclose(of);
+    size_t stream_bytes = out.size();
+    if (streaming) {
+        stream_bytes = static_cast<size_t>(out_bytes);
+        if (out_fd != 1 && ::close(out_fd) != 0) die("cannot write " + out_name);
+    } else {
+        FILE* of = fopen(a.str("o").c_str(), "wb");
+        if (!of || fwrite(out.data(), 1, out.size(), of) != out.size()) die("cannot write " + a.str("o"));
+        fclose(of);
+        for (LatencyUnit& lu : latency) lu.out_ms = now_ms();
+    }
+    if (!pipe.latency_log.empty()) {
+        std::string js = "{\"units\": [";
+        for (size_t i = 0; i < latency.size(); ++i) {
+            const LatencyUnit& u = latency[i];
+            js += std::string(i ? ", " : "") + "{\"type\": \"" + (u.intra ? "I" : "P") + "\", \"first_picture\": " + std::to_string(u.first_picture) +
+                  ", \"pictures\": " + std::to_string(u.pictures) + ", \"qp\": " + std::to_string(u.qp) + ", \"bytes\": " + std::to_string(u.bytes) +
+                  ", \"read_ms\": " + jnum(u.read_ms) + ", \"out_ms\": " + jnum(u.out_ms) + "}";
+        }
+        js += "], \"pictures\": " + std::to_string(frame_num) + ", \"bytes\": " + std::to_string(stream_bytes) + "}\n";
+        FILE* lf = fopen(pipe.latency_log.c_str(), "wb");
+        if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + pipe.latency_log);
+        fclose(lf);
+    }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    printf("encoded %d pictures (%dx%d) -> %zu bytes, %.4f bpp, %.1f pictures/s (file I/O included)\n", frame_num, g.W, g.H,
-           out.size(), 8.0 * out.size() / (static_cast<double>(frame_num) * g.H * g.W), frame_num / secs);
+    fprintf(g_msg, "encoded %d pictures (%dx%d) -> %zu bytes, %.4f bpp, %.1f pictures/s (file I/O included)\n", frame_num, g.W, g.H,
+            stream_bytes, 8.0 * stream_bytes / (static_cast<double>(frame_num) * g.H * g.W), frame_num / secs);
+    if (!input_error.empty()) die(input_error);
     return 0;
 }
+
+// The coded stream of decode -i, read front to back through dcvc_stream_next_unit: a regular file, stdin ("-")
+// or a FIFO alike. One buffer, grown to the largest need and reused, holds the units of one codec call - one unit, or the I
+// units --batch groups - plus the one unit of lookahead the grouping peeks at; every read asks for exactly what next_unit
+// says is missing, so nothing behind a unit's end is read before the unit has been decoded.
+struct UnitStream {
+    int fd = -1;
+    std::vector<uint8_t> buf;
+    size_t pos = 0, end = 0;       // the read position, and the bytes in the buffer
+    bool eof = false;
+    void open(const std::string& p)
+    {
+        fd = is_dash(p) ? 0 : ::open(p.c_str(), O_RDONLY);
+        if (fd < 0) die("cannot open " + p);
+    }
+    // the unit at the read position, whole in memory, without consuming it; false at the clean end of the stream. Truncated
+    // and malformed input throw dcvc::stream::StreamError, as the whole-buffer reader does.
+    bool peek(dcvc_stream_unit& u)
+    {
+        for (;;) {
+            if (dcvc::stream::next_unit(buf.data() + pos, end - pos, eof, u) > 0) return true;
+            if (u.need == 0) return false;
+            if (buf.size() < pos + u.need) buf.resize(pos + u.need);
+            const ssize_t k = read_upto(fd, buf.data() + end, pos + u.need - end);
+            if (k < 0) die(std::string("cannot read the stream: ") + strerror(errno));
+            end += static_cast<size_t>(k);
+            if (end - pos < u.need) eof = true;
+        }
+    }
+    // what lies in front of the read position has been decoded
+    void drop()
+    {
+        if (pos == 0) return;
+        std::memmove(buf.data(), buf.data() + pos, end - pos);
+        end -= pos;
+        pos = 0;
+    }
+    void close()
+    {
+        if (fd > 0) ::close(fd);
+        fd = -1;
+    }
+};
 
 // ------------------------------------------------------------------------------------ decode
 int decode(const Args& a)
@@ -2092,8 +2511,10 @@ int decode(const Args& a)
         die("--calc-ssim needs both picture sides >= 176 (the chroma planes must be at least 88 x 88 for MS-SSIM), --out-size is " +
             std::to_string(out_size.W) + "x" + std::to_string(out_size.H));
     }
-    // -o *.y4m: what the flags alone decide is refused before a model is loaded
-    const bool rec_y4m = a.has("o") && is_y4m_name(a.str("o"));
+    const PipeArgs pipe = pipe_args(a, false);
+    if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
+    // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
+    const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));
     int fps_num = 25, fps_den = 1;
     const bool has_fps = fps_arg(a, fps_num, fps_den);
     if (has_fps && !rec_y4m) die("--fps is the rate in the header of -o *.y4m");
@@ -2108,14 +2529,8 @@ int decode(const Args& a)
         if (is_rgb_name(t)) die("-o " + a.str("o") + ": a Y4M file holds YUV pictures, not --src-type " + t);
     }
     Codecs c = make_codecs(a.str("intra"), a.str("inter"));
-    std::vector<uint8_t> bin;
-    {
-        std::ifstream f(a.str("i"), std::ios::binary | std::ios::ate);
-        if (!f) die("cannot open " + a.str("i"));
-        bin.resize(static_cast<size_t>(f.tellg()));
-        f.seekg(0);
-        f.read(reinterpret_cast<char*>(bin.data()), static_cast<std::streamsize>(bin.size()));
-    }
+    UnitStream rd;
+    rd.open(a.str("i"));
     SrcType type = src_type(a.str("src-type", "yuv420"));
     int depth = bit_depth_arg(a, type);
     const bool has_rec = a.has("o"), has_ref = a.has("ref");
@@ -2124,7 +2539,7 @@ int decode(const Args& a)
     // type and the bit depth when the flags do not, and must agree with them when they do
     PictureFile ref_file;
     if (has_ref && !png) {
-        ref_file.open(a.str("ref"));
+        ref_file.open(a.str("ref"), pipe.in_format);
         if (ref_file.y4m) {
             const Y4mSource y = y4m_source(ref_file, a, false);
             type = y.type; depth = y.depth;
@@ -2137,8 +2552,20 @@ int decode(const Args& a)
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
     }
     hash.begin(wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
-    FILE* rec = has_rec && !png ? fopen(a.str("o").c_str(), "wb") : nullptr;
+    FILE* rec = !has_rec || png ? nullptr : is_dash(a.str("o")) ? stdout : fopen(a.str("o").c_str(), "wb");
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
+    // -o on a pipe ("-", a FIFO): every picture is flushed as it is written; a reader that has gone ends the run with status 1
+    const bool rec_piped = rec != nullptr && !fd_is_regular(fileno(rec));
+    auto rec_put = [&](const void* p, size_t n) {
+        if (fwrite(p, 1, n, rec) == n) return;
+        if (errno == EPIPE) output_closed(a.str("o"));
+        die("short write");
+    };
+    auto rec_flush = [&]() {
+        if (!rec_piped || fflush(rec) == 0) return;
+        if (errno == EPIPE) output_closed(a.str("o"));
+        die("short write");
+    };
     // -o *.y4m: the header once the first picture's size is known, then a FRAME line in front of every picture
     bool rec_header_done = false;
     auto rec_frame = [&](const Geometry& og) {
@@ -2151,10 +2578,10 @@ int decode(const Args& a)
             char line[256];
             const int n = dcvc_y4m_write_header(line, sizeof(line), &hi);
             abi_ok(n, "y4m header");
-            if (fwrite(line, 1, static_cast<size_t>(n), rec) != static_cast<size_t>(n)) die("short write");
+            rec_put(line, static_cast<size_t>(n));
             rec_header_done = true;
         }
-        if (fwrite("FRAME\n", 1, 6, rec) != 6) die("short write");
+        rec_put("FRAME\n", 6);
     };
     PngDir ref_pngs, rec_pngs;
     if (png && has_ref) ref_pngs = png_dir(a.str("ref"));
@@ -2167,7 +2594,6 @@ int decode(const Args& a)
     const bool calc_ssim = a.num("calc-ssim", 0) != 0, verbose_json = a.num("verbose-json", 0) != 0;
     if (calc_ssim && !has_ref) die("--calc-ssim needs --ref (the source pictures)");
     const int limit = a.num("n", 1 << 30);
-    dcvc::stream::Reader rd(bin.data(), bin.size());
     dcvc::stream::SpsTable sps;
     Geometry g;
     DeviceBuffers b;
@@ -2191,15 +2617,16 @@ int decode(const Args& a)
         fprintf(stderr, "dcvc: warning: %d-picture chunks and neither -n nor --ref: a short last chunk is written with its "
                         "padding pictures (the container does not carry the picture count)\n", c.frames_per_p);
     }
-    while (!rd.at_end() && decoded < limit && !source_ended) {
-        int nal = 0, sid = 0;
-        const size_t unit_start = rd.position();
-        rd.header(nal, sid);
+    while (decoded < limit && !source_ended) {
+        rd.drop();                         // the units of the previous codec call leave the buffer
+        dcvc_stream_unit u;
+        if (!rd.peek(u)) break;
+        const size_t payload_at = rd.pos + u.payload_offset;
+        rd.pos += u.unit_bytes;
+        const int nal = u.nal_type, sid = u.sps_id;
         if (nal == dcvc::stream::kSps) {
-            int h = 0, w = 0;
-            rd.sps_remaining(h, w);
-            sps.add(sid, h, w);
-            pending_sps_bits += 8 * (rd.position() - unit_start);
+            sps.add(sid, u.height, u.width);
+            pending_sps_bits += 8 * u.unit_bytes;
             continue;
         }
         const dcvc::stream::SpsTable::Sps* s = sps.find(sid);
@@ -2244,43 +2671,37 @@ int decode(const Args& a)
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
-        int qp = 0, ec = 0;
-        bool reset = false;
-        const uint8_t* payload = nullptr;
-        size_t n = 0;
-        rd.ip_remaining(qp, ec, reset, payload, n);
+        const int qp = u.qp, ec = u.ec_part;
+        const bool reset = u.reset != 0;
+        const size_t n = u.payload_bytes;
         const bool intra = nal == dcvc::stream::kIntra;
         int frames = 1;
         // bits of each picture's unit (an 8-picture chunk: all on its first picture); a new parameter set counts with the next unit
-        std::vector<double> unit_bits{8.0 * (rd.position() - unit_start) + pending_sps_bits};
+        std::vector<double> unit_bits{8.0 * u.unit_bytes + pending_sps_bits};
         pending_sps_bits = 0;
         if (intra && batch > 1) {
             // --batch: this and up to batch - 1 following I units of the same size and qp in one call (a parameter set, a P unit,
-            // another size or qp ends the group)
-            std::vector<const uint8_t*> pls{payload};
+            // another size or qp ends the group). The buffer may move while it takes the next unit in: offsets until the call.
+            std::vector<size_t> at{payload_at};
             std::vector<size_t> sizes{n};
             std::vector<int> ecs{ec};
-            while (static_cast<int>(pls.size()) < batch && decoded + static_cast<int>(pls.size()) < limit && !rd.at_end()) {
-                dcvc::stream::Reader peek = rd;
-                const size_t start = peek.position();
-                int nal2 = 0, sid2 = 0, qp2 = 0, ec2 = 0;
-                bool reset2 = false;
-                const uint8_t* pl2 = nullptr;
-                size_t n2 = 0;
+            while (static_cast<int>(at.size()) < batch && decoded + static_cast<int>(at.size()) < limit) {
+                dcvc_stream_unit u2;
                 try {
-                    peek.header(nal2, sid2);
-                    if (nal2 != dcvc::stream::kIntra) break;
-                    const dcvc::stream::SpsTable::Sps* s2 = sps.find(sid2);
-                    if (s2 == nullptr || s2->height != g.H || s2->width != g.W) break;
-                    peek.ip_remaining(qp2, ec2, reset2, pl2, n2);
+                    if (!rd.peek(u2)) break;
                 } catch (const std::exception&) {
                     break;              // a malformed unit: the single path below reports it
                 }
-                if (qp2 != qp) break;
-                rd = peek;
-                pls.push_back(pl2); sizes.push_back(n2); ecs.push_back(ec2);
-                unit_bits.push_back(8.0 * (rd.position() - start));
+                if (u2.nal_type != dcvc::stream::kIntra) break;
+                const dcvc::stream::SpsTable::Sps* s2 = sps.find(u2.sps_id);
+                if (s2 == nullptr || s2->height != g.H || s2->width != g.W) break;
+                if (u2.qp != qp) break;
+                at.push_back(rd.pos + u2.payload_offset); sizes.push_back(u2.payload_bytes); ecs.push_back(u2.ec_part);
+                rd.pos += u2.unit_bytes;
+                unit_bits.push_back(8.0 * u2.unit_bytes);
             }
+            std::vector<const uint8_t*> pls;
+            for (size_t off : at) pls.push_back(rd.buf.data() + off);
             frames = static_cast<int>(pls.size());
             abi_ok(dcvc_dmci_decompress_batch(c.intra, frames, pls.data(), sizes.data(), ecs.data(), qp, g.H, g.W, b.x_hat, b.st),
                    "intra decompress");
@@ -2290,13 +2711,13 @@ int decode(const Args& a)
                 if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, xh, g.Hp, g.Wp, 0, b.st), "add_ref");
             }
         } else if (intra) {
-            abi_ok(dcvc_dmci_decompress(c.intra, payload, n, qp, g.H, g.W, ec, b.x_hat, b.st), "intra decompress");
+            abi_ok(dcvc_dmci_decompress(c.intra, rd.buf.data() + payload_at, n, qp, g.H, g.W, ec, b.x_hat, b.st), "intra decompress");
             if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 0, b.st), "add_ref");
             if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 0, b.st), "add_ref");
         } else if (c.ld) {
-            abi_ok(dcvc_dmcld_decompress(c.ld, payload, n, qp, g.H, g.W, ec, reset ? 1 : 0, b.x_hat, b.st), "inter decompress");
+            abi_ok(dcvc_dmcld_decompress(c.ld, rd.buf.data() + payload_at, n, qp, g.H, g.W, ec, reset ? 1 : 0, b.x_hat, b.st), "inter decompress");
         } else if (c.ht) {
-            abi_ok(dcvc_dmcht_decompress(c.ht, payload, n, qp, g.H, g.W, ec, reset ? 1 : 0, b.x_hat, b.st), "inter decompress");
+            abi_ok(dcvc_dmcht_decompress(c.ht, rd.buf.data() + payload_at, n, qp, g.H, g.W, ec, reset ? 1 : 0, b.x_hat, b.st), "inter decompress");
             frames = c.frames_per_p;
         } else {
             die("the stream holds P pictures but no inter model was given");
@@ -2348,7 +2769,8 @@ int decode(const Args& a)
                 if (has_rec) {
                     hip_ok(hipStreamSynchronize(b.st), "sync");
                     rec_frame(go);
-                    if (fwrite(so.h_out, 1, go.frame_bytes(), rec) != go.frame_bytes()) die("short write");
+                    rec_put(so.h_out, go.frame_bytes());
+                    rec_flush();
                 }
                 types.push_back(intra ? 0 : 1);
                 bits.push_back(j < static_cast<int>(unit_bits.size()) ? unit_bits[static_cast<size_t>(j)] : 0.0);
@@ -2370,7 +2792,8 @@ int decode(const Args& a)
             if (has_rec && wire >= 0) {
                 hip_ok(hipMemcpyAsync(ws.h_out, ws.out, g.file_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
-                if (fwrite(ws.h_out, 1, g.file_bytes(), rec) != g.file_bytes()) die("short write");
+                rec_put(ws.h_out, g.file_bytes());
+                rec_flush();
             } else if (has_rec) {
                 hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
@@ -2380,7 +2803,8 @@ int decode(const Args& a)
                     abi_ok(dcvc_png_write_rgb(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
                 } else {
                     rec_frame(g);
-                    if (fwrite(b.h_yuv, 1, g.frame_bytes(), rec) != g.frame_bytes()) die("short write");
+                    rec_put(b.h_yuv, g.frame_bytes());
+                    rec_flush();
                 }
             }
             if (has_ref && g.rgb16()) {
@@ -2516,16 +2940,20 @@ int decode(const Args& a)
     if (have_buffers) free_buffers(b);
     ws.destroy();
     so.destroy();
-    if (rec) fclose(rec);
+    if (rec && fclose(rec) != 0) {
+        if (errno == EPIPE) output_closed(a.str("o"));
+        die("short write");
+    }
     ref_file.close();
+    rd.close();
     hash.finish();
     const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (out_size.on) {
-        printf("decoded %d pictures (%dx%d, output at %dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, go.W, go.H,
-               decoded / secs);
+        fprintf(g_msg, "decoded %d pictures (%dx%d, output at %dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, go.W, go.H,
+                decoded / secs);
     } else {
-        printf("decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
+        fprintf(g_msg, "decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
     }
     if (a.has("json")) {
         if (psnr.size() != types.size()) die("--json needs --ref (PSNR per picture)");
@@ -2599,6 +3027,8 @@ int main(int argc, char** argv)
     // with ROCclr's default of 4 the throughput of several codec objects in one process depends on their creation order);
     // a value in the environment wins
     setenv("GPU_MAX_HW_QUEUES", "1", 0);
+    // a pipe whose reader has gone: the write fails with EPIPE and the run ends with status 1 and one line (output_closed)
+    signal(SIGPIPE, SIG_IGN);
     if (argc < 2) die("usage: dcvc encode|decode ... (see the head of dcvc_cli.hip)");
     const std::string mode = argv[1];
     try {

@@ -92,6 +92,59 @@ void Reader::ip_remaining(int& qp, int& ec_part, bool& reset, const uint8_t*& pa
     payload = take(n);
 }
 
+namespace {
+
+// bytes of the varuint whose first byte is `first`
+size_t uint_bytes(uint8_t first)
+{
+    const int tag = first >> 6;
+    return tag < 2 ? 1 : tag == 2 ? 2 : 4;
+}
+
+}  // namespace
+
+int64_t next_unit(const uint8_t* src, size_t n, bool at_eof, dcvc_stream_unit& u)
+{
+    u = dcvc_stream_unit{};
+    if (n == 0 && at_eof) return 0;                   // the clean end of the stream
+    // the buffer ends inside the unit: `total` bytes are known to belong to it so far
+    auto more = [&](size_t total) -> int64_t {
+        if (at_eof) throw StreamError(-2, "container: truncated stream");
+        u.need = total;
+        return 0;
+    };
+    if (n == 0) return more(1);
+    u.nal_type = src[0] >> 4;
+    u.sps_id = src[0] & 0x0F;
+    if (u.nal_type > kInter) throw StreamError(-3, "container: unknown unit type");
+    if (u.nal_type == kSps) {
+        // header, varuint height, varuint width: at least one byte each
+        if (n < 2) return more(3);
+        const size_t lh = uint_bytes(src[1]);
+        if (n < 2 + lh) return more(2 + lh);
+        const size_t total = 1 + lh + uint_bytes(src[1 + lh]);
+        if (n < total) return more(total);
+        Reader r(src + 1, total - 1);
+        r.sps_remaining(u.height, u.width);
+        u.unit_bytes = total;
+        return static_cast<int64_t>(total);
+    }
+    // header, qp, flags, varuint length (at least one byte), payload
+    if (n < 4) return more(4);
+    const size_t head = 3 + uint_bytes(src[3]);
+    if (n < head) return more(head);
+    Reader r(src + 3, head - 3);
+    const size_t len = r.get_uint();
+    if (n < head + len) return more(head + len);
+    u.qp = src[1];
+    u.ec_part = src[2] >> 1;
+    u.reset = src[2] & 1;
+    u.payload_offset = head;
+    u.payload_bytes = len;
+    u.unit_bytes = head + len;
+    return static_cast<int64_t>(u.unit_bytes);
+}
+
 int SpsTable::id_for(int height, int width, bool& is_new)
 {
     int top = -1;
@@ -226,6 +279,11 @@ int64_t dcvc_stream_read_ip_remaining(const uint8_t* src, size_t n, int* qp, int
         *reset_feature_memory = reset ? 1 : 0;
         return static_cast<int64_t>(r.position());
     });
+}
+
+int64_t dcvc_stream_next_unit(const uint8_t* src, size_t n, int at_eof, dcvc_stream_unit* u)
+{
+    return guarded_stream([&] { return dcvc::stream::next_unit(src, n, at_eof != 0, *u); });
 }
 
 }  // extern "C"

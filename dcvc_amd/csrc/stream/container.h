@@ -2,6 +2,8 @@
 // (stream_helper.py:37-154). C++ face of the C ABI, used by the standalone encoder / decoder.
 #pragma once
 
+#include "dcvc_amd_stream.h"
+
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
@@ -40,6 +42,11 @@ private:
     size_t m_n;
     size_t m_pos = 0;
 };
+
+// feed-style parser over a buffer that may end inside a unit (dcvc_stream_next_unit, include/dcvc_amd_stream.h): the bytes of
+// the unit at src, or 0 with u.need set (at_eof: 0 with u.need 0 at n == 0, else StreamError -2); StreamError -3 where
+// Reader::header refuses
+int64_t next_unit(const uint8_t* src, size_t n, bool at_eof, dcvc_stream_unit& u);
 
 // sequence parameter sets by picture size, ids 0..15 (SPSHelper, stream_helper.py:157-192)
 class SpsTable {

@@ -9,6 +9,7 @@ Format (restated from /root/reference/src/utils/stream_helper.py:37-154):
   varuint       < 2^7: 1 byte 0vvvvvvv;  < 2^14: 2 bytes 10vvvvvv vvvvvvvv;  < 2^30: 4 bytes 11vvvvvv ...
                 (big endian; the tag lives in the two top bits of the first byte)
 """
+import ctypes
 import enum
 
 
@@ -89,6 +90,55 @@ def read_ip_remaining(f):
     qp, flag = _get(f, 2)
     length = read_uint_adaptive(f)
     return qp, flag >> 1, flag & 1, _get(f, length)
+
+
+class _Unit(ctypes.Structure):
+    """dcvc_stream_unit (include/dcvc_amd_stream.h)"""
+    _fields_ = [("nal_type", ctypes.c_int), ("sps_id", ctypes.c_int), ("height", ctypes.c_int), ("width", ctypes.c_int),
+                ("qp", ctypes.c_int), ("ec_part", ctypes.c_int), ("reset", ctypes.c_int),
+                ("payload_offset", ctypes.c_size_t), ("payload_bytes", ctypes.c_size_t), ("unit_bytes", ctypes.c_size_t),
+                ("need", ctypes.c_size_t)]
+
+
+def next_unit(buf, at_eof):
+    """dcvc_stream_next_unit on the bytes read so far -> (rc, unit). rc > 0: ``unit`` (a dict) starts at buf[0] and takes rc
+    bytes, an I / P unit's payload included as bytes; rc == 0: ``unit`` is {"need": n} - the buffer must hold n bytes before
+    the next call (0: the clean end of the stream). Truncated (-2) and malformed (-3) input raise DcvcError."""
+    from . import _lib
+    fn = _lib.fn("dcvc_stream_next_unit", ctypes.c_int64, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(_Unit)])
+    data = bytes(buf)
+    u = _Unit()
+    rc = _lib.check(fn(data, len(data), 1 if at_eof else 0, ctypes.byref(u)))
+    if rc == 0:
+        return 0, {"need": u.need}
+    if u.nal_type == NalType.NAL_SPS:
+        return rc, {"nal_type": NalType.NAL_SPS, "sps_id": u.sps_id, "height": u.height, "width": u.width}
+    return rc, {"nal_type": NalType(u.nal_type), "sps_id": u.sps_id, "qp": u.qp, "ec_part": u.ec_part, "reset": u.reset,
+                "payload": data[u.payload_offset:u.payload_offset + u.payload_bytes]}
+
+
+def iter_units(fileobj):
+    """The units of a stream that arrives through ``fileobj.read(n)`` alone (a pipe, a socket's file): never reads past the end
+    of a unit, never seeks. A stream that ends inside a unit raises DcvcError."""
+    buf = b""
+    need = 1
+    while True:
+        at_eof = False
+        while len(buf) < need:
+            got = fileobj.read(need - len(buf))
+            if not got:
+                at_eof = True
+                break
+            buf += got
+        rc, unit = next_unit(buf, at_eof)
+        if rc > 0:
+            yield unit
+            buf = buf[rc:]
+            need = 1
+        elif unit["need"] == 0:
+            return
+        else:
+            need = unit["need"]
 
 
 class SPSHelper:

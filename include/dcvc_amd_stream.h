@@ -14,6 +14,11 @@
  * Everything works on caller memory (no FILE*, no allocation): writers return the number of bytes
  * produced, readers the number consumed; a negative value is an error (dcvc_last_error()):
  * -1 destination too small / value out of range, -2 truncated input, -3 malformed input.
+ *
+ * The readers above want the whole unit in memory. dcvc_stream_next_unit is the feed-style parser beside them, for
+ * streams that arrive through a pipe: it is given whatever has been read so far and either returns one complete unit
+ * or says how many bytes the buffer must hold before it is worth calling again - so a caller reads exactly that much
+ * and never past the end of a unit (stream_helper.iter_units; dcvc decode reads every stream through it).
  */
 #ifndef DCVC_AMD_STREAM_H
 #define DCVC_AMD_STREAM_H
@@ -54,6 +59,23 @@ int dcvc_stream_read_sps_remaining(const uint8_t* src, size_t n, int* height, in
  * *payload points into src. Returns header + payload bytes consumed. */
 int64_t dcvc_stream_read_ip_remaining(const uint8_t* src, size_t n, int* qp, int* ec_part,
                                       int* reset_feature_memory, const uint8_t** payload, size_t* payload_bytes);
+
+/* one unit as dcvc_stream_next_unit found it: the payload of an I / P unit is src + payload_offset */
+typedef struct {
+    int nal_type, sps_id;                  /* DCVC_NAL_* */
+    int height, width;                     /* SPS */
+    int qp, ec_part, reset;                /* I / P */
+    size_t payload_offset, payload_bytes, unit_bytes, need;
+} dcvc_stream_unit;
+
+/* The unit that starts at src, of which n bytes are in memory; at_eof != 0: no more bytes will follow.
+ *   > 0   one complete unit (SPS, I or P): that many bytes are consumed, the fields are filled (need = 0)
+ *   0     the buffer ends inside a unit and at_eof == 0: nothing is consumed; u->need is the smallest total length known
+ *         so far to be required - greater than n, never more than the unit's length: read up to it and call again
+ *   0     with need 0: n == 0 and at_eof != 0, the clean end of the stream
+ *   -2    at_eof != 0 and n > 0, but the buffer ends inside a unit
+ *   -3    malformed input, where dcvc_stream_read_header says so (an unknown unit type), with its message */
+int64_t dcvc_stream_next_unit(const uint8_t* src, size_t n, int at_eof, dcvc_stream_unit* u);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,10 @@ struct dcvc_rc {
     dcvc::TargetBpp ctl;
 };
 
+struct dcvc_rc_vbv {
+    dcvc::Vbv vbv;
+};
+
 struct dcvc_scd {
     dcvc::SceneCut scd;
 };
@@ -48,9 +52,69 @@ int dcvc_rc_update(dcvc_rc* rc, double bits, int pictures, int is_intra)
     });
 }
 
+int dcvc_rc_update_at(dcvc_rc* rc, double bits, int pictures, int is_intra, int qp)
+{
+    return dcvc::guarded([&] {
+        if (rc == nullptr) throw std::invalid_argument("null rate controller");
+        rc->ctl.update_at(bits, pictures, is_intra != 0, qp);
+    });
+}
+
 double dcvc_rc_state_qp(const dcvc_rc* rc)
 {
     return rc ? rc->ctl.qp() : -1.0;
+}
+
+dcvc_rc_vbv* dcvc_rc_vbv_create(double maxrate_bpp, double bufsize_pictures, double init, long long pixels)
+{
+    dcvc_rc_vbv* v = nullptr;
+    dcvc::guarded([&] { v = new dcvc_rc_vbv{dcvc::Vbv(maxrate_bpp, bufsize_pictures, init, pixels)}; });
+    return v;
+}
+
+void dcvc_rc_vbv_destroy(dcvc_rc_vbv* v)
+{
+    delete v;
+}
+
+int64_t dcvc_rc_vbv_available(const dcvc_rc_vbv* v)
+{
+    int64_t avail = -1;
+    const int e = dcvc::guarded([&] {
+        if (v == nullptr) throw std::invalid_argument("null vbv model");
+        avail = v->vbv.available();
+    });
+    return e < 0 ? e : avail;
+}
+
+int dcvc_rc_vbv_admit(dcvc_rc_vbv* v, int64_t bits, int pictures)
+{
+    int violated = 0;
+    const int e = dcvc::guarded([&] {
+        if (v == nullptr) throw std::invalid_argument("null vbv model");
+        violated = v->vbv.admit(bits, pictures) ? 1 : 0;
+    });
+    return e < 0 ? e : violated;
+}
+
+double dcvc_rc_vbv_fullness(const dcvc_rc_vbv* v)
+{
+    return v ? v->vbv.fullness() : -1.0;
+}
+
+double dcvc_rc_vbv_capacity(const dcvc_rc_vbv* v)
+{
+    return v ? v->vbv.capacity() : -1.0;
+}
+
+double dcvc_rc_vbv_rate(const dcvc_rc_vbv* v)
+{
+    return v ? v->vbv.rate() : -1.0;
+}
+
+int64_t dcvc_rc_vbv_underflow(const dcvc_rc_vbv* v)
+{
+    return v ? v->vbv.underflow() : -1;
 }
 
 int dcvc_rc_pick_qp_for_budget(dcvc_rc_estimate_fn estimate, void* user, int64_t budget_bits, int qp_min, int qp_max,

@@ -16,6 +16,7 @@
 //               [--target-psnr DB [--qp-min 0] [--qp-max 63]] [--quality-log log.json]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
+//               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
@@ -127,6 +128,28 @@
 //               that start value plus --rc-intra-bonus, and their bits count as spent. --rc-log: "mode": "probe", P units
 //               with probes >= 1 and predicted_bytes, I units with probes 0 and null. All-intra runs ignore the flag (they
 //               probe already); the stream format and the decoder do not change.
+//               --vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init F] [--vbv-log FILE] (encode): a capped rate, on top of
+//               any rate mode - constant --qp-i / --qp-p, --target-bpp in both modes, all-intra runs - with LD, HT-S and HT-L, --scene-cut,
+//               --scale, pipes, --read-ahead and --flush-units. The decoder-buffer model of dcvc_amd_rc.h (dcvc_rc_vbv_*): r = BPP W H
+//               bits arrive per picture period (W H of the coded size), the buffer holds C = PICTURES r bits and starts at F C
+//               (default 0.9). A unit - 8 times every byte it adds to the file, --latency-log's bytes - must fit avail = floor(fullness)
+//               when its first picture is due; behind it the fullness is min(C, fullness - bits + n r), n = the source pictures it holds
+//               (1, 8 for an HT chunk, what the source held for a ragged last chunk). Nothing is padded at the top. Every unit is coded
+//               at the q_index its rate mode gives (the modes that search on a budget search on the smaller of theirs and the buffer's)
+//               and written when it fits: a P unit then costs one export of the inter codec's state, no probe, and a bucket that never
+//               binds leaves the file of the run without the flags. When it does not fit, the state is put back, the largest q_index
+//               below whose predicted stream fits is searched on the unit's size probe (dcvc_rc_pick_qp_near from q - 1, down to
+//               --qp-min with --target-bpp, else 0) and coded; the coder may exceed the prediction, so the q_index then steps down
+//               until the unit fits. At the floor a unit that does not fit is written anyway, with a warning on stderr, and counts as
+//               a violation; the exit status stays 0. One summary line: capacity, minimum fullness, units lowered, recodes, violations.
+//               --vbv-log: {maxrate_bpp, bufsize_pictures, init, width, height, rate_bits, capacity_bits, units: [{type,
+//               first_picture, pictures, qp_mode, qp, probes, recodes, predicted_bytes | null, bytes, fullness_before, fullness_after,
+//               violated, underflow_bits}], min_fullness, lowered, recodes, violations}; qp_mode is what the rate mode gave - for a
+//               unit whose search was held under the buffer's budget, the largest probed q_index that fits the mode's own budget.
+//               --rc-log keeps its keys and reports the final q_index. The stream format and the decoder do not change. Refused before
+//               a model is loaded: one of the pair without the other, a value that is not finite or not positive, --vbv-init outside
+//               (0, 1], --vbv-init / --vbv-log without the pair, --batch above 1, --target-psnr, a log named "-", any of the flags on
+//               decode.
 //               --quality-log FILE (encode, any rate mode): the encoder measures every coded unit's reconstruction - an
 //               I picture's intra x_hat, a P unit's pictures from dcvc_dmcld_reconstruct / dcvc_dmcht_reconstruct, which leave the
 //               temporal state as it is - against the source samples it uploaded (with --scale: the resampled planes, at the coded
@@ -1064,7 +1087,7 @@ PipeArgs pipe_args(const Args& a, bool encoding)
         if (a.has("in-format") || a.has("out-format")) die("--in-format / --out-format are for raw and Y4M files: --src-type " + t + " is a directory of PNG pictures");
     }
     if (a.has("ref") && is_dash(a.str("i")) && is_dash(a.str("ref"))) die("-i - together with --ref -: stdin carries one of the two");
-    for (const char* k : {"json", "rc-log", "scene-log", "quality-log", "hash-log", "latency-log"}) {
+    for (const char* k : {"json", "rc-log", "scene-log", "quality-log", "hash-log", "latency-log", "vbv-log"}) {
         if (a.has(k) && is_dash(a.str(k))) {
             die(std::string("--") + k + " -: a log goes to a file of its own" + (a.has("o") && is_dash(a.str("o")) ? " (-o - has the standard output)" : ""));
         }
@@ -1147,6 +1170,66 @@ RateArgs rate_args(const Args& a, int batch)
     r.probe = mode == "probe";
     return r;
 }
+
+// --vbv-maxrate / --vbv-bufsize with --vbv-init and --vbv-log, refused before a model is loaded
+struct VbvArgs {
+    bool on = false;
+    double maxrate = 0, bufsize = 0, init = 0.9;
+    std::string log;
+};
+
+VbvArgs vbv_args(const Args& a, int batch, bool encoding)
+{
+    VbvArgs v;
+    if (!encoding) {
+        for (const char* k : {"vbv-maxrate", "vbv-bufsize", "vbv-init", "vbv-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+        }
+        return v;
+    }
+    if (a.has("vbv-maxrate") != a.has("vbv-bufsize")) {
+        die(a.has("vbv-maxrate") ? "--vbv-maxrate needs --vbv-bufsize: the rate and the buffer size make the model together"
+                                 : "--vbv-bufsize needs --vbv-maxrate: the rate and the buffer size make the model together");
+    }
+    if (!a.has("vbv-maxrate")) {
+        for (const char* k : {"vbv-init", "vbv-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --vbv-maxrate and --vbv-bufsize");
+        }
+        return v;
+    }
+    v.on = true;
+    auto number = [&](const char* k, double def) {
+        if (!a.has(k)) return def;
+        const std::string s = a.str(k);
+        char* end = nullptr;
+        const double d = strtod(s.c_str(), &end);
+        if (s.empty() || *end != '\0') die(std::string("--") + k + " must be a number, got " + s);
+        return d;
+    };
+    v.maxrate = number("vbv-maxrate", 0);
+    v.bufsize = number("vbv-bufsize", 0);
+    v.init = number("vbv-init", 0.9);
+    // what dcvc_rc_vbv_create refuses of the three values, in its words; the picture size comes later
+    dcvc_rc_vbv* probe = dcvc_rc_vbv_create(v.maxrate, v.bufsize, v.init, 1);
+    if (!probe) {
+        die(std::string("--vbv-maxrate ") + a.str("vbv-maxrate") + " --vbv-bufsize " + a.str("vbv-bufsize") + " --vbv-init " + a.str("vbv-init", "0.9") +
+            ": " + dcvc_last_error());
+    }
+    dcvc_rc_vbv_destroy(probe);
+    if (batch > 1) die("--vbv-maxrate cannot be combined with --batch above 1: a batch has one q_index");
+    if (a.has("target-psnr")) die("--vbv-maxrate cannot be combined with --target-psnr: coding to a quality under a cap is not built");
+    v.log = a.str("vbv-log");
+    if (a.has("vbv-log") && v.log.empty()) die("--vbv-log needs a file name");
+    return v;
+}
+
+// one coded unit in --vbv-log
+struct VbvUnit {
+    bool intra = false, violated = false;
+    int first_picture = 0, pictures = 0, qp_mode = -1, qp = 0, probes = 0, recodes = 0;
+    long long predicted_bytes = -1, bytes = 0, underflow_bits = 0;      // -1: no prediction; bytes: what the unit added to the file
+    double fullness_before = 0, fullness_after = 0;
+};
 
 // --target-psnr with --qp-min / --qp-max, and --quality-log, refused before anything touches the device
 struct QualityArgs {
@@ -1811,6 +1894,7 @@ int encode(const Args& a)
     HashRun hash;
     hash.parse(a, true);
     const PipeArgs pipe = pipe_args(a, true);
+    const VbvArgs vbv_arg = vbv_args(a, batch, true);
     if (is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the stream
     if (batch > 1 && a.has("inter") && a.num("intra-period", -1) != 1) {
         die("--batch codes intra pictures only: all-intra runs (no --inter, or --intra-period 1)");
@@ -1850,6 +1934,12 @@ int encode(const Args& a)
     if (rgb) colour.apply(gs);
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
+    // --vbv-maxrate / --vbv-bufsize: the decoder-buffer model counts the pixels of the coded size, as the rate controller does
+    dcvc_rc_vbv* vbv = nullptr;
+    if (vbv_arg.on) {
+        vbv = dcvc_rc_vbv_create(vbv_arg.maxrate, vbv_arg.bufsize, vbv_arg.init, static_cast<long long>(g.H) * g.W);
+        if (!vbv) die(std::string("--vbv-maxrate / --vbv-bufsize: ") + dcvc_last_error());
+    }
     if (scene.on) {
         const int kind = weight_kind(a.str("inter"));      // from the file's header, before either model is built
         if (kind == 2 || kind == 3) {
@@ -1881,7 +1971,7 @@ int encode(const Args& a)
     QualityMeter meter;
     if (quality.on()) meter.create(g, std::max(delay, batch));
     std::vector<QualityUnit> quality_units;
-    void* trial_state = nullptr;           // --target-psnr: the inter codec's state in front of a P unit's trials
+    void* trial_state = nullptr;           // --target-psnr, --vbv-*: the inter codec's state in front of a P unit's trials / codings
     long long trial_state_bytes = 0;
     void* kept_dev = nullptr;              // ... and what the last trial that met left: the intra x_hat, or the inter codec's state
     size_t kept_cap = 0;
@@ -2003,6 +2093,7 @@ int encode(const Args& a)
         slot_held = false;
     };
     // the unit of `pictures` source pictures from first_picture on, the last of them read at read_ms
+    // -> the bytes the unit added to the stream, a parameter set in front of it included
     auto put_unit = [&](bool intra, int qp, int ec, int reset, const std::vector<uint8_t>& pl, int first_picture, int pictures, double read_ms) {
         const size_t before = out.size();
         bool is_new = false;
@@ -2023,6 +2114,7 @@ int encode(const Args& a)
             lu.out_ms = now_ms();
         }
         if (!pipe.latency_log.empty()) latency.push_back(lu);
+        return lu.bytes;
     };
     // --target-bpp: all-intra runs search the q_index of every picture on the size probe, runs with an inter model follow the
     // feedback controller (rate_control.code_sequence with TargetBpp)
@@ -2039,9 +2131,21 @@ int encode(const Args& a)
     }
     std::vector<RateUnit> rate_units;
     long long spent_bits = 0;
+    std::vector<VbvUnit> vbv_units;
+    bool vbv_first_unit = true;            // the first unit has the parameter set in front (one coded size per run)
     struct Probe {
         dcvc_dmci* codec; const void* x; int H, W, pad_b, pad_r; void* st;
         std::map<int, long long> bytes;                // predicted stream bytes of every q_index probed
+    };
+    // --vbv-*: qp_mode of a unit whose search ran on min(the mode's own budget, the buffer's payload budget) - the largest probed
+    // q_index whose prediction fits the own budget (rate_control.vbv_searched_qp_mode): the mode's answer when the cap does not
+    // bind, a lower bound of it when it does
+    auto searched_qp_mode = [](int qp, const std::map<int, long long>& probed, int64_t own_budget) {
+        int best = qp;
+        for (const auto& kv : probed) {
+            if (8 * kv.second <= own_budget && kv.first > best) best = kv.first;
+        }
+        return best;
     };
     auto probe_bits = [](int qp, void* user) -> int64_t {
         Probe& p = *static_cast<Probe*>(user);
@@ -2151,12 +2255,26 @@ int encode(const Args& a)
         long long nbytes = 0;
         RateUnit ru;
         ru.intra = intra;
+        // --vbv-*: what the unit may take, and what its payload may (rate_control.vbv_payload_budget): the container's bytes
+        // around the longest payload that fits bound those around every shorter one
+        VbvUnit vu;
+        int64_t vbv_avail = 0, vbv_payload_avail = 0;
+        auto vbv_overhead = [&](size_t payload_bytes) {
+            return static_cast<long long>(dcvc::stream::unit_overhead(payload_bytes, vbv_first_unit, g.H, g.W));
+        };
+        if (vbv) {
+            vu.fullness_before = dcvc_rc_vbv_fullness(vbv);
+            vbv_avail = dcvc_rc_vbv_available(vbv);
+            const int64_t longest = std::min<int64_t>(std::max<int64_t>(vbv_avail, 0) / 8, (1 << 30) - 1);
+            vbv_payload_avail = vbv_avail - 8 * vbv_overhead(static_cast<size_t>(longest));
+        }
         if (rate_search) {
             Probe p{c.intra, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
-            const int64_t budget = dcvc_rc_intra_budget_bits(rate.target_bpp, pixels, idx, spent_bits);
-            qp = dcvc_rc_pick_qp_for_budget(probe_bits, &p, budget, rate.qp_min, rate.qp_max, &ru.probes);
+            const int64_t own = dcvc_rc_intra_budget_bits(rate.target_bpp, pixels, idx, spent_bits);
+            qp = dcvc_rc_pick_qp_for_budget(probe_bits, &p, vbv ? std::min(own, vbv_payload_avail) : own, rate.qp_min, rate.qp_max, &ru.probes);
             abi_ok(qp, "size probe");
             ru.predicted_bytes = p.bytes.at(qp);
+            vu.qp_mode = searched_qp_mode(qp, p.bytes, own);
         } else if (ctl) {
             qp = dcvc_rc_next_qp(ctl, intra ? 1 : 0);
             abi_ok(qp, "rate control");
@@ -2166,9 +2284,11 @@ int encode(const Args& a)
             InterProbe p{c.ld, c.ht, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
             const int64_t budget = dcvc_rc_unit_budget_bits(rate.target_bpp, pixels, pictures_coded, spent_bits, rate.horizon, want);
             abi_ok(budget, "rate control");
-            qp = dcvc_rc_pick_qp_near(inter_probe_bits, &p, budget, start_q, rate.qp_min, rate.qp_max, &ru.probes);
+            qp = dcvc_rc_pick_qp_near(inter_probe_bits, &p, vbv ? std::min(budget, vbv_payload_avail) : budget, start_q, rate.qp_min, rate.qp_max,
+                                      &ru.probes);
             abi_ok(qp, "size probe");
             ru.predicted_bytes = p.bytes.at(qp);
+            vu.qp_mode = searched_qp_mode(qp, p.bytes, budget);
             start_q = qp;
         }
         // --quality-log / --target-psnr: the unit's reconstruction measured on the device. An I picture's is the intra x_hat; a P
@@ -2290,6 +2410,62 @@ int encode(const Args& a)
                 if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
                 if (hash.on()) hash_x_hat(static_cast<const char*>(b.x_hat));
             }
+        } else if (vbv) {
+            // rate_control.vbv_fit: coded at the mode's q_index and accepted when the unit fits the buffer - one
+            // state export per P unit, no probe. On a miss the state goes back, the largest q_index below whose predicted stream
+            // fits the payload budget is searched on the size probe (which leaves the state alone) and coded; the coder may
+            // exceed the prediction, so the q_index then steps down until the unit fits or the floor is reached.
+            if (!intra && !ctl && !rate_probe) qp = qp_p;
+            const int floor_q = rate.on ? rate.qp_min : 0;
+            if (vu.qp_mode < 0) vu.qp_mode = qp;      // no search under the cap: what the mode gave
+            if (!intra) {
+                const long long sb = c.ld ? dcvc_dmcld_export_state(c.ld, nullptr, 0, b.st) : dcvc_dmcht_export_state(c.ht, nullptr, 0, b.st);
+                abi_ok(sb, "export_state");
+                if (sb != trial_state_bytes) {
+                    if (trial_state) hip_ok(hipFree(trial_state), "hipFree");
+                    hip_ok(hipMalloc(&trial_state, static_cast<size_t>(sb)), "hipMalloc");
+                    trial_state_bytes = sb;
+                }
+                abi_ok(c.ld ? dcvc_dmcld_export_state(c.ld, trial_state, static_cast<size_t>(sb), b.st)
+                            : dcvc_dmcht_export_state(c.ht, trial_state, static_cast<size_t>(sb), b.st), "export_state");
+            }
+            auto restore = [&]() {
+                if (intra) return;
+                abi_ok(c.ld ? dcvc_dmcld_import_state(c.ld, trial_state, static_cast<size_t>(trial_state_bytes), g.H, g.W, b.st)
+                            : dcvc_dmcht_import_state(c.ht, trial_state, static_cast<size_t>(trial_state_bytes), g.H, g.W, b.st), "import_state");
+            };
+            auto code = [&](int q) {
+                if (intra) code_intra(q); else code_inter(q);
+            };
+            auto conforms = [&]() { return 8 * (static_cast<long long>(payload.size()) + vbv_overhead(payload.size())) <= vbv_avail; };
+            code(qp);
+            if (!conforms() && qp > floor_q) {
+                restore();      // the probes read the temporal state in front of the unit, and leave it alone
+                Probe pi{c.intra, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
+                InterProbe pp{c.ld, c.ht, b.x, g.H, g.W, pad_b, pad_r, b.st, {}};
+                std::map<int, long long>& predicted = intra ? pi.bytes : pp.bytes;
+                int probes = 0;
+                qp = intra ? dcvc_rc_pick_qp_near(probe_bits, &pi, vbv_payload_avail, qp - 1, floor_q, qp - 1, &probes)
+                           : dcvc_rc_pick_qp_near(inter_probe_bits, &pp, vbv_payload_avail, qp - 1, floor_q, qp - 1, &probes);
+                abi_ok(qp, "size probe");
+                ru.probes += probes;
+                ru.predicted_bytes = predicted.at(qp);
+                code(qp);
+                ++vu.recodes;
+                while (!conforms() && qp > floor_q) {
+                    restore();
+                    --qp;
+                    ru.predicted_bytes = predicted.count(qp) ? predicted.at(qp) : -1;
+                    code(qp);
+                    ++vu.recodes;
+                }
+            }
+            if (rate_probe && !intra) start_q = qp;
+            if (intra) {
+                if (c.ld) abi_ok(dcvc_dmcld_add_ref_feature_from_frame(c.ld, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (c.ht) abi_ok(dcvc_dmcht_add_ref_feature_from_frame(c.ht, b.x_hat, g.Hp, g.Wp, 1, b.st), "add_ref");
+                if (hash.on()) hash_x_hat(static_cast<const char*>(b.x_hat));
+            }
         } else if (intra) {
             ec = dcvc_dmci_compress(c.intra, b.x, g.H, g.W, qp, pad_b, pad_r, b.x_hat, b.st);
             abi_ok(ec, "intra compress");
@@ -2320,9 +2496,28 @@ int encode(const Args& a)
             qu.qp = qp; qu.bytes = static_cast<long long>(payload.size());
             quality_units.push_back(qu);
         }
-        put_unit(intra, qp, ec, reset, payload, idx, want, last_read_ms);
+        const long long unit_bytes = put_unit(intra, qp, ec, reset, payload, idx, want, last_read_ms);
+        if (vbv) {
+            // the model counts what the unit added to the file; then the mode's own book-keeping, with the final q_index
+            if (unit_bytes != static_cast<long long>(payload.size()) + vbv_overhead(payload.size())) die("vbv: the unit's bytes are not the ones counted");
+            const int violated = dcvc_rc_vbv_admit(vbv, 8 * unit_bytes, want);
+            abi_ok(violated, "vbv");
+            vu.intra = intra; vu.first_picture = idx; vu.pictures = want; vu.qp = qp; vu.probes = ru.probes;
+            vu.predicted_bytes = ru.predicted_bytes; vu.bytes = unit_bytes; vu.violated = violated != 0;
+            vu.underflow_bits = dcvc_rc_vbv_underflow(vbv);
+            vu.fullness_after = dcvc_rc_vbv_fullness(vbv);
+            if (vu.violated) {
+                fprintf(stderr, "dcvc: warning: the unit at picture %d (%lld bits at q_index %d) exceeds the decoder buffer by %lld bits\n", idx,
+                        8 * unit_bytes, qp, vu.underflow_bits);
+            }
+            vbv_units.push_back(vu);
+            vbv_first_unit = false;
+        }
         if (rate.on) {
-            if (ctl) abi_ok(dcvc_rc_update(ctl, 8.0 * payload.size(), want, intra ? 1 : 0), "rate control");
+            if (ctl) {
+                abi_ok(vbv ? dcvc_rc_update_at(ctl, 8.0 * payload.size(), want, intra ? 1 : 0, qp)
+                           : dcvc_rc_update(ctl, 8.0 * payload.size(), want, intra ? 1 : 0), "rate control");
+            }
             spent_bits += 8LL * static_cast<long long>(payload.size());
             pictures_coded += want;
             ru.qp = qp;
@@ -2388,8 +2583,42 @@ int encode(const Args& a)
             fclose(lf);
         }
     }
+    if (vbv) {
+        double min_fullness = vbv_arg.init * dcvc_rc_vbv_capacity(vbv);
+        long long lowered = 0, recodes = 0, violations = 0;
+        for (const VbvUnit& u : vbv_units) {
+            min_fullness = std::min(min_fullness, u.fullness_after);
+            lowered += u.qp < u.qp_mode;
+            recodes += u.recodes;
+            violations += u.violated;
+        }
+        fprintf(g_msg, "vbv: capacity %.0f bits, minimum fullness %.0f bits, %lld of %zu units lowered, %lld recodes, %lld violations\n",
+                dcvc_rc_vbv_capacity(vbv), min_fullness, lowered, vbv_units.size(), recodes, violations);
+        if (!vbv_arg.log.empty()) {
+            std::string js = "{\"maxrate_bpp\": " + jnum(vbv_arg.maxrate) + ", \"bufsize_pictures\": " + jnum(vbv_arg.bufsize) + ", \"init\": " +
+                             jnum(vbv_arg.init) + ", \"width\": " + std::to_string(g.W) + ", \"height\": " + std::to_string(g.H) +
+                             ", \"rate_bits\": " + jnum(dcvc_rc_vbv_rate(vbv)) + ", \"capacity_bits\": " + jnum(dcvc_rc_vbv_capacity(vbv)) +
+                             ", \"units\": [";
+            for (size_t i = 0; i < vbv_units.size(); ++i) {
+                const VbvUnit& u = vbv_units[i];
+                js += std::string(i ? ", " : "") + "{\"type\": \"" + (u.intra ? "I" : "P") + "\", \"first_picture\": " + std::to_string(u.first_picture) +
+                      ", \"pictures\": " + std::to_string(u.pictures) + ", \"qp_mode\": " + std::to_string(u.qp_mode) + ", \"qp\": " +
+                      std::to_string(u.qp) + ", \"probes\": " + std::to_string(u.probes) + ", \"recodes\": " + std::to_string(u.recodes) +
+                      ", \"predicted_bytes\": " + (u.predicted_bytes < 0 ? std::string("null") : std::to_string(u.predicted_bytes)) +
+                      ", \"bytes\": " + std::to_string(u.bytes) + ", \"fullness_before\": " + jnum(u.fullness_before) +
+                      ", \"fullness_after\": " + jnum(u.fullness_after) + ", \"violated\": " + (u.violated ? "true" : "false") +
+                      ", \"underflow_bits\": " + std::to_string(u.underflow_bits) + "}";
+            }
+            js += "], \"min_fullness\": " + jnum(min_fullness) + ", \"lowered\": " + std::to_string(lowered) + ", \"recodes\": " +
+                  std::to_string(recodes) + ", \"violations\": " + std::to_string(violations) + "}\n";
+            FILE* lf = fopen(vbv_arg.log.c_str(), "wb");
+            if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size()) die("cannot write " + vbv_arg.log);
+            fclose(lf);
+        }
+        dcvc_rc_vbv_destroy(vbv);
+    }
+    if (trial_state) hip_ok(hipFree(trial_state), "hipFree");
     if (quality.on()) {
-        if (trial_state) hip_ok(hipFree(trial_state), "hipFree");
         if (kept_dev) hip_ok(hipFree(kept_dev), "hipFree");
         meter.destroy();
         double sum = 0;
@@ -2512,6 +2741,7 @@ int decode(const Args& a)
             std::to_string(out_size.W) + "x" + std::to_string(out_size.H));
     }
     const PipeArgs pipe = pipe_args(a, false);
+    vbv_args(a, batch, false);
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
     // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
     const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));

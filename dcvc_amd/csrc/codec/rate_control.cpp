@@ -27,11 +27,21 @@ int TargetBpp::next_qp(bool is_intra) const
 
 void TargetBpp::update(double bits, int pictures, bool is_intra)
 {
+    update(bits, pictures, is_intra, next_qp(is_intra));
+}
+
+void TargetBpp::update_at(double bits, int pictures, bool is_intra, int qp)
+{
+    update(bits, pictures, is_intra, qp);
+}
+
+void TargetBpp::update(double bits, int pictures, bool is_intra, int used_qp)
+{
     if (pictures <= 0) return;
+    const bool moved = !is_intra && used_qp != next_qp(false);      // coded at another q_index than the controller's
     m_spent += bits;
     m_pictures += pictures;
     double per_picture = std::max(bits / pictures, 1.0);
-    const int used_qp = next_qp(is_intra);
     if (!is_intra) {
         if (m_has_last && used_qp != m_last_qp) {
             const double s = (std::log2(per_picture) - m_last_log) / (used_qp - m_last_qp);
@@ -46,6 +56,8 @@ void TargetBpp::update(double bits, int pictures, bool is_intra)
     if (is_intra) {
         if (!m_has_last) return;
         per_picture = std::pow(2.0, m_last_log + m_slope * (m_qp - m_last_qp));
+    } else if (moved) {
+        per_picture = std::pow(2.0, m_last_log + m_slope * (m_qp - m_last_qp));      // the unit just stored, at the controller's q_index
     }
     const double step = (std::log2(want) - std::log2(per_picture)) / m_slope;
     m_qp += std::min(m_max_step, std::max(-m_max_step, step));
@@ -145,6 +157,41 @@ int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, i
     const double share = target_bpp * pixels_per_picture;
     const double budget = std::max(share * (k + 1) - static_cast<double>(spent_bits), share / 4.0);
     return static_cast<int64_t>(std::floor(budget));
+}
+
+Vbv::Vbv(double maxrate_bpp, double bufsize_pictures, double init, long long pixels)
+{
+    if (!std::isfinite(maxrate_bpp) || !(maxrate_bpp > 0.0)) throw std::invalid_argument("vbv: maxrate must be a positive number of bits per pixel");
+    if (!std::isfinite(bufsize_pictures) || !(bufsize_pictures > 0.0)) {
+        throw std::invalid_argument("vbv: bufsize must be a positive number of picture periods");
+    }
+    if (!std::isfinite(init) || !(init > 0.0) || init > 1.0) throw std::invalid_argument("vbv: init must be in (0, 1] (a fraction of the capacity)");
+    if (pixels < 1) throw std::invalid_argument("vbv: pixels must be at least 1");
+    m_rate = maxrate_bpp * static_cast<double>(pixels);
+    m_capacity = bufsize_pictures * m_rate;
+    if (!(m_capacity < 4611686018427387904.0)) throw std::invalid_argument("vbv: the capacity must be below 2^62 bits");
+    m_fullness = init * m_capacity;
+}
+
+int64_t Vbv::available() const
+{
+    return static_cast<int64_t>(std::floor(m_fullness));
+}
+
+bool Vbv::admit(int64_t bits, int pictures)
+{
+    if (bits < 0 || pictures < 1) throw std::invalid_argument("vbv: a unit has bits >= 0 and at least 1 picture");
+    const int64_t avail = available();
+    const double refill = static_cast<double>(pictures) * m_rate;      // a statement of its own: never fused into the sum below
+    const double left = m_fullness - static_cast<double>(bits);
+    if (bits <= avail) {
+        m_underflow = 0;
+        m_fullness = std::min(m_capacity, left + refill);
+        return false;
+    }
+    m_underflow = bits - avail;
+    m_fullness = std::min(m_capacity, std::max(0.0, left) + refill);
+    return true;
 }
 
 SceneCut::SceneCut(double threshold, int min_gap, long long pixels) : m_threshold(threshold), m_min_gap(min_gap), m_pixels(pixels)

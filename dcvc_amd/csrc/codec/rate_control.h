@@ -15,11 +15,16 @@ public:
               int qp_min = 0, int qp_max = 63, double slope = 0.049);
     int next_qp(bool is_intra) const;
     void update(double bits, int pictures, bool is_intra);
+    // ... of a unit that was coded at `qp`, not at next_qp(is_intra) (a decoder-buffer cap lowered it): the slope
+    // estimate and the last P unit take `qp`, and the size the step compares is projected from `qp` to the q_index the
+    // controller stands at, 2^(log2(per_picture) + slope (m_qp - qp)), as the update behind an I picture projects the last P unit
+    void update_at(double bits, int pictures, bool is_intra, int qp);
     double qp() const { return m_qp; }
     double spent() const { return m_spent; }
     int pictures() const { return m_pictures; }
 
 private:
+    void update(double bits, int pictures, bool is_intra, int used_qp);
     double m_target_bits, m_qp, m_slope, m_max_step = 4.0, m_spent = 0.0;
     int m_horizon, m_intra_bonus, m_qp_min, m_qp_max, m_pictures = 0;
     bool m_has_last = false;
@@ -56,6 +61,28 @@ int64_t unit_budget_bits(double target_bpp, double pixels_per_picture, int pictu
 // Budget of picture k (0-based) of an all-intra run towards target_bpp: what the k + 1 pictures may take together minus what
 // the first k took, floored at a quarter of one picture's share. floor() of the double value.
 int64_t intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);
+
+// Decoder-buffer model of dcvc encode --vbv-maxrate / --vbv-bufsize (rate_control.Vbv is the restatement): a
+// bucket of capacity C = bufsize_pictures * r bits that fills with r = maxrate_bpp * pixels bits per picture period and starts
+// at F = init * C. A unit of `bits` bits that holds n source pictures must be whole in the bucket when its first picture is
+// due: it conforms iff bits <= avail = floor(F). Behind it F = min(C, (F - bits) + n * r); behind a unit that does not conform
+// F = min(C, max(0.0, F - bits) + n * r), and underflow = bits - avail. Nothing is padded at the top: a cap, not filler CBR.
+// All in double, in this operation order.
+class Vbv {
+public:
+    // every value finite and positive, init in (0, 1], pixels >= 1, and a capacity below 2^62 bits
+    Vbv(double maxrate_bpp, double bufsize_pictures, double init, long long pixels);
+    int64_t available() const;
+    bool admit(int64_t bits, int pictures);      // true: a violation. bits >= 0, pictures >= 1 (std::invalid_argument)
+    double fullness() const { return m_fullness; }
+    double capacity() const { return m_capacity; }
+    double rate() const { return m_rate; }
+    int64_t underflow() const { return m_underflow; }
+
+private:
+    double m_rate = 0.0, m_capacity = 0.0, m_fullness = 0.0;
+    int64_t m_underflow = 0;
+};
 
 // Scene-cut decisions of dcvc encode --scene-cut (dcvc_amd/scene.py SceneCut is the restatement). Pictures
 // are pushed in source order with the luma SAD against their predecessor (dcvc_luma_sad). mafd = 100.0 * sad /

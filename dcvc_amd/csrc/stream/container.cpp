@@ -49,6 +49,21 @@ void put_ip(std::vector<uint8_t>& out, bool is_i, int sps_id, int qp, int ec_par
     out.insert(out.end(), payload, payload + n);
 }
 
+size_t unit_overhead(size_t payload_bytes, bool with_sps, int height, int width)
+{
+    auto varuint = [](size_t v) -> size_t { return v < (1u << 7) ? 1 : v < (1u << 14) ? 2 : 4; };
+    if (payload_bytes >= (1u << 30)) throw StreamError(-1, "container: payload too long for the length field");
+    size_t n = 3 + varuint(payload_bytes);
+    if (with_sps) {
+        if (height < 0 || width < 0) throw StreamError(-1, "container: SPS field out of range");
+        if (static_cast<uint32_t>(height) >= (1u << 30) || static_cast<uint32_t>(width) >= (1u << 30)) {
+            throw StreamError(-1, "container: value does not fit a 30-bit varuint");
+        }
+        n += 1 + varuint(static_cast<size_t>(height)) + varuint(static_cast<size_t>(width));
+    }
+    return n;
+}
+
 const uint8_t* Reader::take(size_t k)
 {
     if (m_n - m_pos < k) throw StreamError(-2, "container: truncated stream");
@@ -249,6 +264,11 @@ int64_t dcvc_stream_write_ip(uint8_t* dst, size_t cap, int is_i_frame, int sps_i
         dcvc::stream::put_ip(v, is_i_frame != 0, sps_id, qp, ec_part, reset_feature_memory != 0, payload, payload_bytes);
         return emit(v, dst, cap);
     });
+}
+
+int64_t dcvc_stream_unit_overhead(size_t payload_bytes, int with_sps, int height, int width)
+{
+    return guarded_stream([&] { return static_cast<int64_t>(dcvc::stream::unit_overhead(payload_bytes, with_sps != 0, height, width)); });
 }
 
 int dcvc_stream_read_header(const uint8_t* src, size_t n, int* nal_type, int* sps_id)

@@ -25,6 +25,11 @@ void put_sps(std::vector<uint8_t>& out, int sps_id, int height, int width);
 void put_ip(std::vector<uint8_t>& out, bool is_i, int sps_id, int qp, int ec_part, bool reset,
             const uint8_t* payload, size_t payload_bytes);
 
+// bytes put_ip adds around a payload of that length - 3 header bytes and the varuint length - plus, with_sps, the bytes of the
+// put_sps in front of it: what a unit adds to the stream is payload_bytes + unit_overhead(...). Refuses what the two refuse.
+// Never smaller for a longer payload: a varuint grows with its value.
+size_t unit_overhead(size_t payload_bytes, bool with_sps, int height, int width);
+
 // sequential reader over caller memory
 class Reader {
 public:

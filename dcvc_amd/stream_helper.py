@@ -74,6 +74,22 @@ def write_ip(f, is_i_frame, sps_id, qp, ec_part, reset_feature_memory, bit_strea
     return n
 
 
+def unit_overhead(payload_bytes, sps=None):
+    """Bytes write_ip adds around a payload of that length, plus - ``sps`` = {"height", "width"} - those of the write_sps in
+    front of it, without writing anything (dcvc_stream_unit_overhead, include/dcvc_amd_stream.h). Never smaller for a longer
+    payload: a varuint grows with its value."""
+    def varuint(value):
+        value = int(value)
+        if value < 0 or value >= 1 << 30:
+            raise ValueError("varuint out of range: %d" % value)
+        return 1 if value < 1 << 7 else 2 if value < 1 << 14 else 4
+
+    n = 3 + varuint(payload_bytes)
+    if sps is not None:
+        n += 1 + varuint(sps["height"]) + varuint(sps["width"])
+    return n
+
+
 def read_header(f):
     flag = _get(f, 1)[0]
     nal_type = NalType(flag >> 4)

@@ -1,6 +1,6 @@
 /* Rate control of the dcvc tool (no reference counterpart): the one-pass controller towards a target rate and the
  * q_index search on a size probe. Host code only, no GPU. dcvc_amd/rate_control.py is the same arithmetic in Python
- * (TargetBpp, pick_qp_for_budget, pick_qp_for_quality, intra_budget_bits); the two are tested against each other.
+ * (TargetBpp, pick_qp_for_budget, pick_qp_for_quality, intra_budget_bits, Vbv); the two are tested against each other.
  *
  * Errors: a negative return code, message through dcvc_last_error() (dcvc_amd_ops.h). */
 #ifndef DCVC_AMD_RC_H
@@ -23,6 +23,10 @@ void dcvc_rc_destroy(dcvc_rc* rc);
 int dcvc_rc_next_qp(const dcvc_rc* rc, int is_intra);
 /* the unit took `bits` for `pictures` pictures */
 int dcvc_rc_update(dcvc_rc* rc, double bits, int pictures, int is_intra);
+/* ... of a unit that was coded at qp instead of dcvc_rc_next_qp (a decoder-buffer cap lowered it, below): the slope estimate
+ * and the last P unit take qp, and the size the step compares is the unit's projected to the q_index the controller stands
+ * at, 2^(log2(bits / pictures) + slope (state_qp - qp)). With qp = dcvc_rc_next_qp(rc, is_intra) it is dcvc_rc_update. */
+int dcvc_rc_update_at(dcvc_rc* rc, double bits, int pictures, int is_intra, int qp);
 double dcvc_rc_state_qp(const dcvc_rc* rc);      /* the controller's fractional q_index */
 
 /* Largest q_index in [qp_min, qp_max] whose predicted stream fits budget_bits, by bisection on
@@ -62,6 +66,33 @@ int64_t dcvc_rc_unit_budget_bits(double target_bpp, double pixels_per_picture, i
 /* Budget of picture k (0-based) of an all-intra run: floor(max(target_bpp * pixels * (k + 1) - spent_bits,
  * target_bpp * pixels / 4)) in double arithmetic. */
 int64_t dcvc_rc_intra_budget_bits(double target_bpp, double pixels_per_picture, int k, int64_t spent_bits);
+
+/* Decoder-buffer (VBV) model of dcvc encode --vbv-maxrate / --vbv-bufsize (rate_control.Vbv is the same
+ * arithmetic in Python, compared with == on the fullness). All in IEEE double, in the operation order written here:
+ *   r = maxrate_bpp * pixels         bits that arrive per picture period (pixels = W * H of the coded size)
+ *   C = bufsize_pictures * r         the capacity
+ *   F = init * C                     the start fullness
+ * A unit of `bits` bits - 8 times every byte it adds to the output: container header, payload, and a parameter set written
+ * in front of it - that holds n source pictures (an I picture or an LD P unit 1, an HT chunk 8, a ragged last chunk what
+ * the source really held) must be whole in the buffer when its first picture is due: it conforms iff bits <= avail =
+ * floor(F) as int64. Behind a unit that conforms F = min(C, (F - bits) + n * r). Behind one that does not, underflow = bits -
+ * avail is recorded and F = min(C, max(0.0, F - bits) + n * r). Nothing is padded when the buffer would overflow: a cap (VBR
+ * under a ceiling), not filler CBR.
+ * dcvc_rc_vbv_create returns NULL, with a message, for a value that is not finite or not positive, init outside (0, 1],
+ * pixels < 1, or a capacity of 2^62 bits or more. */
+typedef struct dcvc_rc_vbv dcvc_rc_vbv;
+dcvc_rc_vbv* dcvc_rc_vbv_create(double maxrate_bpp, double bufsize_pictures, double init, long long pixels);
+void dcvc_rc_vbv_destroy(dcvc_rc_vbv* v);
+/* avail = floor(F): the bits the next unit may take; negative on a null handle */
+int64_t dcvc_rc_vbv_available(const dcvc_rc_vbv* v);
+/* the unit took `bits` for `pictures` source pictures: 0 = it conforms, 1 = a violation (F and the underflow as above);
+ * negative, the model unchanged, for bits < 0 or pictures < 1 */
+int dcvc_rc_vbv_admit(dcvc_rc_vbv* v, int64_t bits, int pictures);
+double dcvc_rc_vbv_fullness(const dcvc_rc_vbv* v);      /* F */
+double dcvc_rc_vbv_capacity(const dcvc_rc_vbv* v);      /* C */
+double dcvc_rc_vbv_rate(const dcvc_rc_vbv* v);          /* r */
+/* bits - avail of the last admitted unit when it was a violation, else 0 */
+int64_t dcvc_rc_vbv_underflow(const dcvc_rc_vbv* v);
 
 
 /* Scene-cut decisions of dcvc encode --scene-cut (dcvc_amd/scene.py SceneCut is the same arithmetic in

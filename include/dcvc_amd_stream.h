@@ -51,6 +51,13 @@ int dcvc_stream_write_sps(uint8_t* dst, size_t cap, int sps_id, int height, int 
 int64_t dcvc_stream_write_ip(uint8_t* dst, size_t cap, int is_i_frame, int sps_id, int qp, int ec_part,
                              int reset_feature_memory, const uint8_t* payload, size_t payload_bytes);
 
+/* Bytes an I / P unit adds to the stream on top of a payload of payload_bytes, without writing it: the 3 header bytes and the
+ * varuint length of dcvc_stream_write_ip, plus - with_sps != 0 - the dcvc_stream_write_sps(height, width) in front of it. Exact:
+ * payload_bytes + the result is what the two writers return together. Never smaller for a longer payload (a varuint grows
+ * with its value), so the overhead at a length bounds that of every shorter payload. -1 for a payload of 2^30 bytes or more,
+ * or, with_sps, a size the parameter set cannot carry. */
+int64_t dcvc_stream_unit_overhead(size_t payload_bytes, int with_sps, int height, int width);
+
 /* stream_helper.py:64-70 read_header(f) -> nal_type, sps_id */
 int dcvc_stream_read_header(const uint8_t* src, size_t n, int* nal_type, int* sps_id);
 /* stream_helper.py:73-79 read_sps_remaining(f, sps_id) -> height, width */

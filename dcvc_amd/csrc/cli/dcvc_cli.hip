@@ -17,6 +17,7 @@
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
 //               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
+//               [--denoise S[:T] [--denoise-out filtered.yuv]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
@@ -185,6 +186,21 @@
 //               reads them; the parameter set carries W x H and everything behind - --batch, --target-bpp, --scene-cut -
 //               sees a clip of that size. W and H positive and even, each side's ratio in [1/8, 8]; the source size gives
 //               the file of a run without the flag. RGB sources are not resampled yet.
+//               --denoise S[:T] (encode): a denoising prefilter. S, the spatial strength, and T, the temporal one,
+//               are integers in 0..64 in 8-bit code values; one number sets both. Every source picture, once and in source
+//               order, goes through dcvc_denoise_planes (Y in one call, U and V in one call) where load_picture leaves it:
+//               behind the upload, --scale's resampler and dcvc_wire_unpack, in front of dcvc_pix_to_x. The state is the
+//               previous OUTPUT picture at the coded size, in two device buffers used in turn; the conversion and the quality
+//               meter read the filter's output buffer where it lies (no copy). Everything behind sees the filtered clip, as
+//               with --scale: --batch, --target-bpp, --target-psnr / --quality-log (measured against the filtered samples),
+//               --scene-cut, the --vbv-* recodes (which code b.x again: nothing is filtered twice), --read-ahead, pipes and
+//               the padding pictures of a ragged last chunk (repeats of the last filtered picture). The stream is the one of a
+//               run without the flag on the pre-filtered clip; --denoise 0 gives the file of a run without the flag. For
+//               yuv420 / yuv422 / yuv444 at 8..16 bits (.y4m too) and the wire types with a planar 4:2:2 carrier (nv16, p210,
+//               uyvy, yuy2, y210, v210: filtered on the carrier); nv12 / p010 / nv21 and the RGB types are refused ("sources
+//               are not filtered yet"). --denoise-out FILE (needs --denoise, not "-"): the filtered pictures at the coded size
+//               in the carrier type's raw layout and depth, one copy to the host per picture; no padding pictures. One summary
+//               line: "denoise: spatial S, temporal T, N pictures filtered". The stream format and the decoder do not change.
 //               --out-size WxH (decode, yuv420): the reconstruction's integer samples (what -o writes at the coded size) are
 //               resampled on the device to W x H; -o, --ref (the original clip), PSNR (dcvc_sse_ws on the u8 / u16 output
 //               samples against the reference's) and --calc-ssim (dcvc_msssim_range_ws on the same planes) work
@@ -1374,6 +1390,106 @@ struct Resampler {
     }
 };
 
+// --denoise S[:T] / --denoise-out FILE (encode): what the flags alone decide is refused before a model is loaded
+struct DenoiseArgs {
+    bool on = false;
+    int spatial = 0, temporal = 0;
+    std::string out;               // --denoise-out: the filtered clip as coded, raw
+};
+
+// "S" or "S:T": decimal integers in 0..64, nothing else
+bool parse_strengths(const std::string& s, int& spatial, int& temporal)
+{
+    const size_t colon = s.find(':');
+    const std::string part[2] = {s.substr(0, colon), colon == std::string::npos ? s.substr(0, colon) : s.substr(colon + 1)};
+    int v[2];
+    for (int i = 0; i < 2; ++i) {
+        if (part[i].empty() || part[i].size() > 2 || part[i].find_first_not_of("0123456789") != std::string::npos) return false;
+        v[i] = atoi(part[i].c_str());
+        if (v[i] > 64) return false;
+    }
+    spatial = v[0]; temporal = v[1];
+    return true;
+}
+
+DenoiseArgs denoise_args(const Args& a, bool encoding)
+{
+    DenoiseArgs d;
+    if (!encoding) {
+        for (const char* k : {"denoise", "denoise-out"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+        }
+        return d;
+    }
+    if (!a.has("denoise")) {
+        if (a.has("denoise-out")) die("--denoise-out needs --denoise");
+        return d;
+    }
+    if (!parse_strengths(a.str("denoise"), d.spatial, d.temporal)) {
+        die("--denoise must be S or S:T with integers in 0..64, got " + a.str("denoise"));
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (is_rgb_name(type)) die("--denoise is for planar YUV sources: RGB sources are not filtered yet");
+    if (type == "nv12" || type == "p010" || type == "nv21") {
+        die("--denoise is for planar YUV sources: " + type + " sources are not filtered yet");
+    }
+    d.out = a.str("denoise-out");
+    if (a.has("denoise-out") && (d.out.empty() || is_dash(d.out))) die("--denoise-out needs a file name (not -: stdout is for the stream)");
+    d.on = true;
+    return d;
+}
+
+// --denoise: the planes of a picture at the coded size through dcvc_denoise_planes, Y in one call, U and V in one call. The
+// state is the previous output picture, on the device in two buffers used in turn.
+struct Denoiser {
+    DenoiseArgs arg;
+    uint8_t* hist[2] = {nullptr, nullptr};
+    uint8_t* h_out = nullptr;      // pinned: --denoise-out's picture
+    FILE* file = nullptr;
+    int turn = 0;
+    long long pictures = 0;
+    void create(const Geometry& g, const DenoiseArgs& d)
+    {
+        arg = d;
+        for (uint8_t*& p : hist) hip_ok(hipMalloc(&p, g.frame_bytes()), "hipMalloc");
+        if (!arg.out.empty()) {
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+            file = fopen(arg.out.c_str(), "wb");
+            if (!file) die("cannot write " + arg.out);
+        }
+    }
+    // the picture in `src` (planes Y, U, V back to back, u8 or u16 by the bit depth) -> the filtered picture, which stays valid
+    // until the call after the next one
+    uint8_t* run(const Geometry& g, const uint8_t* src, hipStream_t st)
+    {
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
+        const uint8_t* prev = pictures > 0 ? hist[turn ^ 1] : nullptr;
+        uint8_t* dst = hist[turn];
+        abi_ok(dcvc_denoise_planes(src, g.W, ny, prev, g.W, ny, dst, g.W, ny, dt, g.bit_depth, g.H, g.W, 1, arg.spatial, arg.temporal, st),
+               "denoise (Y)");
+        abi_ok(dcvc_denoise_planes(src + ny * es, g.Wc(), nc, prev ? prev + ny * es : nullptr, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt,
+                                   g.bit_depth, g.Hc(), g.Wc(), 2, arg.spatial, arg.temporal, st), "denoise (U, V)");
+        if (file) {
+            hip_ok(hipMemcpyAsync(h_out, dst, g.frame_bytes(), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            if (fwrite(h_out, 1, g.frame_bytes(), file) != g.frame_bytes()) die("cannot write " + arg.out);
+        }
+        turn ^= 1;
+        ++pictures;
+        return dst;
+    }
+    void destroy()
+    {
+        for (uint8_t* p : hist) {
+            if (p) hip_ok(hipFree(p), "hipFree");
+        }
+        if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
+        if (file && fclose(file) != 0) die("cannot write " + arg.out);
+        *this = Denoiser{};
+    }
+};
+
 // --out-size: the output picture on the device and what measures it against the reference, all at the output size
 struct ScaledOut {
     Resampler rs;
@@ -1904,6 +2020,7 @@ int encode(const Args& a)
     const SizeArg scale = size_arg(a, "scale");
     const int wire = wire_arg(a, true);
     rgb16_arg(a, true);
+    const DenoiseArgs denoise = denoise_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
@@ -1997,6 +2114,11 @@ int encode(const Args& a)
         hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_full), gs.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
         hip_ok(hipMalloc(&d_full, gs.frame_bytes()), "hipMalloc");
     }
+    // --denoise: the uploads, the resampler and the unpack fill `staging`; the filter's output buffer takes b.yuv8's place, so
+    // the conversion, the quality meter and the padding pictures of a ragged chunk read the filtered picture where it lies
+    uint8_t* const staging = b.yuv8;
+    Denoiser dn;
+    if (denoise.on) dn.create(g, denoise);
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
@@ -2063,12 +2185,14 @@ int encode(const Args& a)
         if (h == nullptr) return false;
         if (scale.on) {
             hip_ok(hipMemcpyAsync(d_full, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
-            rs.run(d_full, b.yuv8, b.st);
+            rs.run(d_full, staging, b.st);
         } else if (wire >= 0) {
-            ws.upload(g, b.yuv8, b.st, h);
+            ws.upload(g, staging, b.st, h);
         } else {
-            hip_ok(hipMemcpyAsync(b.yuv8, h, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            hip_ok(hipMemcpyAsync(staging, h, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
         }
+        // once per source picture, in source order: recodes and padding pictures come from what this left
+        if (denoise.on) b.yuv8 = dn.run(g, staging, b.st);
         return true;
     };
     // measure (--scene-cut): the picture's luma and its SAD against the previous one ride on the same synchronisation
@@ -2537,6 +2661,11 @@ int encode(const Args& a)
         hip_ok(hipHostFree(h_full), "hipHostFree");
         hip_ok(hipFree(d_full), "hipFree");
     }
+    if (denoise.on) {
+        fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered\n", denoise.spatial, denoise.temporal, dn.pictures);
+        b.yuv8 = staging;
+        dn.destroy();
+    }
     if (ctl) dcvc_rc_destroy(ctl);
     hash.finish();
     if (scd) {
@@ -2742,6 +2871,7 @@ int decode(const Args& a)
     }
     const PipeArgs pipe = pipe_args(a, false);
     vbv_args(a, batch, false);
+    denoise_args(a, false);
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
     // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
     const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));

@@ -432,6 +432,21 @@ void resample_validate(const ResamplePlan& p, const ResampleDesc& d);     // thr
 // two launches on `stream`: validates first, allocates nothing, never waits for the host
 void resample_planes(const ResamplePlan& p, const ResampleDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- denoising prefilter (denoise.hip)
+// Planes of u8 / u16 samples through an edge-preserving 3x3 spatial stage and a motion-adaptive recursive temporal stage
+// against the previous output picture (the filter is stated at the head of denoise.hip). Strides in samples.
+constexpr int kDenoiseMaxSide = 16384;
+struct DenoiseDesc {
+    const void* src = nullptr; int src_row_stride = 0; long long src_plane_stride = 0;
+    const void* prev = nullptr; int prev_row_stride = 0; long long prev_plane_stride = 0;      // nullptr: no history
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0, n_planes = 1;
+    int spatial = 0, temporal = 0;                   // 0..64, in 8-bit code values
+};
+void denoise_validate(const DenoiseDesc& d);         // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void denoise_planes(const DenoiseDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

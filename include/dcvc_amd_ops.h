@@ -424,6 +424,25 @@ int dcvc_resample_planes(const void* plan, const void* src, int src_dtype, int s
                          int dst_dtype, int dst_row_stride, long long dst_plane_stride, int n_planes, int max_val, void* workspace,
                          long long workspace_bytes, void* stream);
 
+/* Denoising prefilter on the GPU (no reference counterpart): planes of integer samples through an
+ * edge-preserving 3x3 spatial stage and a motion-adaptive recursive temporal stage, every output sample defined exactly in
+ * signed 32-bit integers. Per plane, sh = bit_depth - 8, Ts = spatial << sh, Tt = temporal << sh, indexes clamped to the plane:
+ *   spatial:  c the centre, n_i the 9 samples of its 3x3 neighbourhood, w_i = max(0, Ts - |n_i - c|), num = sum w_i (n_i - c),
+ *             ws = sum w_i, sp = c + floor((2 num + ws) / (2 ws)), a true floor; spatial == 0: sp = c.
+ *   temporal: prev is the same plane of the previous output picture. prev == NULL or temporal == 0: out = sp. Otherwise
+ *             m = sum over the 3x3 neighbourhood q of |sp[q] - prev[q]| (sp at a clamped index is the sp of the clamped
+ *             position), L = 9 Tt, k = (192 max(0, L - m)) / L, out = sp + ((k (prev - sp) + 128) >> 8), an arithmetic shift.
+ * Every output lies between the smallest and the largest sample it read; spatial == temporal == 0 copies.
+ *   dcvc_denoise_planes: n_planes planes src [H][W] (and prev) -> dst, every plane on its own; samples are DCVC_SAMPLE_U8
+ *   (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16); strides in samples (plane strides are not read for one
+ *   plane, prev's strides not without prev). One launch on `stream`: nothing is allocated and nothing waits for the host.
+ *   Refused before anything is enqueued: NULL src or dst; another sample type; a bit_depth that is not the type's; H or W
+ *   outside 1..16384; n_planes outside 1..65535; a strength outside 0..64; a row stride below W or a plane stride below the
+ *   plane; a 16-bit plane at an odd address; dst overlapping src or prev. */
+int dcvc_denoise_planes(const void* src, int src_row_stride, long long src_plane_stride, const void* prev, int prev_row_stride,
+                        long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth,
+                        int H, int W, int n_planes, int spatial, int temporal, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

@@ -925,6 +925,21 @@ int dcvc_denoise_planes(const void* src, int src_row_stride, long long src_plane
     });
 }
 
+int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_plane_stride, const void* prev, int prev_row_stride,
+                            long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype,
+                            int bit_depth, int H, int W, int n_planes, int keep, int weave_from_prev, int threshold, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::DeinterlaceDesc d;
+        d.cur = cur; d.cur_row_stride = cur_row_stride; d.cur_plane_stride = cur_plane_stride;
+        d.prev = prev; d.prev_row_stride = prev_row_stride; d.prev_plane_stride = prev_plane_stride;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.n_planes = n_planes;
+        d.keep = keep; d.weave_from_prev = weave_from_prev; d.threshold = threshold;
+        dcvc::deinterlace_planes(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_mask_step_enc(void* y, int ldy, const void* q_dec, int ldq, const void* scales, int lds,
                        const void* means, int ldm, void* y_hat, int ldh, void* sym, void* cond,
                        void* block_count, void* compact_out, void* totals, int Hh, int W, int C,

@@ -18,6 +18,7 @@
 //               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
 //               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
 //               [--denoise S[:T] [--denoise-out filtered.yuv]]
+//               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
@@ -201,6 +202,27 @@
 //               are not filtered yet"). --denoise-out FILE (needs --denoise, not "-"): the filtered pictures at the coded size
 //               in the carrier type's raw layout and depth, one copy to the host per picture; no padding pictures. One summary
 //               line: "denoise: spatial S, temporal T, N pictures filtered". The stream format and the decoder do not change.
+//               --deinterlace MODE[:T] (encode): the source holds woven interlaced frames. MODE frame codes one
+//               picture per source frame, field one per field (twice the pictures); T, the motion threshold, is an integer in
+//               0..64 in 8-bit code values (default 10; 0: the purely spatial interpolator). --field-order tff | bff (default
+//               tff) says which field is the earlier one; a Y4M file with It / Ib supplies it (a flag that disagrees is refused;
+//               without --deinterlace such a file is refused as ever). With p0 = 0 for tff, 1 for bff, source frame f gives:
+//               frame: picture f = keep p0, woven sample from f itself; field: picture 2f = keep p0, woven sample from frame
+//               f - 1, picture 2f + 1 = keep 1 - p0, woven sample from f. Every picture goes through
+//               dcvc_deinterlace_planes (Y in one call, U and V in one call) in load_picture: upload -> dcvc_wire_unpack ->
+//               deinterlace -> --scale's resampler -> --denoise -> dcvc_pix_to_x. The last two input frames stay on the
+//               device in two buffers used in turn; a frame is read once and serves both of its pictures. The filter writes the
+//               buffer the next stage reads (no copy). In field mode -n counts coded pictures while the reader and
+//               --read-ahead count source frames; a pipe's end ends the clip behind both fields of its last frame.
+//               Everything behind sees progressive pictures: --batch, --target-bpp, --target-psnr / --quality-log (measured
+//               against the deinterlaced samples), --scene-cut, the --vbv-* recodes, pipes, --latency-log, and the padding
+//               pictures of a ragged last chunk (repeats of the last output picture). For yuv420 / yuv422 / yuv444 at 8..16
+//               bits (.y4m too) and the wire types with a planar 4:2:2 carrier (nv16, p210, uyvy, yuy2, y210, v210); nv12 /
+//               p010 / nv21 and the RGB types are refused ("sources are not deinterlaced yet"). --deinterlace-out FILE (needs
+//               --deinterlace, not "-"): the deinterlaced pictures at the SOURCE size (in front of --scale and --denoise) in
+//               the carrier type's raw layout and depth: what decode --ref should be given; no padding pictures. One summary
+//               line: "deinterlace: MODE, tff|bff, threshold T, N pictures from M frames". The stream format and the decoder
+//               do not change.
 //               --out-size WxH (decode, yuv420): the reconstruction's integer samples (what -o writes at the coded size) are
 //               resampled on the device to W x H; -o, --ref (the original clip), PSNR (dcvc_sse_ws on the u8 / u16 output
 //               samples against the reference's) and --calc-ssim (dcvc_msssim_range_ws on the same planes) work
@@ -743,12 +765,13 @@ struct PictureFile {
     std::string path;                          // as the messages name it
     bool y4m = false, regular = true;
     dcvc_y4m_info info{};
+    int interlacing = 0;                       // Y4M, open(..., true): 1 for It, 2 for Ib
     std::vector<uint8_t> buf;                  // bytes read ahead of the pictures: header and FRAME lines
     size_t pos = 0, end = 0;
     size_t partial = 0;                        // End: bytes of a trailing partial raw picture
     std::string error;
-    // format: "" = by name, "raw" or "y4m" (--in-format)
-    void open(const std::string& p, const std::string& format = "")
+    // format: "" = by name, "raw" or "y4m" (--in-format); interlaced: a Y4M file may say It or Ib (--deinterlace)
+    void open(const std::string& p, const std::string& format = "", bool interlaced = false)
     {
         path = is_dash(p) ? "stdin" : p;
         fd = is_dash(p) ? 0 : ::open(p.c_str(), O_RDONLY);
@@ -758,7 +781,8 @@ struct PictureFile {
         y4m = format.empty() ? is_y4m_name(p) : format == "y4m";
         if (!y4m) return;
         const size_t n = fill_line();
-        if (dcvc_y4m_parse_header(buf.data() + pos, n, &info) < 0) die(path + " is no Y4M file: " + dcvc_last_error());
+        const int rc = interlaced ? dcvc_y4m_parse_header_i(buf.data() + pos, n, &info, &interlacing) : dcvc_y4m_parse_header(buf.data() + pos, n, &info);
+        if (rc < 0) die(path + " is no Y4M file: " + dcvc_last_error());
         pos += static_cast<size_t>(info.header_bytes);
     }
     // reads until the buffer holds a whole line, 1024 bytes or the end of the input; the bytes it holds
@@ -1490,6 +1514,126 @@ struct Denoiser {
     }
 };
 
+// --deinterlace MODE[:T] / --field-order / --deinterlace-out FILE (encode): what the flags alone decide is refused
+// before a model is loaded
+struct DeinterlaceArgs {
+    bool on = false;
+    bool field = false;            // field: two coded pictures a source frame; frame: one
+    bool bff = false;              // --field-order bff, or a Y4M file's Ib
+    int threshold = 10;
+    std::string out;               // --deinterlace-out: the deinterlaced clip at the source size, raw
+    const char* mode() const { return field ? "field" : "frame"; }
+    const char* order() const { return bff ? "bff" : "tff"; }
+};
+
+DeinterlaceArgs deinterlace_args(const Args& a, bool encoding)
+{
+    DeinterlaceArgs d;
+    if (!encoding) {
+        for (const char* k : {"deinterlace", "field-order", "deinterlace-out"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+        }
+        return d;
+    }
+    if (!a.has("deinterlace")) {
+        for (const char* k : {"field-order", "deinterlace-out"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --deinterlace");
+        }
+        return d;
+    }
+    // "frame" or "field", then ":T" with a decimal integer in 0..64, nothing else
+    const std::string s = a.str("deinterlace");
+    const size_t colon = s.find(':');
+    const std::string mode = s.substr(0, colon);
+    bool good = mode == "frame" || mode == "field";
+    if (good && colon != std::string::npos) {
+        const std::string t = s.substr(colon + 1);
+        good = !t.empty() && t.size() <= 2 && t.find_first_not_of("0123456789") == std::string::npos && atoi(t.c_str()) <= 64;
+        if (good) d.threshold = atoi(t.c_str());
+    }
+    if (!good) die("--deinterlace must be frame or field, or either with :T, T an integer in 0..64, got " + s);
+    d.field = mode == "field";
+    if (a.has("field-order")) {
+        const std::string o = a.str("field-order");
+        if (o != "tff" && o != "bff") die("--field-order must be tff or bff, got " + o);
+        d.bff = o == "bff";
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (is_rgb_name(type)) die("--deinterlace is for planar YUV sources: RGB sources are not deinterlaced yet");
+    if (type == "nv12" || type == "p010" || type == "nv21") {
+        die("--deinterlace is for planar YUV sources: " + type + " sources are not deinterlaced yet");
+    }
+    d.out = a.str("deinterlace-out");
+    if (a.has("deinterlace-out") && (d.out.empty() || is_dash(d.out))) {
+        die("--deinterlace-out needs a file name (not -: stdout is for the stream)");
+    }
+    d.on = true;
+    return d;
+}
+
+// --deinterlace: the planes of a woven source frame through dcvc_deinterlace_planes, Y in one call, U and V in one call. The
+// last two INPUT frames (behind the upload and the unpack) stay on the device in two buffers used in turn; in field mode a
+// frame serves two pictures: its first field's (woven with the previous frame's second field), then its second field's.
+struct Deinterlacer {
+    DeinterlaceArgs arg;
+    uint8_t* in[2] = {nullptr, nullptr};
+    uint8_t* h_out = nullptr;      // pinned: --deinterlace-out's picture
+    FILE* file = nullptr;
+    int turn = 0, phase = 0;       // phase 1: the second picture of in[turn] is due
+    long long frames = 0, pictures = 0;
+    void create(const Geometry& g, const DeinterlaceArgs& d)
+    {
+        arg = d;
+        for (uint8_t*& p : in) hip_ok(hipMalloc(&p, g.frame_bytes()), "hipMalloc");
+        if (!arg.out.empty()) {
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+            file = fopen(arg.out.c_str(), "wb");
+            if (!file) die("cannot write " + arg.out);
+        }
+    }
+    bool wants_frame() const { return phase == 0; }
+    // where the next source frame goes (planes Y, U, V back to back, u8 or u16 by the bit depth) when wants_frame()
+    uint8_t* next_input()
+    {
+        ++frames;
+        return in[turn];
+    }
+    // the next picture of the frame in in[turn] -> dst
+    void run(const Geometry& g, uint8_t* dst, hipStream_t st)
+    {
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
+        const int p0 = arg.bff ? 1 : 0, keep = phase == 0 ? p0 : 1 - p0, weave = arg.field && phase == 0 ? 1 : 0;
+        const uint8_t* cur = in[turn];
+        const uint8_t* prev = frames > 1 ? in[turn ^ 1] : nullptr;
+        abi_ok(dcvc_deinterlace_planes(cur, g.W, ny, prev, g.W, ny, dst, g.W, ny, dt, g.bit_depth, g.H, g.W, 1, keep, weave, arg.threshold, st),
+               "deinterlace (Y)");
+        abi_ok(dcvc_deinterlace_planes(cur + ny * es, g.Wc(), nc, prev ? prev + ny * es : nullptr, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt,
+                                       g.bit_depth, g.Hc(), g.Wc(), 2, keep, weave, arg.threshold, st), "deinterlace (U, V)");
+        if (file) {
+            hip_ok(hipMemcpyAsync(h_out, dst, g.frame_bytes(), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            if (fwrite(h_out, 1, g.frame_bytes(), file) != g.frame_bytes()) die("cannot write " + arg.out);
+        }
+        ++pictures;
+        if (arg.field && phase == 0) {
+            phase = 1;
+        } else {
+            phase = 0;
+            turn ^= 1;
+        }
+    }
+    void destroy()
+    {
+        for (uint8_t* p : in) {
+            if (p) hip_ok(hipFree(p), "hipFree");
+        }
+        if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
+        if (file && fclose(file) != 0) die("cannot write " + arg.out);
+        *this = Deinterlacer{};
+    }
+};
+
 // --out-size: the output picture on the device and what measures it against the reference, all at the output size
 struct ScaledOut {
     Resampler rs;
@@ -2021,12 +2165,22 @@ int encode(const Args& a)
     const int wire = wire_arg(a, true);
     rgb16_arg(a, true);
     const DenoiseArgs denoise = denoise_args(a, true);
+    DeinterlaceArgs deint = deinterlace_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
     if (pipe.in_is_y4m(a.str("i"))) {
-        src_file.open(a.str("i"), pipe.in_format);
+        src_file.open(a.str("i"), pipe.in_format, deint.on);
         const Y4mSource y = y4m_source(src_file, a, true);
+        // an It / Ib file supplies the field order; without --deinterlace it was refused above
+        if (src_file.interlacing != 0) {
+            const bool bff = src_file.interlacing == 2;
+            if (a.has("field-order") && deint.bff != bff) {
+                die(src_file.path + " is " + (bff ? "bottom" : "top") + " field first (I" + (bff ? "b" : "t") + "), not --field-order " +
+                    a.str("field-order"));
+            }
+            deint.bff = bff;
+        }
         type = y.type; depth = y.depth;
         pic_w = src_file.info.width; pic_h = src_file.info.height;
         if (scale.on && pix_fmt_of(type) >= 0) {
@@ -2051,6 +2205,7 @@ int encode(const Args& a)
     if (rgb) colour.apply(gs);
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
+    if (deint.on && gs.Hc() < 2) die("--deinterlace needs planes of at least 2 rows");
     // --vbv-maxrate / --vbv-bufsize: the decoder-buffer model counts the pixels of the coded size, as the rate controller does
     dcvc_rc_vbv* vbv = nullptr;
     if (vbv_arg.on) {
@@ -2080,9 +2235,13 @@ int encode(const Args& a)
         total = src_file.regular ? src_file.count(gs.file_bytes()) : (1 << 30);
     }
     const bool piped_in = !is_png(type) && !src_file.regular;
+    // --deinterlace field: two coded pictures a source frame; -n counts coded pictures, the reader source frames
+    const bool two_fields = deint.on && deint.field;
+    if (two_fields) total = std::min<long long>(2 * total, 1 << 30);
     // pictures to code; from a pipe: an upper bound until the input ends
     int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
+    const int source_frames = two_fields ? (frame_num + 1) / 2 : frame_num;
     const int read_ahead = pipe.read_ahead >= 0 ? pipe.read_ahead : piped_in ? 2 : 0;    DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
     // --quality-log / --target-psnr: every converted picture's source samples stay on the device, one slot per picture of a unit
     QualityMeter meter;
@@ -2119,6 +2278,10 @@ int encode(const Args& a)
     uint8_t* const staging = b.yuv8;
     Denoiser dn;
     if (denoise.on) dn.create(g, denoise);
+    // --deinterlace: the upload and the unpack fill one of the filter's two input buffers at the source size; it writes where
+    // they would have: the resampler's input with --scale, `staging` without
+    Deinterlacer di;
+    if (deint.on) di.create(gs, deint);
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
@@ -2137,7 +2300,7 @@ int encode(const Args& a)
     auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     // --read-ahead: the source's pictures arrive in the ring's pinned slots instead of the one pinned buffer of each path
     ReadAhead ra;
-    if (read_ahead > 0) ra.start(src_file, gs.file_bytes(), read_ahead + 1, frame_num, t0);
+    if (read_ahead > 0) ra.start(src_file, gs.file_bytes(), read_ahead + 1, source_frames, t0);
     bool slot_held = false;                // a slot whose upload is in flight: released behind convert()'s synchronisation
     double last_read_ms = 0;               // when the last source picture was complete in host memory
     std::string input_error;               // a pipe that broke off inside a picture: the run ends as at the end of the input, with status 2
@@ -2181,9 +2344,19 @@ int encode(const Args& a)
             hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
             return true;
         }
-        const uint8_t* h = next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv);
-        if (h == nullptr) return false;
-        if (scale.on) {
+        // --deinterlace field: the second picture of a frame comes from the frame on the device
+        const bool fresh = !deint.on || di.wants_frame();
+        const uint8_t* h = fresh ? next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv) : nullptr;
+        if (fresh && h == nullptr) return false;
+        if (deint.on) {
+            if (fresh) {
+                uint8_t* in = di.next_input();
+                if (wire >= 0) ws.upload(gs, in, b.st, h);
+                else hip_ok(hipMemcpyAsync(in, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            }
+            di.run(gs, scale.on ? d_full : staging, b.st);
+            if (scale.on) rs.run(d_full, staging, b.st);
+        } else if (scale.on) {
             hip_ok(hipMemcpyAsync(d_full, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
             rs.run(d_full, staging, b.st);
         } else if (wire >= 0) {
@@ -2661,6 +2834,11 @@ int encode(const Args& a)
         hip_ok(hipHostFree(h_full), "hipHostFree");
         hip_ok(hipFree(d_full), "hipFree");
     }
+    if (deint.on) {
+        fprintf(g_msg, "deinterlace: %s, %s, threshold %d, %lld pictures from %lld frames\n", deint.mode(), deint.order(), deint.threshold,
+                di.pictures, di.frames);
+        di.destroy();
+    }
     if (denoise.on) {
         fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered\n", denoise.spatial, denoise.temporal, dn.pictures);
         b.yuv8 = staging;
@@ -2872,6 +3050,7 @@ int decode(const Args& a)
     const PipeArgs pipe = pipe_args(a, false);
     vbv_args(a, batch, false);
     denoise_args(a, false);
+    deinterlace_args(a, false);
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
     // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
     const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));

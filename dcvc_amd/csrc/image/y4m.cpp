@@ -48,10 +48,12 @@ void chroma_tag(const char* who, const std::string& tag, int& fmt, int& depth)
     else fail(who, "unsupported chroma tag " + field + " (C420jpeg, C420mpeg2, C420paldv, C420, C422, C444 and their pN forms)");
 }
 
-void parse_header(const void* bytes, size_t n, dcvc_y4m_info* out)
+// interlacing == nullptr: the entry that refuses interlaced material; else It -> 1, Ib -> 2 (Ip, I?, no I field: 0)
+void parse_header(const void* bytes, size_t n, dcvc_y4m_info* out, int* interlacing)
 {
     const char* who = "y4m_parse_header";
     if (bytes == nullptr || out == nullptr) fail(who, "null argument");
+    int fields = 0;
     const char* p = static_cast<const char*>(bytes);
     const size_t ml = sizeof(kMagic) - 1;
     if (n < ml + 1 || std::memcmp(p, kMagic, ml) != 0 || (p[ml] != ' ' && p[ml] != '\n')) fail(who, "no YUV4MPEG2 magic");
@@ -90,7 +92,9 @@ void parse_header(const void* bytes, size_t n, dcvc_y4m_info* out)
             break;
         }
         case 'I':
-            if (val != "p" && val != "?") fail(who, "field " + field + ": interlaced material is not supported");
+            if (val == "p" || val == "?") fields = 0;
+            else if (interlacing != nullptr && (val == "t" || val == "b")) fields = val == "t" ? 1 : 2;
+            else fail(who, "field " + field + ": interlaced material is not supported");
             break;
         case 'C':
             chroma_tag(who, val, info.pix_fmt, info.bit_depth);
@@ -105,6 +109,7 @@ void parse_header(const void* bytes, size_t n, dcvc_y4m_info* out)
     if (!has_w) fail(who, "no W field");
     if (!has_h) fail(who, "no H field");
     *out = info;
+    if (interlacing != nullptr) *interlacing = fields;
 }
 
 int write_header(char* dst, size_t cap, const dcvc_y4m_info* info)
@@ -134,7 +139,15 @@ extern "C" {
 
 int dcvc_y4m_parse_header(const void* bytes, size_t n, dcvc_y4m_info* out)
 {
-    return dcvc::guarded([&] { parse_header(bytes, n, out); });
+    return dcvc::guarded([&] { parse_header(bytes, n, out, nullptr); });
+}
+
+int dcvc_y4m_parse_header_i(const void* bytes, size_t n, dcvc_y4m_info* out, int* interlacing)
+{
+    return dcvc::guarded([&] {
+        if (interlacing == nullptr) fail("y4m_parse_header", "null argument");
+        parse_header(bytes, n, out, interlacing);
+    });
 }
 
 int dcvc_y4m_frame_header_bytes(const void* bytes, size_t n)

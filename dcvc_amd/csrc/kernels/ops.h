@@ -447,6 +447,23 @@ void denoise_validate(const DenoiseDesc& d);         // throws std::invalid_argu
 // one launch on `stream`: validates first, allocates nothing, never waits for the host
 void denoise_planes(const DenoiseDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- deinterlacer (deinterlace.hip)
+// Planes of u8 / u16 samples of a woven frame: the rows of parity `keep` are copied, the others made from an edge-directed
+// spatial interpolation blended, by a motion measure against the previous input frame, with the woven sample (DESIGN.md 27;
+// the filter is stated at the head of deinterlace.hip). Strides in samples.
+constexpr int kDeinterlaceMaxSide = 16384;
+struct DeinterlaceDesc {
+    const void* cur = nullptr; int cur_row_stride = 0; long long cur_plane_stride = 0;
+    const void* prev = nullptr; int prev_row_stride = 0; long long prev_plane_stride = 0;      // nullptr: spatial only
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0, n_planes = 1;
+    int keep = 0, weave_from_prev = 0;               // 0 or 1
+    int threshold = 0;                               // 0..64, in 8-bit code values
+};
+void deinterlace_validate(const DeinterlaceDesc& d);      // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void deinterlace_planes(const DeinterlaceDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -33,6 +33,7 @@ _SIGS = {
     "dcvc_pix_to_x": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp]),
     "dcvc_x_to_pix": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
     "dcvc_y4m_parse_header": (_ci, [ctypes.c_char_p, _sz, ctypes.POINTER(Y4mInfo)]),
+    "dcvc_y4m_parse_header_i": (_ci, [ctypes.c_char_p, _sz, ctypes.POINTER(Y4mInfo), ctypes.POINTER(_ci)]),
     "dcvc_y4m_frame_header_bytes": (_ci, [ctypes.c_char_p, _sz]),
     "dcvc_y4m_write_header": (_ci, [ctypes.c_char_p, _sz, ctypes.POINTER(Y4mInfo)]),
 }
@@ -153,6 +154,17 @@ def y4m_header(data):
     return {k: getattr(info, k) for k, _ in Y4mInfo._fields_}
 
 
+def y4m_header_i(data):
+    """y4m_header for material that may be field-interlaced (dcvc_y4m_parse_header_i): the same dict plus ``interlacing``,
+    0 for Ip / I? / no I field, 1 for It (top field first), 2 for Ib (bottom field first); Im is refused"""
+    info, fields = Y4mInfo(), _ci(0)
+    data = bytes(data[:1024])
+    _lib.check(_fn("dcvc_y4m_parse_header_i")(data, len(data), ctypes.byref(info), ctypes.byref(fields)))
+    d = {k: getattr(info, k) for k, _ in Y4mInfo._fields_}
+    d["interlacing"] = fields.value
+    return d
+
+
 def y4m_frame_header_bytes(data):
     """length of the "FRAME...\\n" line at the start of ``data``; raises DcvcError if there is none"""
     data = bytes(data[:1024])
@@ -168,5 +180,5 @@ def y4m_write_header(width, height, pix_fmt, bit_depth, fps_num=25, fps_den=1):
 
 
 __all__ = ["DCVC_PIX_YUV420P", "DCVC_PIX_YUV422P", "DCVC_PIX_YUV444P", "DCVC_PIX_NV12", "FORMATS", "picture_samples", "plane_shapes",
-           "to_x", "from_x", "split_planes", "psnr", "msssim_picture", "max_val", "y4m_header", "y4m_frame_header_bytes",
+           "to_x", "from_x", "split_planes", "psnr", "msssim_picture", "max_val", "y4m_header", "y4m_header_i", "y4m_frame_header_bytes",
            "y4m_write_header"]

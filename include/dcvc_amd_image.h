@@ -51,6 +51,10 @@ int dcvc_png_write_rgb16(const char* path, const void* rgb16, int width, int hei
  * pix_fmt is a DCVC_PIX_* value, header_bytes the length of the header line with its '\n'. */
 typedef struct { int width, height, fps_num, fps_den, pix_fmt, bit_depth; long long header_bytes; } dcvc_y4m_info;
 int dcvc_y4m_parse_header(const void* bytes, size_t n, dcvc_y4m_info* out);
+/* as dcvc_y4m_parse_header, but field-interlaced material is accepted and reported (dcvc encode --deinterlace):
+ * *interlacing = 0 for Ip, I? or no I field, 1 for It (top field first), 2 for Ib (bottom field first). Im (mixed) stays
+ * refused. */
+int dcvc_y4m_parse_header_i(const void* bytes, size_t n, dcvc_y4m_info* out, int* interlacing);
 /* length of a "FRAME...\n" line (parameters included), < 0 if it is none */
 int dcvc_y4m_frame_header_bytes(const void* bytes, size_t n);
 /* writes "YUV4MPEG2 W.. H.. F..:.. Ip C..\n" (8-bit 4:2:0 as C420jpeg; header_bytes is not read); returns the bytes written.

@@ -443,6 +443,27 @@ int dcvc_denoise_planes(const void* src, int src_row_stride, long long src_plane
                         long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth,
                         int H, int W, int n_planes, int spatial, int temporal, void* stream);
 
+/* Deinterlacer on the GPU (no reference counterpart): planes of a woven frame -> progressive planes, every
+ * output sample defined exactly in signed 32-bit integers. Per plane, T = threshold << (bit_depth - 8):
+ *   rows y with y % 2 == keep are copied from cur. For a missing row y: ya = y - 1 (y + 1 at the top), yb = y + 1 (y - 1 at
+ *   the bottom), A = cur[ya], B = cur[yb], column indexes clamped to the plane.
+ *   spatial:  for d in the order 0, -1, +1: score_d = sum over j in -1..1 of |A[x + j + d] - B[x + j - d]|,
+ *             pred_d = (A[x + d] + B[x - d] + 1) >> 1; the smallest score wins, a later direction only when strictly smaller.
+ *   prev == NULL or threshold == 0: out = sp. Otherwise prev is the previous INPUT frame,
+ *             m = max over rows {ya, y, yb} and columns x - 1 .. x + 1 of |cur - prev|, k = (256 max(0, T - m)) / T,
+ *             wv = weave_from_prev ? prev[y][x] : cur[y][x], out = sp + ((k (wv - sp) + 128) >> 8), an arithmetic shift.
+ * Where nothing moved out = wv exactly; every output lies between samples it read.
+ *   dcvc_deinterlace_planes: n_planes planes cur [H][W] (and prev) -> dst, every plane on its own; samples are DCVC_SAMPLE_U8
+ *   (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16); strides in samples (plane strides are not read for one
+ *   plane, prev's strides not without prev). One launch on `stream`: nothing is allocated and nothing waits for the host.
+ *   Refused before anything is enqueued: NULL cur or dst; another sample type; a bit_depth that is not the type's; H outside
+ *   2..16384 or W outside 1..16384; n_planes outside 1..65535; keep or weave_from_prev outside {0, 1}; a threshold outside
+ *   0..64; a row stride below W or a plane stride below the plane; a 16-bit plane at an odd address; dst overlapping cur or
+ *   prev. */
+int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_plane_stride, const void* prev, int prev_row_stride,
+                            long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype,
+                            int bit_depth, int H, int W, int n_planes, int keep, int weave_from_prev, int threshold, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

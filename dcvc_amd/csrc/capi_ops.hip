@@ -940,6 +940,30 @@ int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_p
     });
 }
 
+int dcvc_field_match(const void* cur, int cur_row_stride, const void* prev, int prev_row_stride, int dtype, int bit_depth, int H, int W,
+                     int first, int cthresh, void* out8, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::FieldMatchDesc d;
+        d.cur = cur; d.cur_row_stride = cur_row_stride; d.prev = prev; d.prev_row_stride = prev_row_stride;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.first = first; d.cthresh = cthresh; d.out8 = out8;
+        dcvc::field_match(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_weave_fields(const void* a, int a_row_stride, long long a_plane_stride, const void* b, int b_row_stride, long long b_plane_stride,
+                      void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int H, int W, int n_planes, int first, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::WeaveFieldsDesc d;
+        d.a = a; d.a_row_stride = a_row_stride; d.a_plane_stride = a_plane_stride;
+        d.b = b; d.b_row_stride = b_row_stride; d.b_plane_stride = b_plane_stride;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.dtype = dtype; d.H = H; d.W = W; d.n_planes = n_planes; d.first = first;
+        dcvc::weave_fields(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_mask_step_enc(void* y, int ldy, const void* q_dec, int ldq, const void* scales, int lds,
                        const void* means, int ldm, void* y_hat, int ldh, void* sym, void* cond,
                        void* block_count, void* compact_out, void* totals, int Hh, int W, int C,

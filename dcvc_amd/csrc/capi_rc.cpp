@@ -17,6 +17,10 @@ struct dcvc_scd {
     dcvc::SceneCut scd;
 };
 
+struct dcvc_ivtc {
+    dcvc::Ivtc ivtc;
+};
+
 extern "C" {
 
 dcvc_rc* dcvc_rc_create(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus,
@@ -195,6 +199,33 @@ int dcvc_scd_last(const dcvc_scd* s, double* mafd, double* score, int* detected)
         if (score) *score = s->scd.score();
         if (detected) *detected = s->scd.detected() ? 1 : 0;
     });
+}
+
+dcvc_ivtc* dcvc_ivtc_create(int cycle, int mi)
+{
+    dcvc_ivtc* t = nullptr;
+    dcvc::guarded([&] { t = new dcvc_ivtc{dcvc::Ivtc(cycle, mi)}; });
+    return t;
+}
+
+void dcvc_ivtc_destroy(dcvc_ivtc* t)
+{
+    delete t;
+}
+
+int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8])
+{
+    int r = 0;
+    const int e = dcvc::guarded([&] {
+        if (t == nullptr) throw std::invalid_argument("null ivtc handle");
+        r = t->ivtc.push(idx, has_prev != 0, m);
+    });
+    return e < 0 ? e : r;
+}
+
+int dcvc_ivtc_drop(const dcvc_ivtc* t)
+{
+    return t ? t->ivtc.drop() : -1;
 }
 
 }  // extern "C"

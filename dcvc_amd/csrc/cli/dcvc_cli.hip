@@ -19,6 +19,7 @@
 //               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
 //               [--denoise S[:T] [--denoise-out filtered.yuv]]
 //               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
+//               [--ivtc film|match[:CTHRESH[:MI[:T]]] [--field-order tff|bff] [--ivtc-out film.yuv] [--ivtc-log log.json]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
@@ -223,6 +224,22 @@
 //               the carrier type's raw layout and depth: what decode --ref should be given; no padding pictures. One summary
 //               line: "deinterlace: MODE, tff|bff, threshold T, N pictures from M frames". The stream format and the decoder
 //               do not change.
+//               --ivtc MODE[:CTHRESH[:MI[:T]]] (encode): the source is film carried as interlaced video by 3:2
+//               pulldown. Every source frame f is measured against f - 1 (dcvc_field_match on the luma planes; the eight words
+//               are copied to the host) and pushed (dcvc_ivtc_push): its first field is woven (dcvc_weave_fields, Y in one call,
+//               U and V in one) with its own second field (match c) or with the previous frame's (match p, when that fits
+//               strictly better); a frame whose chosen match still has a block of more than MI combed samples (video, or a
+//               frame whose partner lies outside the clip) goes through dcvc_deinterlace_planes as --deinterlace frame:T does.
+//               MODE match codes one picture per frame; MODE film also drops, from every complete cycle of 5 frames counted
+//               from frame 0, the frame whose first field differs least from its predecessor's (dcvc_ivtc_drop): 4 (M / 5) +
+//               M % 5 pictures from M frames, a ragged last cycle drops nothing. CTHRESH 0..255 (default 9), MI 0..512 (80), T
+//               0..64 (10). The stage sits where the deinterlacer does: upload -> dcvc_wire_unpack -> ivtc -> --scale ->
+//               --denoise -> dcvc_pix_to_x; the last cycle + 1 source frames stay on the device. -n counts coded pictures, the
+//               reader and --read-ahead count source frames (film: whole cycles are read), a pipe's end closes a ragged cycle.
+//               --field-order, Y4M It / Ib files and the source types are those of --deinterlace, which --ivtc excludes.
+//               --ivtc-out FILE: the pictures at the SOURCE size, as --deinterlace-out; --ivtc-log FILE: JSON, per source frame
+//               the eight words, the match, combed and dropped. One summary line: "ivtc: MODE, tff|bff, cthresh C, mi MI,
+//               threshold T, N pictures from M frames (P matched to the previous frame, K deinterlaced, D dropped)".
 //               --out-size WxH (decode, yuv420): the reconstruction's integer samples (what -o writes at the coded size) are
 //               resampled on the device to W x H; -o, --ref (the original clip), PSNR (dcvc_sse_ws on the u8 / u16 output
 //               samples against the reference's) and --calc-ssim (dcvc_msssim_range_ws on the same planes) work
@@ -1536,9 +1553,9 @@ DeinterlaceArgs deinterlace_args(const Args& a, bool encoding)
         return d;
     }
     if (!a.has("deinterlace")) {
-        for (const char* k : {"field-order", "deinterlace-out"}) {
-            if (a.has(k)) die(std::string("--") + k + " needs --deinterlace");
-        }
+        // --field-order belongs to --ivtc as well (ivtc_args reads it)
+        if (a.has("field-order") && !a.has("ivtc")) die("--field-order needs --deinterlace or --ivtc");
+        if (a.has("deinterlace-out")) die("--deinterlace-out needs --deinterlace");
         return d;
     }
     // "frame" or "field", then ":T" with a decimal integer in 0..64, nothing else
@@ -1631,6 +1648,213 @@ struct Deinterlacer {
         if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
         if (file && fclose(file) != 0) die("cannot write " + arg.out);
         *this = Deinterlacer{};
+    }
+};
+
+// --ivtc film|match[:CTHRESH[:MI[:T]]] / --ivtc-out FILE / --ivtc-log FILE (encode): what the flags alone decide is
+// refused before a model is loaded
+struct IvtcArgs {
+    bool on = false;
+    bool film = false;             // film: matching and decimation with cycle 5; match: matching only
+    bool bff = false;              // --field-order bff, or a Y4M file's Ib
+    int cthresh = 9, mi = 80;      // the TIVTC defaults for a 256-sample block
+    int threshold = 10;            // the deinterlacer's, for combed frames
+    std::string out;               // --ivtc-out: the pictures at the source size, raw
+    std::string log;               // --ivtc-log: the words and decisions of every source frame, JSON
+    const char* mode() const { return film ? "film" : "match"; }
+    const char* order() const { return bff ? "bff" : "tff"; }
+};
+
+IvtcArgs ivtc_args(const Args& a, bool encoding)
+{
+    IvtcArgs d;
+    if (!encoding) {
+        for (const char* k : {"ivtc", "ivtc-out", "ivtc-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+        }
+        return d;
+    }
+    if (!a.has("ivtc")) {
+        for (const char* k : {"ivtc-out", "ivtc-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --ivtc");
+        }
+        return d;
+    }
+    if (a.has("deinterlace")) die("--ivtc and --deinterlace exclude each other: --ivtc deinterlaces the frames it finds combed itself");
+    // "film" or "match", then up to three ":N" with decimal integers: CTHRESH 0..255, MI 0..512, T 0..64
+    const std::string s = a.str("ivtc");
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = s.find(':', at);
+        parts.push_back(s.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    bool good = (parts[0] == "film" || parts[0] == "match") && parts.size() <= 4;
+    const int top[3] = {255, 512, 64};
+    int* into[3] = {&d.cthresh, &d.mi, &d.threshold};
+    for (size_t k = 1; good && k < parts.size(); ++k) {
+        const std::string& t = parts[k];
+        good = !t.empty() && t.size() <= 3 && t.find_first_not_of("0123456789") == std::string::npos && atoi(t.c_str()) <= top[k - 1];
+        if (good) *into[k - 1] = atoi(t.c_str());
+    }
+    if (!good) {
+        die("--ivtc must be film or match, or either with :CTHRESH[:MI[:T]], integers in 0..255, 0..512 and 0..64, got " + s);
+    }
+    d.film = parts[0] == "film";
+    if (a.has("field-order")) {
+        const std::string o = a.str("field-order");
+        if (o != "tff" && o != "bff") die("--field-order must be tff or bff, got " + o);
+        d.bff = o == "bff";
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (is_rgb_name(type)) die("--ivtc is for planar YUV sources: RGB sources are not deinterlaced yet");
+    if (type == "nv12" || type == "p010" || type == "nv21") {
+        die("--ivtc is for planar YUV sources: " + type + " sources are not deinterlaced yet");
+    }
+    d.out = a.str("ivtc-out");
+    if (a.has("ivtc-out") && (d.out.empty() || is_dash(d.out))) die("--ivtc-out needs a file name (not -: stdout is for the stream)");
+    d.log = a.str("ivtc-log");
+    if (a.has("ivtc-log") && (d.log.empty() || is_dash(d.log))) die("--ivtc-log needs a file name (not -: stdout is for the stream)");
+    d.on = true;
+    return d;
+}
+
+// --ivtc: the last cycle + 1 source frames (behind the upload and the unpack) stay on the device in a ring. A cycle of frames is
+// read, every frame measured against its predecessor (dcvc_field_match on the luma planes, the eight words copied to the
+// host) and pushed (dcvc_ivtc_push); a complete cycle of film mode then loses the frame dcvc_ivtc_drop names, and the frames that
+// stay are served in order: woven (dcvc_weave_fields) from their own first field and the second field of the match, or, when
+// combed, deinterlaced as --deinterlace frame:T would. match mode is a cycle of one frame without a drop.
+struct IvtcStage {
+    struct Frame {
+        unsigned long long words[8];
+        int match = 0;
+        bool combed = false, dropped = false;
+    };
+    static constexpr int kCycle = 5;
+    IvtcArgs arg;
+    std::vector<uint8_t*> ring;
+    unsigned long long* words = nullptr;       // device: dcvc_field_match's eight words
+    unsigned long long* h_words = nullptr;     // pinned
+    uint8_t* h_out = nullptr;                  // pinned: --ivtc-out's picture
+    FILE* file = nullptr;
+    dcvc_ivtc* decide = nullptr;
+    std::vector<Frame> log;                    // every source frame read
+    std::vector<long long> queue;              // the source frames that wait to be served, in order
+    size_t served = 0;                         // ... and how many of them are
+    long long pictures = 0, matched_prev = 0, deinterlaced = 0, dropped = 0;
+    int cycle() const { return arg.film ? kCycle : 1; }
+    long long frames() const { return static_cast<long long>(log.size()); }
+    bool pending() const { return served < queue.size(); }
+    void create(const Geometry& g, const IvtcArgs& d)
+    {
+        arg = d;
+        ring.assign(static_cast<size_t>(cycle() + 1), nullptr);
+        for (uint8_t*& p : ring) hip_ok(hipMalloc(&p, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&words, 8 * sizeof(unsigned long long)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_words), 8 * sizeof(unsigned long long), hipHostMallocDefault), "hipHostMalloc");
+        decide = dcvc_ivtc_create(arg.film ? kCycle : 0, arg.mi);
+        if (!decide) die(std::string("ivtc: ") + dcvc_last_error());
+        if (!arg.out.empty()) {
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+            file = fopen(arg.out.c_str(), "wb");
+            if (!file) die("cannot write " + arg.out);
+        }
+    }
+    uint8_t* slot(long long f) const { return ring[static_cast<size_t>(f) % ring.size()]; }
+    // where the next source frame goes (planes Y, U, V back to back, u8 or u16 by the bit depth)
+    uint8_t* next_input() const { return slot(frames()); }
+    // the frame next_input() took: measured against its predecessor and pushed; waits for the stream (the words are needed here,
+    // and the pinned memory the upload read is free again)
+    void measure(const Geometry& g, hipStream_t st)
+    {
+        const long long f = frames();
+        const int dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        abi_ok(dcvc_field_match(slot(f), g.W, f > 0 ? slot(f - 1) : nullptr, g.W, dt, g.bit_depth, g.H, g.W, arg.bff ? 1 : 0, arg.cthresh, words, st),
+               "field_match");
+        hip_ok(hipMemcpyAsync(h_words, words, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        Frame fr;
+        uint64_t m[8];
+        for (int k = 0; k < 8; ++k) m[k] = fr.words[k] = h_words[k];
+        const int r = dcvc_ivtc_push(decide, static_cast<int>(f), f > 0 ? 1 : 0, m);
+        abi_ok(r, "ivtc");
+        fr.match = r & 1;
+        fr.combed = (r & 2) != 0;
+        log.push_back(fr);
+    }
+    // the `got` frames read last are the cycle: a complete one of film mode loses the frame dcvc_ivtc_drop names
+    void close_cycle(int got)
+    {
+        queue.clear();
+        served = 0;
+        const long long f0 = frames() - got;
+        const int drop = arg.film && got == kCycle ? dcvc_ivtc_drop(decide) : -1;
+        for (int k = 0; k < got; ++k) {
+            if (k == drop) {
+                log[static_cast<size_t>(f0 + k)].dropped = true;
+                ++dropped;
+            } else {
+                queue.push_back(f0 + k);
+            }
+        }
+    }
+    // the next frame that waits -> dst
+    void serve(const Geometry& g, uint8_t* dst, hipStream_t st)
+    {
+        const long long f = queue[served++];
+        const Frame& fr = log[static_cast<size_t>(f)];
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8, first = arg.bff ? 1 : 0;
+        const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
+        const uint8_t* cur = slot(f);
+        const uint8_t* prev = f > 0 ? slot(f - 1) : nullptr;
+        if (fr.combed) {
+            abi_ok(dcvc_deinterlace_planes(cur, g.W, ny, prev, g.W, ny, dst, g.W, ny, dt, g.bit_depth, g.H, g.W, 1, first, 0, arg.threshold, st),
+                   "deinterlace (Y)");
+            abi_ok(dcvc_deinterlace_planes(cur + ny * es, g.Wc(), nc, prev ? prev + ny * es : nullptr, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt,
+                                           g.bit_depth, g.Hc(), g.Wc(), 2, first, 0, arg.threshold, st), "deinterlace (U, V)");
+            ++deinterlaced;
+        } else {
+            const uint8_t* second = fr.match ? prev : cur;
+            abi_ok(dcvc_weave_fields(cur, g.W, ny, second, g.W, ny, dst, g.W, ny, dt, g.H, g.W, 1, first, st), "weave_fields (Y)");
+            abi_ok(dcvc_weave_fields(cur + ny * es, g.Wc(), nc, second + ny * es, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt, g.Hc(), g.Wc(), 2,
+                                     first, st), "weave_fields (U, V)");
+        }
+        if (fr.match) ++matched_prev;
+        if (file) {
+            hip_ok(hipMemcpyAsync(h_out, dst, g.frame_bytes(), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            if (fwrite(h_out, 1, g.frame_bytes(), file) != g.frame_bytes()) die("cannot write " + arg.out);
+        }
+        ++pictures;
+    }
+    void write_log() const
+    {
+        if (arg.log.empty()) return;
+        std::string js = std::string("{\"mode\": \"") + arg.mode() + "\", \"field_order\": \"" + arg.order() + "\", \"cthresh\": " +
+                         std::to_string(arg.cthresh) + ", \"mi\": " + std::to_string(arg.mi) + ", \"threshold\": " + std::to_string(arg.threshold) +
+                         ", \"pictures\": " + std::to_string(pictures) + ", \"frames\": [";
+        for (size_t f = 0; f < log.size(); ++f) {
+            js += f ? ",\n  {\"words\": [" : "\n  {\"words\": [";
+            for (int k = 0; k < 8; ++k) js += (k ? ", " : "") + std::to_string(log[f].words[k]);
+            js += std::string("], \"match\": \"") + (log[f].match ? "p" : "c") + "\", \"combed\": " + (log[f].combed ? "true" : "false") +
+                  ", \"dropped\": " + (log[f].dropped ? "true" : "false") + "}";
+        }
+        js += "\n]}\n";
+        FILE* lf = fopen(arg.log.c_str(), "wb");
+        if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size() || fclose(lf) != 0) die("cannot write " + arg.log);
+    }
+    void destroy()
+    {
+        for (uint8_t* p : ring) {
+            if (p) hip_ok(hipFree(p), "hipFree");
+        }
+        if (words) hip_ok(hipFree(words), "hipFree");
+        if (h_words) hip_ok(hipHostFree(h_words), "hipHostFree");
+        if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
+        if (decide) dcvc_ivtc_destroy(decide);
+        if (file && fclose(file) != 0) die("cannot write " + arg.out);
+        *this = IvtcStage{};
     }
 };
 
@@ -2165,21 +2389,22 @@ int encode(const Args& a)
     const int wire = wire_arg(a, true);
     rgb16_arg(a, true);
     const DenoiseArgs denoise = denoise_args(a, true);
+    IvtcArgs ivtc = ivtc_args(a, true);
     DeinterlaceArgs deint = deinterlace_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
     if (pipe.in_is_y4m(a.str("i"))) {
-        src_file.open(a.str("i"), pipe.in_format, deint.on);
+        src_file.open(a.str("i"), pipe.in_format, deint.on || ivtc.on);
         const Y4mSource y = y4m_source(src_file, a, true);
-        // an It / Ib file supplies the field order; without --deinterlace it was refused above
+        // an It / Ib file supplies the field order; without --deinterlace or --ivtc it was refused above
         if (src_file.interlacing != 0) {
             const bool bff = src_file.interlacing == 2;
-            if (a.has("field-order") && deint.bff != bff) {
+            if (a.has("field-order") && (deint.on ? deint.bff : ivtc.bff) != bff) {
                 die(src_file.path + " is " + (bff ? "bottom" : "top") + " field first (I" + (bff ? "b" : "t") + "), not --field-order " +
                     a.str("field-order"));
             }
-            deint.bff = bff;
+            deint.bff = ivtc.bff = bff;
         }
         type = y.type; depth = y.depth;
         pic_w = src_file.info.width; pic_h = src_file.info.height;
@@ -2206,6 +2431,7 @@ int encode(const Args& a)
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
     if (deint.on && gs.Hc() < 2) die("--deinterlace needs planes of at least 2 rows");
+    if (ivtc.on && gs.Hc() < 2) die("--ivtc needs planes of at least 2 rows");
     // --vbv-maxrate / --vbv-bufsize: the decoder-buffer model counts the pixels of the coded size, as the rate controller does
     dcvc_rc_vbv* vbv = nullptr;
     if (vbv_arg.on) {
@@ -2238,10 +2464,17 @@ int encode(const Args& a)
     // --deinterlace field: two coded pictures a source frame; -n counts coded pictures, the reader source frames
     const bool two_fields = deint.on && deint.field;
     if (two_fields) total = std::min<long long>(2 * total, 1 << 30);
+    // --ivtc film: a complete cycle of 5 source frames gives 4 coded pictures, a ragged last one all of its frames; -n counts coded
+    // pictures, the reader source frames
+    const long long file_frames = total;
+    if (ivtc.on && ivtc.film) total = 4 * (total / IvtcStage::kCycle) + total % IvtcStage::kCycle;
     // pictures to code; from a pipe: an upper bound until the input ends
     int frame_num = a.has("n") ? std::min<long long>(a.num("n", 0), total) : static_cast<int>(total);
     if (frame_num <= 0) die("no pictures to code");
-    const int source_frames = two_fields ? (frame_num + 1) / 2 : frame_num;
+    // ... film: whole cycles are read until they hold the pictures wanted
+    const int source_frames = two_fields ? (frame_num + 1) / 2
+                              : ivtc.on && ivtc.film ? static_cast<int>(std::min<long long>(file_frames, IvtcStage::kCycle * ((frame_num + 3LL) / 4)))
+                                                     : frame_num;
     const int read_ahead = pipe.read_ahead >= 0 ? pipe.read_ahead : piped_in ? 2 : 0;    DeviceBuffers b = make_buffers(g, std::max(delay, batch), false, scene.on);
     // --quality-log / --target-psnr: every converted picture's source samples stay on the device, one slot per picture of a unit
     QualityMeter meter;
@@ -2282,6 +2515,9 @@ int encode(const Args& a)
     // they would have: the resampler's input with --scale, `staging` without
     Deinterlacer di;
     if (deint.on) di.create(gs, deint);
+    // --ivtc sits where the deinterlacer does
+    IvtcStage iv;
+    if (ivtc.on) iv.create(gs, ivtc);
     const int pad_b = g.Hp - g.H, pad_r = g.Wp - g.W;
     std::vector<uint8_t> out, payload;
     dcvc::stream::SpsTable sps;
@@ -2342,6 +2578,30 @@ int encode(const Args& a)
             if (!pngs.read(b.h_yuv, g)) die("short read");
             last_read_ms = now_ms();
             hip_ok(hipMemcpyAsync(b.yuv8, b.h_yuv, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            return true;
+        }
+        if (ivtc.on) {
+            // a cycle of source frames is read and measured when no frame waits; every upload is waited for (the words are needed
+            // on the host), so the pinned memory it read is free again at once
+            if (!iv.pending()) {
+                int got = 0;
+                while (got < iv.cycle() && iv.frames() < source_frames && !input_done) {
+                    const uint8_t* h = next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv);
+                    if (h == nullptr) break;
+                    uint8_t* in = iv.next_input();
+                    if (wire >= 0) ws.upload(gs, in, b.st, h);
+                    else hip_ok(hipMemcpyAsync(in, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                    iv.measure(gs, b.st);
+                    if (slot_held) ra.release();
+                    slot_held = false;
+                    ++got;
+                }
+                iv.close_cycle(got);
+                if (!iv.pending()) return false;
+            }
+            iv.serve(gs, scale.on ? d_full : staging, b.st);
+            if (scale.on) rs.run(d_full, staging, b.st);
+            if (denoise.on) b.yuv8 = dn.run(g, staging, b.st);
             return true;
         }
         // --deinterlace field: the second picture of a frame comes from the frame on the device
@@ -2481,7 +2741,8 @@ int encode(const Args& a)
         if (!scd) die(std::string("scene cut: ") + dcvc_last_error());
     }
     int idx = 0;
-    while (idx < frame_num && !input_done) {
+    // (--ivtc: frames of the last cycle may still wait when the pipe has ended)
+    while (idx < frame_num && (!input_done || iv.pending())) {
         bool intra = is_intra_picture(idx, intra_period);
         if (scd) {
             if (!load_picture()) break;
@@ -2839,6 +3100,13 @@ int encode(const Args& a)
                 di.pictures, di.frames);
         di.destroy();
     }
+    if (ivtc.on) {
+        fprintf(g_msg, "ivtc: %s, %s, cthresh %d, mi %d, threshold %d, %lld pictures from %lld frames (%lld matched to the previous frame, "
+                "%lld deinterlaced, %lld dropped)\n", ivtc.mode(), ivtc.order(), ivtc.cthresh, ivtc.mi, ivtc.threshold, iv.pictures, iv.frames(),
+                iv.matched_prev, iv.deinterlaced, iv.dropped);
+        iv.write_log();
+        iv.destroy();
+    }
     if (denoise.on) {
         fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered\n", denoise.spatial, denoise.temporal, dn.pictures);
         b.yuv8 = staging;
@@ -3051,6 +3319,7 @@ int decode(const Args& a)
     vbv_args(a, batch, false);
     denoise_args(a, false);
     deinterlace_args(a, false);
+    ivtc_args(a, false);
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
     // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
     const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));

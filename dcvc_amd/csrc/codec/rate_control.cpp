@@ -232,4 +232,35 @@ bool SceneCut::push(int idx, long long sad, bool scheduled_intra)
     return intra;
 }
 
+Ivtc::Ivtc(int cycle, int mi) : m_cycle(cycle), m_mi(mi)
+{
+    if (cycle != 0 && (cycle < 2 || cycle > 32)) throw std::invalid_argument("ivtc: the cycle must be 0 (no decimation) or in 2..32");
+    if (mi < 0 || mi > 512) throw std::invalid_argument("ivtc: mi must be in 0..512");
+}
+
+int Ivtc::push(int idx, bool has_prev, const uint64_t m[8])
+{
+    if (m == nullptr) throw std::invalid_argument("ivtc: null words");
+    if (idx != m_next) throw std::invalid_argument("ivtc: frame " + std::to_string(idx) + " pushed, " + std::to_string(m_next) + " is next");
+    if (idx == 0 && has_prev) throw std::invalid_argument("ivtc: frame 0 has no previous frame");
+    if (m[2] > static_cast<uint64_t>(kMaxSamples) || m[3] > static_cast<uint64_t>(kMaxSamples)) {
+        throw std::invalid_argument("ivtc: a comb count is above the samples of the largest plane");
+    }
+    m_next = idx + 1;
+    const int match = has_prev && m[1] < m[0] ? 1 : 0;
+    const int is_combed = m[4 + match] > static_cast<uint64_t>(m_mi) ? 1 : 0;
+    if (m_cycle > 0) {
+        const int pos = idx % m_cycle;
+        if (pos == 0) m_best_pos = -1;
+        if (has_prev && (m_best_pos < 0 || m[6] < m_best)) {
+            m_best = m[6];
+            m_best_pos = pos;
+        }
+        m_drop = pos == m_cycle - 1 ? m_best_pos : -1;
+    }
+    return match | 2 * is_combed;
+}
+
+int Ivtc::drop() const { return m_drop; }
+
 }  // namespace dcvc

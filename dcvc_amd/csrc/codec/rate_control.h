@@ -107,4 +107,25 @@ private:
     bool m_has_base = false, m_has_intra = false, m_detected = false;
 };
 
+// Inverse-telecine decisions of dcvc encode --ivtc (dcvc_amd/ivtc.py Ivtc is the restatement). Source frames
+// are pushed in order with the eight words of dcvc_field_match against their predecessor: m = [match_c, match_p, comb_c,
+// comb_p, blkmax_c, blkmax_p, dup, 0]. The match is p when has_prev and match_p < match_c (strictly), else c; the frame is
+// combed when the chosen match's blkmax > mi. The cycle grid is fixed from frame 0: frames cycle k .. cycle k + cycle - 1 are
+// one cycle, and once all of them are pushed drop() names the one with the smallest dup (ties: the lowest position; a frame
+// without prev has no dup and is never dropped).
+class Ivtc {
+public:
+    static constexpr long long kMaxSamples = 16384LL * 16384;      // the largest plane dcvc_field_match takes
+    Ivtc(int cycle, int mi);                         // cycle 0 (no decimation) or 2..32, mi 0..512
+    // match | 2 * combed. idx must follow the previous one (0 first), has_prev is false at idx 0, comb_c and comb_p at most
+    // kMaxSamples. A refused push (std::invalid_argument) changes nothing.
+    int push(int idx, bool has_prev, const uint64_t m[8]);
+    int drop() const;                                // the position in the cycle just completed; -1: incomplete, or cycle 0
+
+private:
+    int m_cycle, m_mi, m_next = 0, m_drop = -1;
+    uint64_t m_best = 0;
+    int m_best_pos = -1;
+};
+
 }  // namespace dcvc

@@ -464,6 +464,33 @@ void deinterlace_validate(const DeinterlaceDesc& d);      // throws std::invalid
 // one launch on `stream`: validates first, allocates nothing, never waits for the host
 void deinterlace_planes(const DeinterlaceDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- inverse telecine (ivtc.hip)
+// field_match: how well the second field of a woven luma plane (rows of parity 1 - first) fits the first field of the same
+// frame (c) or the second field of the previous frame fits it (p), and how much the first field differs from the previous
+// frame's (dup): eight exact uint64 words on the device (stated at the head of ivtc.hip). Strides in samples.
+constexpr int kIvtcMaxSide = 16384;
+struct FieldMatchDesc {
+    const void* cur = nullptr; int cur_row_stride = 0;
+    const void* prev = nullptr; int prev_row_stride = 0;      // nullptr: words 1, 3, 5 and 6 are 0
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0;
+    int first = 0;                                   // 0 or 1: the parity of the rows of the field shown first
+    int cthresh = 0;                                 // 0..255, in 8-bit code values
+    void* out8 = nullptr;                            // device, 8-byte aligned: [match_c, match_p, comb_c, comb_p, blkmax_c, blkmax_p, dup, 0]
+};
+void field_match_validate(const FieldMatchDesc& d);       // throws std::invalid_argument for what is refused
+// two launches on `stream`: validates first, allocates nothing, never waits for the host
+void field_match(const FieldMatchDesc& d, hipStream_t stream);
+// weave_fields: dst rows of parity `first` from plane set a, the others from b, every plane on its own
+struct WeaveFieldsDesc {
+    const void* a = nullptr; int a_row_stride = 0; long long a_plane_stride = 0;
+    const void* b = nullptr; int b_row_stride = 0; long long b_plane_stride = 0;
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int dtype = kSampleU8, H = 0, W = 0, n_planes = 1, first = 0;
+};
+void weave_fields_validate(const WeaveFieldsDesc& d);     // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void weave_fields(const WeaveFieldsDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

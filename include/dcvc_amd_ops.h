@@ -464,6 +464,33 @@ int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_p
                             long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype,
                             int bit_depth, int H, int W, int n_planes, int keep, int weave_from_prev, int threshold, void* stream);
 
+/* Inverse telecine on the GPU (no reference counterpart): the measurement and the weave; the decisions are
+ * dcvc_ivtc_* (dcvc_amd_rc.h). first = the parity (0, 1) of the rows of the field shown first (0 for tff, 1 for bff),
+ * q = 1 - first, t = cthresh << (bit_depth - 8). cur and prev are the luma planes of source frames f and f - 1. For a candidate
+ * second field S in {cur (match c), prev (match p)}, over the rows y with y % 2 == q and 1 <= y <= H - 2 and every x, with
+ * a = cur[y-1][x], b = cur[y+1][x], s = S[y][x]:
+ *   match_S  = sum |2 s - a - b|
+ *   comb_S   = the number of samples with (s - a > t and s - b > t) or (s - a < -t and s - b < -t)
+ *   blkmax_S = the largest count of such samples in a block (y / 16, x / 32); blocks are aligned to the plane's origin, edge
+ *              blocks count what they hold
+ *   dup      = sum |cur[y][x] - prev[y][x]| over ALL rows with y % 2 == first
+ *   dcvc_field_match: out8 (device, eight uint64) = [match_c, match_p, comb_c, comb_p, blkmax_c, blkmax_p, dup, 0]; with
+ *   prev == NULL words 1, 3, 5 and 6 are 0 (prev's stride is not read). H == 2 has no interior row: the match words are 0.
+ *   Exact integers, the same for every launch geometry and every run. Two launches on `stream`: nothing is allocated and
+ *   nothing waits for the host. Samples are DCVC_SAMPLE_U8 (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16);
+ *   strides in samples. Refused before anything is enqueued: NULL cur or out8; another sample type; a bit_depth that is not
+ *   the type's; H outside 2..16384 or W outside 1..16384; first outside {0, 1}; cthresh outside 0..255; a row stride below W;
+ *   a 16-bit plane at an odd address; an out8 that is not 8-byte aligned.
+ *   dcvc_weave_fields: n_planes planes [H][W]: dst rows of parity `first` are a's, the others b's, every plane on its own (a
+ *   and b may be the same planes: a copy). One launch; plane strides are not read for one plane. Refused before anything is
+ *   enqueued: NULL a, b or dst; another sample type; H outside 2..16384 or W outside 1..16384; n_planes outside 1..65535; first
+ *   outside {0, 1}; a row stride below W or a plane stride below the plane; a 16-bit plane at an odd address; dst overlapping
+ *   a or b. */
+int dcvc_field_match(const void* cur, int cur_row_stride, const void* prev, int prev_row_stride, int dtype, int bit_depth, int H, int W,
+                     int first, int cthresh, void* out8, void* stream);
+int dcvc_weave_fields(const void* a, int a_row_stride, long long a_plane_stride, const void* b, int b_row_stride, long long b_plane_stride,
+                      void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int H, int W, int n_planes, int first, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

@@ -113,6 +113,24 @@ int dcvc_scd_push(dcvc_scd* scd, int idx, long long sad, int scheduled_intra);
 int dcvc_scd_last(const dcvc_scd* scd, double* mafd, double* score, int* detected);
 void dcvc_scd_destroy(dcvc_scd* scd);
 
+/* Inverse-telecine decisions of dcvc encode --ivtc (dcvc_amd/ivtc.py Ivtc is the same arithmetic in Python).
+ * Source frames are pushed in order, idx = 0, 1, ..., with the eight words m = [match_c, match_p, comb_c, comb_p, blkmax_c,
+ * blkmax_p, dup, 0] of dcvc_field_match of frame idx against idx - 1 (has_prev = 0: the frame was measured alone).
+ *   match: p (1) when has_prev and match_p < match_c, strictly; else c (0). combed: the chosen match's blkmax > mi.
+ *   dcvc_ivtc_push returns match | 2 * combed; negative = refused, the state unchanged: an idx that is not the previous one
+ *   plus 1, has_prev at idx 0, a comb count above 16384 * 16384 (the samples of the largest plane dcvc_field_match takes), a
+ *   NULL handle or NULL words.
+ *   The cycle grid is fixed from frame 0: frames cycle * k .. cycle * k + cycle - 1 are one cycle. dcvc_ivtc_drop is valid
+ *   once all `cycle` frames of a cycle are pushed, until the next push: the position 0 .. cycle - 1 of the frame with the
+ *   smallest dup, ties to the lowest position; a frame pushed without prev (frame 0 of the clip) has no dup and is never
+ *   dropped. -1 while the cycle is incomplete, when cycle == 0, or on a NULL handle. A ragged last cycle drops nothing.
+ * dcvc_ivtc_create returns NULL for a cycle that is neither 0 (no decimation) nor in 2..32, or mi outside 0..512. */
+typedef struct dcvc_ivtc dcvc_ivtc;
+dcvc_ivtc* dcvc_ivtc_create(int cycle, int mi);
+int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8]);
+int dcvc_ivtc_drop(const dcvc_ivtc* t);
+void dcvc_ivtc_destroy(dcvc_ivtc* t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -964,6 +964,38 @@ int dcvc_weave_fields(const void* a, int a_row_stride, long long a_plane_stride,
     });
 }
 
+int dcvc_grain_apply(const void* rec, int rec_row_stride, long long rec_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl,
+                     void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth, int H, int W, int n_planes,
+                     int first_plane, int sx, int sy, const int16_t* template_y, const int16_t* template_u, const int16_t* template_v,
+                     const uint8_t* lut, uint32_t seed, uint32_t pic, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::GrainApplyDesc d;
+        d.rec = rec; d.rec_row_stride = rec_row_stride; d.rec_plane_stride = rec_plane_stride;
+        d.luma = luma; d.luma_row_stride = luma_row_stride; d.Hl = Hl; d.Wl = Wl;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.n_planes = n_planes; d.first_plane = first_plane; d.sx = sx; d.sy = sy;
+        d.templates[0] = template_y; d.templates[1] = template_u; d.templates[2] = template_v;
+        d.lut = lut; d.seed = seed; d.pic = pic;
+        dcvc::grain_apply(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_grain_stats(const void* src, int src_row_stride, long long src_plane_stride, const void* den, int den_row_stride,
+                     long long den_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl, int dtype, int bit_depth, int H,
+                     int W, int n_planes, int sx, int sy, int flat, int accumulate, void* words, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::GrainStatsDesc d;
+        d.src = src; d.src_row_stride = src_row_stride; d.src_plane_stride = src_plane_stride;
+        d.den = den; d.den_row_stride = den_row_stride; d.den_plane_stride = den_plane_stride;
+        d.luma = luma; d.luma_row_stride = luma_row_stride; d.Hl = Hl; d.Wl = Wl;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.n_planes = n_planes; d.sx = sx; d.sy = sy;
+        d.flat = flat; d.accumulate = accumulate; d.words = words;
+        dcvc::grain_stats(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_mask_step_enc(void* y, int ldy, const void* q_dec, int ldq, const void* scales, int lds,
                        const void* means, int ldm, void* y_hat, int ldh, void* sym, void* cond,
                        void* block_count, void* compact_out, void* totals, int Hh, int W, int C,

@@ -1,5 +1,6 @@
 // C ABI of the rate control (include/dcvc_amd_rc.h).
 #include "capi_common.h"
+#include "codec/grain.h"
 #include "codec/rate_control.h"
 #include "dcvc_amd_rc.h"
 
@@ -226,6 +227,16 @@ int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8])
 int dcvc_ivtc_drop(const dcvc_ivtc* t)
 {
     return t ? t->ivtc.drop() : -1;
+}
+
+int dcvc_grain_template(uint32_t seed, int plane, int size, int16_t* out)
+{
+    return dcvc::guarded([&] { dcvc::grain_template(seed, plane, size, out); });
+}
+
+int dcvc_grain_fit(const uint64_t* words, int bit_depth, int gain_percent, long long min_count, uint8_t* lut_out)
+{
+    return dcvc::guarded([&] { dcvc::grain_fit(words, bit_depth, gain_percent, min_count, lut_out); });
 }
 
 }  // extern "C"

@@ -17,7 +17,8 @@
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
 //               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
-//               [--denoise S[:T] [--denoise-out filtered.yuv]]
+//               [--denoise S[:T] [--denoise-out filtered.yuv]
+//                [--grain-log grain.json [--grain-size 0..37] [--grain-window N] [--grain-gain PCT] [--grain-flat F] [--grain-seed N]]]
 //               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
 //               [--ivtc film|match[:CTHRESH[:MI[:T]]] [--field-order tff|bff] [--ivtc-out film.yuv] [--ivtc-log log.json]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
@@ -25,6 +26,22 @@
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--out-format raw|y4m]                                               (-i - | --ref - | -o -: pipes)
+//               [--film-grain grain.json | --grain-strength Y[:C[:SIZE]]]
+//               Film grain. encode --denoise S[:T] --grain-log FILE: every source picture and the filter's output for
+//               it go through dcvc_grain_stats (Y in one call, U and V in one, accumulating on the device; the words come to the
+//               host every 8 pictures and at a window's end); per window of --grain-window source pictures (0, the default: the
+//               whole clip) dcvc_grain_fit makes a record - seed --grain-seed (1) plus the record's index, size --grain-size (12),
+//               tables scaled by --grain-gain percent (100), measured where the filtered picture is flat within --grain-flat (4)
+//               code values; untuned defaults - and the records are written as JSON. The stream does not change. decode
+//               --film-grain FILE (or --grain-strength: constant tables in sixteenths of an 8-bit code value, SIZE 12, seed 1):
+//               behind the conversion and --out-size's resampler every output picture goes through dcvc_grain_apply into a
+//               buffer of its own, Y against itself, U and V against the ungrained Y; that buffer is what -o, --hash-log and
+//               --verify-hash see - hashes cover the grain - while --ref's metrics and the JSON log read the ungrained picture.
+//               The picture index is the output picture's; pictures past the last record keep it. yuv420, yuv422 and yuv444 at
+//               8..16 bits. Refused with status 2: --grain-log without --denoise or named -, its options without it or malformed;
+//               both decoder flags at once, either without -o or a hash flag, another --src-type ("... pictures are not grained
+//               yet"), a malformed file or value, a file of another depth, chroma format or (without --out-size) size, and either
+//               side's flags on the other.
 //               Pipes: "-" names stdin for -i (and for decode --ref) and stdout for -o; a FIFO, /dev/stdin or any other
 //               name that is no regular file (fstat, S_ISREG) works in the same places. Such a source is read front to back and
 //               never seeked; a regular file keeps its count up front and every refusal. A name cannot end in .y4m there, so
@@ -1431,6 +1448,427 @@ struct Resampler {
     }
 };
 
+// ------------------------------------------------------------------------------------ film grain
+// encode --denoise S[:T] --grain-log FILE measures what the filter removes (dcvc_grain_stats) and fits grain records
+// (dcvc_grain_fit); decode --film-grain FILE / --grain-strength Y[:C[:SIZE]] puts grain of those records onto the output pictures
+// (dcvc_grain_template, dcvc_grain_apply). The defaults below are untuned first guesses.
+constexpr int kGrainSize = 12, kGrainGain = 100, kGrainFlat = 4, kGrainMinCount = 256;
+
+struct GrainRecord {
+    long long first = 0, pictures = 0;     // output pictures first .. first + pictures - 1 (the last record: and all that follow)
+    uint32_t seed = 1;
+    int size = kGrainSize;
+    uint8_t lut[27] = {};                  // [3][9]: Y, U, V
+    uint64_t words[48] = {};               // [3][16]: the window's summed dcvc_grain_stats words
+};
+
+struct GrainFile {
+    int bit_depth = 0, width = 0, height = 0, spatial = 0, temporal = 0;      // bit_depth 0: --grain-strength, which fits any run
+    std::string chroma;
+    std::vector<GrainRecord> records;
+};
+
+// a decimal integer in 0..max, digits only
+bool parse_uint(const std::string& s, unsigned long long max, unsigned long long& v)
+{
+    if (s.empty() || s.size() > 20 || s.find_first_not_of("0123456789") != std::string::npos || (s.size() > 1 && s[0] == '0')) return false;
+    errno = 0;
+    v = strtoull(s.c_str(), nullptr, 10);
+    return errno == 0 && v <= max;
+}
+
+// the JSON a grain file needs: objects, arrays, strings without escapes and non-negative integers
+struct Json {
+    enum Kind { Number, String, Array, Object } kind = Number;
+    std::string text;                      // a number's digits, a string's characters
+    std::vector<std::string> keys;         // an object's keys, beside items
+    std::vector<Json> items;
+    const Json* get(const std::string& k) const
+    {
+        for (size_t i = 0; i < keys.size(); ++i) {
+            if (keys[i] == k) return &items[i];
+        }
+        return nullptr;
+    }
+};
+
+struct JsonReader {
+    const std::string& s;
+    std::function<void(const std::string&)> bad;
+    size_t at = 0;
+    void space()
+    {
+        while (at < s.size() && (s[at] == ' ' || s[at] == '\n' || s[at] == '\t' || s[at] == '\r')) ++at;
+    }
+    bool take(char c)
+    {
+        space();
+        if (at < s.size() && s[at] == c) { ++at; return true; }
+        return false;
+    }
+    std::string string()
+    {
+        if (!take('"')) bad("a string is expected at byte " + std::to_string(at));
+        const size_t end = s.find('"', at);
+        if (end == std::string::npos) bad("a string does not end");
+        const std::string t = s.substr(at, end - at);
+        if (t.find('\\') != std::string::npos) bad("escapes in strings are not read");
+        at = end + 1;
+        return t;
+    }
+    Json value(int depth)
+    {
+        if (depth > 6) bad("nested too deep");
+        Json v;
+        space();
+        if (at >= s.size()) bad("the text ends inside a value");
+        const char c = s[at];
+        if (c == '{' || c == '[') {
+            const char close = c == '{' ? '}' : ']';
+            v.kind = c == '{' ? Json::Object : Json::Array;
+            ++at;
+            if (take(close)) return v;
+            do {
+                if (v.kind == Json::Object) {
+                    v.keys.push_back(string());
+                    if (!take(':')) bad("no ':' behind the key " + v.keys.back());
+                }
+                v.items.push_back(value(depth + 1));
+            } while (take(','));
+            if (!take(close)) bad(std::string("no '") + close + "' at byte " + std::to_string(at));
+        } else if (c == '"') {
+            v.kind = Json::String;
+            v.text = string();
+        } else {
+            const size_t end = s.find_first_not_of("0123456789", at);
+            v.text = s.substr(at, end == std::string::npos ? end : end - at);
+            if (v.text.empty()) bad("a non-negative integer, a string, an array or an object is expected at byte " + std::to_string(at));
+            at += v.text.size();
+        }
+        return v;
+    }
+};
+
+const char* chroma_name(const Geometry& g)
+{
+    return g.pix_fmt == DCVC_PIX_YUV422P ? "yuv422" : g.pix_fmt == DCVC_PIX_YUV444P ? "yuv444" : "yuv420";
+}
+
+// the structure of a grain file, strictly; whether it fits the run is decode's business
+GrainFile read_grain_file(const std::string& path)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) die("--film-grain: cannot open " + path);
+    const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    std::function<void(const std::string&)> bad = [&](const std::string& why) { die("--film-grain: " + path + " is no grain file: " + why); };
+    JsonReader rd{text, bad};
+    const Json top = rd.value(0);
+    rd.space();
+    if (rd.at != text.size()) bad("text behind the value");
+    if (top.kind != Json::Object) bad("no object");
+    auto num = [&](const Json& o, const std::string& key, unsigned long long lo, unsigned long long hi) {
+        const Json* v = o.get(key);
+        unsigned long long n = 0;
+        if (!v || v->kind != Json::Number || !parse_uint(v->text, hi, n) || n < lo) {
+            bad("\"" + key + "\" must be an integer in " + std::to_string(lo) + ".." + std::to_string(hi));
+        }
+        return n;
+    };
+    auto list = [&](const Json& o, const std::string& key, size_t count) -> const Json& {
+        const Json* v = o.get(key);
+        if (!v || v->kind != Json::Array || v->items.size() != count) bad("\"" + key + "\" must be a list of " + std::to_string(count));
+        return *v;
+    };
+    auto elem = [&](const Json& l, size_t i, const std::string& key, unsigned long long hi) {
+        unsigned long long n = 0;
+        if (l.items[i].kind != Json::Number || !parse_uint(l.items[i].text, hi, n)) bad("\"" + key + "\" holds integers in 0.." + std::to_string(hi));
+        return n;
+    };
+    GrainFile g;
+    if (num(top, "version", 0, 1000000) != 1) bad("version " + top.get("version")->text + " (this tool reads version 1)");
+    g.bit_depth = static_cast<int>(num(top, "bit_depth", 8, 16));
+    const Json* cf = top.get("chroma_format");
+    if (!cf || cf->kind != Json::String || (cf->text != "yuv420" && cf->text != "yuv422" && cf->text != "yuv444")) {
+        bad("\"chroma_format\" must be yuv420, yuv422 or yuv444");
+    }
+    g.chroma = cf->text;
+    g.width = static_cast<int>(num(top, "width", 2, kMaxPictureSide));
+    g.height = static_cast<int>(num(top, "height", 2, kMaxPictureSide));
+    const Json& dn = list(top, "denoise", 2);
+    g.spatial = static_cast<int>(elem(dn, 0, "denoise", 64));
+    g.temporal = static_cast<int>(elem(dn, 1, "denoise", 64));
+    const Json* recs = top.get("records");
+    if (!recs || recs->kind != Json::Array || recs->items.empty()) bad("\"records\" must be a list of at least one record");
+    long long next = 0;
+    for (const Json& r : recs->items) {
+        if (r.kind != Json::Object) bad("a record is no object");
+        GrainRecord rec;
+        rec.first = static_cast<long long>(num(r, "first", 0, 1ull << 40));
+        if (rec.first != next) bad("record " + std::to_string(g.records.size()) + " must start at picture " + std::to_string(next));
+        rec.pictures = static_cast<long long>(num(r, "pictures", 1, 1ull << 40));
+        next = rec.first + rec.pictures;
+        rec.seed = static_cast<uint32_t>(num(r, "seed", 0, 0xFFFFFFFFull));
+        rec.size = static_cast<int>(num(r, "size", 0, 37));
+        const char* names[3] = {"y", "u", "v"};
+        for (int p = 0; p < 3; ++p) {
+            const Json& t = list(r, names[p], 9);
+            for (size_t k = 0; k < 9; ++k) rec.lut[9 * p + static_cast<int>(k)] = static_cast<uint8_t>(elem(t, k, names[p], 255));
+        }
+        const Json& w = list(r, "words", 3);
+        for (size_t p = 0; p < 3; ++p) {
+            if (w.items[p].kind != Json::Array || w.items[p].items.size() != 16) bad("\"words\" must hold three lists of 16");
+            for (size_t k = 0; k < 16; ++k) rec.words[16 * p + k] = elem(w.items[p], k, "words", (1ull << 63) - 1);
+        }
+        g.records.push_back(rec);
+    }
+    return g;
+}
+
+std::string grain_file_text(const GrainFile& g)
+{
+    std::string s = "{\n  \"version\": 1,\n  \"bit_depth\": " + std::to_string(g.bit_depth) + ",\n  \"chroma_format\": \"" + g.chroma +
+                    "\",\n  \"width\": " + std::to_string(g.width) + ",\n  \"height\": " + std::to_string(g.height) + ",\n  \"denoise\": [" +
+                    std::to_string(g.spatial) + ", " + std::to_string(g.temporal) + "],\n  \"records\": [";
+    for (size_t i = 0; i < g.records.size(); ++i) {
+        const GrainRecord& r = g.records[i];
+        s += std::string(i ? "," : "") + "\n    {\"first\": " + std::to_string(r.first) + ", \"pictures\": " + std::to_string(r.pictures) +
+             ", \"seed\": " + std::to_string(r.seed) + ", \"size\": " + std::to_string(r.size);
+        const char* names[3] = {"y", "u", "v"};
+        for (int p = 0; p < 3; ++p) {
+            s += std::string(",\n     \"") + names[p] + "\": [";
+            for (int k = 0; k < 9; ++k) s += (k ? ", " : "") + std::to_string(r.lut[9 * p + k]);
+            s += "]";
+        }
+        s += ",\n     \"words\": [";
+        for (int p = 0; p < 3; ++p) {
+            s += p ? ", [" : "[";
+            for (int k = 0; k < 16; ++k) s += (k ? ", " : "") + std::to_string(r.words[16 * p + k]);
+            s += "]";
+        }
+        s += "]}";
+    }
+    return s + "\n  ]\n}\n";
+}
+
+// what the flags alone decide is refused before a model is loaded; --film-grain's file is read there too
+struct GrainArgs {
+    bool on = false;                       // decode: pictures are grained
+    bool from_file = false;
+    std::string flag;                      // "--film-grain" or "--grain-strength"
+    GrainFile file;
+    bool log_on = false;                   // encode: --grain-log
+    std::string log;
+    int size = kGrainSize, window = 0, gain = kGrainGain, flat = kGrainFlat;
+    uint32_t seed = 1;
+};
+
+GrainArgs grain_args(const Args& a, bool encoding)
+{
+    GrainArgs g;
+    const char* enc_flags[] = {"grain-log", "grain-size", "grain-window", "grain-gain", "grain-flat", "grain-seed"};
+    if (encoding) {
+        for (const char* k : {"film-grain", "grain-strength"}) {
+            if (a.has(k)) die(std::string("--") + k + " is a decoder flag: encode measures the grain with --denoise S[:T] --grain-log FILE");
+        }
+        if (!a.has("grain-log")) {
+            for (const char* k : enc_flags) {
+                if (a.has(k)) die(std::string("--") + k + " needs --grain-log");
+            }
+            return g;
+        }
+        if (!a.has("denoise")) die("--grain-log needs --denoise: it measures what the filter removes");
+        g.log = a.str("grain-log");
+        if (g.log.empty() || is_dash(g.log)) die("--grain-log needs a file name (not -: stdout is for the stream)");
+        auto opt = [&](const char* k, unsigned long long lo, unsigned long long hi, unsigned long long def) {
+            unsigned long long v = def;
+            if (a.has(k) && (!parse_uint(a.str(k), hi, v) || v < lo)) {
+                die(std::string("--") + k + " must be an integer in " + std::to_string(lo) + ".." + std::to_string(hi) + ", got " + a.str(k));
+            }
+            return v;
+        };
+        g.size = static_cast<int>(opt("grain-size", 0, 37, kGrainSize));
+        g.window = static_cast<int>(opt("grain-window", 0, 1 << 30, 0));
+        g.gain = static_cast<int>(opt("grain-gain", 1, 400, kGrainGain));
+        g.flat = static_cast<int>(opt("grain-flat", 0, 255, kGrainFlat));
+        g.seed = static_cast<uint32_t>(opt("grain-seed", 0, 0xFFFFFFFFull, 1));
+        g.log_on = true;
+        return g;
+    }
+    for (const char* k : enc_flags) {
+        if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
+    }
+    if (a.has("film-grain") && a.has("grain-strength")) die("--film-grain and --grain-strength: exactly one of them may be given");
+    if (!a.has("film-grain") && !a.has("grain-strength")) return g;
+    g.flag = a.has("film-grain") ? "--film-grain" : "--grain-strength";
+    if (!a.has("o") && !a.has("hash-log") && !a.has("verify-hash")) {
+        die(g.flag + " changes what -o writes and the hashes cover, nothing else: it needs -o, --hash-log or --verify-hash");
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (type != "yuv420" && type != "yuv422" && type != "yuv444") {
+        die(g.flag + " is for planar YUV pictures: " + type + " pictures are not grained yet");
+    }
+    if (a.has("film-grain")) {
+        if (a.str("film-grain").empty()) die("--film-grain needs a file name");
+        g.file = read_grain_file(a.str("film-grain"));
+        g.from_file = true;
+    } else {
+        // Y[:C[:SIZE]]: constant tables in sixteenths of an 8-bit code value, C = Y and SIZE = 12 when left out
+        const std::string s = a.str("grain-strength");
+        std::vector<std::string> part;
+        for (size_t at = 0; at <= s.size();) {
+            const size_t colon = std::min(s.find(':', at), s.size());
+            part.push_back(s.substr(at, colon - at));
+            at = colon + 1;
+        }
+        unsigned long long v[3] = {0, 0, static_cast<unsigned long long>(kGrainSize)};
+        bool ok = part.size() >= 1 && part.size() <= 3;
+        for (size_t i = 0; ok && i < part.size(); ++i) ok = parse_uint(part[i], i == 2 ? 37 : 255, v[i]);
+        if (!ok) die("--grain-strength must be Y, Y:C or Y:C:SIZE with Y and C in 0..255 and SIZE in 0..37, got " + s);
+        if (part.size() == 1) v[1] = v[0];
+        GrainRecord r;
+        r.pictures = 1;
+        r.size = static_cast<int>(v[2]);
+        for (int k = 0; k < 27; ++k) r.lut[k] = static_cast<uint8_t>(k < 9 ? v[0] : v[1]);
+        g.file.records.push_back(r);
+    }
+    g.on = true;
+    return g;
+}
+
+// the file against the run's pictures, once their type and depth are settled (a Y4M --ref may supply them)
+void grain_check_run(const GrainArgs& ga, const char* type, int depth)
+{
+    const std::string t = type;
+    if (t != "yuv420" && t != "yuv422" && t != "yuv444") die(ga.flag + " is for planar YUV pictures: " + t + " pictures are not grained yet");
+    if (!ga.from_file) return;
+    if (ga.file.bit_depth != depth || ga.file.chroma != t) {
+        die("--film-grain: the file describes " + ga.file.chroma + " pictures of " + std::to_string(ga.file.bit_depth) + " bits, this run's are " + t +
+            " of " + std::to_string(depth) + " bits");
+    }
+}
+
+// decode: the output picture in `rec` (planes Y, U, V back to back) -> the grained picture in a buffer of the stage's own; rec
+// stays as it is (the metrics read it). Templates are made on the host and uploaded when a record starts.
+struct GrainSynth {
+    GrainArgs arg;
+    uint8_t* out = nullptr;
+    int16_t* d_tpl = nullptr;
+    int16_t* h_tpl = nullptr;              // pinned
+    int current = -1;
+    long long pic = 0;                     // the output picture's index in output order
+    void create(const Geometry& og, const GrainArgs& ga)
+    {
+        arg = ga;
+        if (out) hip_ok(hipFree(out), "hipFree");
+        hip_ok(hipMalloc(&out, og.frame_bytes()), "hipMalloc");
+        if (d_tpl) return;
+        hip_ok(hipMalloc(&d_tpl, 3 * 4096 * sizeof(int16_t)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_tpl), 3 * 4096 * sizeof(int16_t), hipHostMallocDefault), "hipHostMalloc");
+    }
+    const uint8_t* run(const Geometry& og, const uint8_t* rec, hipStream_t st)
+    {
+        const std::vector<GrainRecord>& rs = arg.file.records;
+        int r = std::max(current, 0);
+        while (r + 1 < static_cast<int>(rs.size()) && pic >= rs[static_cast<size_t>(r) + 1].first) ++r;      // past the last record: it stays
+        if (r != current) {
+            hip_ok(hipStreamSynchronize(st), "sync");      // the previous record's templates may still be on their way
+            for (int p = 0; p < 3; ++p) abi_ok(dcvc_grain_template(rs[static_cast<size_t>(r)].seed, p, rs[static_cast<size_t>(r)].size, h_tpl + 4096 * p), "grain template");
+            hip_ok(hipMemcpyAsync(d_tpl, h_tpl, 3 * 4096 * sizeof(int16_t), hipMemcpyHostToDevice, st), "H2D");
+            current = r;
+        }
+        const GrainRecord& g = rs[static_cast<size_t>(r)];
+        const int es = og.hbd() ? 2 : 1, dt = og.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const long long ny = static_cast<long long>(og.H) * og.W, nc = static_cast<long long>(og.Hc()) * og.Wc();
+        const int sx = og.Wc() != og.W ? 1 : 0, sy = og.Hc() != og.H ? 1 : 0;
+        const uint32_t idx = static_cast<uint32_t>(pic);
+        abi_ok(dcvc_grain_apply(rec, og.W, ny, rec, og.W, og.H, og.W, out, og.W, ny, dt, og.bit_depth, og.H, og.W, 1, 0, 0, 0, d_tpl, d_tpl + 4096,
+                                d_tpl + 8192, g.lut, g.seed, idx, st), "grain (Y)");
+        abi_ok(dcvc_grain_apply(rec + ny * es, og.Wc(), nc, rec, og.W, og.H, og.W, out + ny * es, og.Wc(), nc, dt, og.bit_depth, og.Hc(), og.Wc(), 2,
+                                1, sx, sy, d_tpl, d_tpl + 4096, d_tpl + 8192, g.lut, g.seed, idx, st), "grain (U, V)");
+        ++pic;
+        return out;
+    }
+    void destroy()
+    {
+        if (out) hip_ok(hipFree(out), "hipFree");
+        if (d_tpl) hip_ok(hipFree(d_tpl), "hipFree");
+        if (h_tpl) hip_ok(hipHostFree(h_tpl), "hipHostFree");
+        *this = GrainSynth{};
+    }
+};
+
+// encode: what the denoiser took out of every source picture, summed on the device and, every 8 pictures, on the host (8 calls
+// of less than 2^60 a word stay below 2^63); a record is fitted at the end of every window of source pictures
+struct GrainMeter {
+    GrainArgs arg;
+    GrainFile file;
+    uint64_t* d_words = nullptr;
+    uint64_t* h_words = nullptr;           // pinned
+    uint64_t sum[48] = {};
+    int on_device = 0;                     // pictures summed in d_words
+    long long in_window = 0, first = 0;
+    void create(const Geometry& g, const GrainArgs& ga, int spatial, int temporal)
+    {
+        arg = ga;
+        file.bit_depth = g.bit_depth; file.chroma = chroma_name(g); file.width = g.W; file.height = g.H;
+        file.spatial = spatial; file.temporal = temporal;
+        hip_ok(hipMalloc(&d_words, 48 * sizeof(uint64_t)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_words), 48 * sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc");
+    }
+    // src: a source picture at the coded size, den: the filter's output for it (planes Y, U, V back to back)
+    void measure(const Geometry& g, const uint8_t* src, const uint8_t* den, hipStream_t st)
+    {
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
+        const int sx = g.Wc() != g.W ? 1 : 0, sy = g.Hc() != g.H ? 1 : 0, acc = on_device > 0 ? 1 : 0;
+        abi_ok(dcvc_grain_stats(src, g.W, ny, den, g.W, ny, den, g.W, g.H, g.W, dt, g.bit_depth, g.H, g.W, 1, 0, 0, arg.flat, acc, d_words, st),
+               "grain stats (Y)");
+        abi_ok(dcvc_grain_stats(src + ny * es, g.Wc(), nc, den + ny * es, g.Wc(), nc, den, g.W, g.H, g.W, dt, g.bit_depth, g.Hc(), g.Wc(), 2, sx, sy,
+                                arg.flat, acc, d_words + 16, st), "grain stats (U, V)");
+        ++in_window;
+        if (++on_device == 8) flush(st);
+        if (arg.window > 0 && in_window == arg.window) close(st);
+    }
+    void flush(hipStream_t st)
+    {
+        if (on_device == 0) return;
+        hip_ok(hipMemcpyAsync(h_words, d_words, 48 * sizeof(uint64_t), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        for (int i = 0; i < 48; ++i) {
+            sum[i] += h_words[i];
+            if (sum[i] >> 63) die("--grain-log: a window's sums pass 2^63; use a shorter --grain-window");
+        }
+        on_device = 0;
+    }
+    void close(hipStream_t st)
+    {
+        flush(st);
+        if (in_window == 0) return;
+        GrainRecord r;
+        r.first = first; r.pictures = in_window;
+        r.seed = arg.seed + static_cast<uint32_t>(file.records.size());
+        r.size = arg.size;
+        std::memcpy(r.words, sum, sizeof(sum));
+        abi_ok(dcvc_grain_fit(sum, file.bit_depth, arg.gain, kGrainMinCount, r.lut), "grain fit");
+        file.records.push_back(r);
+        first += in_window;
+        in_window = 0;
+        std::memset(sum, 0, sizeof(sum));
+    }
+    void finish(hipStream_t st)
+    {
+        close(st);
+        const std::string text = grain_file_text(file);
+        FILE* lf = fopen(arg.log.c_str(), "wb");
+        if (!lf || fwrite(text.data(), 1, text.size(), lf) != text.size() || fclose(lf) != 0) die("cannot write " + arg.log);
+        fprintf(g_msg, "grain: %zu record%s over %lld pictures (size %d, gain %d%%, flat %d, window %d) -> %s\n", file.records.size(),
+                file.records.size() == 1 ? "" : "s", first, arg.size, arg.gain, arg.flat, arg.window, arg.log.c_str());
+        hip_ok(hipFree(d_words), "hipFree");
+        hip_ok(hipHostFree(h_words), "hipHostFree");
+        d_words = h_words = nullptr;
+    }
+};
+
 // --denoise S[:T] / --denoise-out FILE (encode): what the flags alone decide is refused before a model is loaded
 struct DenoiseArgs {
     bool on = false;
@@ -1489,6 +1927,7 @@ struct Denoiser {
     FILE* file = nullptr;
     int turn = 0;
     long long pictures = 0;
+    GrainMeter* meter = nullptr;   // --grain-log: every source picture and the filter's output for it are measured
     void create(const Geometry& g, const DenoiseArgs& d)
     {
         arg = d;
@@ -1511,6 +1950,7 @@ struct Denoiser {
                "denoise (Y)");
         abi_ok(dcvc_denoise_planes(src + ny * es, g.Wc(), nc, prev ? prev + ny * es : nullptr, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt,
                                    g.bit_depth, g.Hc(), g.Wc(), 2, arg.spatial, arg.temporal, st), "denoise (U, V)");
+        if (meter) meter->measure(g, src, dst, st);
         if (file) {
             hip_ok(hipMemcpyAsync(h_out, dst, g.frame_bytes(), hipMemcpyDeviceToHost, st), "D2H");
             hip_ok(hipStreamSynchronize(st), "sync");
@@ -2389,6 +2829,7 @@ int encode(const Args& a)
     const int wire = wire_arg(a, true);
     rgb16_arg(a, true);
     const DenoiseArgs denoise = denoise_args(a, true);
+    const GrainArgs grain = grain_args(a, true);
     IvtcArgs ivtc = ivtc_args(a, true);
     DeinterlaceArgs deint = deinterlace_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
@@ -2511,6 +2952,11 @@ int encode(const Args& a)
     uint8_t* const staging = b.yuv8;
     Denoiser dn;
     if (denoise.on) dn.create(g, denoise);
+    GrainMeter gm;
+    if (grain.log_on) {
+        gm.create(g, grain, denoise.spatial, denoise.temporal);
+        dn.meter = &gm;
+    }
     // --deinterlace: the upload and the unpack fill one of the filter's two input buffers at the source size; it writes where
     // they would have: the resampler's input with --scale, `staging` without
     Deinterlacer di;
@@ -3109,6 +3555,7 @@ int encode(const Args& a)
     }
     if (denoise.on) {
         fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered\n", denoise.spatial, denoise.temporal, dn.pictures);
+        if (grain.log_on) gm.finish(b.st);
         b.yuv8 = staging;
         dn.destroy();
     }
@@ -3318,6 +3765,12 @@ int decode(const Args& a)
     const PipeArgs pipe = pipe_args(a, false);
     vbv_args(a, batch, false);
     denoise_args(a, false);
+    const GrainArgs grain = grain_args(a, false);
+    // the file against what the flags say of the run, before a model is loaded; a Y4M --ref's header is checked against it below
+    if (grain.on && !(a.has("ref") && pipe.in_is_y4m(a.str("ref")))) {
+        const SrcType t = src_type(a.str("src-type", "yuv420"));
+        grain_check_run(grain, src_type_name(t), bit_depth_arg(a, t));
+    }
     deinterlace_args(a, false);
     ivtc_args(a, false);
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
@@ -3359,6 +3812,7 @@ int decode(const Args& a)
     if (out_size.on && pix_fmt >= 0) {
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
     }
+    if (grain.on) grain_check_run(grain, src_type_name(type), depth);
     hash.begin(wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
     FILE* rec = !has_rec || png ? nullptr : is_dash(a.str("o")) ? stdout : fopen(a.str("o").c_str(), "wb");
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
@@ -3414,6 +3868,8 @@ int decode(const Args& a)
     Geometry go;
     ScaledOut so;
     if (out_size.on) go = geometry(out_size.H, out_size.W, false, depth);
+    // --film-grain / --grain-strength: the grained copy of every output picture, which -o and the hashes see
+    GrainSynth gr;
     // log (src/utils/common.py:46-116)
     std::vector<int> types;
     std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v, ssim, ssim_y, ssim_u, ssim_v;
@@ -3469,6 +3925,10 @@ int decode(const Args& a)
                     "stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
             if (out_size.on) check_ratio("--out-size", s->width, s->height, go.W, go.H);
+            if (grain.from_file && !out_size.on && (grain.file.width != s->width || grain.file.height != s->height)) {
+                die("--film-grain: the file describes " + std::to_string(grain.file.width) + "x" + std::to_string(grain.file.height) +
+                    " pictures, the stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
+            }
             hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth, pix_fmt, wire);
@@ -3476,6 +3936,7 @@ int decode(const Args& a)
             b = make_buffers(g, std::max(c.frames_per_p, batch), calc_ssim);
             ws.create(g);
             if (out_size.on) so.create(g, go, has_ref, calc_ssim);
+            if (grain.on) gr.create(out_size.on ? go : g, grain);
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
@@ -3544,8 +4005,10 @@ int decode(const Args& a)
                     die("reference file is shorter than the stream");
                 }
                 so.rs.run(b.out8, so.out, b.st);
-                if (hash.on()) hash.picture(so.out, go, b.st);
-                if (has_rec) hip_ok(hipMemcpyAsync(so.h_out, so.out, go.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                // the metrics below read so.out, the ungrained picture
+                const uint8_t* shown = grain.on ? gr.run(go, so.out, b.st) : so.out;
+                if (hash.on()) hash.picture(shown, go, b.st);
+                if (has_rec) hip_ok(hipMemcpyAsync(so.h_out, shown, go.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 if (has_ref) {
                     const int dt = go.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
                     const double peak = static_cast<double>((1 << go.bit_depth) - 1);
@@ -3596,14 +4059,16 @@ int decode(const Args& a)
                 }
             }
             if (wire >= 0 && (has_rec || hash.on())) ws.pack(g, b.out8, b.st);
-            if (hash.on()) hash.picture(wire >= 0 ? ws.out : b.out8, g, b.st);
+            // grain behind the source check above: a padding picture of a ragged chunk takes no picture index
+            const uint8_t* shown = grain.on ? gr.run(g, b.out8, b.st) : b.out8;
+            if (hash.on()) hash.picture(wire >= 0 ? ws.out : shown, g, b.st);
             if (has_rec && wire >= 0) {
                 hip_ok(hipMemcpyAsync(ws.h_out, ws.out, g.file_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 rec_put(ws.h_out, g.file_bytes());
                 rec_flush();
             } else if (has_rec) {
-                hip_ok(hipMemcpyAsync(b.h_yuv, b.out8, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                hip_ok(hipMemcpyAsync(b.h_yuv, shown, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 if (png && g.rgb16()) {
                     abi_ok(dcvc_png_write_rgb16(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
@@ -3748,6 +4213,7 @@ int decode(const Args& a)
     if (have_buffers) free_buffers(b);
     ws.destroy();
     so.destroy();
+    gr.destroy();
     if (rec && fclose(rec) != 0) {
         if (errno == EPIPE) output_closed(a.str("o"));
         die("short write");

@@ -491,6 +491,38 @@ void weave_fields_validate(const WeaveFieldsDesc& d);     // throws std::invalid
 // one launch on `stream`: validates first, allocates nothing, never waits for the host
 void weave_fields(const WeaveFieldsDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- film grain (grain.hip)
+// grain_apply: synthetic grain onto the planes of a decoded picture - a 64 x 64 template per plane at a hashed offset per 32 x 32
+// block, scaled by a table over the collocated luma; grain_stats: what a denoiser took out of a source picture, per luma bin,
+// in 16 exact uint64 words a plane (both stated at the head of grain.hip). Strides in samples.
+constexpr int kGrainMaxSide = 16384;
+struct GrainApplyDesc {
+    const void* rec = nullptr; int rec_row_stride = 0; long long rec_plane_stride = 0;
+    const void* luma = nullptr; int luma_row_stride = 0; int Hl = 0, Wl = 0;      // the ungrained luma plane all planes share
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;  // may be rec
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0, n_planes = 1;
+    int first_plane = 0;                             // the planes are first_plane .. first_plane + n_planes - 1 of Y, U, V
+    int sx = 0, sy = 0;                              // 0 or 1: the planes' subsampling against the luma plane
+    const int16_t* templates[3] = {nullptr, nullptr, nullptr};      // device, int16 [64][64] each; read for the call's planes
+    const uint8_t* lut = nullptr;                    // host, [3][9]
+    uint32_t seed = 0, pic = 0;
+};
+void grain_apply_validate(const GrainApplyDesc& d);  // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void grain_apply(const GrainApplyDesc& d, hipStream_t stream);
+struct GrainStatsDesc {
+    const void* src = nullptr; int src_row_stride = 0; long long src_plane_stride = 0;
+    const void* den = nullptr; int den_row_stride = 0; long long den_plane_stride = 0;
+    const void* luma = nullptr; int luma_row_stride = 0; int Hl = 0, Wl = 0;      // den's luma plane
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0, n_planes = 1, sx = 0, sy = 0;
+    int flat = 0;                                    // 0..255, in 8-bit code values
+    int accumulate = 0;                              // 0: the words are zeroed first; 1: added to
+    void* words = nullptr;                           // device, 8-byte aligned: per plane n[0..7], S[0..7]
+};
+void grain_stats_validate(const GrainStatsDesc& d);  // throws std::invalid_argument for what is refused
+// one launch (two with accumulate == 0) on `stream`: validates first, allocates nothing, never waits for the host
+void grain_stats(const GrainStatsDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -491,6 +491,42 @@ int dcvc_field_match(const void* cur, int cur_row_stride, const void* prev, int 
 int dcvc_weave_fields(const void* a, int a_row_stride, long long a_plane_stride, const void* b, int b_row_stride, long long b_plane_stride,
                       void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int H, int W, int n_planes, int first, void* stream);
 
+/* Film grain on the GPU (no reference counterpart): synthesis onto decoded planes and the measurement of what
+ * dcvc_denoise_planes removed; the template and the fit are host code, dcvc_grain_template / dcvc_grain_fit (dcvc_amd_rc.h).
+ * Every value is an exact integer. sh = bit_depth - 8, max_val = 2^bit_depth - 1, u32 arithmetic wraps, shifts of signed values
+ * are arithmetic. The planes of a call have one size [H][W] and share one luma plane Yl [Hl][Wl] against which they are
+ * subsampled by (sx, sy) in {0, 1}; Hl >= ((H-1) << sy) + 1 and Wl >= ((W-1) << sx) + 1, indexes clamped into the luma plane:
+ *   sx == 1: L = (Yl[y << sy][2x] + Yl[y << sy][2x + 1] + 1) >> 1;   sx == 0: L = Yl[y << sy][x];   i = min(L >> sh, 255)
+ *   dcvc_grain_apply: plane p = first_plane + 0 .. n_planes - 1 (0, 1, 2 = Y, U, V) of output picture `pic`, block (by, bx) =
+ *   (y / 32, x / 32) in the plane's own coordinates:
+ *     h = seed*0x9E3779B1 + pic*0x85EBCA77 + p*0xC2B2AE3D + by*0x27D4EB2F + bx*0x165667B1; h ^= h >> 15; h *= 0x2C1B3C6D;
+ *     h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15; ox = h & 63; oy = (h >> 8) & 63
+ *     t = template_p[(oy + (y & 31)) & 63][(ox + (x & 31)) & 63]   (device, int16 [64][64], |t| <= 1023: dcvc_grain_template)
+ *     k = i >> 5, fr = i & 31, v = (lut[p][k] (32 - fr) + lut[p][k+1] fr + 16) >> 5   (lut: host, uint8 [3][9], sixteenths of an
+ *     8-bit code value at luma 0, 32, .., 256), n = (t v + (1 << (9 - sh))) >> (10 - sh), dst = clamp(rec + n, 0, max_val)
+ *   A table of zeros copies. The luma is the UNGRAINED reconstruction. dst may be rec (the same pointer and strides); dst may
+ *   overlap the luma plane only in a call of one plane that is rec and the luma at once (sx = sy = 0). Templates of planes
+ *   outside the call are not read and may be NULL. One launch on `stream`.
+ *   dcvc_grain_stats: src, and den = the denoiser's output for it, n_planes (1..2) planes; luma is DEN's luma plane.
+ *   d = src - den; a sample counts when den's four 4-neighbours in its own plane (indexes clamped) each differ from den[y][x] by
+ *   at most flat << sh; its bin is i >> 5. words (device, 8-byte aligned, 16 uint64 a plane): n[0..7] the counts, S[0..7] the
+ *   sums of d^2. accumulate == 0: a first launch zeroes the words; 1: the call adds to them (less than 2^60 a call). Exact
+ *   integers, the same for every launch geometry and every run.
+ *   Both: samples are DCVC_SAMPLE_U8 (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16); strides in samples (plane
+ *   strides are not read for one plane); nothing is allocated and nothing waits for the host. Refused before anything is
+ *   enqueued: a NULL operand; another sample type; a bit_depth that is not the type's; H or W outside 1..16384; n_planes
+ *   outside 1..3 (apply, and first_plane + n_planes above 3) or 1..2 (stats); sx or sy outside {0, 1}; a luma plane that is too
+ *   small (or above 32768 a side); flat outside 0..255; accumulate outside {0, 1}; a row stride below the width or a plane stride
+ *   below the plane; a 16-bit plane or a template at an odd address; words that are not 8-byte aligned; dst overlapping rec
+ *   (unless it is rec), the luma (but for the case above) or a template. */
+int dcvc_grain_apply(const void* rec, int rec_row_stride, long long rec_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl,
+                     void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth, int H, int W, int n_planes,
+                     int first_plane, int sx, int sy, const int16_t* template_y, const int16_t* template_u, const int16_t* template_v,
+                     const uint8_t* lut, uint32_t seed, uint32_t pic, void* stream);
+int dcvc_grain_stats(const void* src, int src_row_stride, long long src_plane_stride, const void* den, int den_row_stride,
+                     long long den_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl, int dtype, int bit_depth, int H,
+                     int W, int n_planes, int sx, int sy, int flat, int accumulate, void* words, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

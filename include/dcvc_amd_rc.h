@@ -131,6 +131,22 @@ int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8]);
 int dcvc_ivtc_drop(const dcvc_ivtc* t);
 void dcvc_ivtc_destroy(dcvc_ivtc* t);
 
+/* Film grain, the host side (dcvc_amd/grain.py grain_template and grain_fit are the same arithmetic in Python).
+ *   dcvc_grain_template: out (host, int16 [64][64]) = the grain template of (seed, plane 0..2, size 0..37) that
+ *   dcvc_grain_apply (dcvc_amd_ops.h) tiles over a plane. s = seed*0x9E3779B1 + plane*0xC2B2AE3D + 1 (u32, wrapping); per
+ *   position in row-major order four draws s = s*1664525 + 1013904223, byte = s >> 24, w = the four bytes' sum - 510; with
+ *   a = size, b = 128 - 2a: h = a w[x-1] + b w[x] + a w[x+1], then the same pass down the columns of h gives f, both on the
+ *   64 x 64 torus; rms = isqrt(sum f^2 / 4096), T = floor((128 f + rms) / (2 rms)): a standard deviation of about 64, a lag-1
+ *   correlation of about 2ab / (2a^2 + b^2). Refused: NULL out, plane outside 0..2, size outside 0..37, rms == 0, |T| > 1023.
+ *   dcvc_grain_fit: words (host, [3][16]: the words of dcvc_grain_stats of Y, U, V, summed over a window of pictures) ->
+ *   lut_out (host, uint8 [3][9]). Per plane and bin with n >= min_count the value is min(255, isqrt((256 S gain_percent^2) /
+ *   (n 10000 << 2 (bit_depth - 8)))), floor division in 128 bits: the residual's standard deviation in sixteenths of an 8-bit
+ *   code value. A bin below min_count takes the nearest valid bin's value, ties to the lower bin; a plane without a valid bin
+ *   gets zeros. lut[0] = bin 0, lut[8] = bin 7, lut[k] = (bin[k-1] + bin[k] + 1) >> 1. Refused: a NULL pointer, bit_depth
+ *   outside 8..16, gain_percent outside 1..400, min_count below 1, a word of 2^63 or above. */
+int dcvc_grain_template(uint32_t seed, int plane, int size, int16_t* out);
+int dcvc_grain_fit(const uint64_t* words, int bit_depth, int gain_percent, long long min_count, uint8_t* lut_out);
+
 #ifdef __cplusplus
 }
 #endif

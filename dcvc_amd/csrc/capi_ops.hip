@@ -964,6 +964,28 @@ int dcvc_weave_fields(const void* a, int a_row_stride, long long a_plane_stride,
     });
 }
 
+int dcvc_crop_stats(const void* luma, int row_stride, int dtype, int bit_depth, int H, int W, int limit, void* counts, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::CropStatsDesc d;
+        d.luma = luma; d.row_stride = row_stride; d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.limit = limit;
+        d.counts = counts;
+        dcvc::crop_stats(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_window_planes(const void* src, int src_row_stride, long long src_plane_stride, int Hs, int Ws, void* dst, int dst_row_stride,
+                       long long dst_plane_stride, int Hd, int Wd, int dtype, int n_planes, int ox, int oy, const int* fill, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::WindowPlanesDesc d;
+        d.src = src; d.src_row_stride = src_row_stride; d.src_plane_stride = src_plane_stride; d.Hs = Hs; d.Ws = Ws;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride; d.Hd = Hd; d.Wd = Wd;
+        d.dtype = dtype; d.n_planes = n_planes; d.ox = ox; d.oy = oy; d.fill = fill;
+        dcvc::window_planes(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_grain_apply(const void* rec, int rec_row_stride, long long rec_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl,
                      void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth, int H, int W, int n_planes,
                      int first_plane, int sx, int sy, const int16_t* template_y, const int16_t* template_u, const int16_t* template_v,

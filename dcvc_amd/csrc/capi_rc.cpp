@@ -22,6 +22,10 @@ struct dcvc_ivtc {
     dcvc::Ivtc ivtc;
 };
 
+struct dcvc_cropdet {
+    dcvc::CropDetect det;
+};
+
 extern "C" {
 
 dcvc_rc* dcvc_rc_create(double target_bpp, double pixels_per_picture, double qp0, int horizon, int intra_bonus,
@@ -227,6 +231,38 @@ int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8])
 int dcvc_ivtc_drop(const dcvc_ivtc* t)
 {
     return t ? t->ivtc.drop() : -1;
+}
+
+dcvc_cropdet* dcvc_cropdet_create(int H, int W, int frac, int min_bar, int ax, int ay)
+{
+    dcvc_cropdet* t = nullptr;
+    dcvc::guarded([&] { t = new dcvc_cropdet{dcvc::CropDetect(H, W, frac, min_bar, ax, ay)}; });
+    return t;
+}
+
+void dcvc_cropdet_destroy(dcvc_cropdet* t)
+{
+    delete t;
+}
+
+int dcvc_cropdet_push(dcvc_cropdet* t, const uint32_t* counts)
+{
+    int r = 0;
+    const int e = dcvc::guarded([&] {
+        if (t == nullptr) throw std::invalid_argument("null cropdet handle");
+        r = t->det.push(counts) ? 1 : 0;
+    });
+    return e < 0 ? e : r;
+}
+
+int dcvc_cropdet_result(const dcvc_cropdet* t, int* x, int* y, int* w, int* h)
+{
+    int r = 0;
+    const int e = dcvc::guarded([&] {
+        if (t == nullptr || x == nullptr || y == nullptr || w == nullptr || h == nullptr) throw std::invalid_argument("cropdet: null operand");
+        r = t->det.result(*x, *y, *w, *h);
+    });
+    return e < 0 ? e : r;
 }
 
 int dcvc_grain_template(uint32_t seed, int plane, int size, int16_t* out)

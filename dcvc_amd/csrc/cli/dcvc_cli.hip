@@ -21,12 +21,43 @@
 //                [--grain-log grain.json [--grain-size 0..37] [--grain-window N] [--grain-gain PCT] [--grain-flat F] [--grain-seed N]]]
 //               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
 //               [--ivtc film|match[:CTHRESH[:MI[:T]]] [--field-order tff|bff] [--ivtc-out film.yuv] [--ivtc-log log.json]]
+//               [--crop auto[:LIMIT[:FRAC[:MINBAR[:N]]]] | --crop WxH+X+Y [--crop-log crop.json] [--crop-out cropped.yuv] [--crop-fill Y:U:V]]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--out-format raw|y4m]                                               (-i - | --ref - | -o -: pipes)
 //               [--film-grain grain.json | --grain-strength Y[:C[:SIZE]]]
+//               [--uncrop crop.json | --pad SWxSH+X+Y [--pad-fill Y:U:V]]
+//               Black bars. encode --crop WxH+X+Y codes the window of every source picture; --crop auto finds it:
+//               before the first picture is coded N' = min(N, M) of the M source frames the run will read (N 16, 1..256), frames
+//               ((2k + 1) M) / (2 N'), are read with pread from the regular -i file (a pipe is refused), uploaded, unpacked when a
+//               wire type, measured by dcvc_crop_stats on the luma plane (per row and column the samples above LIMIT, 24, in
+//               8-bit code values; the (H + W) * 4 bytes come to the host) and pushed to dcvc_cropdet_*: a row or column is active
+//               with more than FRAC / 256 (4) of its samples above the limit, a picture without an active row or column casts no
+//               vote, the window is the union of the voting pictures' rectangles, a bar below MINBAR (8) stays and the others are
+//               rounded down to multiples of 2 (the chroma grid; the codec takes even sides only) and of 4 vertically with
+//               --deinterlace / --ivtc, so content is never cut; untuned defaults. A manual window must lie inside the picture
+//               with positive sides on the same grid. The stage sits behind the upload and dcvc_wire_unpack, which land in a
+//               buffer of the file's size, and in front of everything else: two dcvc_window_planes calls (Y; U and V) write the
+//               window where the upload would have landed - upload -> unpack -> crop -> deinterlace | ivtc -> --scale -> --denoise
+//               -> dcvc_pix_to_x - and the run is that of the cropped clip: the parameter set, --batch, the rate and quality
+//               flags, --scene-cut, --vbv-*, pipes (manual window), read-ahead and padding pictures see the window's size. A window
+//               that is the whole picture issues no launch and gives the file of a run without the flag. yuv420 / yuv422 / yuv444
+//               at 8..16 bits, Y4M and the wire types on their 4:2:2 carrier; nv12 / p010 / nv21 and RGB are refused ("sources are
+//               not cropped yet"). --crop-out FILE: the cropped pictures in the carrier's raw layout, what decode --ref should be
+//               given; --crop-log FILE: JSON - mode, limit, frac, min_bar, source_width / source_height, src_type,
+//               chroma_format, bit_depth, probes [{idx, voted, top, bottom, left, right | null}], votes, window {x, y, width,
+//               height}, fill [Y, U, V] (limited-range black 16, 128, 128 at the depth, or --crop-fill). One summary line: "crop:
+//               auto|manual, WxH+X+Y of SWxSH (V of N' pictures voted)". decode --uncrop FILE (that log) or --pad SWxSH+X+Y:
+//               the last stage on the output picture, behind the conversion, --out-size and the grain - the bars carry no grain:
+//               two dcvc_window_planes calls with negative offsets write the picture into a buffer of the source's size, the rest
+//               at the fill values (--pad-fill Y:U:V over the log's or the default). -o (a Y4M header included), --hash-log and
+//               --verify-hash hold the padded picture; --ref, PSNR, --calc-ssim and the JSON log read the unpadded one. Refused
+//               with status 2: malformed values, --crop-out / --crop-log / --crop-fill without --crop or named -, a window that
+//               does not fit, auto on a pipe, either side's flags on the other; --uncrop with --pad, either without -o or a hash
+//               flag, --pad-fill without either, a malformed log, a log of another depth or chroma format, a picture of another
+//               size than the log's window or one that does not fit the source, another --src-type ("pictures are not padded yet").
 //               Film grain. encode --denoise S[:T] --grain-log FILE: every source picture and the filter's output for
 //               it go through dcvc_grain_stats (Y in one call, U and V in one, accumulating on the device; the words come to the
 //               host every 8 pictures and at a window's end); per window of --grain-window source pictures (0, the default: the
@@ -859,6 +890,25 @@ struct PictureFile {
             ++n;
         }
     }
+    // where the first n pictures of a regular file start (--crop auto reads some of them with pread); the reader's position is
+    // not touched
+    std::vector<long long> offsets(size_t frame_bytes, long long n)
+    {
+        std::vector<long long> at_of;
+        long long at = y4m ? info.header_bytes : 0;
+        char line[1024];
+        for (long long i = 0; i < n; ++i) {
+            if (y4m) {
+                const ssize_t got = pread(fd, line, sizeof(line), at);
+                const int len = got <= 0 ? -1 : dcvc_y4m_frame_header_bytes(line, static_cast<size_t>(got));
+                if (len < 0) die(path + ": no FRAME line where picture " + std::to_string(i + 1) + " should start");
+                at += len;
+            }
+            at_of.push_back(at);
+            at += static_cast<long long>(frame_bytes);
+        }
+        return at_of;
+    }
     // the next picture. Calls nothing that dies and nothing from HIP: the read-ahead thread runs it.
     Status next(uint8_t* dst, size_t frame_bytes)
     {
@@ -1479,8 +1529,8 @@ bool parse_uint(const std::string& s, unsigned long long max, unsigned long long
 
 // the JSON a grain file needs: objects, arrays, strings without escapes and non-negative integers
 struct Json {
-    enum Kind { Number, String, Array, Object } kind = Number;
-    std::string text;                      // a number's digits, a string's characters
+    enum Kind { Number, String, Array, Object, Literal } kind = Number;      // Literal: null, true or false (a crop log)
+    std::string text;                      // a number's digits, a string's characters, a literal's name
     std::vector<std::string> keys;         // an object's keys, beside items
     std::vector<Json> items;
     const Json* get(const std::string& k) const
@@ -1539,6 +1589,12 @@ struct JsonReader {
         } else if (c == '"') {
             v.kind = Json::String;
             v.text = string();
+        } else if (c >= 'a' && c <= 'z') {
+            const size_t end = s.find_first_not_of("abcdefghijklmnopqrstuvwxyz", at);
+            v.kind = Json::Literal;
+            v.text = s.substr(at, end == std::string::npos ? end : end - at);
+            if (v.text != "null" && v.text != "true" && v.text != "false") bad("the word " + v.text + " at byte " + std::to_string(at));
+            at += v.text.size();
         } else {
             const size_t end = s.find_first_not_of("0123456789", at);
             v.text = s.substr(at, end == std::string::npos ? end : end - at);
@@ -2298,6 +2354,451 @@ struct IvtcStage {
     }
 };
 
+// ------------------------------------------------------------------------------------ black bars
+// "A:B:C" -> three integers in 0..max
+bool parse_triple(const std::string& s, unsigned long long max, int (&v)[3])
+{
+    size_t at = 0;
+    for (int k = 0; k < 3; ++k) {
+        const size_t colon = k < 2 ? s.find(':', at) : s.size();
+        unsigned long long n = 0;
+        if (colon == std::string::npos || !parse_uint(s.substr(at, colon - at), max, n)) return false;
+        v[k] = static_cast<int>(n);
+        at = colon + 1;
+    }
+    return true;
+}
+
+// "WxH+X+Y" -> the four, each at most kMaxPictureSide
+bool parse_window(const std::string& s, int& w, int& h, int& x, int& y)
+{
+    const size_t ex = s.find('x'), p1 = s.find('+'), p2 = p1 == std::string::npos ? p1 : s.find('+', p1 + 1);
+    if (ex == std::string::npos || p2 == std::string::npos || ex > p1) return false;
+    unsigned long long v[4];
+    const std::string part[4] = {s.substr(0, ex), s.substr(ex + 1, p1 - ex - 1), s.substr(p1 + 1, p2 - p1 - 1), s.substr(p2 + 1)};
+    for (int k = 0; k < 4; ++k) {
+        if (!parse_uint(part[k], kMaxPictureSide, v[k])) return false;
+    }
+    w = static_cast<int>(v[0]); h = static_cast<int>(v[1]); x = static_cast<int>(v[2]); y = static_cast<int>(v[3]);
+    return true;
+}
+
+// the chroma planes' subsampling of a picture against its luma plane: 2, 2 for 4:2:0; 2, 1 for 4:2:2; 1, 1 for 4:4:4
+int chroma_sx(const Geometry& g) { return g.W / g.Wc(); }
+int chroma_sy(const Geometry& g) { return g.H / g.Hc(); }
+
+// a window of the planes (Y, U, V back to back) of a `from` picture -> the planes of a `to` picture, the window's origin at
+// (x, y) of `from` in luma samples (negative: `to` is the larger one and `from` lies at (-x, -y) in it): dcvc_window_planes,
+// Y in one call, U and V in one call
+void window_picture(const Geometry& from, const uint8_t* src, const Geometry& to, uint8_t* dst, int x, int y, const int (&fill)[3], hipStream_t st)
+{
+    const int es = from.hbd() ? 2 : 1, dt = from.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+    const long long fy = static_cast<long long>(from.H) * from.W, fc = static_cast<long long>(from.Hc()) * from.Wc();
+    const long long ty = static_cast<long long>(to.H) * to.W, tc = static_cast<long long>(to.Hc()) * to.Wc();
+    abi_ok(dcvc_window_planes(src, from.W, fy, from.H, from.W, dst, to.W, ty, to.H, to.W, dt, 1, x, y, fill, st), "window (Y)");
+    abi_ok(dcvc_window_planes(src + fy * es, from.Wc(), fc, from.Hc(), from.Wc(), dst + ty * es, to.Wc(), tc, to.Hc(), to.Wc(), dt, 2,
+                              x / chroma_sx(from), y / chroma_sy(from), fill + 1, st), "window (U, V)");
+}
+
+// --crop auto[:LIMIT[:FRAC[:MINBAR[:N]]]] | WxH+X+Y / --crop-log FILE / --crop-out FILE / --crop-fill Y:U:V (encode):
+// what the flags alone decide is refused before a model is loaded
+struct CropArgs {
+    bool on = false, automatic = false;
+    int limit = 24, frac = 4, min_bar = 8, probes = 16;      // nobody has tuned these for this project
+    int x = 0, y = 0, w = 0, h = 0;                          // the window: manual, or what the detection found
+    bool fill_given = false;
+    int fill[3] = {16, 128, 128};                            // at the source's depth once that is known
+    std::string log, out;
+    const char* mode() const { return automatic ? "auto" : "manual"; }
+};
+
+CropArgs crop_args(const Args& a, bool encoding)
+{
+    CropArgs c;
+    if (!encoding) {
+        for (const char* k : {"crop", "crop-log", "crop-out", "crop-fill"}) {
+            if (a.has(k)) die(std::string("--") + k + " is an encoder flag: decode puts the bars back with --uncrop FILE or --pad SWxSH+X+Y");
+        }
+        return c;
+    }
+    for (const char* k : {"uncrop", "pad", "pad-fill"}) {
+        if (a.has(k)) die(std::string("--") + k + " is a decoder flag: encode drops the bars with --crop");
+    }
+    if (!a.has("crop")) {
+        for (const char* k : {"crop-log", "crop-out", "crop-fill"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --crop");
+        }
+        return c;
+    }
+    const std::string s = a.str("crop");
+    const char* form = "--crop must be auto, auto:LIMIT[:FRAC[:MINBAR[:N]]] with integers in 0..255, 0..255, 0..4096 and 1..256, or WxH+X+Y, got ";
+    if (s.rfind("auto", 0) == 0) {
+        std::vector<std::string> parts;
+        for (size_t at = 0;;) {
+            const size_t colon = s.find(':', at);
+            parts.push_back(s.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
+            if (colon == std::string::npos) break;
+            at = colon + 1;
+        }
+        bool good = parts[0] == "auto" && parts.size() <= 5;
+        const unsigned long long top[4] = {255, 255, 4096, 256};
+        int* into[4] = {&c.limit, &c.frac, &c.min_bar, &c.probes};
+        for (size_t k = 1; good && k < parts.size(); ++k) {
+            unsigned long long v = 0;
+            good = parse_uint(parts[k], top[k - 1], v) && (k < 4 || v >= 1);
+            if (good) *into[k - 1] = static_cast<int>(v);
+        }
+        if (!good) die(form + s);
+        c.automatic = true;
+    } else if (!parse_window(s, c.w, c.h, c.x, c.y)) {
+        die(form + s);
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (is_rgb_name(type)) die("--crop is for planar YUV sources: RGB sources are not cropped yet");
+    if (type == "nv12" || type == "p010" || type == "nv21") die("--crop is for planar YUV sources: " + type + " sources are not cropped yet");
+    for (const char* k : {"crop-log", "crop-out"}) {
+        if (a.has(k) && (a.str(k).empty() || is_dash(a.str(k)))) die(std::string("--") + k + " needs a file name (not -: stdout is for the stream)");
+    }
+    c.log = a.str("crop-log");
+    c.out = a.str("crop-out");
+    if (a.has("crop-fill")) {
+        if (!parse_triple(a.str("crop-fill"), 65535, c.fill)) die("--crop-fill must be Y:U:V, three sample values, got " + a.str("crop-fill"));
+        c.fill_given = true;
+    }
+    if (c.automatic && (is_dash(a.str("i")) || names_a_pipe(a.str("i")))) die("--crop auto needs a seekable source; give --crop WxH+X+Y");
+    c.on = true;
+    return c;
+}
+
+// one probed picture of --crop auto
+struct CropProbe {
+    long long idx = 0;
+    bool voted = false;
+    int top = 0, bottom = 0, left = 0, right = 0;
+};
+
+// --crop: the window is settled before the first picture is coded - checked (manual) or found (auto: N' = min(N, M) of the M
+// source frames the run will read, frame ((2k + 1) M) / (2 N') for k = 0 .. N' - 1, each read with pread, uploaded, unpacked when
+// it is a wire type, measured by dcvc_crop_stats and pushed to dcvc_cropdet_*). Then every source picture's upload (and unpack)
+// lands in a buffer of the file's size, and dcvc_window_planes writes the window where the upload would have landed.
+struct CropStage {
+    CropArgs arg;
+    bool active = false;           // the window is smaller than the picture: there is something to cut
+    int ax = 2, ay = 2;
+    std::vector<CropProbe> probes;
+    int votes = 0;
+    WireStage wsf;                 // a wire format's pictures at the FILE's size
+    uint8_t* full = nullptr;       // the file's picture on the device: planes Y, U, V
+    uint8_t* h_in = nullptr;       // pinned: the file's picture
+    uint8_t* h_out = nullptr;      // pinned: --crop-out's picture
+    FILE* file = nullptr;
+    long long pictures = 0;
+    // the source type's alignment; the codec takes even sides only, so a 4:4:4 or 4:2:2 window is even all the same
+    void align(const Geometry& gf, bool fields)
+    {
+        ax = std::max(chroma_sx(gf), 2);
+        ay = std::max(chroma_sy(gf), 2) * (fields ? 2 : 1);
+    }
+    void check_manual(const Geometry& gf) const
+    {
+        const std::string w = std::to_string(arg.w) + "x" + std::to_string(arg.h) + "+" + std::to_string(arg.x) + "+" + std::to_string(arg.y);
+        if (arg.w < 1 || arg.h < 1) die("--crop " + w + ": the window's sides must be positive");
+        if (arg.x + arg.w > gf.W || arg.y + arg.h > gf.H) {
+            die("--crop " + w + " does not lie inside the " + std::to_string(gf.W) + "x" + std::to_string(gf.H) + " picture");
+        }
+        if (arg.x % ax || arg.w % ax || arg.y % ay || arg.h % ay) {
+            die("--crop " + w + ": offsets and sides must be multiples of " + std::to_string(ax) + " (horizontal) and " + std::to_string(ay) +
+                " (vertical) for this source" + (ay > 2 ? " (field rows: --deinterlace / --ivtc double the vertical step)" : ""));
+        }
+    }
+    // auto: M = the source frames the run will read
+    void detect(PictureFile& f, const Geometry& gf, long long M)
+    {
+        allocate(gf);
+        if (gf.H % ay || gf.W % ax) {
+            die("--crop auto: the " + std::to_string(gf.W) + "x" + std::to_string(gf.H) + " picture is no multiple of the window's step, " +
+                std::to_string(ax) + "x" + std::to_string(ay));
+        }
+        dcvc_cropdet* det = dcvc_cropdet_create(gf.H, gf.W, arg.frac, arg.min_bar, ax, ay);
+        if (!det) die(std::string("--crop auto: ") + dcvc_last_error());
+        const long long n = std::min<long long>(arg.probes, M);
+        const std::vector<long long> at = f.offsets(gf.file_bytes(), M);
+        const size_t words = static_cast<size_t>(gf.H + gf.W);
+        hipStream_t st = nullptr;
+        uint32_t* counts = nullptr;
+        uint32_t* h_counts = nullptr;
+        hip_ok(hipStreamCreate(&st), "hipStreamCreate");
+        hip_ok(hipMalloc(&counts, words * sizeof(uint32_t)), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_counts), words * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+        const int dt = gf.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        for (long long k = 0; k < n; ++k) {
+            CropProbe p;
+            p.idx = ((2 * k + 1) * M) / (2 * n);
+            size_t got = 0;
+            while (got < gf.file_bytes()) {
+                const ssize_t r = pread(f.fd, h_in + got, gf.file_bytes() - got, at[static_cast<size_t>(p.idx)] + static_cast<long long>(got));
+                if (r < 0 && errno == EINTR) continue;
+                if (r <= 0) die("cannot read picture " + std::to_string(p.idx + 1) + " of " + f.path);
+                got += static_cast<size_t>(r);
+            }
+            if (gf.wire >= 0) wsf.upload(gf, full, st, h_in);
+            else hip_ok(hipMemcpyAsync(full, h_in, gf.frame_bytes(), hipMemcpyHostToDevice, st), "H2D");
+            abi_ok(dcvc_crop_stats(full, gf.W, dt, gf.bit_depth, gf.H, gf.W, arg.limit, counts, st), "crop_stats");
+            hip_ok(hipMemcpyAsync(h_counts, counts, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+            const int voted = dcvc_cropdet_push(det, h_counts);
+            abi_ok(voted, "cropdet");
+            p.voted = voted == 1;
+            if (p.voted) {
+                // the picture's own rectangle for the log: the same words through a detector of its own, nothing dropped or rounded
+                dcvc_cropdet* one = dcvc_cropdet_create(gf.H, gf.W, arg.frac, 0, 1, 1);
+                if (!one) die(std::string("--crop auto: ") + dcvc_last_error());
+                int x = 0, y = 0, w = 0, h = 0;
+                abi_ok(dcvc_cropdet_push(one, h_counts), "cropdet");
+                abi_ok(dcvc_cropdet_result(one, &x, &y, &w, &h), "cropdet");
+                dcvc_cropdet_destroy(one);
+                p.top = y; p.bottom = y + h - 1; p.left = x; p.right = x + w - 1;
+            }
+            probes.push_back(p);
+        }
+        votes = dcvc_cropdet_result(det, &arg.x, &arg.y, &arg.w, &arg.h);
+        abi_ok(votes, "cropdet");
+        dcvc_cropdet_destroy(det);
+        active = arg.w != gf.W || arg.h != gf.H;
+        hip_ok(hipFree(counts), "hipFree");
+        hip_ok(hipHostFree(h_counts), "hipHostFree");
+        hip_ok(hipStreamDestroy(st), "hipStreamDestroy");
+    }
+    // what needs no device: the step, the fill values, a manual window's check. gf: the file's pictures.
+    void create(const CropArgs& c, const Geometry& gf, bool fields)
+    {
+        arg = c;
+        align(gf, fields);
+        if (!arg.fill_given) {
+            for (int& v : arg.fill) v <<= gf.bit_depth - 8;
+        }
+        for (int v : arg.fill) {
+            if (v > (1 << gf.bit_depth) - 1) die("--crop-fill: " + std::to_string(v) + " is no sample of " + std::to_string(gf.bit_depth) + " bits");
+        }
+        if (!arg.automatic) {
+            check_manual(gf);
+            active = arg.w != gf.W || arg.h != gf.H;
+        }
+    }
+    // the buffers of the file's size: in front of the detection, or of the first picture
+    void allocate(const Geometry& gf)
+    {
+        if (full) return;
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_in), gf.file_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        hip_ok(hipMalloc(&full, gf.frame_bytes()), "hipMalloc");
+        wsf.create(gf);
+    }
+    // --crop-out opens once the window, and with it the pictures' size, is known
+    void open_out(const Geometry& gs)
+    {
+        if (arg.out.empty()) return;
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), gs.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+        file = fopen(arg.out.c_str(), "wb");
+        if (!file) die("cannot write " + arg.out);
+    }
+    // the file's picture in pinned memory at h -> the window's planes at dst, where the upload of a picture of that size lands
+    void upload(const Geometry& gf, const Geometry& gs, uint8_t* dst, const uint8_t* h, hipStream_t st)
+    {
+        if (gf.wire >= 0) wsf.upload(gf, full, st, h);
+        else hip_ok(hipMemcpyAsync(full, h, gf.frame_bytes(), hipMemcpyHostToDevice, st), "H2D");
+        window_picture(gf, full, gs, dst, arg.x, arg.y, arg.fill, st);
+    }
+    // --crop-out: the source picture as everything behind the stage sees it, the carrier's raw layout
+    void written(const Geometry& gs, const uint8_t* dst, hipStream_t st)
+    {
+        ++pictures;
+        if (!file) return;
+        hip_ok(hipMemcpyAsync(h_out, dst, gs.frame_bytes(), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        if (fwrite(h_out, 1, gs.frame_bytes(), file) != gs.frame_bytes()) die("cannot write " + arg.out);
+    }
+    void write_log(const Geometry& gf, const std::string& type_name) const
+    {
+        if (arg.log.empty()) return;
+        auto num_or_null = [&](int v) { return arg.automatic ? std::to_string(v) : std::string("null"); };
+        std::string js = std::string("{\"mode\": \"") + arg.mode() + "\", \"limit\": " + num_or_null(arg.limit) + ", \"frac\": " + num_or_null(arg.frac) +
+                         ", \"min_bar\": " + num_or_null(arg.min_bar) + ", \"source_width\": " + std::to_string(gf.W) + ", \"source_height\": " +
+                         std::to_string(gf.H) + ", \"src_type\": \"" + type_name + "\", \"chroma_format\": \"" + chroma_name(gf) +
+                         "\", \"bit_depth\": " + std::to_string(gf.bit_depth) + ", \"probes\": [";
+        for (size_t i = 0; i < probes.size(); ++i) {
+            const CropProbe& p = probes[i];
+            auto side = [&](int v) { return p.voted ? std::to_string(v) : std::string("null"); };
+            js += std::string(i ? ", " : "") + "{\"idx\": " + std::to_string(p.idx) + ", \"voted\": " + (p.voted ? "true" : "false") + ", \"top\": " +
+                  side(p.top) + ", \"bottom\": " + side(p.bottom) + ", \"left\": " + side(p.left) + ", \"right\": " + side(p.right) + "}";
+        }
+        js += "], \"votes\": " + std::to_string(votes) + ", \"window\": {\"x\": " + std::to_string(arg.x) + ", \"y\": " + std::to_string(arg.y) +
+              ", \"width\": " + std::to_string(arg.w) + ", \"height\": " + std::to_string(arg.h) + "}, \"fill\": [" + std::to_string(arg.fill[0]) + ", " +
+              std::to_string(arg.fill[1]) + ", " + std::to_string(arg.fill[2]) + "]}\n";
+        FILE* lf = fopen(arg.log.c_str(), "wb");
+        if (!lf || fwrite(js.data(), 1, js.size(), lf) != js.size() || fclose(lf) != 0) die("cannot write " + arg.log);
+    }
+    void destroy()
+    {
+        wsf.destroy();
+        if (full) hip_ok(hipFree(full), "hipFree");
+        if (h_in) hip_ok(hipHostFree(h_in), "hipHostFree");
+        if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
+        if (file && fclose(file) != 0) die("cannot write " + arg.out);
+        *this = CropStage{};
+    }
+};
+
+// --uncrop crop.json | --pad SWxSH+X+Y [--pad-fill Y:U:V] (decode): what the flags alone decide is refused before a
+// model is loaded
+struct PadArgs {
+    bool on = false, from_file = false;
+    std::string flag;              // the one that was given, for messages
+    int W = 0, H = 0, x = 0, y = 0;            // the source's size and where the window lies in it
+    int w = 0, h = 0;                          // --uncrop: the window's size
+    bool fill_given = false;
+    int fill[3] = {16, 128, 128};
+    int bit_depth = 0;                         // --uncrop: what the log says of the pictures
+    std::string chroma;
+};
+
+PadArgs pad_args(const Args& a)
+{
+    PadArgs p;
+    if (a.has("uncrop") && a.has("pad")) die("--uncrop and --pad: exactly one of them may be given");
+    if (!a.has("uncrop") && !a.has("pad")) {
+        if (a.has("pad-fill")) die("--pad-fill needs --uncrop or --pad");
+        return p;
+    }
+    p.flag = a.has("uncrop") ? "--uncrop" : "--pad";
+    if (!a.has("o") && !a.has("hash-log") && !a.has("verify-hash")) {
+        die(p.flag + " changes what -o writes and the hashes cover, nothing else: it needs -o, --hash-log or --verify-hash");
+    }
+    const std::string type = a.str("src-type", "yuv420");
+    if (type != "yuv420" && type != "yuv422" && type != "yuv444") die(p.flag + " is for planar YUV pictures: " + type + " pictures are not padded yet");
+    if (a.has("pad")) {
+        if (!parse_window(a.str("pad"), p.W, p.H, p.x, p.y) || p.W < 2 || p.H < 2) {
+            die("--pad must be SWxSH+X+Y: the source's size and where the picture lies in it, got " + a.str("pad"));
+        }
+    } else {
+        const std::string path = a.str("uncrop");
+        std::ifstream f(path, std::ios::binary);
+        if (path.empty() || !f) die("--uncrop: cannot open " + path);
+        const std::string text((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        std::function<void(const std::string&)> bad = [&](const std::string& why) { die("--uncrop: " + path + " is no crop log: " + why); };
+        JsonReader rd{text, bad};
+        const Json top = rd.value(0);
+        rd.space();
+        if (rd.at != text.size()) bad("text behind the value");
+        if (top.kind != Json::Object) bad("no object");
+        auto num = [&](const Json& o, const std::string& key, unsigned long long lo, unsigned long long hi) {
+            const Json* v = o.get(key);
+            unsigned long long n = 0;
+            if (!v || v->kind != Json::Number || !parse_uint(v->text, hi, n) || n < lo) {
+                bad("\"" + key + "\" must be an integer in " + std::to_string(lo) + ".." + std::to_string(hi));
+            }
+            return static_cast<int>(n);
+        };
+        p.W = num(top, "source_width", 2, kMaxPictureSide);
+        p.H = num(top, "source_height", 2, kMaxPictureSide);
+        p.bit_depth = num(top, "bit_depth", 8, 16);
+        const Json* cf = top.get("chroma_format");
+        if (!cf || cf->kind != Json::String || (cf->text != "yuv420" && cf->text != "yuv422" && cf->text != "yuv444")) {
+            bad("\"chroma_format\" must be yuv420, yuv422 or yuv444");
+        }
+        p.chroma = cf->text;
+        const Json* win = top.get("window");
+        if (!win || win->kind != Json::Object) bad("\"window\" must be an object");
+        p.x = num(*win, "x", 0, kMaxPictureSide);
+        p.y = num(*win, "y", 0, kMaxPictureSide);
+        p.w = num(*win, "width", 2, kMaxPictureSide);
+        p.h = num(*win, "height", 2, kMaxPictureSide);
+        if (p.x + p.w > p.W || p.y + p.h > p.H) bad("the window does not lie inside the source");
+        const Json* fl = top.get("fill");
+        if (!fl || fl->kind != Json::Array || fl->items.size() != 3) bad("\"fill\" must be a list of 3");
+        for (size_t k = 0; k < 3; ++k) {
+            unsigned long long n = 0;
+            if (fl->items[k].kind != Json::Number || !parse_uint(fl->items[k].text, 65535, n)) bad("\"fill\" holds integers in 0..65535");
+            p.fill[k] = static_cast<int>(n);
+        }
+        p.fill_given = true;
+        p.from_file = true;
+    }
+    if (a.has("pad-fill")) {
+        if (!parse_triple(a.str("pad-fill"), 65535, p.fill)) die("--pad-fill must be Y:U:V, three sample values, got " + a.str("pad-fill"));
+        p.fill_given = true;
+    }
+    p.on = true;
+    return p;
+}
+
+// the log against the run's pictures, once their type and depth are settled (a Y4M --ref may supply them)
+void pad_check_run(const PadArgs& p, const char* type, int depth)
+{
+    const std::string t = type;
+    if (t != "yuv420" && t != "yuv422" && t != "yuv444") die(p.flag + " is for planar YUV pictures: " + t + " pictures are not padded yet");
+    if (p.from_file && (p.bit_depth != depth || p.chroma != t)) {
+        die("--uncrop: the log describes " + p.chroma + " pictures of " + std::to_string(p.bit_depth) + " bits, this run's are " + t + " of " +
+            std::to_string(depth) + " bits");
+    }
+}
+
+// decode: the output picture (planes Y, U, V back to back, behind the conversion, --out-size and the grain) -> the picture at
+// the source's size in a buffer of the stage's own, the bars at the fill values: what -o, --hash-log and --verify-hash see. The
+// metrics read the unpadded picture.
+struct PadStage {
+    PadArgs arg;
+    Geometry g;                    // the padded picture's
+    uint8_t* out = nullptr;
+    uint8_t* h_out = nullptr;      // pinned
+    // og: the picture arriving at the stage
+    void create(const PadArgs& p, const Geometry& og)
+    {
+        destroy();                 // a stream may switch parameter sets
+        arg = p;
+        const std::string size = std::to_string(og.W) + "x" + std::to_string(og.H);
+        if (og.rgb || og.wire >= 0 || (og.pix() && og.pix_fmt != DCVC_PIX_YUV422P && og.pix_fmt != DCVC_PIX_YUV444P)) {
+            die(arg.flag + " is for planar YUV pictures: these pictures are not padded yet");
+        }
+        if (arg.from_file) {
+            if (arg.w != og.W || arg.h != og.H) {
+                die("--uncrop: the log's window is " + std::to_string(arg.w) + "x" + std::to_string(arg.h) + ", the pictures arriving are " + size);
+            }
+            if (arg.bit_depth != og.bit_depth || arg.chroma != chroma_name(og)) {
+                die("--uncrop: the log describes " + arg.chroma + " pictures of " + std::to_string(arg.bit_depth) + " bits, this run's are " +
+                    chroma_name(og) + " of " + std::to_string(og.bit_depth) + " bits");
+            }
+        }
+        if (arg.x + og.W > arg.W || arg.y + og.H > arg.H) {
+            die(arg.flag + ": a " + size + " picture at +" + std::to_string(arg.x) + "+" + std::to_string(arg.y) + " does not lie inside " +
+                std::to_string(arg.W) + "x" + std::to_string(arg.H));
+        }
+        if ((arg.W & 1) || (arg.H & 1) || arg.x % chroma_sx(og) || arg.y % chroma_sy(og)) {
+            die(arg.flag + ": the source's sides must be even and the offsets multiples of the chroma subsampling, " +
+                std::to_string(chroma_sx(og)) + "x" + std::to_string(chroma_sy(og)));
+        }
+        if (!arg.fill_given) {
+            for (int& v : arg.fill) v <<= og.bit_depth - 8;
+        }
+        for (int v : arg.fill) {
+            if (v > (1 << og.bit_depth) - 1) die(arg.flag + ": fill value " + std::to_string(v) + " is no sample of " + std::to_string(og.bit_depth) + " bits");
+        }
+        g = geometry(arg.H, arg.W, false, og.bit_depth, og.pix_fmt);
+        hip_ok(hipMalloc(&out, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+    }
+    const uint8_t* run(const Geometry& og, const uint8_t* shown, hipStream_t st)
+    {
+        window_picture(og, shown, g, out, -arg.x, -arg.y, arg.fill, st);
+        return out;
+    }
+    void destroy()
+    {
+        if (out) hip_ok(hipFree(out), "hipFree");
+        if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
+        *this = PadStage{};
+    }
+};
+
 // --out-size: the output picture on the device and what measures it against the reference, all at the output size
 struct ScaledOut {
     Resampler rs;
@@ -2807,6 +3308,18 @@ struct LatencyUnit {
     double read_ms = 0, out_ms = 0;
 };
 
+// the source frames a run reads from a regular file of file_total pictures: encode's own arithmetic below (-n counts coded
+// pictures; --deinterlace field codes two a frame; --ivtc film reads whole cycles of 5 for 4), for --crop auto, which spreads
+// its probes over them before the loop is set up
+long long source_frames_of(long long file_total, bool has_n, long long n, bool two_fields, bool film)
+{
+    long long total = two_fields ? std::min<long long>(2 * file_total, 1 << 30) : file_total;
+    if (film) total = 4 * (total / 5) + total % 5;
+    const long long frame_num = has_n ? std::min(n, total) : total;
+    if (frame_num <= 0) return 0;
+    return two_fields ? (frame_num + 1) / 2 : film ? std::min(file_total, 5 * ((frame_num + 3) / 4)) : frame_num;
+}
+
 // ------------------------------------------------------------------------------------ encode
 int encode(const Args& a)
 {
@@ -2832,6 +3345,7 @@ int encode(const Args& a)
     const GrainArgs grain = grain_args(a, true);
     IvtcArgs ivtc = ivtc_args(a, true);
     DeinterlaceArgs deint = deinterlace_args(a, true);
+    const CropArgs crop = crop_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
@@ -2866,8 +3380,27 @@ int encode(const Args& a)
     } else if (rgb && (!a.has("W") || !a.has("H"))) {
         die(std::string("--src-type ") + src_type_name(type) + " needs -W and -H");
     }
-    // gs: the source's pictures; g: the pictures that are coded (--scale: another size, resampled on the device)
-    Geometry gs = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type), wire);
+    // gf: the file's pictures, which the reader and the upload see; gs: the source's pictures, which everything else derives from
+    // (--crop: the window's); g: the pictures that are coded (--scale: another size, resampled on the device)
+    const Geometry gf = geometry(pic_h, pic_w, rgb, depth, pix_fmt_of(type), wire);
+    CropStage cs;
+    if (crop.on) {
+        // the window is settled before a model is loaded: a manual one is checked, auto probes the clip
+        cs.create(crop, gf, deint.on || ivtc.on);
+        if (crop.automatic) {
+            if (src_file.fd < 0) src_file.open(a.str("i"), pipe.in_format);
+            if (!src_file.regular) die("--crop auto needs a seekable source; give --crop WxH+X+Y");
+            const long long probe_frames = source_frames_of(src_file.count(gf.file_bytes()), a.has("n"), a.num("n", 0), deint.on && deint.field,
+                                                            ivtc.on && ivtc.film);
+            if (probe_frames <= 0) die("no pictures to code");
+            cs.detect(src_file, gf, probe_frames);
+        }
+        fprintf(g_msg, "crop: %s, %dx%d+%d+%d of %dx%d (%d of %zu pictures voted)\n", cs.arg.mode(), cs.arg.w, cs.arg.h, cs.arg.x, cs.arg.y, gf.W,
+                gf.H, cs.votes, cs.probes.size());
+        cs.write_log(gf, wire >= 0 ? wire_name(wire) : src_type_name(type));
+    }
+    Geometry gs = cs.active ? geometry(cs.arg.h, cs.arg.w, rgb, depth, pix_fmt_of(type), wire) : gf;
+    if (cs.active && wire >= 0) gs.file_bytes();      // a window the wire format has no picture of is refused here
     if (rgb) colour.apply(gs);
     if (scale.on) check_ratio("--scale", gs.W, gs.H, scale.W, scale.H);
     const Geometry g = scale.on ? geometry(scale.H, scale.W, false, depth) : gs;
@@ -2899,7 +3432,7 @@ int encode(const Args& a)
     } else {
         if (src_file.fd < 0) src_file.open(a.str("i"), pipe.in_format);
         // a pipe's length is unknown: the loop below learns the clip's end from the reader, -n still caps it
-        total = src_file.regular ? src_file.count(gs.file_bytes()) : (1 << 30);
+        total = src_file.regular ? src_file.count(gf.file_bytes()) : (1 << 30);
     }
     const bool piped_in = !is_png(type) && !src_file.regular;
     // --deinterlace field: two coded pictures a source frame; -n counts coded pictures, the reader source frames
@@ -2982,7 +3515,7 @@ int encode(const Args& a)
     auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     // --read-ahead: the source's pictures arrive in the ring's pinned slots instead of the one pinned buffer of each path
     ReadAhead ra;
-    if (read_ahead > 0) ra.start(src_file, gs.file_bytes(), read_ahead + 1, source_frames, t0);
+    if (read_ahead > 0) ra.start(src_file, gf.file_bytes(), read_ahead + 1, source_frames, t0);
     bool slot_held = false;                // a slot whose upload is in flight: released behind convert()'s synchronisation
     double last_read_ms = 0;               // when the last source picture was complete in host memory
     std::string input_error;               // a pipe that broke off inside a picture: the run ends as at the end of the input, with status 2
@@ -2994,7 +3527,7 @@ int encode(const Args& a)
             input_error = src_file.error;
         } else if (src_file.partial > 0) {
             fprintf(stderr, "dcvc: warning: %s ends with %zu bytes that are no whole picture (%zu bytes each): dropped\n",
-                    src_file.path.c_str(), src_file.partial, gs.file_bytes());
+                    src_file.path.c_str(), src_file.partial, gf.file_bytes());
         }
     };
     // the next picture of -i in pinned memory - `own`, or a read-ahead slot; nullptr when a pipe has ended
@@ -3009,13 +3542,25 @@ int encode(const Args& a)
             last_read_ms = s.read_ms;
             return s.p;
         }
-        const PictureFile::Status st = src_file.next(own, gs.file_bytes());
+        const PictureFile::Status st = src_file.next(own, gf.file_bytes());
         if (st != PictureFile::Picture) {
             source_ended(st);
             return nullptr;
         }
         last_read_ms = now_ms();
         return own;
+    };
+    if (cs.active) cs.allocate(gf);
+    if (crop.on) cs.open_out(gs);
+    // the pinned buffer a source picture is read into when no read-ahead slot holds it
+    uint8_t* const h_own = cs.active ? cs.h_in : scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv;
+    // the source picture in pinned memory at h -> its planes at dst on the device: the upload, a wire format's unpack, and with
+    // --crop the window (the upload then lands in the stage's buffer of the file's size)
+    auto upload = [&](uint8_t* dst, const uint8_t* h) {
+        if (cs.active) cs.upload(gf, gs, dst, h, b.st);
+        else if (wire >= 0) ws.upload(gs, dst, b.st, h);
+        else hip_ok(hipMemcpyAsync(dst, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+        if (crop.on) cs.written(gs, dst, b.st);
     };
     // the next source picture -> the device's staging planes; convert() turns them into fp16 x at dst (pixel stride ldx).
     // false: the input has ended (a pipe; a regular file was counted)
@@ -3032,11 +3577,9 @@ int encode(const Args& a)
             if (!iv.pending()) {
                 int got = 0;
                 while (got < iv.cycle() && iv.frames() < source_frames && !input_done) {
-                    const uint8_t* h = next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv);
+                    const uint8_t* h = next_source(h_own);
                     if (h == nullptr) break;
-                    uint8_t* in = iv.next_input();
-                    if (wire >= 0) ws.upload(gs, in, b.st, h);
-                    else hip_ok(hipMemcpyAsync(in, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+                    upload(iv.next_input(), h);
                     iv.measure(gs, b.st);
                     if (slot_held) ra.release();
                     slot_held = false;
@@ -3052,23 +3595,17 @@ int encode(const Args& a)
         }
         // --deinterlace field: the second picture of a frame comes from the frame on the device
         const bool fresh = !deint.on || di.wants_frame();
-        const uint8_t* h = fresh ? next_source(scale.on ? h_full : wire >= 0 ? ws.h_in : b.h_yuv) : nullptr;
+        const uint8_t* h = fresh ? next_source(h_own) : nullptr;
         if (fresh && h == nullptr) return false;
         if (deint.on) {
-            if (fresh) {
-                uint8_t* in = di.next_input();
-                if (wire >= 0) ws.upload(gs, in, b.st, h);
-                else hip_ok(hipMemcpyAsync(in, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
-            }
+            if (fresh) upload(di.next_input(), h);
             di.run(gs, scale.on ? d_full : staging, b.st);
             if (scale.on) rs.run(d_full, staging, b.st);
         } else if (scale.on) {
-            hip_ok(hipMemcpyAsync(d_full, h, gs.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            upload(d_full, h);
             rs.run(d_full, staging, b.st);
-        } else if (wire >= 0) {
-            ws.upload(g, staging, b.st, h);
         } else {
-            hip_ok(hipMemcpyAsync(staging, h, g.frame_bytes(), hipMemcpyHostToDevice, b.st), "H2D");
+            upload(staging, h);
         }
         // once per source picture, in source order: recodes and padding pictures come from what this left
         if (denoise.on) b.yuv8 = dn.run(g, staging, b.st);
@@ -3541,6 +4078,7 @@ int encode(const Args& a)
         hip_ok(hipHostFree(h_full), "hipHostFree");
         hip_ok(hipFree(d_full), "hipFree");
     }
+    if (crop.on) cs.destroy();
     if (deint.on) {
         fprintf(g_msg, "deinterlace: %s, %s, threshold %d, %lld pictures from %lld frames\n", deint.mode(), deint.order(), deint.threshold,
                 di.pictures, di.frames);
@@ -3773,6 +4311,13 @@ int decode(const Args& a)
     }
     deinterlace_args(a, false);
     ivtc_args(a, false);
+    crop_args(a, false);
+    const PadArgs pad = pad_args(a);
+    // the log against what the flags say of the run, before a model is loaded; a Y4M --ref's header is checked against it below
+    if (pad.on && !(a.has("ref") && pipe.in_is_y4m(a.str("ref")))) {
+        const SrcType t = src_type(a.str("src-type", "yuv420"));
+        pad_check_run(pad, src_type_name(t), bit_depth_arg(a, t));
+    }
     if (a.has("o") && is_dash(a.str("o"))) g_msg = stderr;      // stdout carries the pictures
     // -o *.y4m (or --out-format y4m): what the flags alone decide is refused before a model is loaded
     const bool rec_y4m = a.has("o") && pipe.out_is_y4m(a.str("o"));
@@ -3813,6 +4358,7 @@ int decode(const Args& a)
         die(std::string("--out-size is for --src-type yuv420: ") + src_type_name(type) + " sources are not resampled yet");
     }
     if (grain.on) grain_check_run(grain, src_type_name(type), depth);
+    if (pad.on) pad_check_run(pad, wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
     hash.begin(wire >= 0 ? wire_name(wire) : src_type_name(type), depth);
     FILE* rec = !has_rec || png ? nullptr : is_dash(a.str("o")) ? stdout : fopen(a.str("o").c_str(), "wb");
     if (has_rec && !png && !rec) die("cannot write " + a.str("o"));
@@ -3870,6 +4416,8 @@ int decode(const Args& a)
     if (out_size.on) go = geometry(out_size.H, out_size.W, false, depth);
     // --film-grain / --grain-strength: the grained copy of every output picture, which -o and the hashes see
     GrainSynth gr;
+    // --uncrop / --pad: the last stage, shown = pad(grain(resample(picture))): the bars carry no grain
+    PadStage pd;
     // log (src/utils/common.py:46-116)
     std::vector<int> types;
     std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v, ssim, ssim_y, ssim_u, ssim_v;
@@ -3929,7 +4477,13 @@ int decode(const Args& a)
                 die("--film-grain: the file describes " + std::to_string(grain.file.width) + "x" + std::to_string(grain.file.height) +
                     " pictures, the stream holds " + std::to_string(s->width) + "x" + std::to_string(s->height));
             }
-            hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
+            if (pad.on) {
+                // the picture arriving at the stage must be the window; -o and the hashes hold the source's size
+                pd.create(pad, out_size.on ? go : geometry(s->height, s->width, rgb, depth, pix_fmt, wire));
+                hash.size(pd.g.W, pd.g.H);
+            } else {
+                hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
+            }
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth, pix_fmt, wire);
             if (rgb) colour.apply(g);
@@ -4007,8 +4561,11 @@ int decode(const Args& a)
                 so.rs.run(b.out8, so.out, b.st);
                 // the metrics below read so.out, the ungrained picture
                 const uint8_t* shown = grain.on ? gr.run(go, so.out, b.st) : so.out;
-                if (hash.on()) hash.picture(shown, go, b.st);
-                if (has_rec) hip_ok(hipMemcpyAsync(so.h_out, shown, go.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                if (pad.on) shown = pd.run(go, shown, b.st);
+                const Geometry& gw = pad.on ? pd.g : go;      // what -o writes and the hashes cover
+                uint8_t* const h_w = pad.on ? pd.h_out : so.h_out;
+                if (hash.on()) hash.picture(shown, gw, b.st);
+                if (has_rec) hip_ok(hipMemcpyAsync(h_w, shown, gw.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 if (has_ref) {
                     const int dt = go.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
                     const double peak = static_cast<double>((1 << go.bit_depth) - 1);
@@ -4039,8 +4596,8 @@ int decode(const Args& a)
                 }
                 if (has_rec) {
                     hip_ok(hipStreamSynchronize(b.st), "sync");
-                    rec_frame(go);
-                    rec_put(so.h_out, go.frame_bytes());
+                    rec_frame(gw);
+                    rec_put(h_w, gw.frame_bytes());
                     rec_flush();
                 }
                 types.push_back(intra ? 0 : 1);
@@ -4061,22 +4618,25 @@ int decode(const Args& a)
             if (wire >= 0 && (has_rec || hash.on())) ws.pack(g, b.out8, b.st);
             // grain behind the source check above: a padding picture of a ragged chunk takes no picture index
             const uint8_t* shown = grain.on ? gr.run(g, b.out8, b.st) : b.out8;
-            if (hash.on()) hash.picture(wire >= 0 ? ws.out : shown, g, b.st);
+            if (pad.on) shown = pd.run(g, shown, b.st);        // (no wire format, no RGB: refused above)
+            const Geometry& gw = pad.on ? pd.g : g;            // what -o writes and the hashes cover
+            uint8_t* const h_w = pad.on ? pd.h_out : b.h_yuv;
+            if (hash.on()) hash.picture(wire >= 0 ? ws.out : shown, gw, b.st);
             if (has_rec && wire >= 0) {
                 hip_ok(hipMemcpyAsync(ws.h_out, ws.out, g.file_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 rec_put(ws.h_out, g.file_bytes());
                 rec_flush();
             } else if (has_rec) {
-                hip_ok(hipMemcpyAsync(b.h_yuv, shown, g.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                hip_ok(hipMemcpyAsync(h_w, shown, gw.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
                 hip_ok(hipStreamSynchronize(b.st), "sync");
                 if (png && g.rgb16()) {
                     abi_ok(dcvc_png_write_rgb16(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
                 } else if (png) {
                     abi_ok(dcvc_png_write_rgb(rec_pngs.path(rec_pngs.next++).c_str(), b.h_yuv, g.W, g.H), "png write");
                 } else {
-                    rec_frame(g);
-                    rec_put(b.h_yuv, g.frame_bytes());
+                    rec_frame(gw);
+                    rec_put(h_w, gw.frame_bytes());
                     rec_flush();
                 }
             }
@@ -4214,6 +4774,7 @@ int decode(const Args& a)
     ws.destroy();
     so.destroy();
     gr.destroy();
+    pd.destroy();
     if (rec && fclose(rec) != 0) {
         if (errno == EPIPE) output_closed(a.str("o"));
         die("short write");

@@ -263,4 +263,60 @@ int Ivtc::push(int idx, bool has_prev, const uint64_t m[8])
 
 int Ivtc::drop() const { return m_drop; }
 
+CropDetect::CropDetect(int H, int W, int frac, int min_bar, int ax, int ay) : m_H(H), m_W(W), m_frac(frac), m_min_bar(min_bar), m_ax(ax), m_ay(ay)
+{
+    if (H < 1 || H > kMaxSide || W < 1 || W > kMaxSide) throw std::invalid_argument("cropdet: H and W must be in 1..16384");
+    if (frac < 0 || frac > 255) throw std::invalid_argument("cropdet: frac must be in 0..255");
+    if (min_bar < 0 || min_bar > 4096) throw std::invalid_argument("cropdet: min_bar must be in 0..4096");
+    if ((ax != 1 && ax != 2 && ax != 4) || (ay != 1 && ay != 2 && ay != 4)) throw std::invalid_argument("cropdet: ax and ay must be 1, 2 or 4");
+    if (H % ay != 0 || W % ax != 0) throw std::invalid_argument("cropdet: H must be a multiple of ay and W of ax");
+}
+
+bool CropDetect::push(const uint32_t* counts)
+{
+    if (counts == nullptr) throw std::invalid_argument("cropdet: null words");
+    for (int r = 0; r < m_H; ++r) {
+        if (counts[r] > static_cast<uint32_t>(m_W)) throw std::invalid_argument("cropdet: a row count is above the width");
+    }
+    for (int c = 0; c < m_W; ++c) {
+        if (counts[m_H + c] > static_cast<uint32_t>(m_H)) throw std::invalid_argument("cropdet: a column count is above the height");
+    }
+    // counts <= 2^14 and sides <= 2^14: both products are below 2^22
+    const uint32_t row_t = static_cast<uint32_t>(m_W) * static_cast<uint32_t>(m_frac), col_t = static_cast<uint32_t>(m_H) * static_cast<uint32_t>(m_frac);
+    int top = -1, bottom = -1, left = -1, right = -1;
+    for (int r = 0; r < m_H; ++r) {
+        if (counts[r] * 256u > row_t) {
+            if (top < 0) top = r;
+            bottom = r;
+        }
+    }
+    for (int c = 0; c < m_W; ++c) {
+        if (counts[m_H + c] * 256u > col_t) {
+            if (left < 0) left = c;
+            right = c;
+        }
+    }
+    if (top < 0 || left < 0) return false;
+    if (m_votes == 0) {
+        m_top = top; m_bottom = bottom; m_left = left; m_right = right;
+    } else {
+        m_top = std::min(m_top, top); m_bottom = std::max(m_bottom, bottom);
+        m_left = std::min(m_left, left); m_right = std::max(m_right, right);
+    }
+    ++m_votes;
+    return true;
+}
+
+int CropDetect::result(int& x, int& y, int& w, int& h) const
+{
+    int T = 0, B = 0, L = 0, R = 0;
+    if (m_votes > 0) {
+        T = m_top; B = m_H - 1 - m_bottom; L = m_left; R = m_W - 1 - m_right;
+    }
+    auto bar = [&](int v, int a) { return v < m_min_bar ? 0 : v - v % a; };
+    T = bar(T, m_ay); B = bar(B, m_ay); L = bar(L, m_ax); R = bar(R, m_ax);
+    x = L; y = T; w = m_W - L - R; h = m_H - T - B;
+    return m_votes;
+}
+
 }  // namespace dcvc

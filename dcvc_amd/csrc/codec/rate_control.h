@@ -128,4 +128,25 @@ private:
     int m_best_pos = -1;
 };
 
+// Black-bar decision of dcvc encode --crop auto (dcvc_amd/crop.py CropDetect is the restatement). Pictures are
+// pushed, in any order, with the H + W words of dcvc_crop_stats: rowcnt, then colcnt. Row r is active iff rowcnt[r] * 256 >
+// W * frac, column c iff colcnt[c] * 256 > H * frac; a picture without an active row or column casts no vote, a voting one's
+// rectangle runs from its first to its last active row and column, and the result is the union of the rectangles. The bars
+// T, B, L, R around it: one below min_bar becomes 0, then each is rounded down to a multiple of ay (T, B) or ax (L, R), so
+// picture content is never cut. Without a vote the window is the whole picture.
+class CropDetect {
+public:
+    static constexpr int kMaxSide = 16384;           // the largest plane dcvc_crop_stats takes
+    // H, W 1..16384 and multiples of ay, ax; frac 0..255; min_bar 0..4096; ax, ay each 1, 2 or 4
+    CropDetect(int H, int W, int frac, int min_bar, int ax, int ay);
+    // true: the picture voted. A row count above W or a column count above H is refused (std::invalid_argument), the state unchanged.
+    bool push(const uint32_t* counts);
+    int result(int& x, int& y, int& w, int& h) const;      // the number of votes
+    int words() const { return m_H + m_W; }
+
+private:
+    int m_H, m_W, m_frac, m_min_bar, m_ax, m_ay, m_votes = 0;
+    int m_top = 0, m_bottom = 0, m_left = 0, m_right = 0;  // the union, valid with m_votes > 0
+};
+
 }  // namespace dcvc

@@ -523,6 +523,31 @@ void grain_stats_validate(const GrainStatsDesc& d);  // throws std::invalid_argu
 // one launch (two with accumulate == 0) on `stream`: validates first, allocates nothing, never waits for the host
 void grain_stats(const GrainStatsDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- black-bar crop (crop.hip)
+// crop_stats: per row and per column of a luma plane the number of samples above limit << (bit_depth - 8): H + W exact uint32
+// words on the device, rows first (stated at the head of crop.hip). Strides in samples.
+constexpr int kCropMaxSide = 16384;
+struct CropStatsDesc {
+    const void* luma = nullptr; int row_stride = 0;
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0;
+    int limit = 0;                                   // 0..255, in 8-bit code values
+    void* counts = nullptr;                          // device, 4-byte aligned: uint32 [H + W]
+};
+void crop_stats_validate(const CropStatsDesc& d);    // throws std::invalid_argument for what is refused
+// two launches on `stream`: validates first, allocates nothing, never waits for the host
+void crop_stats(const CropStatsDesc& d, hipStream_t stream);
+// window_planes: dst[p][y][x] = src[p][y + oy][x + ox] inside the source, fill[p] outside: a crop, a pad or any mixture
+struct WindowPlanesDesc {
+    const void* src = nullptr; int src_row_stride = 0; long long src_plane_stride = 0; int Hs = 0, Ws = 0;
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0; int Hd = 0, Wd = 0;
+    int dtype = kSampleU8, n_planes = 1;
+    int ox = 0, oy = 0;                              // signed, |.| <= kCropMaxSide
+    const int* fill = nullptr;                       // host, [n_planes]
+};
+void window_planes_validate(const WindowPlanesDesc& d);   // throws std::invalid_argument for what is refused
+// one launch for every 16 planes on `stream`: validates first, allocates nothing, never waits for the host
+void window_planes(const WindowPlanesDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

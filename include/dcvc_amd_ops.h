@@ -527,6 +527,26 @@ int dcvc_grain_stats(const void* src, int src_row_stride, long long src_plane_st
                      long long den_plane_stride, const void* luma, int luma_row_stride, int Hl, int Wl, int dtype, int bit_depth, int H,
                      int W, int n_planes, int sx, int sy, int flat, int accumulate, void* words, void* stream);
 
+/* Black-bar cropping on the GPU (no reference counterpart): the measurement and the window copy; the decision
+ * is dcvc_cropdet_* (dcvc_amd_rc.h). Every value is an exact integer.
+ *   dcvc_crop_stats: t = limit << (bit_depth - 8); for the luma plane Y [H][W], rowcnt[r] = the number of x with Y[r][x] > t and
+ *   colcnt[c] = the number of y with Y[y][c] > t. counts (device, uint32 [H + W], 4-byte aligned) = rowcnt, then colcnt; what it
+ *   held is overwritten. The same words for every launch geometry and every run. Two launches on `stream`: nothing is allocated
+ *   and nothing waits for the host. Samples are DCVC_SAMPLE_U8 (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16);
+ *   strides in samples. Refused before anything is enqueued: NULL luma or counts; another sample type; a bit_depth that is not
+ *   the type's; H or W outside 1..16384; limit outside 0..255; a row stride below W; a 16-bit plane at an odd address; counts
+ *   that are not 4-byte aligned.
+ *   dcvc_window_planes: n_planes planes, src [Hs][Ws] and dst [Hd][Wd]: dst[p][y][x] = src[p][y + oy][x + ox] where
+ *   0 <= y + oy < Hs and 0 <= x + ox < Ws, else fill[p] (host, [n_planes], read during the call). ox, oy are signed: a crop is
+ *   ox, oy >= 0 with the window inside the source, a pad ox, oy <= 0 with the source inside the window, any mixture is defined
+ *   by the same line. Nothing is written past Wd in a row. One launch for every 16 planes; plane strides are not read for one
+ *   plane. Refused before anything is enqueued: NULL src, dst or fill; another sample type; Hs, Ws, Hd or Wd outside 1..16384;
+ *   n_planes outside 1..65535; |ox| or |oy| above 16384; a fill value outside the type (0..255, 0..65535); a row stride below
+ *   the width or a plane stride below the plane; a 16-bit plane at an odd address; dst overlapping src. */
+int dcvc_crop_stats(const void* luma, int row_stride, int dtype, int bit_depth, int H, int W, int limit, void* counts, void* stream);
+int dcvc_window_planes(const void* src, int src_row_stride, long long src_plane_stride, int Hs, int Ws, void* dst, int dst_row_stride,
+                       long long dst_plane_stride, int Hd, int Wd, int dtype, int n_planes, int ox, int oy, const int* fill, void* stream);
+
 /* Tuning aid (no reference counterpart): device buffer of [blocks][16] int64 shader-clock stamps
  * written by wave 0 of every workgroup of the following contraction launches; NULL = off. */
 int dcvc_gemm_timeline_buffer(void* device_buffer);

@@ -131,6 +131,23 @@ int dcvc_ivtc_push(dcvc_ivtc* t, int idx, int has_prev, const uint64_t m[8]);
 int dcvc_ivtc_drop(const dcvc_ivtc* t);
 void dcvc_ivtc_destroy(dcvc_ivtc* t);
 
+/* Black-bar decision of dcvc encode --crop auto (dcvc_amd/crop.py CropDetect is the same arithmetic in Python).
+ * counts = the H + W words of dcvc_crop_stats of a probed picture: rowcnt, then colcnt. Exact integers:
+ *   row r is active iff rowcnt[r] * 256 > W * frac, column c iff colcnt[c] * 256 > H * frac. A picture with no active row or
+ *   no active column casts no vote (a fade, a black leader); a voting picture's rectangle runs from its first to its last
+ *   active row and column; the result is the union over the voting pictures. The bars T = top, B = H - 1 - bottom, L = left,
+ *   R = W - 1 - right: one below min_bar becomes 0, then each is rounded DOWN to a multiple of ay (T, B) or ax (L, R), so
+ *   picture content is never cut. The window is x = L, y = T, w = W - L - R, h = H - T - B; with no vote the whole picture.
+ *   dcvc_cropdet_push returns 1 (voted) or 0 (no vote); negative = refused, the state unchanged: NULL, a row count above W or
+ *   a column count above H. dcvc_cropdet_result returns the number of votes (negative: a NULL argument).
+ * dcvc_cropdet_create returns NULL for H or W outside 1..16384, frac outside 0..255, min_bar outside 0..4096, ax or ay other
+ * than 1, 2 or 4, or H / W that are not multiples of ay / ax. */
+typedef struct dcvc_cropdet dcvc_cropdet;
+dcvc_cropdet* dcvc_cropdet_create(int H, int W, int frac, int min_bar, int ax, int ay);
+int dcvc_cropdet_push(dcvc_cropdet* t, const uint32_t* counts);
+int dcvc_cropdet_result(const dcvc_cropdet* t, int* x, int* y, int* w, int* h);
+void dcvc_cropdet_destroy(dcvc_cropdet* t);
+
 /* Film grain, the host side (dcvc_amd/grain.py grain_template and grain_fit are the same arithmetic in Python).
  *   dcvc_grain_template: out (host, int16 [64][64]) = the grain template of (seed, plane 0..2, size 0..37) that
  *   dcvc_grain_apply (dcvc_amd_ops.h) tiles over a plane. s = seed*0x9E3779B1 + plane*0xC2B2AE3D + 1 (u32, wrapping); per

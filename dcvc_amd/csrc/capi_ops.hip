@@ -925,6 +925,38 @@ int dcvc_denoise_planes(const void* src, int src_row_stride, long long src_plane
     });
 }
 
+long long dcvc_motion_search_workspace_bytes(int H, int W)
+{
+    if (H < 1 || W < 1 || H > dcvc::kMotionMaxSide || W > dcvc::kMotionMaxSide) return 0;
+    return static_cast<long long>(dcvc::motion_search_workspace_bytes(H, W));
+}
+
+int dcvc_motion_search(const void* cur, int cur_row_stride, const void* ref, int ref_row_stride, int dtype, int bit_depth, int H, int W,
+                       int range, int lambda, void* mv, int mv_bh, int mv_bw, void* sad, void* moved, void* workspace,
+                       long long workspace_bytes, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::MotionSearchDesc d;
+        d.cur = cur; d.cur_row_stride = cur_row_stride; d.ref = ref; d.ref_row_stride = ref_row_stride;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.range = range; d.lambda = lambda;
+        d.mv = mv; d.mv_bh = mv_bh; d.mv_bw = mv_bw; d.sad = sad; d.moved = moved; d.workspace = workspace; d.workspace_bytes = workspace_bytes;
+        dcvc::motion_search(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_motion_compensate_planes(const void* prev, int prev_row_stride, long long prev_plane_stride, void* dst, int dst_row_stride,
+                                  long long dst_plane_stride, int dtype, int H, int W, int n_planes, int sx, int sy, const void* mv,
+                                  int mv_bh, int mv_bw, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::MotionCompensateDesc d;
+        d.prev = prev; d.prev_row_stride = prev_row_stride; d.prev_plane_stride = prev_plane_stride;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.dtype = dtype; d.H = H; d.W = W; d.n_planes = n_planes; d.sx = sx; d.sy = sy; d.mv = mv; d.mv_bh = mv_bh; d.mv_bw = mv_bw;
+        dcvc::motion_compensate_planes(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_plane_stride, const void* prev, int prev_row_stride,
                             long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype,
                             int bit_depth, int H, int W, int n_planes, int keep, int weave_from_prev, int threshold, void* stream)

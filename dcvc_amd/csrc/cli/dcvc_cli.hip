@@ -17,7 +17,7 @@
 //               [--matrix bt601|bt709|bt2020] [--range full|limited [--yuv-depth 8..16]]
 //               [--in-format raw|y4m] [--read-ahead 0..8] [--flush-units 1] [--latency-log log.json]      (-i - | -o -: pipes)
 //               [--vbv-maxrate BPP --vbv-bufsize PICTURES [--vbv-init 0.9] [--vbv-log log.json]]
-//               [--denoise S[:T] [--denoise-out filtered.yuv]
+//               [--denoise S[:T] [--denoise-out filtered.yuv] [--denoise-mc R[:LAMBDA] [--mv-log mv.json]]
 //                [--grain-log grain.json [--grain-size 0..37] [--grain-window N] [--grain-gain PCT] [--grain-flat F] [--grain-seed N]]]
 //               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
 //               [--ivtc film|match[:CTHRESH[:MI[:T]]] [--field-order tff|bff] [--ivtc-out film.yuv] [--ivtc-log log.json]]
@@ -251,6 +251,18 @@
 //               are not filtered yet"). --denoise-out FILE (needs --denoise, not "-"): the filtered pictures at the coded size
 //               in the carrier type's raw layout and depth, one copy to the host per picture; no padding pictures. One summary
 //               line: "denoise: spatial S, temporal T, N pictures filtered". The stream format and the decoder do not change.
+//               --denoise-mc R[:LAMBDA] (needs --denoise): the temporal stage reads the previous output picture
+//               motion-compensated. R, the search range in half-resolution samples, is an integer in 0..15; LAMBDA, the
+//               penalty a sample of vector length, in 0..255 (default 4). Both defaults are untuned: 7 and 4 are the values the
+//               design was checked with, nobody has searched for better ones. Per picture with a previous output and T > 0:
+//               dcvc_motion_search of the source luma against the previous output's luma, dcvc_motion_compensate_planes of the
+//               previous output into a third picture-sized device buffer (Y in one call, U and V in one call with the chroma
+//               format's subsampling), and that buffer is dcvc_denoise_planes' prev. The recursive state stays the
+//               uncompensated output; the first picture and T == 0 run as without the flag (no launch is added, the stream is
+//               the same). --mv-log FILE (needs --denoise-mc, not "-"): JSON with range, lambda, block, width, height and per
+//               searched picture {idx, blocks, nonzero, sum_abs_dx, sum_abs_dy, max_abs, sum_sad}; only with it are the
+//               vectors copied to the host (one copy and one wait a picture). The summary line gains
+//               ", mc range R lambda L (K of B blocks moved)", K counted on the device.
 //               --deinterlace MODE[:T] (encode): the source holds woven interlaced frames. MODE frame codes one
 //               picture per source frame, field one per field (twice the pictures); T, the motion threshold, is an integer in
 //               0..64 in 8-bit code values (default 10; 0: the purely spatial interpolator). --field-order tff | bff (default
@@ -1930,7 +1942,21 @@ struct DenoiseArgs {
     bool on = false;
     int spatial = 0, temporal = 0;
     std::string out;               // --denoise-out: the filtered clip as coded, raw
+    bool mc = false;               // --denoise-mc R[:LAMBDA]
+    int mc_range = 0, mc_lambda = 4;
+    std::string mv_log;            // --mv-log: what the search found, JSON
 };
+
+// "R" or "R:LAMBDA": decimal integers in 0..15 and 0..255, nothing else
+bool parse_mc(const std::string& s, int& range, int& lambda)
+{
+    const size_t colon = s.find(':');
+    unsigned long long r = 0, l = 4;
+    if (!parse_uint(s.substr(0, colon), 15, r)) return false;
+    if (colon != std::string::npos && !parse_uint(s.substr(colon + 1), 255, l)) return false;
+    range = static_cast<int>(r); lambda = static_cast<int>(l);
+    return true;
+}
 
 // "S" or "S:T": decimal integers in 0..64, nothing else
 bool parse_strengths(const std::string& s, int& spatial, int& temporal)
@@ -1951,14 +1977,25 @@ DenoiseArgs denoise_args(const Args& a, bool encoding)
 {
     DenoiseArgs d;
     if (!encoding) {
-        for (const char* k : {"denoise", "denoise-out"}) {
+        for (const char* k : {"denoise", "denoise-out", "denoise-mc", "mv-log"}) {
             if (a.has(k)) die(std::string("--") + k + " is an encoder flag");
         }
         return d;
     }
     if (!a.has("denoise")) {
-        if (a.has("denoise-out")) die("--denoise-out needs --denoise");
+        for (const char* k : {"denoise-out", "denoise-mc", "mv-log"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --denoise");
+        }
         return d;
+    }
+    if (a.has("mv-log") && !a.has("denoise-mc")) die("--mv-log needs --denoise-mc");
+    if (a.has("denoise-mc")) {
+        if (!parse_mc(a.str("denoise-mc"), d.mc_range, d.mc_lambda)) {
+            die("--denoise-mc must be R or R:LAMBDA with integers in 0..15 and 0..255, got " + a.str("denoise-mc"));
+        }
+        d.mc = true;
+        d.mv_log = a.str("mv-log");
+        if (a.has("mv-log") && (d.mv_log.empty() || is_dash(d.mv_log))) die("--mv-log needs a file name (not -: stdout is for the stream)");
     }
     if (!parse_strengths(a.str("denoise"), d.spatial, d.temporal)) {
         die("--denoise must be S or S:T with integers in 0..64, got " + a.str("denoise"));
@@ -1984,10 +2021,36 @@ struct Denoiser {
     int turn = 0;
     long long pictures = 0;
     GrainMeter* meter = nullptr;   // --grain-log: every source picture and the filter's output for it are measured
+    // --denoise-mc: the previous output picture motion-compensated, the vectors, their SADs, the count of moved blocks and the
+    // search's workspace, all on the device; h_mv (pinned: vectors, then SADs) only with --mv-log
+    uint8_t* comp = nullptr;
+    int16_t* d_mv = nullptr;
+    uint32_t* d_sad = nullptr;
+    uint32_t* d_moved = nullptr;
+    void* d_ws = nullptr;
+    long long ws_bytes = 0;
+    uint8_t* h_mv = nullptr;
+    int bh = 0, bw = 0;
+    long long searched = 0;        // pictures that went through the search
+    std::string mv_records;
     void create(const Geometry& g, const DenoiseArgs& d)
     {
         arg = d;
         for (uint8_t*& p : hist) hip_ok(hipMalloc(&p, g.frame_bytes()), "hipMalloc");
+        if (arg.mc && arg.temporal > 0) {
+            bh = (g.H + 15) / 16; bw = (g.W + 15) / 16;
+            ws_bytes = dcvc_motion_search_workspace_bytes(g.H, g.W);
+            if (ws_bytes <= 0) die("--denoise-mc: the coded size is outside the search's limits");
+            hip_ok(hipMalloc(&comp, g.frame_bytes()), "hipMalloc");
+            hip_ok(hipMalloc(&d_mv, static_cast<size_t>(bh) * bw * 2 * sizeof(int16_t)), "hipMalloc");
+            hip_ok(hipMalloc(&d_sad, static_cast<size_t>(bh) * bw * sizeof(uint32_t)), "hipMalloc");
+            hip_ok(hipMalloc(&d_moved, sizeof(uint32_t)), "hipMalloc");
+            hip_ok(hipMemset(d_moved, 0, sizeof(uint32_t)), "hipMemset");
+            hip_ok(hipMalloc(&d_ws, static_cast<size_t>(ws_bytes)), "hipMalloc");
+            if (!arg.mv_log.empty()) {
+                hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_mv), static_cast<size_t>(bh) * bw * 8, hipHostMallocDefault), "hipHostMalloc");
+            }
+        }
         if (!arg.out.empty()) {
             hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_out), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
             file = fopen(arg.out.c_str(), "wb");
@@ -2002,6 +2065,17 @@ struct Denoiser {
         const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
         const uint8_t* prev = pictures > 0 ? hist[turn ^ 1] : nullptr;
         uint8_t* dst = hist[turn];
+        if (prev && comp) {
+            const int sx = g.Wc() != g.W ? 1 : 0, sy = g.Hc() != g.H ? 1 : 0;
+            abi_ok(dcvc_motion_search(src, g.W, prev, g.W, dt, g.bit_depth, g.H, g.W, arg.mc_range, arg.mc_lambda, d_mv, bh, bw, d_sad, d_moved,
+                                      d_ws, ws_bytes, st), "motion search");
+            abi_ok(dcvc_motion_compensate_planes(prev, g.W, ny, comp, g.W, ny, dt, g.H, g.W, 1, 0, 0, d_mv, bh, bw, st), "motion compensate (Y)");
+            abi_ok(dcvc_motion_compensate_planes(prev + ny * es, g.Wc(), nc, comp + ny * es, g.Wc(), nc, dt, g.Hc(), g.Wc(), 2, sx, sy, d_mv,
+                                                 bh, bw, st), "motion compensate (U, V)");
+            if (h_mv) log_vectors(st);
+            ++searched;
+            prev = comp;
+        }
         abi_ok(dcvc_denoise_planes(src, g.W, ny, prev, g.W, ny, dst, g.W, ny, dt, g.bit_depth, g.H, g.W, 1, arg.spatial, arg.temporal, st),
                "denoise (Y)");
         abi_ok(dcvc_denoise_planes(src + ny * es, g.Wc(), nc, prev ? prev + ny * es : nullptr, g.Wc(), nc, dst + ny * es, g.Wc(), nc, dt,
@@ -2016,11 +2090,56 @@ struct Denoiser {
         ++pictures;
         return dst;
     }
+    // --mv-log: the vectors and SADs of the picture just searched -> one record
+    void log_vectors(hipStream_t st)
+    {
+        const size_t nb = static_cast<size_t>(bh) * bw;
+        hip_ok(hipMemcpyAsync(h_mv, d_mv, nb * 4, hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipMemcpyAsync(h_mv + nb * 4, d_sad, nb * 4, hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipStreamSynchronize(st), "sync");
+        const int16_t* v = reinterpret_cast<const int16_t*>(h_mv);
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(h_mv + nb * 4);
+        long long nonzero = 0, sdx = 0, sdy = 0, mx = 0;
+        unsigned long long ssad = 0;
+        for (size_t b = 0; b < nb; ++b) {
+            const long long ax = std::abs(static_cast<int>(v[2 * b])), ay = std::abs(static_cast<int>(v[2 * b + 1]));
+            nonzero += (ax | ay) != 0;
+            sdx += ax; sdy += ay;
+            mx = std::max(mx, std::max(ax, ay));
+            ssad += s[b];
+        }
+        mv_records += std::string(mv_records.empty() ? "" : ",") + "\n    {\"idx\": " + std::to_string(pictures) + ", \"blocks\": " + std::to_string(nb) +
+                      ", \"nonzero\": " + std::to_string(nonzero) + ", \"sum_abs_dx\": " + std::to_string(sdx) + ", \"sum_abs_dy\": " +
+                      std::to_string(sdy) + ", \"max_abs\": " + std::to_string(mx) + ", \"sum_sad\": " + std::to_string(ssad) + "}";
+    }
+    // the summary line's tail and --mv-log's file; g supplies the coded size
+    std::string finish_mc(const Geometry& g, hipStream_t st)
+    {
+        if (!arg.mc) return "";
+        uint32_t moved = 0;
+        if (d_moved) {
+            hip_ok(hipMemcpyAsync(&moved, d_moved, sizeof(moved), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+        }
+        if (!arg.mv_log.empty()) {
+            const std::string text = "{\n  \"range\": " + std::to_string(arg.mc_range) + ",\n  \"lambda\": " + std::to_string(arg.mc_lambda) +
+                                     ",\n  \"block\": 16,\n  \"width\": " + std::to_string(g.W) + ",\n  \"height\": " + std::to_string(g.H) +
+                                     ",\n  \"pictures\": [" + mv_records + (mv_records.empty() ? "" : "\n  ") + "]\n}\n";
+            FILE* lf = fopen(arg.mv_log.c_str(), "wb");
+            if (!lf || fwrite(text.data(), 1, text.size(), lf) != text.size() || fclose(lf) != 0) die("cannot write " + arg.mv_log);
+        }
+        return ", mc range " + std::to_string(arg.mc_range) + " lambda " + std::to_string(arg.mc_lambda) + " (" + std::to_string(moved) + " of " +
+               std::to_string(searched * bh * bw) + " blocks moved)";
+    }
     void destroy()
     {
         for (uint8_t* p : hist) {
             if (p) hip_ok(hipFree(p), "hipFree");
         }
+        for (void* p : {static_cast<void*>(comp), static_cast<void*>(d_mv), static_cast<void*>(d_sad), static_cast<void*>(d_moved), d_ws}) {
+            if (p) hip_ok(hipFree(p), "hipFree");
+        }
+        if (h_mv) hip_ok(hipHostFree(h_mv), "hipHostFree");
         if (h_out) hip_ok(hipHostFree(h_out), "hipHostFree");
         if (file && fclose(file) != 0) die("cannot write " + arg.out);
         *this = Denoiser{};
@@ -4092,7 +4211,8 @@ int encode(const Args& a)
         iv.destroy();
     }
     if (denoise.on) {
-        fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered\n", denoise.spatial, denoise.temporal, dn.pictures);
+        fprintf(g_msg, "denoise: spatial %d, temporal %d, %lld pictures filtered%s\n", denoise.spatial, denoise.temporal, dn.pictures,
+                dn.finish_mc(g, b.st).c_str());
         if (grain.log_on) gm.finish(b.st);
         b.yuv8 = staging;
         dn.destroy();

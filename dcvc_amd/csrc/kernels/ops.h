@@ -548,6 +548,40 @@ void window_planes_validate(const WindowPlanesDesc& d);   // throws std::invalid
 // one launch for every 16 planes on `stream`: validates first, allocates nothing, never waits for the host
 void window_planes(const WindowPlanesDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- block motion search and compensation (motion.hip)
+// motion_search: one integer vector per 16 x 16 block of a luma plane against a reference plane, a two-level search in exact
+// integers; motion_compensate_planes: planes fetched through those vectors (both stated at the head of
+// motion.hip). Strides in samples.
+constexpr int kMotionMaxSide = 16384;
+constexpr int kMotionBlock = 16;
+constexpr int kMotionMaxRange = 15;
+constexpr int kMotionMaxLambda = 255;
+struct MotionSearchDesc {
+    const void* cur = nullptr; int cur_row_stride = 0;
+    const void* ref = nullptr; int ref_row_stride = 0;           // may be cur
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0;
+    int range = 0;                                   // 0..15, in half-resolution samples
+    int lambda = 0;                                  // 0..255, in 8-bit code values a sample of vector length
+    void* mv = nullptr; int mv_bh = 0, mv_bw = 0;    // device int16 [mv_bh][mv_bw][2] holding (dx, dy); the grid's own pitch
+    void* sad = nullptr;                             // device uint32 [mv_bh][mv_bw], or nullptr
+    void* moved = nullptr;                           // device uint32, or nullptr: + the number of blocks with a vector != (0, 0)
+    void* workspace = nullptr; long long workspace_bytes = 0;
+};
+size_t motion_search_workspace_bytes(int H, int W);  // the two half-resolution planes
+void motion_search_validate(const MotionSearchDesc& d);      // throws std::invalid_argument for what is refused
+// two launches on `stream`: validates first, allocates nothing, never waits for the host
+void motion_search(const MotionSearchDesc& d, hipStream_t stream);
+struct MotionCompensateDesc {
+    const void* prev = nullptr; int prev_row_stride = 0; long long prev_plane_stride = 0;
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int dtype = kSampleU8, H = 0, W = 0, n_planes = 1;
+    int sx = 0, sy = 0;                              // the planes' subsampling against the luma plane of the search
+    const void* mv = nullptr; int mv_bh = 0, mv_bw = 0;
+};
+void motion_compensate_validate(const MotionCompensateDesc& d);   // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void motion_compensate_planes(const MotionCompensateDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -443,6 +443,44 @@ int dcvc_denoise_planes(const void* src, int src_row_stride, long long src_plane
                         long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int bit_depth,
                         int H, int W, int n_planes, int spatial, int temporal, void* stream);
 
+/* Block motion search and motion compensation on the GPU (no reference counterpart), every value defined exactly
+ * in signed 32-bit integers. cur and ref are luma planes [H][W]; sh = bit_depth - 8, L = lambda << sh; blocks are 16 x 16 luma
+ * samples, Bh = ceil(H / 16), Bw = ceil(W / 16):
+ *   half resolution: H1 = ceil(H / 2), W1 = ceil(W / 2),
+ *                    a1[y][x] = (a[2y][2x] + a[2y][2x+1] + a[2y+1][2x] + a[2y+1][2x+1] + 2) >> 2, indexes clamped to the plane.
+ *   block SAD:       over the block's samples inside cur (a partial block at the right or bottom edge sums fewer samples); the
+ *                    reference index (y + dy, x + dx) is clamped to the plane.
+ *   order:           the smallest tuple (cost, |dx| + |dy|, dy, dx) wins.
+ *   level 1:         block (by, bx) is the 8 x 8 block of the half-resolution planes; every dx, dy in -range..range is a
+ *                    candidate, cost = SAD + L (|dx| + |dy|); the winner is (dx1, dy1).
+ *   level 0:         full resolution, the 16 x 16 block; the candidates are (2 dx1 + ex, 2 dy1 + ey), ex, ey in -1..1, and
+ *                    (0, 0); cost = SAD + 4 L (|dx| + |dy|). The winner is the block's vector, |dx|, |dy| <= 2 range + 1.
+ *   dcvc_motion_search_workspace_bytes: the two half-resolution planes of a search on [H][W]; 0 for bad arguments.
+ *   dcvc_motion_search: mv (device, int16 [mv_bh][mv_bw][2]) takes (dx, dy) of blocks [0, Bh) x [0, Bw), the rest of the grid
+ *   is left alone; sad (device, uint32 [mv_bh][mv_bw], or NULL) the winner's SAD without the penalty; moved (device, one
+ *   uint32, or NULL) is increased by the number of blocks whose vector is not (0, 0), the caller zeroes it. Samples are
+ *   DCVC_SAMPLE_U8 (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned, bit_depth 9..16); strides in samples; cur == ref is
+ *   allowed. Two launches on `stream`: nothing is allocated and nothing waits for the host, and the workspace is the caller's
+ *   until they have run. Refused before anything is enqueued: NULL cur, ref, mv or workspace; another sample type; a bit_depth
+ *   that is not the type's; H or W outside 1..16384; range outside 0..15; lambda outside 0..255; an mv grid below Bh x Bw; a
+ *   row stride below W; a 16-bit plane, mv or the workspace at an odd address; a sad or moved that is not 4-byte aligned; a workspace
+ *   below dcvc_motion_search_workspace_bytes.
+ *   dcvc_motion_compensate_planes: n_planes planes prev [H][W] -> dst, every plane on its own, the planes subsampled by
+ *   (sx, sy) in {0, 1} against the luma plane the vectors were searched on: the block of sample (y, x) is
+ *   (y / (16 >> sy), x / (16 >> sx)), dxc = dx >> sx, dyc = dy >> sy (arithmetic shifts: a floor),
+ *   dst[y][x] = prev[clamp(y + dyc)][clamp(x + dxc)]. The vectors are device data and are not validated: the clamp makes any
+ *   int16 vector safe; all-zero vectors copy. One launch on `stream`; plane strides are not read for one plane. Refused before
+ *   anything is enqueued: NULL prev, dst or mv; another sample type; H or W outside 1..16384; sx or sy outside {0, 1}; n_planes
+ *   outside 1..65535; an mv grid below ceil(H / (16 >> sy)) x ceil(W / (16 >> sx)); a row stride below W or a plane stride
+ *   below the plane; a 16-bit plane or mv at an odd address; dst overlapping prev or mv. */
+long long dcvc_motion_search_workspace_bytes(int H, int W);
+int dcvc_motion_search(const void* cur, int cur_row_stride, const void* ref, int ref_row_stride, int dtype, int bit_depth, int H, int W,
+                       int range, int lambda, void* mv, int mv_bh, int mv_bw, void* sad, void* moved, void* workspace,
+                       long long workspace_bytes, void* stream);
+int dcvc_motion_compensate_planes(const void* prev, int prev_row_stride, long long prev_plane_stride, void* dst, int dst_row_stride,
+                                  long long dst_plane_stride, int dtype, int H, int W, int n_planes, int sx, int sy, const void* mv,
+                                  int mv_bh, int mv_bw, void* stream);
+
 /* Deinterlacer on the GPU (no reference counterpart): planes of a woven frame -> progressive planes, every
  * output sample defined exactly in signed 32-bit integers. Per plane, T = threshold << (bit_depth - 8):
  *   rows y with y % 2 == keep are copied from cur. For a missing row y: ya = y - 1 (y + 1 at the top), yb = y + 1 (y - 1 at

@@ -957,6 +957,35 @@ int dcvc_motion_compensate_planes(const void* prev, int prev_row_stride, long lo
     });
 }
 
+int dcvc_interp_select(const void* a, int a_row_stride, const void* b, int b_row_stride, int dtype, int bit_depth, int H, int W,
+                       const void* mv, int mv_bh, int mv_bw, int k, int n, int limit, void* plan, void* wb, int plan_bh, int plan_bw,
+                       void* sad, void* fallen, void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::InterpSelectDesc d;
+        d.a = a; d.a_row_stride = a_row_stride; d.b = b; d.b_row_stride = b_row_stride;
+        d.dtype = dtype; d.bit_depth = bit_depth; d.H = H; d.W = W; d.mv = mv; d.mv_bh = mv_bh; d.mv_bw = mv_bw;
+        d.k = k; d.n = n; d.limit = limit; d.plan = plan; d.wb = wb; d.plan_bh = plan_bh; d.plan_bw = plan_bw; d.sad = sad; d.fallen = fallen;
+        dcvc::interp_select(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
+int dcvc_interp_planes(const void* a, int a_row_stride, long long a_plane_stride, const void* b, int b_row_stride, long long b_plane_stride,
+                       void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int H, int W, int n_planes, int sx, int sy,
+                       const void* plan, const void* wb, int plan_bh, int plan_bw, int k, int n, const void* fallen, int n_blocks,
+                       void* stream)
+{
+    return dcvc::guarded([&] {
+        dcvc::InterpPlanesDesc d;
+        d.a = a; d.a_row_stride = a_row_stride; d.a_plane_stride = a_plane_stride;
+        d.b = b; d.b_row_stride = b_row_stride; d.b_plane_stride = b_plane_stride;
+        d.dst = dst; d.dst_row_stride = dst_row_stride; d.dst_plane_stride = dst_plane_stride;
+        d.dtype = dtype; d.H = H; d.W = W; d.n_planes = n_planes; d.sx = sx; d.sy = sy;
+        d.plan = plan; d.wb = wb; d.plan_bh = plan_bh; d.plan_bw = plan_bw; d.k = k; d.n = n; d.fallen = fallen; d.n_blocks = n_blocks;
+        dcvc::interp_planes(d, S(stream));      // validates before it enqueues anything
+    });
+}
+
 int dcvc_deinterlace_planes(const void* cur, int cur_row_stride, long long cur_plane_stride, const void* prev, int prev_row_stride,
                             long long prev_plane_stride, void* dst, int dst_row_stride, long long dst_plane_stride, int dtype,
                             int bit_depth, int H, int W, int n_planes, int keep, int weave_from_prev, int threshold, void* stream)

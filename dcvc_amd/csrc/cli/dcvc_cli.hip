@@ -22,6 +22,7 @@
 //               [--deinterlace frame|field[:T] [--field-order tff|bff] [--deinterlace-out progressive.yuv]]
 //               [--ivtc film|match[:CTHRESH[:MI[:T]]] [--field-order tff|bff] [--ivtc-out film.yuv] [--ivtc-log log.json]]
 //               [--crop auto[:LIMIT[:FRAC[:MINBAR[:N]]]] | --crop WxH+X+Y [--crop-log crop.json] [--crop-out cropped.yuv] [--crop-fill Y:U:V]]
+//               [--frame-step 2..8]
 //   dcvc decode --intra I.dcvw [--inter P.dcvw] -i out.bin [-o rec.yuv] [-n frames] [--ref in.yuv --json log.json]
 //               [--calc-ssim 1] [--verbose-json 1] [--src-type yuv420|yuv422|yuv444|nv12|p010|nv21|nv16|p210|uyvy|yuy2|y210|v210|rgb24|png|rgb48|png16] [--bit-depth 8|9..16] [--out-size WxH]
 //               [--fps N:D] [--hash-log hashes.txt] [--verify-hash hashes.txt]
@@ -29,6 +30,28 @@
 //               [--in-format raw|y4m] [--out-format raw|y4m]                                               (-i - | --ref - | -o -: pipes)
 //               [--film-grain grain.json | --grain-strength Y[:C[:SIZE]]]
 //               [--uncrop crop.json | --pad SWxSH+X+Y [--pad-fill Y:U:V]]
+//               [--interpolate N[:R[:LAMBDA[:LIMIT]]] [--interp-log log.json [--interp-ref clip.yuv]]]
+//               Frame-rate conversion. decode --interpolate N (2..8; R 0..15, default 7, and LAMBDA 0..255, default
+//               4, are the search's, LIMIT 0..255, default 8, is the selection's: 8-bit code values a sample above which a block
+//               repeats the nearer picture; the defaults are untuned) puts N - 1 pictures between every two decoded pictures of
+//               one size: n decoded pictures give N (n - 1) + 1 output pictures. The stage keeps a device copy of the previous
+//               output picture as the metrics see it (behind --out-size, before grain and pad); when the next one arrives its luma
+//               is searched against it once (dcvc_motion_search), then per phase k = 1..N-1 dcvc_interp_select and two
+//               dcvc_interp_planes calls (Y; U and V with the format's subsampling) make the picture, which goes through grain,
+//               pad, the hashes and -o as a decoded one does, then the decoded picture follows. Hashes and the grain's picture
+//               index count output pictures; a -o *.y4m header states N times the rate; --ref, PSNR, MS-SSIM and --json stay those
+//               of the decoded pictures; the padding pictures of a ragged chunk do not reach the stage; a change of size restarts
+//               it. --interp-log FILE (not "-"): JSON with n, range, lambda, limit, block, width, height and per in-between picture
+//               {out_idx, after, k, blocks, fallen, repeated, sum_sad}; one small copy and one wait a picture only with it.
+//               --interp-ref FILE (needs the log; raw or Y4M, at the output rate and size): output picture j is measured against
+//               its picture j; the log's in-between entries gain psnr_y / psnr_u / psnr_v (before grain and pad), the decoded
+//               pictures' entries are read and dropped. The summary line gains ", interpolate xN (K in-between pictures, F
+//               repeated)", F from the device's counters, read back once at the end. Planar yuv420 / yuv422 / yuv444 at 8..16 bits;
+//               RGB, PNG, wire types, nv12 / p010, --verify-hash and the flags on encode are refused with status 2.
+//               encode --frame-step N (2..8): of every N source pictures the first is coded, the others are read and dropped (on a
+//               pipe too); the reader does it, in front of every stage, so -n, --crop auto and --read-ahead see the decimated
+//               clip and the stream is that of the clip decimated beforehand. Refused with --deinterlace, --ivtc, PNG
+//               directories and on decode.
 //               Black bars. encode --crop WxH+X+Y codes the window of every source picture; --crop auto finds it:
 //               before the first picture is coded N' = min(N, M) of the M source frames the run will read (N 16, 1..256), frames
 //               ((2k + 1) M) / (2 N'), are read with pread from the regular -i file (a pipe is refused), uploaded, unpacked when a
@@ -847,6 +870,10 @@ struct PictureFile {
     size_t pos = 0, end = 0;
     size_t partial = 0;                        // End: bytes of a trailing partial raw picture
     std::string error;
+    // --frame-step N (encode): of every `step` pictures the first is a picture of this file, the others are read
+    // and dropped: count, offsets and next see the decimated clip, and so does everything behind them
+    int step = 1;
+    long long served = 0;                      // pictures next has handed out
     // format: "" = by name, "raw" or "y4m" (--in-format); interlaced: a Y4M file may say It or Ib (--deinterlace)
     void open(const std::string& p, const std::string& format = "", bool interlaced = false)
     {
@@ -886,12 +913,12 @@ struct PictureFile {
         struct stat st;
         if (fstat(fd, &st) != 0) die("cannot read " + path);
         const long long size = st.st_size;
-        if (!y4m) return size / static_cast<long long>(frame_bytes);
+        if (!y4m) return (size / static_cast<long long>(frame_bytes) + step - 1) / step;
         long long n = 0, at = info.header_bytes;
         char line[1024];
         for (;;) {
             const ssize_t got = pread(fd, line, sizeof(line), at);
-            if (got <= 0) return n;
+            if (got <= 0) return (n + step - 1) / step;
             const int len = dcvc_y4m_frame_header_bytes(line, static_cast<size_t>(got));
             if (len < 0) die(path + ": no FRAME line where a picture should start (" + dcvc_last_error() + ")");
             at += len;
@@ -909,20 +936,31 @@ struct PictureFile {
         std::vector<long long> at_of;
         long long at = y4m ? info.header_bytes : 0;
         char line[1024];
-        for (long long i = 0; i < n; ++i) {
+        for (long long i = 0; i < (n - 1) * step + 1; ++i) {
             if (y4m) {
                 const ssize_t got = pread(fd, line, sizeof(line), at);
                 const int len = got <= 0 ? -1 : dcvc_y4m_frame_header_bytes(line, static_cast<size_t>(got));
                 if (len < 0) die(path + ": no FRAME line where picture " + std::to_string(i + 1) + " should start");
                 at += len;
             }
-            at_of.push_back(at);
+            if (i % step == 0) at_of.push_back(at);
             at += static_cast<long long>(frame_bytes);
         }
         return at_of;
     }
     // the next picture. Calls nothing that dies and nothing from HIP: the read-ahead thread runs it.
     Status next(uint8_t* dst, size_t frame_bytes)
+    {
+        // the pictures between two that are kept pass through dst: a pipe is read, never skipped
+        for (int k = 1; k < step && served > 0; ++k) {
+            const Status s = next_of_file(dst, frame_bytes);
+            if (s != Picture) return s;
+        }
+        const Status s = next_of_file(dst, frame_bytes);
+        if (s == Picture) ++served;
+        return s;
+    }
+    Status next_of_file(uint8_t* dst, size_t frame_bytes)
     {
         if (y4m) {
             const size_t n = fill_line();
@@ -2968,6 +3006,271 @@ struct ScaledOut {
     }
 };
 
+// --interpolate N[:R[:LAMBDA[:LIMIT]]] / --interp-log FILE / --interp-ref FILE (decode) and --frame-step N (encode):
+// what the flags alone decide is refused before a model is loaded
+struct InterpArgs {
+    bool on = false;
+    int n = 2, range = 7, lambda = 4, limit = 8;       // the defaults are untuned
+    std::string log, ref;
+};
+
+InterpArgs interp_args(const Args& a, bool encoding)
+{
+    InterpArgs p;
+    if (encoding) {
+        for (const char* k : {"interpolate", "interp-log", "interp-ref"}) {
+            if (a.has(k)) die(std::string("--") + k + " is a decoder flag: encode codes every N-th picture with --frame-step N");
+        }
+        return p;
+    }
+    if (a.has("frame-step")) die("--frame-step is an encoder flag: decode shows N times the pictures with --interpolate N");
+    if (!a.has("interpolate")) {
+        for (const char* k : {"interp-log", "interp-ref"}) {
+            if (a.has(k)) die(std::string("--") + k + " needs --interpolate");
+        }
+        return p;
+    }
+    if (a.has("interp-ref") && !a.has("interp-log")) die("--interp-ref needs --interp-log: the PSNRs of the in-between pictures go there");
+    const std::string s = a.str("interpolate");
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t c = s.find(':', at);
+        parts.push_back(s.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    const unsigned long long hi[4] = {8, 15, 255, 255};
+    unsigned long long v[4] = {2, 7, 4, 8};
+    bool ok = parts.size() <= 4;
+    for (size_t i = 0; ok && i < parts.size(); ++i) ok = parse_uint(parts[i], hi[i], v[i]);
+    if (!ok || v[0] < 2) {
+        die("--interpolate must be N[:R[:LAMBDA[:LIMIT]]] with integers in 2..8, 0..15, 0..255 and 0..255, got " + s);
+    }
+    p.n = static_cast<int>(v[0]); p.range = static_cast<int>(v[1]); p.lambda = static_cast<int>(v[2]); p.limit = static_cast<int>(v[3]);
+    const std::string t = a.str("src-type", "yuv420");
+    if (t != "yuv420" && t != "yuv422" && t != "yuv444") die("--interpolate is for planar YUV pictures: --src-type " + t + " pictures are not interpolated yet");
+    p.log = a.str("interp-log");
+    if (a.has("interp-log") && (p.log.empty() || is_dash(p.log))) die("--interp-log needs a file name (not -: a log goes to a file of its own)");
+    p.ref = a.str("interp-ref");
+    if (a.has("interp-ref") && (p.ref.empty() || is_dash(p.ref))) die("--interp-ref needs a file name (not -)");
+    p.on = true;
+    return p;
+}
+
+int frame_step_arg(const Args& a)
+{
+    if (!a.has("frame-step")) return 1;
+    const int n = int_arg(a, "frame-step", 1, 2, 8);
+    if (a.has("deinterlace")) die("--frame-step and --deinterlace: a field's neighbour in time would be dropped; decimate the deinterlaced clip");
+    if (a.has("ivtc")) die("--frame-step and --ivtc: the pulldown cycle would be broken; decimate the restored clip");
+    const std::string t = a.str("src-type", "yuv420");
+    if (t == "png" || t == "png16") die("--frame-step reads raw and Y4M sources: --src-type " + t + " is a directory of PNG pictures");
+    return n;
+}
+
+// decode --interpolate: N - 1 pictures between every two decoded pictures of one size. The state is a device copy of the previous
+// output picture as the metrics see it (behind --out-size, before grain and pad). begin() searches the arriving picture's luma
+// against it once; between() makes the picture of phase k: the selection, Y in one interpolation call, U and V in another; keep()
+// takes the arriving picture as the next pair's first.
+struct Interpolator {
+    InterpArgs arg;
+    Geometry g;                    // the pictures arriving
+    bool active = false, have_prev = false;
+    uint8_t* prev = nullptr;
+    uint8_t* mid = nullptr;
+    int16_t* d_mv = nullptr;
+    int16_t* d_plan = nullptr;
+    uint8_t* d_wb = nullptr;
+    uint32_t* d_sad = nullptr;     // --interp-log: the winners' SADs
+    // the counters of fallen blocks, one per in-between picture, read back when all have been used and at the end: the summary
+    // line counts the repeated pictures without a wait per picture
+    static constexpr int kRing = 1024;
+    uint32_t* d_fall = nullptr;
+    int ring_n = 0;
+    void* d_ws = nullptr;
+    long long ws_bytes = 0;
+    uint32_t* h_sad = nullptr;     // pinned, --interp-log
+    int bh = 0, bw = 0;
+    long long out_idx = 0, decoded = 0, between_n = 0, repeated = 0;
+    std::string records;
+    // --interp-ref
+    PictureFile ref_file;
+    uint8_t* h_ref = nullptr;      // pinned
+    uint8_t* d_ref = nullptr;
+    double* d_sse = nullptr;
+    double* h_sse = nullptr;       // pinned
+    void* sse_ws = nullptr;
+    long long sse_ws_bytes = 0;
+    void create(const InterpArgs& p, const Geometry& og, const std::string& in_format)
+    {
+        // a stream may switch parameter sets: the stage restarts (the caller has flushed the counters), the counts and the log go on
+        release();
+        arg = p;
+        g = og;
+        active = true;
+        have_prev = false;
+        if (og.rgb || og.wire >= 0 || (og.pix() && og.pix_fmt != DCVC_PIX_YUV422P && og.pix_fmt != DCVC_PIX_YUV444P)) {
+            die("--interpolate is for planar YUV pictures: these pictures are not interpolated yet");
+        }
+        bh = (g.H + 15) / 16; bw = (g.W + 15) / 16;
+        const size_t nb = static_cast<size_t>(bh) * bw;
+        ws_bytes = dcvc_motion_search_workspace_bytes(g.H, g.W);
+        if (ws_bytes <= 0) die("--interpolate: the output size is outside the search's limits");
+        hip_ok(hipMalloc(&prev, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&mid, g.frame_bytes()), "hipMalloc");
+        hip_ok(hipMalloc(&d_mv, nb * 2 * sizeof(int16_t)), "hipMalloc");
+        hip_ok(hipMalloc(&d_plan, nb * 4 * sizeof(int16_t)), "hipMalloc");
+        hip_ok(hipMalloc(&d_wb, nb), "hipMalloc");
+        hip_ok(hipMalloc(&d_sad, nb * sizeof(uint32_t)), "hipMalloc");
+        hip_ok(hipMalloc(&d_fall, kRing * sizeof(uint32_t)), "hipMalloc");
+        hip_ok(hipMalloc(&d_ws, static_cast<size_t>(ws_bytes)), "hipMalloc");
+        if (!arg.log.empty()) hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_sad), (nb + 1) * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+        if (!arg.ref.empty()) {
+            if (ref_file.fd < 0) ref_file.open(arg.ref, in_format);
+            if (ref_file.y4m) {
+                const dcvc_y4m_info& i = ref_file.info;
+                const int fmt = g.pix() ? g.pix_fmt : DCVC_PIX_YUV420P;
+                if (i.width != g.W || i.height != g.H || i.bit_depth != g.bit_depth || i.pix_fmt != fmt) {
+                    die("--interp-ref: " + ref_file.path + " holds " + std::to_string(i.width) + "x" + std::to_string(i.height) + " pictures of " +
+                        std::to_string(i.bit_depth) + " bits, the output is " + std::to_string(g.W) + "x" + std::to_string(g.H) + " " + chroma_name(g) +
+                        " of " + std::to_string(g.bit_depth) + " bits");
+                }
+            }
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_ref), g.frame_bytes(), hipHostMallocDefault), "hipHostMalloc");
+            hip_ok(hipMalloc(&d_ref, g.frame_bytes()), "hipMalloc");
+            hip_ok(hipMalloc(&d_sse, 3 * sizeof(double)), "hipMalloc");
+            hip_ok(hipHostMalloc(reinterpret_cast<void**>(&h_sse), 3 * sizeof(double), hipHostMallocDefault), "hipHostMalloc");
+            sse_ws_bytes = std::max(dcvc_sse_workspace_bytes(1, g.H, g.W), dcvc_sse_workspace_bytes(2, g.Hc(), g.Wc()));
+            hip_ok(hipMalloc(&sse_ws, static_cast<size_t>(sse_ws_bytes)), "hipMalloc");
+        }
+    }
+    // cur: the picture arriving (planes Y, U, V back to back). false: it is the first of its size, nothing lies in front of it
+    bool begin(const uint8_t* cur, hipStream_t st)
+    {
+        if (!have_prev) return false;
+        const int dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        abi_ok(dcvc_motion_search(cur, g.W, prev, g.W, dt, g.bit_depth, g.H, g.W, arg.range, arg.lambda, d_mv, bh, bw, nullptr, nullptr, d_ws,
+                                  ws_bytes, st), "motion search");
+        return true;
+    }
+    // the picture at k / N between the previous picture and cur; it stays valid until the next call
+    const uint8_t* between(const uint8_t* cur, int k, hipStream_t st)
+    {
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const long long ny = static_cast<long long>(g.H) * g.W, nc = static_cast<long long>(g.Hc()) * g.Wc();
+        const int sx = g.Wc() != g.W ? 1 : 0, sy = g.Hc() != g.H ? 1 : 0;
+        const size_t nb = static_cast<size_t>(bh) * bw;
+        if (ring_n == kRing) flush(st);
+        uint32_t* d_fallen = d_fall + ring_n;
+        hip_ok(hipMemsetAsync(d_fallen, 0, sizeof(uint32_t), st), "hipMemset");
+        abi_ok(dcvc_interp_select(prev, g.W, cur, g.W, dt, g.bit_depth, g.H, g.W, d_mv, bh, bw, k, arg.n, arg.limit, d_plan, d_wb, bh, bw,
+                                  h_sad ? d_sad : nullptr, d_fallen, st), "interp select");
+        abi_ok(dcvc_interp_planes(prev, g.W, ny, cur, g.W, ny, mid, g.W, ny, dt, g.H, g.W, 1, 0, 0, d_plan, d_wb, bh, bw, k, arg.n, d_fallen,
+                                  bh * bw, st), "interp (Y)");
+        abi_ok(dcvc_interp_planes(prev + ny * es, g.Wc(), nc, cur + ny * es, g.Wc(), nc, mid + ny * es, g.Wc(), nc, dt, g.Hc(), g.Wc(), 2, sx, sy,
+                                  d_plan, d_wb, bh, bw, k, arg.n, d_fallen, bh * bw, st), "interp (U, V)");
+        ++between_n;
+        if (h_sad) log_picture(k, d_fallen, st);
+        ++ring_n;
+        ++out_idx;
+        return mid;
+    }
+    // the counters used so far -> repeated
+    void flush(hipStream_t st)
+    {
+        std::vector<uint32_t> f(static_cast<size_t>(ring_n));
+        if (ring_n > 0) {
+            hip_ok(hipMemcpyAsync(f.data(), d_fall, f.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H");
+            hip_ok(hipStreamSynchronize(st), "sync");
+        }
+        for (uint32_t v : f) repeated += 2ULL * v > static_cast<unsigned long long>(bh) * bw;
+        ring_n = 0;
+    }
+    // one output picture of --interp-ref: an in-between picture is measured against it, a decoded picture's entry is dropped
+    bool next_ref()
+    {
+        if (h_ref == nullptr) return false;
+        if (!ref_file.read(h_ref, g.frame_bytes())) die("--interp-ref: " + ref_file.path + " is shorter than the output");
+        return true;
+    }
+    // --interp-log: one small copy and one wait per in-between picture
+    void log_picture(int k, const uint32_t* d_fallen, hipStream_t st)
+    {
+        const size_t nb = static_cast<size_t>(bh) * bw;
+        const int es = g.hbd() ? 2 : 1, dt = g.hbd() ? DCVC_SAMPLE_U16 : DCVC_SAMPLE_U8;
+        const size_t ny = g.y_bytes(), nc = static_cast<size_t>(g.Hc()) * g.Wc();
+        hip_ok(hipMemcpyAsync(h_sad, d_sad, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H");
+        hip_ok(hipMemcpyAsync(h_sad + nb, d_fallen, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "D2H");
+        const bool measured = next_ref();
+        if (measured) {
+            hip_ok(hipMemcpyAsync(d_ref, h_ref, g.frame_bytes(), hipMemcpyHostToDevice, st), "H2D");
+            abi_ok(dcvc_sse_ws(d_ref, dt, mid, dt, 1, g.H, g.W, g.W, static_cast<long long>(ny), d_sse, sse_ws, sse_ws_bytes, st), "sse (Y)");
+            abi_ok(dcvc_sse_ws(d_ref + ny * es, dt, mid + ny * es, dt, 2, g.Hc(), g.Wc(), g.Wc(), static_cast<long long>(nc), d_sse + 1, sse_ws,
+                               sse_ws_bytes, st), "sse (U, V)");
+            hip_ok(hipMemcpyAsync(h_sse, d_sse, 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H");
+        }
+        hip_ok(hipStreamSynchronize(st), "sync");
+        unsigned long long ssad = 0;
+        for (size_t b = 0; b < nb; ++b) ssad += h_sad[b];
+        const unsigned long long fallen = h_sad[nb];
+        const bool rep = 2 * fallen > nb;
+        records += std::string(records.empty() ? "" : ",") + "\n    {\"out_idx\": " + std::to_string(out_idx) + ", \"after\": " + std::to_string(decoded - 1) +
+                   ", \"k\": " + std::to_string(k) + ", \"blocks\": " + std::to_string(nb) + ", \"fallen\": " + std::to_string(fallen) +
+                   ", \"repeated\": " + std::to_string(rep ? 1 : 0) + ", \"sum_sad\": " + std::to_string(ssad);
+        if (measured) {
+            const double peak = static_cast<double>((1 << g.bit_depth) - 1);
+            records += ", \"psnr_y\": " + jnum(psnr_of_sse(h_sse[0], static_cast<double>(ny), peak)) + ", \"psnr_u\": " +
+                       jnum(psnr_of_sse(h_sse[1], static_cast<double>(nc), peak)) + ", \"psnr_v\": " + jnum(psnr_of_sse(h_sse[2], static_cast<double>(nc), peak));
+        }
+        records += "}";
+    }
+    // cur becomes the previous picture; it was output picture out_idx
+    void keep(const uint8_t* cur, hipStream_t st)
+    {
+        hip_ok(hipMemcpyAsync(prev, cur, g.frame_bytes(), hipMemcpyDeviceToDevice, st), "D2D");
+        have_prev = true;
+        ++decoded;
+        ++out_idx;
+        next_ref();
+    }
+    // the summary line's tail and --interp-log's file
+    std::string finish(hipStream_t st)
+    {
+        if (!arg.on) return "";
+        if (active) flush(st);
+        if (!arg.log.empty()) {
+            const std::string text = "{\n  \"n\": " + std::to_string(arg.n) + ",\n  \"range\": " + std::to_string(arg.range) + ",\n  \"lambda\": " +
+                                     std::to_string(arg.lambda) + ",\n  \"limit\": " + std::to_string(arg.limit) + ",\n  \"block\": 16,\n  \"width\": " +
+                                     std::to_string(g.W) + ",\n  \"height\": " + std::to_string(g.H) + ",\n  \"pictures\": [" + records +
+                                     (records.empty() ? "" : "\n  ") + "]\n}\n";
+            FILE* lf = fopen(arg.log.c_str(), "wb");
+            if (!lf || fwrite(text.data(), 1, text.size(), lf) != text.size() || fclose(lf) != 0) die("cannot write " + arg.log);
+        }
+        return ", interpolate x" + std::to_string(arg.n) + " (" + std::to_string(between_n) + " in-between pictures, " + std::to_string(repeated) +
+               " repeated)";
+    }
+    void release()
+    {
+        for (void* p : {static_cast<void*>(prev), static_cast<void*>(mid), static_cast<void*>(d_mv), static_cast<void*>(d_plan), static_cast<void*>(d_wb),
+                        static_cast<void*>(d_sad), static_cast<void*>(d_fall), d_ws, static_cast<void*>(d_ref), static_cast<void*>(d_sse), sse_ws}) {
+            if (p) hip_ok(hipFree(p), "hipFree");
+        }
+        for (void* h : {static_cast<void*>(h_sad), static_cast<void*>(h_ref), static_cast<void*>(h_sse)}) {
+            if (h) hip_ok(hipHostFree(h), "hipHostFree");
+        }
+        prev = mid = d_wb = d_ref = h_ref = nullptr;
+        d_mv = d_plan = nullptr;
+        d_sad = d_fall = h_sad = nullptr;
+        d_ws = sse_ws = nullptr;
+        d_sse = h_sse = nullptr;
+    }
+    void destroy()
+    {
+        release();
+        ref_file.close();
+    }
+};
+
 // ------------------------------------------------------------------------------------ picture hashes
 // --hash-log / --verify-hash: CRC-32 of every output picture's bytes in raw file layout, hashed on the device
 // (dcvc_crc32_segments, one segment per plane); only the CRC words travel to the host.
@@ -3465,9 +3768,11 @@ int encode(const Args& a)
     IvtcArgs ivtc = ivtc_args(a, true);
     DeinterlaceArgs deint = deinterlace_args(a, true);
     const CropArgs crop = crop_args(a, true);
+    interp_args(a, true);
     int pic_w = a.num("W", 0), pic_h = a.num("H", 0);
     // -i *.y4m: the header supplies the size, the source type and the bit depth; flags that disagree are refused
     PictureFile src_file;
+    src_file.step = frame_step_arg(a);         // --frame-step: the reader's clip is the decimated one, in front of every stage
     if (pipe.in_is_y4m(a.str("i"))) {
         src_file.open(a.str("i"), pipe.in_format, deint.on || ivtc.on);
         const Y4mSource y = y4m_source(src_file, a, true);
@@ -4423,6 +4728,8 @@ int decode(const Args& a)
     const PipeArgs pipe = pipe_args(a, false);
     vbv_args(a, batch, false);
     denoise_args(a, false);
+    const InterpArgs interp = interp_args(a, false);
+    if (interp.on && a.has("verify-hash")) die("--verify-hash checks the decoded pictures against the encoder's manifest: not with --interpolate");
     const GrainArgs grain = grain_args(a, false);
     // the file against what the flags say of the run, before a model is loaded; a Y4M --ref's header is checked against it below
     if (grain.on && !(a.has("ref") && pipe.in_is_y4m(a.str("ref")))) {
@@ -4500,7 +4807,10 @@ int decode(const Args& a)
         if (!rec_y4m) return;
         if (!rec_header_done) {
             dcvc_y4m_info hi{};
-            hi.width = og.W; hi.height = og.H; hi.fps_num = fps_num; hi.fps_den = fps_den;
+            // --interpolate N: N times the pictures in the same time
+            const long long rate = static_cast<long long>(fps_num) * (interp.on ? interp.n : 1);
+            if (rate > 2147483647LL) die("--interpolate: the rate of -o *.y4m, " + std::to_string(fps_num) + " times " + std::to_string(interp.n) + ", does not fit its header");
+            hi.width = og.W; hi.height = og.H; hi.fps_num = static_cast<int>(rate); hi.fps_den = fps_den;
             hi.pix_fmt = og.pix() ? og.pix_fmt : DCVC_PIX_YUV420P;
             hi.bit_depth = og.bit_depth;
             char line[256];
@@ -4538,6 +4848,29 @@ int decode(const Args& a)
     GrainSynth gr;
     // --uncrop / --pad: the last stage, shown = pad(grain(resample(picture))): the bars carry no grain
     PadStage pd;
+    // --interpolate: in front of both, on the picture the metrics see; its pictures pass through grain, pad, the hashes and -o as
+    // a decoded picture does, in output order
+    Interpolator ip;
+    // cur: the decoded picture at its output size gq; h_w: the pinned buffer -o's pictures of this path leave from
+    auto interpolate_to = [&](const Geometry& gq, const uint8_t* cur, uint8_t* h_w) {
+        if (ip.begin(cur, b.st)) {
+            for (int k = 1; k < interp.n; ++k) {
+                const uint8_t* shown = ip.between(cur, k, b.st);
+                if (grain.on) shown = gr.run(gq, shown, b.st);
+                if (pad.on) shown = pd.run(gq, shown, b.st);
+                const Geometry& gw = pad.on ? pd.g : gq;
+                if (hash.on()) hash.picture(shown, gw, b.st);
+                if (has_rec) {
+                    hip_ok(hipMemcpyAsync(h_w, shown, gw.frame_bytes(), hipMemcpyDeviceToHost, b.st), "D2H");
+                    hip_ok(hipStreamSynchronize(b.st), "sync");
+                    rec_frame(gw);
+                    rec_put(h_w, gw.frame_bytes());
+                    rec_flush();
+                }
+            }
+        }
+        ip.keep(cur, b.st);
+    };
     // log (src/utils/common.py:46-116)
     std::vector<int> types;
     std::vector<double> bits, psnr, psnr_y, psnr_u, psnr_v, ssim, ssim_y, ssim_u, ssim_v;
@@ -4604,6 +4937,7 @@ int decode(const Args& a)
             } else {
                 hash.size(out_size.on ? go.W : s->width, out_size.on ? go.H : s->height);
             }
+            if (have_buffers && ip.active) ip.flush(b.st);
             if (have_buffers) free_buffers(b);     // a stream may switch parameter sets: do not leak the old set
             g = geometry(s->height, s->width, rgb, depth, pix_fmt, wire);
             if (rgb) colour.apply(g);
@@ -4611,6 +4945,7 @@ int decode(const Args& a)
             ws.create(g);
             if (out_size.on) so.create(g, go, has_ref, calc_ssim);
             if (grain.on) gr.create(out_size.on ? go : g, grain);
+            if (interp.on) ip.create(interp, out_size.on ? go : g, pipe.in_format);
             src.resize(g.frame_bytes());
             have_buffers = true;
         }
@@ -4669,7 +5004,7 @@ int decode(const Args& a)
             const char* xh = static_cast<const char*>(b.x_hat) + static_cast<size_t>(j) * g.Hp * g.Wp * 3 * 2;
             char* y16 = static_cast<char*>(b.y16);
             // --hash-log / --verify-hash without -o: the samples are wanted on the device although nothing is written
-            x_hat_to_picture(g, b, xh, g.hbd() && !g.pix() ? has_rec || out_size.on || hash.on() : has_rec || hash.on());
+            x_hat_to_picture(g, b, xh, g.hbd() && !g.pix() ? has_rec || out_size.on || hash.on() || interp.on : has_rec || hash.on() || interp.on);
             if (out_size.on) {
                 // b.out8 holds the integer samples -o would write at the coded size: resample them, then the output picture is
                 // written and measured at its own size, sample against sample (the source first, as below)
@@ -4679,6 +5014,7 @@ int decode(const Args& a)
                     die("reference file is shorter than the stream");
                 }
                 so.rs.run(b.out8, so.out, b.st);
+                if (interp.on) interpolate_to(go, so.out, pad.on ? pd.h_out : so.h_out);
                 // the metrics below read so.out, the ungrained picture
                 const uint8_t* shown = grain.on ? gr.run(go, so.out, b.st) : so.out;
                 if (pad.on) shown = pd.run(go, shown, b.st);
@@ -4737,6 +5073,7 @@ int decode(const Args& a)
             }
             if (wire >= 0 && (has_rec || hash.on())) ws.pack(g, b.out8, b.st);
             // grain behind the source check above: a padding picture of a ragged chunk takes no picture index
+            if (interp.on) interpolate_to(g, b.out8, pad.on ? pd.h_out : b.h_yuv);
             const uint8_t* shown = grain.on ? gr.run(g, b.out8, b.st) : b.out8;
             if (pad.on) shown = pd.run(g, shown, b.st);        // (no wire format, no RGB: refused above)
             const Geometry& gw = pad.on ? pd.g : g;            // what -o writes and the hashes cover
@@ -4890,11 +5227,13 @@ int decode(const Args& a)
             ++decoded;
         }
     }
+    const std::string interp_tail = ip.finish(b.st);
     if (have_buffers) free_buffers(b);
     ws.destroy();
     so.destroy();
     gr.destroy();
     pd.destroy();
+    ip.destroy();
     if (rec && fclose(rec) != 0) {
         if (errno == EPIPE) output_closed(a.str("o"));
         die("short write");
@@ -4905,10 +5244,10 @@ int decode(const Args& a)
     const int nk = rgb ? 1 : 4;        // the RGB log has no _y / _u / _v keys (common.py:46-116 without include_yuv)
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (out_size.on) {
-        fprintf(g_msg, "decoded %d pictures (%dx%d, output at %dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, go.W, go.H,
-                decoded / secs);
+        fprintf(g_msg, "decoded %d pictures (%dx%d, output at %dx%d), %.1f pictures/s (file I/O included)%s\n", decoded, g.W, g.H, go.W, go.H,
+                decoded / secs, interp_tail.c_str());
     } else {
-        fprintf(g_msg, "decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)\n", decoded, g.W, g.H, decoded / secs);
+        fprintf(g_msg, "decoded %d pictures (%dx%d), %.1f pictures/s (file I/O included)%s\n", decoded, g.W, g.H, decoded / secs, interp_tail.c_str());
     }
     if (a.has("json")) {
         if (psnr.size() != types.size()) die("--json needs --ref (PSNR per picture)");

@@ -582,6 +582,44 @@ void motion_compensate_validate(const MotionCompensateDesc& d);   // throws std:
 // one launch on `stream`: validates first, allocates nothing, never waits for the host
 void motion_compensate_planes(const MotionCompensateDesc& d, hipStream_t stream);
 
+// ---------------------------------------------------------------- frame-rate conversion (interp.hip)
+// The picture at k / n of the way from picture a to picture b, through the vectors of motion_search(cur = b, ref = a):
+// interp_select picks, per 16 x 16 block of the in-between picture, the vector under which a and b agree best and marks the
+// blocks where they do not agree; interp_planes fetches both pictures through that plan and blends (both stated at
+// the head of interp.hip). Strides in samples.
+constexpr int kInterpMinN = 2, kInterpMaxN = 8;
+constexpr int kInterpMaxLimit = 255;
+constexpr int kInterpMaxVec = 31;                    // a component of mv is clamped to -31..31 when read
+struct InterpSelectDesc {
+    const void* a = nullptr; int a_row_stride = 0;   // luma of the earlier picture
+    const void* b = nullptr; int b_row_stride = 0;   // ... of the later one
+    int dtype = kSampleU8, bit_depth = 8, H = 0, W = 0;
+    const void* mv = nullptr; int mv_bh = 0, mv_bw = 0;  // device int16 [mv_bh][mv_bw][2]: (dx, dy), b[p] ~ a[p + v]
+    int k = 1, n = 2;                                // the phase k / n, k in 1..n-1
+    int limit = 8;                                   // 0..255, 8-bit code values a sample: a block above it falls back
+    void* plan = nullptr;                            // device int16 [plan_bh][plan_bw][4]: (ax, ay, bx, by)
+    void* wb = nullptr;                              // device uint8 [plan_bh][plan_bw]: b's weight of n
+    int plan_bh = 0, plan_bw = 0;
+    void* sad = nullptr;                             // device uint32 [plan_bh][plan_bw], or nullptr: the winner's SAD
+    void* fallen = nullptr;                          // device uint32, or nullptr: + the number of blocks that fell back
+};
+void interp_select_validate(const InterpSelectDesc& d);      // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void interp_select(const InterpSelectDesc& d, hipStream_t stream);
+struct InterpPlanesDesc {
+    const void* a = nullptr; int a_row_stride = 0; long long a_plane_stride = 0;
+    const void* b = nullptr; int b_row_stride = 0; long long b_plane_stride = 0;
+    void* dst = nullptr; int dst_row_stride = 0; long long dst_plane_stride = 0;
+    int dtype = kSampleU8, H = 0, W = 0, n_planes = 1;
+    int sx = 0, sy = 0;                              // the planes' subsampling against the luma plane of the selection
+    const void* plan = nullptr; const void* wb = nullptr; int plan_bh = 0, plan_bw = 0;
+    int k = 1, n = 2;
+    const void* fallen = nullptr; int n_blocks = 0;  // device uint32, or nullptr: 2 * fallen > n_blocks repeats the whole picture
+};
+void interp_planes_validate(const InterpPlanesDesc& d);      // throws std::invalid_argument for what is refused
+// one launch on `stream`: validates first, allocates nothing, never waits for the host
+void interp_planes(const InterpPlanesDesc& d, hipStream_t stream);
+
 // ---------------------------------------------------------------- symbol kernels (symbols.hip)
 // Uploads the scale -> Gaussian-table-index lookup table (call once per process before the
 // first symbol kernel and outside any graph capture).

@@ -481,6 +481,46 @@ int dcvc_motion_compensate_planes(const void* prev, int prev_row_stride, long lo
                                   long long dst_plane_stride, int dtype, int H, int W, int n_planes, int sx, int sy, const void* mv,
                                   int mv_bh, int mv_bw, void* stream);
 
+/* Frame-rate conversion on the GPU (no reference counterpart): the picture at k / n of the way from picture a to
+ * picture b, every value defined exactly in signed 32-bit integers. n in 2..8, k in 1..n-1, sh = bit_depth - 8; blocks are
+ * 16 x 16 luma samples, Bh = ceil(H / 16), Bw = ceil(W / 16); all indexes into a plane are clamped to it; all divisions are floor
+ * divisions of signed integers.
+ *   vectors:       mv (device, int16 [mv_bh][mv_bw][2]) is the grid of dcvc_motion_search(cur = b, ref = a), b[p] ~ a[p + v]. It
+ *                  is device data and is not validated: each component is clamped to -31..31 when read.
+ *   split:         per component va = (2 k v + n) / (2 n) (k v / n rounded, halves up), vb = va - v: the in-between sample at p
+ *                  is seen at a[p + va] and at b[p + vb].
+ *   selection:     the candidates of block (y, x) are the clamped vectors of the 3 x 3 neighbourhood of mv[y][x], grid indexes
+ *                  clamped to [0, Bh) x [0, Bw), and (0, 0). SAD(v) = sum of |a[p + va] - b[p + vb]| over the block's samples
+ *                  inside the plane, no penalty; the smallest tuple (SAD, |vx| + |vy|, vy, vx) wins. The block falls back when
+ *                  SAD > (limit << sh) * s, s the number of samples summed.
+ *   dcvc_interp_select: a, b luma planes [H][W]. plan (device, int16 [plan_bh][plan_bw][4]) takes (vax, vay, vbx, vby) and wb
+ *   (device, uint8 [plan_bh][plan_bw]) b's weight k of blocks [0, Bh) x [0, Bw); a block that fell back takes offsets 0 and
+ *   wb = 0 when 2 k <= n, else wb = n: it repeats the nearer picture. The rest of the grids is left alone. sad (device, uint32
+ *   [plan_bh][plan_bw], or NULL) takes the winner's SAD; fallen (device, one uint32, or NULL) is increased by the number of
+ *   blocks that fell back, the caller zeroes it. Samples are DCVC_SAMPLE_U8 (bit_depth 8) or DCVC_SAMPLE_U16 (LSB-aligned,
+ *   bit_depth 9..16); strides in samples. One launch on `stream`: nothing is allocated and nothing waits for the host. Refused
+ *   before anything is enqueued: NULL a, b, mv, plan or wb; another sample type; a bit_depth that is not the type's; H or W
+ *   outside 1..16384; n outside 2..8; k outside 1..n-1; limit outside 0..255; an mv or plan grid below Bh x Bw; a row stride
+ *   below W; a 16-bit plane, mv or plan at an odd address; a sad or fallen that is not 4-byte aligned.
+ *   dcvc_interp_planes: n_planes planes a, b [H][W] -> dst, every plane on its own, the planes subsampled by (sx, sy) in {0, 1}
+ *   against the luma plane of the selection: the block of sample (y, x) is (y / (16 >> sy), x / (16 >> sx)), the offsets are
+ *   vax >> sx, vay >> sy, vbx >> sx, vby >> sy (arithmetic shifts), w = min(wb, n),
+ *   dst[y][x] = ((n - w) a[y + vay][x + vax] + w b[y + vby][x + vbx] + (n >> 1)) / n. plan and wb are device data and are not
+ *   validated: the clamps make any value safe. With fallen (device, one uint32) and 2 * fallen > n_blocks every block is
+ *   treated as fallen: the whole picture repeats a (2 k <= n) or b; the counter is read on the device. With fallen == NULL only
+ *   the plan decides. One launch on `stream`; plane strides are not read for one plane. Refused before anything is enqueued:
+ *   NULL a, b, dst, plan or wb; another sample type; H or W outside 1..16384; n outside 2..8; k outside 1..n-1; sx or sy outside
+ *   {0, 1}; n_planes outside 1..65535; a plan grid below ceil(H / (16 >> sy)) x ceil(W / (16 >> sx)); n_blocks below 1 with
+ *   fallen; a row stride below W or a plane stride below the plane; a 16-bit plane or plan at an odd address; a fallen that is
+ *   not 4-byte aligned; dst overlapping a, b, plan or wb. */
+int dcvc_interp_select(const void* a, int a_row_stride, const void* b, int b_row_stride, int dtype, int bit_depth, int H, int W,
+                       const void* mv, int mv_bh, int mv_bw, int k, int n, int limit, void* plan, void* wb, int plan_bh, int plan_bw,
+                       void* sad, void* fallen, void* stream);
+int dcvc_interp_planes(const void* a, int a_row_stride, long long a_plane_stride, const void* b, int b_row_stride, long long b_plane_stride,
+                       void* dst, int dst_row_stride, long long dst_plane_stride, int dtype, int H, int W, int n_planes, int sx, int sy,
+                       const void* plan, const void* wb, int plan_bh, int plan_bw, int k, int n, const void* fallen, int n_blocks,
+                       void* stream);
+
 /* Deinterlacer on the GPU (no reference counterpart): planes of a woven frame -> progressive planes, every
  * output sample defined exactly in signed 32-bit integers. Per plane, T = threshold << (bit_depth - 8):
  *   rows y with y % 2 == keep are copied from cur. For a missing row y: ya = y - 1 (y + 1 at the top), yb = y + 1 (y - 1 at
